@@ -20,6 +20,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 PROFILE_TAG = "r03"     # profiles/<tag>_traffic.json (PMC bytes) and profiles/<tag>_valu.json (PMC VALU instructions) of this round
 NUM_SIMD, LANES_PER_CYCLE = 256 * 4, 32  # MI355X_MICROARCH.md: 256 CUs x 4 SIMDs, one wave64 VALU instruction per 2 cycles
+DUMP_PROOF_BYTES = 60 * 10 ** 6  # cap on proofs.npy: with status.npy, proof_index.npy and the headers a dump stays under 64 MB
 
 
 def splitmix64(seed):
@@ -142,6 +143,22 @@ def device_identity(torch, index):
     return str(getattr(p, "uuid", index))
 
 
+def dump_outputs(out_dir, proofs, status, B, pb):
+    """--dump-outputs: what a caller of p2_prove_batch_device receives from the last timed step, as float32 (exact for bytes
+    and status codes).  status.npy: (B,) per-proof status; proofs.npy: (k, pb) proof bytes, one row per proof, every proof
+    of the batch or, when they do not fit in DUMP_PROOF_BYTES, a fixed seeded sample; proof_index.npy: (k,) float64, the batch
+    index of each row.  Synthetic inputs are seeded and proving is deterministic, so two builds dump identical files."""
+    import numpy as np
+    import torch
+    k = min(B, DUMP_PROOF_BYTES // (4 * pb))
+    idx = np.arange(B) if k == B else np.sort(np.random.default_rng(0x5EED).choice(B, size=k, replace=False))
+    rows = proofs.view(B, pb)[torch.as_tensor(idx, device=proofs.device)].cpu().numpy()
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "status.npy"), status.cpu().numpy().astype(np.float32))
+    np.save(os.path.join(out_dir, "proof_index.npy"), idx.astype(np.float64))
+    np.save(os.path.join(out_dir, "proofs.npy"), rows.astype(np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -159,7 +176,11 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-threads", type=int, default=32, help="most OpenMP threads of the cpu_baseline leg (the port stops scaling at 16-32 on the GPU boxes' hosts; a cgroup CPU quota below this lowers it)")
     ap.add_argument("--cpu-sample", type=int, default=12, help="proofs timed on the host for cpu_baseline (median, after one warm-up)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write rank 0's proofs and statuses of the last timed step as DIR/<name>.npy (float32, at most 64 MB; see dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.config == 4:
         args.workload, args.batch = "elgamal", 128
@@ -274,6 +295,8 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     assert int(status.abs().sum().item()) == 0
+    if rank == 0 and args.dump_outputs:  # before the PCIe and kernel-timing passes below reuse `proofs`
+        dump_outputs(args.dump_outputs, proofs, status, B, pb)
 
     # PCIe-inclusive rate (never `value`): the same batch through p2_prove_batch -- host assignments in, proof bytes out,
     # via the handle's pinned staging buffers -- the shape of the reference's `data.prove(pw)` returning bytes to the host

@@ -713,6 +713,35 @@ def test_bench_uses_a_counter_file_only_for_the_sources_it_was_measured_on(tmp_p
     assert data["chunk"] == 128 and src["status"] == "current"
 
 
+def test_bench_dump_outputs_is_exact_capped_and_seeded(tmp_path):
+    """bench.py --dump-outputs, on host tensors shaped like the default step (256 proofs of 151372 bytes do not fit in 64 MB as
+    float32): the files hold the bytes and statuses exactly, stay under 64 MB, and sample the same proofs every run; a batch
+    that fits is written whole."""
+    import importlib.util
+    import numpy as np
+    import torch
+    spec = importlib.util.spec_from_file_location("bench_mod3", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    B, pb = 256, 151372
+    proofs = torch.randint(0, 256, (B * pb,), dtype=torch.uint8, generator=torch.Generator().manual_seed(1))
+    status = torch.zeros(B, dtype=torch.int32)
+    status[3] = 2
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), proofs, status, B, pb)
+    assert sum(f.stat().st_size for f in (tmp_path / "a").iterdir()) <= 64 * 10 ** 6
+    idx = np.load(tmp_path / "a" / "proof_index.npy")
+    rows = np.load(tmp_path / "a" / "proofs.npy")
+    assert idx.dtype == np.float64 and rows.dtype == np.float32 and rows.shape == (len(idx), pb) and 0 < len(idx) < B
+    assert (rows == proofs.view(B, pb).numpy()[idx.astype(np.int64)]).all()
+    assert (np.load(tmp_path / "a" / "status.npy") == status.numpy()).all()
+    for name in ("proofs", "proof_index", "status"):
+        assert (tmp_path / "a" / (name + ".npy")).read_bytes() == (tmp_path / "b" / (name + ".npy")).read_bytes()
+    bench.dump_outputs(str(tmp_path / "whole"), proofs[:8 * pb], status[:8], 8, pb)
+    assert (np.load(tmp_path / "whole" / "proof_index.npy") == np.arange(8)).all()
+    assert (np.load(tmp_path / "whole" / "proofs.npy") == proofs[:8 * pb].view(8, pb).numpy()).all()
+
+
 def test_committed_counter_files_were_measured_on_the_committed_kernels():
     """Freshness of profiles/<tag>_traffic.json and _valu.json.  A stale file is not an error of the product -- bench.py then
     reports null with the reason -- so this SKIPS with the reason instead of failing: re-run tools/gpu_profile_round.sh."""
