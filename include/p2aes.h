@@ -14,8 +14,8 @@
  *     aes-gcm/src/circuit_gcm.rs:771, examples/aes_gcm_128.rs:46 (19 sites)  p2_circuit_load (GPU preprocessing)
  *   PartialWitness::new / pw.set_target / data.prove(pw)   ** HOT PATH **    p2_prove_batch
  *     aes-gcm/src/circuit_aes.rs:283, circuit_gcm.rs:779-781 (20 sites)
- *   data.verify(proof)                                                       p2_verify
- *     aes-gcm/src/circuit_gcm.rs:782 (19 sites)
+ *   data.verify(proof)                                                       p2_verify (host),
+ *     aes-gcm/src/circuit_gcm.rs:782 (19 sites)                              p2_verify_batch (GPU, batched)
  *   native_gcm::encrypt (witness values)  aes-gcm/src/native_gcm.rs:16       p2_native_aes_gcm_encrypt
  *
  * Conventions: plain pointers and sizes only; every function that can fail returns 0 on success and a
@@ -46,6 +46,19 @@ enum {
     P2_PROOF_MISSING_INPUT = 2,    /* some generator never ran: an input target was not set */
     P2_PROOF_ZETA_IN_SUBGROUP = 3, /* "Opening point is in the subgroup." */
     P2_PROOF_POW_NOT_FOUND = 4     /* no proof-of-work witness among the 2^21 candidates searched (probability ~e^-32) */
+};
+/* per-proof verdict written by p2_verify_batch: the reason class verify_proof (csrc/verifier.h) would return first */
+enum {
+    P2_VERIFY_OK = 0,
+    P2_VERIFY_SHAPE = 1,             /* "proof truncated", "trailing bytes in proof", "Merkle path of the wrong depth (...)" */
+    P2_VERIFY_NON_CANONICAL = 2,     /* "non-canonical field element" */
+    P2_VERIFY_POW = 3,               /* "Invalid proof-of-work witness." */
+    P2_VERIFY_ZETA_IN_SUBGROUP = 4,  /* "Opening point is in the subgroup." */
+    P2_VERIFY_VANISHING = 5,         /* "vanishing polynomial identity does not hold at zeta" */
+    P2_VERIFY_MERKLE_INITIAL = 6,    /* "Invalid Merkle proof (initial tree)." */
+    P2_VERIFY_FRI_FOLD = 7,          /* "FRI fold consistency check failed." */
+    P2_VERIFY_MERKLE_FRI = 8,        /* "Invalid Merkle proof (FRI round)." */
+    P2_VERIFY_FINAL_POLY = 9         /* "Final polynomial evaluation is invalid." */
 };
 
 const char* p2_last_error(void);
@@ -256,9 +269,26 @@ int p2_prove_batch_multi(p2_circuit* const* handles, size_t n_handles, size_t ba
 int p2_prove_batch_device(p2_circuit*, size_t batch, const p2_target* targets, size_t n_targets, const uint64_t* d_values,
                           uint8_t* d_proofs, int* d_status, void* stream);
 int p2_circuit_synchronize(p2_circuit*);
+/* Batched verification on the GPU: the verdict of verify_proof for each proof, as a P2_VERIFY_* code.
+ * proofs: batch * p2_circuit_proof_bytes() bytes (the fixed layout of DESIGN.md section 8; every Merkle path has the depth the
+ * circuit implies, so a sibling-count byte that differs is P2_VERIFY_SHAPE -- also where the host reader, misled by two count
+ * bytes whose errors cancel, would first meet a non-canonical word).  verifier_data: 4*2^cap_height + 4 u64
+ * (cap || circuit_digest, host memory) or NULL for the handle's own (vd_len is then ignored).  status[i] <- P2_VERIFY_*.
+ * Returns P2_OK when every verdict was produced (rejections are verdicts, not errors), P2_ERR_INVALID / _NO_DEVICE / _HIP
+ * otherwise; batch == 0 is a no-op.  A zeroed slot (a proof p2_prove_batch failed) is P2_VERIFY_SHAPE.  Large batches run in
+ * chunks (option "verify_chunk", default: ~256 MiB of workspace, at most 512 proofs).  Thread safety as p2_prove_batch: any
+ * number of host threads may prove and verify on one handle; verification has its own workspaces and never waits for the
+ * proving streams. */
+int p2_verify_batch(p2_circuit*, size_t batch, const uint8_t* proofs, const uint64_t* verifier_data, size_t vd_len, int* status);
+/* Same with proofs and statuses in device memory, ordered with `stream` (NULL = the default stream) like
+ * p2_prove_batch_device: the kernels run on `stream` behind the work already enqueued there, so prove_batch_device ->
+ * verify_batch_device on one stream needs no host round trip.  Asynchronous: synchronise `stream` before reading d_status. */
+int p2_verify_batch_device(p2_circuit*, size_t batch, const uint8_t* d_proofs, const uint64_t* verifier_data, size_t vd_len,
+                           int* d_status, void* stream);
 /* Tuning knobs of a handle: "chunk" (proofs per workspace, default 128), "streams" (proving streams, default 2),
- * "debug_timing" (host-path phase times on stderr).  The environment variables P2AES_CHUNK / P2AES_STREAMS /
- * P2AES_DEBUG_TIMING set the defaults and are read once, in p2_circuit_load. */
+ * "debug_timing" (host-path phase times on stderr), "verify_chunk" (proofs per p2_verify_batch chunk).  The environment
+ * variables P2AES_CHUNK / P2AES_STREAMS / P2AES_DEBUG_TIMING / P2AES_VERIFY_CHUNK set the defaults and are read once, in
+ * p2_circuit_load. */
 int p2_circuit_set_option(p2_circuit*, const char* name, long value);
 /* Per-kernel timing of the most recent batch (HIP events on the proving stream). */
 typedef struct {

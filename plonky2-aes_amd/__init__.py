@@ -12,6 +12,17 @@ from .api import (  # noqa: F401
     PartialWitness,
     PoseidonEncryptTarget,
     ProveError,
+    VERIFY_FINAL_POLY,
+    VERIFY_FRI_FOLD,
+    VERIFY_MERKLE_FRI,
+    VERIFY_MERKLE_INITIAL,
+    VERIFY_NON_CANONICAL,
+    VERIFY_OK,
+    VERIFY_POW,
+    VERIFY_REASONS,
+    VERIFY_SHAPE,
+    VERIFY_VANISHING,
+    VERIFY_ZETA_IN_SUBGROUP,
     ecgfp5,
     lib,
     lib_path,

@@ -32,6 +32,26 @@ class ProveError(P2Error):
                           4: "no proof-of-work witness found"}.get(status, "prove failed (%d)" % status))
 
 
+# p2_verify_batch verdicts (include/p2aes.h P2_VERIFY_*): the reason class verify_proof would return first
+VERIFY_OK, VERIFY_SHAPE, VERIFY_NON_CANONICAL, VERIFY_POW, VERIFY_ZETA_IN_SUBGROUP, VERIFY_VANISHING = 0, 1, 2, 3, 4, 5
+VERIFY_MERKLE_INITIAL, VERIFY_FRI_FOLD, VERIFY_MERKLE_FRI, VERIFY_FINAL_POLY = 6, 7, 8, 9
+# every reason string of csrc/verifier.h -> its verdict code
+VERIFY_REASONS = {
+    "": VERIFY_OK,
+    "proof truncated": VERIFY_SHAPE,
+    "trailing bytes in proof": VERIFY_SHAPE,
+    "Merkle path of the wrong depth (initial tree).": VERIFY_SHAPE,
+    "Merkle path of the wrong depth (FRI round).": VERIFY_SHAPE,
+    "non-canonical field element": VERIFY_NON_CANONICAL,
+    "Invalid proof-of-work witness.": VERIFY_POW,
+    "Opening point is in the subgroup.": VERIFY_ZETA_IN_SUBGROUP,
+    "vanishing polynomial identity does not hold at zeta": VERIFY_VANISHING,
+    "Invalid Merkle proof (initial tree).": VERIFY_MERKLE_INITIAL,
+    "FRI fold consistency check failed.": VERIFY_FRI_FOLD,
+    "Invalid Merkle proof (FRI round).": VERIFY_MERKLE_FRI,
+    "Final polynomial evaluation is invalid.": VERIFY_FINAL_POLY,
+}
+
 u32p = C.POINTER(C.c_uint32)
 
 
@@ -139,6 +159,8 @@ def lib():
         "p2_prove_batch": (C.c_int, [vp, sz, C.POINTER(_Assignment), C.c_char_p, C.POINTER(C.c_int)]),
         "p2_prove_batch_device": (C.c_int, [vp, sz, u64p, sz, vp, vp, vp, vp]),
         "p2_circuit_synchronize": (C.c_int, [vp]),
+        "p2_verify_batch": (C.c_int, [vp, sz, C.c_char_p, u64p, sz, C.POINTER(C.c_int)]),
+        "p2_verify_batch_device": (C.c_int, [vp, sz, vp, u64p, sz, vp, vp]),
         "p2_circuit_set_timing": (C.c_int, [vp, C.c_int]),
         "p2_circuit_get_timing": (sz, [vp, C.POINTER(_KernelTime), sz]),
         "p2_gpu_device_count": (C.c_int, []),
@@ -415,7 +437,7 @@ class CircuitData:
         return list(self._vd)
 
     def set_option(self, name, value):
-        """Tuning knobs of the GPU handle: "chunk", "streams", "debug_timing" (include/p2aes.h)."""
+        """Tuning knobs of the GPU handle: "chunk", "streams", "debug_timing", "verify_chunk" (include/p2aes.h)."""
         if lib().p2_circuit_set_option(self.gpu(), name.encode(), int(value)):
             raise P2Error(_err())
 
@@ -485,6 +507,39 @@ class CircuitData:
         vd = verifier_data if verifier_data is not None else self.verifier_data()
         if lib().p2_verify(self.blob, len(self.blob), _arr(vd), len(vd), proof, len(proof)):
             raise P2Error("verify failed: " + _err())
+
+    def _vd_arg(self, verifier_data):
+        if verifier_data is None:
+            return None, 0
+        return _arr(verifier_data), len(verifier_data)
+
+    def verify_batch(self, proofs, verifier_data=None):
+        """GPU verification of a batch (p2_verify_batch): one VERIFY_* code per proof, the reason class data.verify(proof)
+        would report first.  `proofs`: a sequence of proof_bytes-long byte strings (None = a failed slot), or their
+        concatenation."""
+        pb = self.proof_bytes
+        if isinstance(proofs, (bytes, bytearray)):
+            if len(proofs) % pb:
+                raise P2Error("verify_batch: %d bytes is not a whole number of %d-byte proofs" % (len(proofs), pb))
+            blob = bytes(proofs)
+        else:
+            parts = [bytes(pb) if p is None else bytes(p) for p in proofs]
+            if any(len(p) != pb for p in parts):
+                raise P2Error("verify_batch: every proof must be %d bytes" % pb)
+            blob = b"".join(parts)
+        B = len(blob) // pb
+        status = (C.c_int * max(B, 1))()
+        vd, n = self._vd_arg(verifier_data)
+        if lib().p2_verify_batch(self.gpu(), B, blob, vd, n, status):
+            raise P2Error("p2_verify_batch failed: " + _err())
+        return list(status[:B])
+
+    def verify_batch_device(self, d_proofs, d_status, batch, verifier_data=None, stream=None):
+        """Device-resident form: `d_proofs` (batch * proof_bytes bytes) and `d_status` (int32[batch]) are raw device pointers,
+        `stream` a raw hipStream_t or None; asynchronous like prove_batch_device."""
+        vd, n = self._vd_arg(verifier_data)
+        if lib().p2_verify_batch_device(self.gpu(), batch, d_proofs, vd, n, d_status, stream):
+            raise P2Error("p2_verify_batch_device failed: " + _err())
 
     def debug_read(self, name, index=0, cap=1 << 26):
         out = (u64 * cap)()

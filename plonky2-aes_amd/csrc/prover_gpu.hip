@@ -16,6 +16,7 @@
 #include "os_random.h"
 #include "kernels.h"
 #include "kernels2.h"
+#include "kernels_verify.h"
 
 using namespace p2;
 using namespace p2k;
@@ -130,6 +131,12 @@ struct p2_circuit {
     // host-path staging (p2_prove_batch): persistent device buffers + pinned host buffers, one set per concurrent caller
     std::vector<struct Staging*> staging_free;
     std::mutex staging_mu;
+    // batched verification (p2_verify_batch): layout tables built at load, workspaces leased per call like the staging sets
+    std::string vfy_error;  // non-empty: a precondition of the verifier kernels does not hold for this circuit
+    VerifyArgs vfy_args{};  // layout and circuit fields; the per-call pointers are filled in by verify_run
+    size_t vfy_chunk = 0;
+    std::vector<struct VerifyWs*> vfy_free;
+    std::mutex vfy_mu;
     long fail_alloc_after = -1;            // test hook, see dalloc_ws
     // timing
     bool timing_on = false;
@@ -1112,6 +1119,267 @@ static int guarded_rc(F&& f) {
         return set_error("unknown exception"), P2_ERR_INVALID;
     }
 }
+// ---------------------------------------------------------------------------------- batched verification (kernels_verify.h)
+// Per-call workspace: device buffers for one chunk of proofs, a stream for the host path and an event that orders the next
+// user of the workspace behind the last kernel that read it (the device path returns before its kernels have run).
+struct VerifyWs {
+    hipStream_t stream = nullptr;
+    hipEvent_t done = nullptr;
+    size_t chunk = 0;
+    u64 *d_words = nullptr, *d_chal = nullptr, *d_vq = nullptr, *d_vd = nullptr;
+    u32 *d_flags = nullptr, *d_qfail = nullptr;
+    uint8_t* d_proofs = nullptr;
+    int *d_status = nullptr, *h_status = nullptr;
+    void release() {
+        for (void* p : {(void*)d_words, (void*)d_chal, (void*)d_vq, (void*)d_vd, (void*)d_flags, (void*)d_qfail, (void*)d_proofs, (void*)d_status})
+            if (p) (void)hipFree(p);
+        if (h_status) (void)hipHostFree(h_status);
+        if (stream) (void)hipStreamDestroy(stream);
+        if (done) (void)hipEventDestroy(done);
+        *this = VerifyWs();
+    }
+};
+struct VdArg {
+    u64 w[4 * 16 + 4];
+};
+__global__ void k_vfy_set_vd(VdArg v, u64* out, u32 count) {
+    if (threadIdx.x < count) out[threadIdx.x] = v.w[threadIdx.x];
+}
+
+// Layout tables of the proof (the reader of verifier.h with every count taken from the circuit) and the host-side checks of
+// what the verifier kernels assume.  Called once from p2_circuit_load.
+static int verify_setup(p2_circuit* C) {
+    const Circuit& c = C->c;
+    const u32 NC = c.cfg.num_challenges, R = c.cfg.num_routed_wires, NW = c.cfg.num_wires, qdf = c.cfg.quotient_degree_factor;
+    const u32 ncc = c.num_constants_cols(), nlp = c.num_lookup_polys(), npp = c.num_partial_products(), zc = c.num_zs_cols();
+    const u32 cap_n = 1u << c.cfg.cap_height, lde_bits = C->lde_bits;
+    // preconditions of k_vfy_vanishing / k_vfy_queries: fixed shapes they index with (cf. the host verifier's fixed arrays)
+    std::string why;
+    if (NC != 2) why = "num_challenges != 2";
+    else if (R != 80 || NW != 135) why = "the lookup, arithmetic and Poseidon terms need 80 routed wires of 135";
+    else if (qdf != 8 || c.cfg.num_constants != 2) why = "quotient_degree_factor / num_constants differ from standard_recursion_config";
+    else if (c.cfg.cap_height != 4) why = "cap_height != 4";
+    else if (c.k_is.size() != R) why = "k_is shape";
+    else if (c.num_gate_constraints > VFY_MAX_GC || c.gates.size() > p2::MAX_GATE_TYPES || c.luts.size() > p2::MAX_LUTS) why = "gate / lookup table count";
+    else if (c.cfg.num_query_rounds > CH_WORDS - CH_QUERY || C->arities.size() > VFY_MAX_ROUNDS) why = "query rounds / FRI rounds";
+    else if (c.cfg.pow_bits == 0 || c.cfg.pow_bits > 32) why = "pow_bits";
+    else if (C->pbytes >= (size_t)UINT32_MAX) why = "proof too large";
+    for (u32 ab : C->arities)
+        if (ab != VFY_ARITY_BITS) why = "FRI arity other than 16";
+    if (!why.empty()) {
+        C->vfy_error = "p2_verify_batch does not support this circuit: " + why;
+        return 0;
+    }
+    std::vector<u32> woff, coff, obs;
+    std::vector<uint8_t> cexp;
+    size_t pos = 0;
+    auto words = [&](size_t k) {
+        u32 first = (u32)woff.size();
+        for (size_t i = 0; i < k; i++, pos += 8) woff.push_back((u32)pos);
+        return first;
+    };
+    auto count = [&](u32 depth) {
+        coff.push_back((u32)pos++);
+        cexp.push_back((uint8_t)depth);
+    };
+    VerifyArgs& a = C->vfy_args;
+    a.cap_words = 4 * cap_n;
+    words(3 * a.cap_words);
+    a.o_const = words(2 * ncc);
+    a.o_sig = words(2 * R);
+    a.o_wires = words(2 * NW);
+    a.o_zs = words(2 * NC);
+    a.o_zsn = words(2 * NC);
+    a.o_lk = words(2 * NC * nlp);
+    a.o_lkn = words(2 * NC * nlp);
+    a.o_pp = words(2 * NC * npp);
+    a.o_quot = words(2 * NC * qdf);
+    a.fri_caps_off = words(C->arities.size() * a.cap_words);
+    const u32 cols[4] = {c.num_preprocessed(), NW + c.salt(), zc + c.salt(), c.num_quotient_cols() + c.salt()};
+    a.init_depth = lde_bits - c.cfg.cap_height;
+    for (u32 q = 0; q < c.cfg.num_query_rounds; q++) {
+        const u32 base = (u32)woff.size();
+        if (q == 0) a.q_off = base;
+        for (int o = 0; o < 4; o++) {
+            a.init_eval_off[o] = words(cols[o]) - base;
+            a.init_width[o] = cols[o];
+            count(a.init_depth);
+            a.init_sib_off[o] = words(4 * a.init_depth) - base;
+        }
+        u32 bits = lde_bits;
+        for (u32 k = 0; k < C->arities.size(); k++) {
+            a.step_eval_off[k] = words(2 * VFY_ARITY) - base;
+            a.step_depth[k] = bits - c.cfg.cap_height - C->arities[k];
+            count(a.step_depth[k]);
+            a.step_sib_off[k] = words(4 * a.step_depth[k]) - base;
+            bits -= C->arities[k];
+        }
+        if (q == 0) a.q_stride = (u32)woff.size() - base;
+    }
+    a.final_len = (u32)(C->n >> (VFY_ARITY_BITS * C->arities.size()));
+    a.final_off = words(2 * a.final_len);
+    a.pow_off = words(1);
+    if (pos != C->pbytes) return set_error("internal: verifier layout differs from the proof size"), P2_ERR_INVALID;
+    // the opening batches in the order they are observed and reduced: constants, sigmas, wires, zs, partial products,
+    // quotient, lookup zs | zs(g zeta), lookup zs(g zeta)
+    auto ext = [&](u32 off, u32 k) {
+        for (u32 i = 0; i < k; i++) obs.push_back(off + 2 * i);
+    };
+    ext(a.o_const, ncc), ext(a.o_sig, R), ext(a.o_wires, NW), ext(a.o_zs, NC), ext(a.o_pp, NC * npp), ext(a.o_quot, NC * qdf), ext(a.o_lk, NC * nlp);
+    a.n_b0 = (u32)obs.size();
+    ext(a.o_zsn, NC), ext(a.o_lkn, NC * nlp);
+    a.n_b1 = (u32)obs.size() - a.n_b0;
+    a.W = (u32)woff.size();
+    a.n_cnt = (u32)coff.size();
+    if (upload(C, (u32**)&a.word_off, woff.data(), woff.size()) || upload(C, (u32**)&a.cnt_off, coff.data(), coff.size()) ||
+        upload(C, (uint8_t**)&a.cnt_exp, cexp.data(), cexp.size()) || upload(C, (u32**)&a.obs_map, obs.data(), obs.size()))
+        return P2_ERR_HIP;
+    a.proof_bytes = C->pbytes;
+    a.degree_bits = c.degree_bits;
+    a.lde_bits = lde_bits;
+    a.cap_height = c.cfg.cap_height;
+    a.pow_bits = c.cfg.pow_bits;
+    a.num_queries = c.cfg.num_query_rounds;
+    a.num_rounds = (u32)C->arities.size();
+    a.has_lookup = nlp ? 1 : 0;
+    a.R = R, a.num_wires = NW, a.NC = NC, a.npp = npp, a.qdf = qdf, a.nlp = nlp, a.nsldc = c.num_sldc_polys();
+    a.lut_deg = nlp ? c.lut_degree() : 0;
+    a.nsel = c.num_selectors(), a.nls = c.num_lookup_selectors, a.ngc = c.num_gate_constraints, a.nzpp = c.num_zs_pp(), a.zc = zc;
+    a.num_gates = (u32)c.gates.size();
+    for (u32 g = 0; g < c.gates.size(); g++) {
+        a.gate_kind[g] = c.gates[g];
+        a.gate_sel[g] = c.selector_index[g];
+        a.group_lo[g] = c.groups[c.selector_index[g]].first;
+        a.group_hi[g] = c.groups[c.selector_index[g]].second;
+    }
+    a.num_luts = (u32)c.luts.size();
+    a.lut_pairs = C->d_lut_pairs;
+    a.lut_offsets = C->d_lut_offsets;
+    a.k_is = C->d_k_is;
+    // chunk: the unpacked words and the staged proofs of a chunk within ~256 MiB, at most 512 proofs
+    const size_t per_proof = 8 * (size_t)a.W + C->pbytes + 8 * (CH_WORDS + VQ_WORDS) + 16;
+    C->vfy_chunk = std::max<size_t>(1, std::min<size_t>(512, ((size_t)256 << 20) / per_proof));
+    if (const char* e = getenv("P2AES_VERIFY_CHUNK")) C->vfy_chunk = (size_t)std::min(4096, std::max(1, atoi(e)));
+    return 0;
+}
+
+static VerifyWs* verify_lease(p2_circuit* C) {
+    VerifyWs* W = nullptr;
+    std::vector<VerifyWs*> stale;  // made before the "verify_chunk" option changed: drained and freed after the lock is released
+    size_t chunk;
+    {
+        std::lock_guard<std::mutex> lock(C->vfy_mu);
+        chunk = C->vfy_chunk;
+        while (!C->vfy_free.empty() && !W) {
+            W = C->vfy_free.back();
+            C->vfy_free.pop_back();
+            if (W->chunk != chunk) {
+                stale.push_back(W);
+                W = nullptr;
+            }
+        }
+    }
+    for (VerifyWs* S : stale) {
+        (void)hipEventSynchronize(S->done);
+        S->release();
+        delete S;
+    }
+    if (W) return W;
+    W = new VerifyWs();
+    const VerifyArgs& a = C->vfy_args;
+    W->chunk = chunk;
+    bool ok = hipStreamCreateWithFlags(&W->stream, hipStreamNonBlocking) == hipSuccess && hipEventCreateWithFlags(&W->done, hipEventDisableTiming) == hipSuccess &&
+              hipMalloc((void**)&W->d_words, chunk * a.W * 8) == hipSuccess && hipMalloc((void**)&W->d_chal, chunk * CH_WORDS * 8) == hipSuccess &&
+              hipMalloc((void**)&W->d_vq, chunk * VQ_WORDS * 8) == hipSuccess && hipMalloc((void**)&W->d_vd, sizeof(VdArg)) == hipSuccess &&
+              hipMalloc((void**)&W->d_flags, chunk * 4) == hipSuccess && hipMalloc((void**)&W->d_qfail, chunk * 4) == hipSuccess &&
+              hipMalloc((void**)&W->d_proofs, chunk * C->pbytes) == hipSuccess && hipMalloc((void**)&W->d_status, chunk * sizeof(int)) == hipSuccess &&
+              hipHostMalloc((void**)&W->h_status, chunk * sizeof(int), hipHostMallocDefault) == hipSuccess;
+    if (!ok) {
+        set_error("verification workspace could not be allocated");
+        W->release();
+        delete W;
+        return nullptr;
+    }
+    return W;
+}
+static void verify_return(p2_circuit* C, VerifyWs* W) {
+    std::lock_guard<std::mutex> lock(C->vfy_mu);
+    C->vfy_free.push_back(W);
+}
+
+// Enqueues the verification of `batch` proofs on `st`.  host: proofs / status are host memory (staged through the workspace,
+// and the call waits for the statuses); otherwise both are device memory and the call returns once everything is enqueued.
+static int verify_run(p2_circuit* C, VerifyWs* W, size_t batch, const uint8_t* proofs, const VdArg& vd, int* status, hipStream_t st, bool host) {
+    const size_t pb = C->pbytes;
+    HIPCHECK(hipStreamWaitEvent(st, W->done, 0));  // the workspace's previous user
+    const u32 vd_words = C->vfy_args.cap_words + 4;
+    hipLaunchKernelGGL(k_vfy_set_vd, dim3(1), dim3(128), 0, st, vd, W->d_vd, vd_words);
+    HIPCHECK(hipGetLastError());
+    for (size_t done = 0; done < batch; done += W->chunk) {
+        const u32 B = (u32)std::min(W->chunk, batch - done);
+        VerifyArgs a = C->vfy_args;
+        a.batch = B;
+        a.words = W->d_words;
+        a.flags = W->d_flags;
+        a.qfail = W->d_qfail;
+        a.chal = W->d_chal;
+        a.vq = W->d_vq;
+        a.vd = W->d_vd;
+        if (host) {
+            HIPCHECK(hipMemcpyAsync(W->d_proofs, proofs + done * pb, B * pb, hipMemcpyHostToDevice, st));
+            a.proofs = W->d_proofs;
+            a.status = W->d_status;
+        } else {
+            a.proofs = proofs + done * pb;
+            a.status = status + done;
+        }
+        HIPCHECK(hipMemsetAsync(W->d_flags, 0, (size_t)B * 4, st));
+        HIPCHECK(hipMemsetAsync(W->d_qfail, 0xFF, (size_t)B * 4, st));
+        const u32 slots = 4 + a.num_rounds + 1;
+        hipLaunchKernelGGL(k_vfy_unpack, dim3((a.W + 255) / 256, B), dim3(256), 0, st, a);
+        HIPCHECK(hipGetLastError());
+        hipLaunchKernelGGL(k_vfy_transcript, g1((size_t)B * 16, 64), dim3(64), 0, st, a);
+        HIPCHECK(hipGetLastError());
+        hipLaunchKernelGGL(k_vfy_vanishing, dim3(B), dim3(256), 0, st, a);
+        HIPCHECK(hipGetLastError());
+        hipLaunchKernelGGL(k_vfy_queries, dim3((u32)(((size_t)B * a.num_queries + 63) / 64), slots), dim3(64), 0, st, a);
+        HIPCHECK(hipGetLastError());
+        hipLaunchKernelGGL(k_vfy_finish, g1(B, 64), dim3(64), 0, st, a, slots);
+        HIPCHECK(hipGetLastError());
+        if (host) {
+            HIPCHECK(hipMemcpyAsync(W->h_status, W->d_status, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, st));
+            HIPCHECK(hipStreamSynchronize(st));
+            memcpy(status + done, W->h_status, (size_t)B * sizeof(int));
+        }
+    }
+    HIPCHECK(hipEventRecord(W->done, st));
+    return P2_OK;
+}
+
+static int verify_batch_impl(p2_circuit* C, size_t batch, const uint8_t* proofs, const uint64_t* verifier_data, size_t vd_len, int* status, hipStream_t st,
+                             bool host) {
+    if (!C) return set_error("p2_verify_batch: null circuit handle"), P2_ERR_INVALID;
+    const size_t vd_words = (size_t)C->vfy_args.cap_words + 4;
+    if (verifier_data && vd_len != vd_words) return set_error("verifier_data must be cap || circuit_digest (" + std::to_string(vd_words) + " words)"), P2_ERR_INVALID;
+    if (!C->vfy_error.empty()) return set_error(C->vfy_error), P2_ERR_INVALID;
+    if (batch == 0) return P2_OK;
+    if (!proofs || !status) return set_error("p2_verify_batch: null proofs or status"), P2_ERR_INVALID;
+    VdArg vd{};
+    const u64* src = verifier_data ? verifier_data : C->verifier_data.data();
+    if (vd_words > sizeof(vd.w) / 8) return set_error("internal: verifier data larger than the kernel argument"), P2_ERR_INVALID;
+    memcpy(vd.w, src, vd_words * 8);
+    HIPCHECK(hipSetDevice(C->device));
+    VerifyWs* W = verify_lease(C);
+    if (!W) return P2_ERR_HIP;
+    int rc = verify_run(C, W, batch, proofs, vd, status, host ? W->stream : st, host);
+    if (rc != P2_OK) {
+        // the workspace may still be in use by what was enqueued before the failure: drain before handing it out again
+        (void)hipStreamSynchronize(host ? W->stream : st);
+    }
+    verify_return(C, W);
+    return rc;
+}
+
 extern "C" {
 
 int p2_gpu_device_count(void) {
@@ -1203,6 +1471,7 @@ p2_circuit* p2_circuit_load(const uint8_t* blob, size_t len, int device) {
         if (fl > C->n_obs) throw std::runtime_error("final polynomial larger than the observation buffer");
         if (upload(C, &C->d_map_obs, obs.data(), obs.size()) || upload(C, &C->d_map_ser, ser.data(), ser.size())) throw std::runtime_error(g_last_error);
         if (circuit_setup(C)) throw std::runtime_error(g_last_error);
+        if (verify_setup(C)) throw std::runtime_error(g_last_error);
         return C;
     } catch (std::exception& e) {
         set_error(e.what());
@@ -1219,6 +1488,10 @@ void p2_circuit_free(p2_circuit* C) {
     for (Staging* S : C->staging_free) {
         S->release();
         delete S;
+    }
+    for (VerifyWs* W : C->vfy_free) {
+        W->release();
+        delete W;
     }
     for (void* p : C->allocs) (void)hipFree(p);
     if (C->stream) (void)hipStreamDestroy(C->stream);
@@ -1495,8 +1768,12 @@ int p2_circuit_set_option(p2_circuit* C, const char* name, long value) {
         C->opt_streams = (size_t)value;
     } else if (k == "debug_timing") {
         C->opt_debug_timing = value != 0;
+    } else if (k == "verify_chunk") {
+        if (value < 1 || value > 4096) return set_error("option verify_chunk: 1..4096 proofs"), P2_ERR_INVALID;
+        std::lock_guard<std::mutex> vlock(C->vfy_mu);
+        C->vfy_chunk = (size_t)value;
     } else {
-        return set_error("unknown option (known: chunk, streams, debug_timing)"), P2_ERR_INVALID;
+        return set_error("unknown option (known: chunk, streams, debug_timing, verify_chunk)"), P2_ERR_INVALID;
     }
     return P2_OK;
 }
@@ -1784,5 +2061,13 @@ int p2_gpu_merkle_cap(const uint64_t* cols_major, size_t cols, size_t num_leaves
     HIPCHECK(hipStreamSynchronize(C->stream));
     HIPCHECK(hipMemcpy(cap, t.dig + cap_off(t, (u32)cap_height), ((size_t)4 << cap_height) * 8, hipMemcpyDeviceToHost));
     return P2_OK;
+}
+
+// ---- batched verification
+int p2_verify_batch(p2_circuit* C, size_t batch, const uint8_t* proofs, const uint64_t* verifier_data, size_t vd_len, int* status) {
+    return guarded_rc([&] { return verify_batch_impl(C, batch, proofs, verifier_data, vd_len, status, nullptr, true); });
+}
+int p2_verify_batch_device(p2_circuit* C, size_t batch, const uint8_t* d_proofs, const uint64_t* verifier_data, size_t vd_len, int* d_status, void* stream) {
+    return guarded_rc([&] { return verify_batch_impl(C, batch, d_proofs, verifier_data, vd_len, d_status, (hipStream_t)stream, false); });
 }
 }
