@@ -345,8 +345,10 @@ __device__ __forceinline__ void wave_lds_sync() {
 // help, vmcnt retires in order.)  Natural-order input and bit-reversed output only (the LDE), which is where the time is.
 // block id -> work id such that the work ids handled by one XCD (block ids congruent mod 8) are consecutive
 __device__ __forceinline__ u32 xcd_swizzle(u32 b, u32 grid) { return (grid & 7) ? b : (b & 7) * (grid >> 3) + (b >> 3); }
-// every global load written above this line is issued before any instruction below it (the loads themselves complete in
-// order; their consumers wait with s_waitcnt vmcnt(n) as usual)
+// A compiler memory barrier: no global load written above it may sink below it.  It does not fix the issue order -- the
+// compiler may still hoist arithmetic above it or split the loads into several batches -- so the property the kernels rely on
+// (every load of a step in flight before its first product) is held by
+// tests/test_codegen.py::test_ntt_kernels_issue_the_loads_of_a_step_together, which reads the emitted code.
 __device__ __forceinline__ void loads_issued() { asm volatile("" ::: "memory"); }
 template <bool SPLIT>
 __global__ __launch_bounds__(1024) void k_ntt_r16(NttArgs a) {
@@ -607,65 +609,26 @@ __global__ __launch_bounds__(1024) void k_ntt_r16(NttArgs a) {
 // workgroups per compute unit = 8 waves per SIMD instead of 4, one more exchange: 21.4 ms against 19.7 ms per 128-proof chunk.
 // Occupancy is not what this kernel lacks; the variant was dropped.)
 
-// ---- large transforms (n > 2^14): four-step split n = n1 * n2.  Pass 1 (this kernel): for a tile of T adjacent
+// ---- large transforms (n > 2^14): four-step split n = n1 * n2.  Pass 1 (k_ntt_pass1_r16): for a tile of T adjacent
 // columns j2, the n1-point DIF over the stride-n2 elements x[j1*n2 + j2], then the twiddle w_n^(j2*k1); the result
-// for k1 lands in row rev(k1).  Pass 2 is k_ntt_lds on the n1 contiguous rows of n2 points.  Together: natural
+// for k1 lands in row rev(k1).  Pass 2 is k_ntt_r16<false> on the n1 contiguous rows of n2 points.  Together: natural
 // order in, bit-reversed order out, exactly like the single-pass kernel.
 struct Pass1Args {
     const u64* in;
     u64* out;
     const u64* tw;   // w^i for i < n (forward or inverse root of order n)
     const u64* pre;  // [cosets][n] scale applied on load, or null
-    const u64* out_tw;  // k_ntt_pass1_r16: [n1][n2] w^(rev(row) j2), the output twiddle in output order
+    const u64* out_tw;  // [n1][n2] w^(rev(row) j2), the output twiddle in output order
     size_t in_col_stride, out_col_stride, in_batch_stride, out_batch_stride;
     int logn, log_n1, log_T, cosets, in_coset_blocks, xcd_swizzle;
     u32 block_of_coset[8];
 };
-__global__ __launch_bounds__(256) void k_ntt_pass1(Pass1Args a) {
-    extern __shared__ __align__(16) u64 lds[];
-    const u32 n = 1u << a.logn, n1 = 1u << a.log_n1, T = 1u << a.log_T;
-    const int log_n2 = a.logn - a.log_n1;
-    const u32 n2 = 1u << log_n2, tiles = n2 >> a.log_T;
-    const u32 tile = blockIdx.x % tiles, cc = blockIdx.x / tiles, col = cc / a.cosets, coset = cc % a.cosets;
-    const u32 blk = a.block_of_coset[coset];
-    const u64* in = a.in + (size_t)blockIdx.y * a.in_batch_stride + (size_t)col * a.in_col_stride + (a.in_coset_blocks ? (size_t)blk * n : 0);
-    u64* out = a.out + (size_t)blockIdx.y * a.out_batch_stride + (size_t)col * a.out_col_stride + (size_t)blk * n;
-    const u64* pre = a.pre ? a.pre + (size_t)coset * n : nullptr;
-    const u32 j2_0 = tile << a.log_T;
-    for (u32 e = threadIdx.x; e < (n1 << a.log_T); e += blockDim.x) {
-        u32 j1 = e >> a.log_T, t = e & (T - 1);
-        size_t idx = (size_t)j1 * n2 + j2_0 + t;
-        u64 v = in[idx];
-        if (pre) v = gl::mul_nb(v, pre[idx]);
-        lds[e] = v;
-    }
-    __syncthreads();
-    for (int s = a.log_n1 - 1; s >= 0; s--) {
-        const u32 h = 1u << s;
-        for (u32 b = threadIdx.x; b < ((n1 >> 1) << a.log_T); b += blockDim.x) {
-            u32 t = b & (T - 1), q = b >> a.log_T;
-            u32 pos = q & (h - 1);
-            u32 i = ((q >> s) << (s + 1)) | pos;
-            u64 x = lds[(i << a.log_T) + t], y = lds[((i + h) << a.log_T) + t];
-            u64 w = a.tw[(size_t)(pos << (a.log_n1 - 1 - s)) << log_n2];  // w_n1^(pos * 2^(log_n1-1-s))
-            lds[(i << a.log_T) + t] = gl::add(x, y);
-            lds[((i + h) << a.log_T) + t] = gl::mul_nb(gl::sub(x, y), w);
-        }
-        __syncthreads();
-    }
-    for (u32 e = threadIdx.x; e < (n1 << a.log_T); e += blockDim.x) {
-        u32 r = e >> a.log_T, t = e & (T - 1);
-        u32 k1 = a.log_n1 ? (__brev(r) >> (32 - a.log_n1)) : 0;
-        u32 j2 = j2_0 + t;
-        out[(size_t)r * n2 + j2] = gl::mul_nb(lds[e], a.tw[(size_t)k1 * j2]);
-    }
-}
 // ---- pass 1, register-blocked (round 3).  The tile of n1 rows x T columns (4096 elements) is ONE flat array e = row * T + t:
 // the n1-point DIF down the rows of every column is then exactly the first log n1 stages of a 4096-point DIF over e -- the
 // same pairs (e, e + h), h >= T -- with twiddles that depend on the ROW part of e only.  So the step structure of k_ntt_r16
 // carries over: 256 threads own 16 points each, the first log n1 mod 4 stages come straight from the (tile-strided) global
 // loads, every further four stages cost one LDS exchange, and a last trip puts the data in store order.  n = 2^19 (n1 = 128):
-// 3 + 4 stages, 2 barriers, where k_ntt_pass1 runs 7 radix-2 LDS stages with 7 barriers and gathers its output twiddle
+// 3 + 4 stages, 2 barriers, where round 2's radix-2 pass ran 7 LDS stages with 7 barriers and gathered its output twiddle
 // w^(k1 j2) with a stride of k1 elements (64 cache lines per wave load); here that twiddle comes from a table laid out in
 // output order (Pass1Args::out_tw: [row][j2] = w^(rev(row) j2), n entries shared by every column, coset and proof).
 __device__ __forceinline__ void ntt_p1_load_tw(u64* w, const u64* __restrict__ tw, u32 tp, int m, int log_T, int tw_log, int nstages) {
@@ -678,12 +641,10 @@ __device__ __forceinline__ void ntt_p1_load_tw(u64* w, const u64* __restrict__ t
             if (j < half) w[base + j] = tw[(size_t)((tp + ((u32)j << m)) >> log_T) << (tw_log - q)];
     }
 }
-// MINW = waves per SIMD the register budget is cut for.  With the tile addresses written as per-thread + uniform parts the
-// kernel needs 122 VGPRs and no scratch at four waves; the two-wave build (P2AES_PASS1_WAVES=2) is kept as an A/B switch.
-// (Before that: 128 VGPRs with 44 bytes of scratch at four waves, 170 and none at two -- and the scratch-free build at half the
-// occupancy was 1.5 x slower, 100.8 vs 67.3 ms per 16 proofs at n = 2^19.)
-template <int MINW>
-__global__ __launch_bounds__(256, MINW) void k_ntt_pass1_r16(Pass1Args a) {
+// Built for four waves per SIMD: with the tile addresses written as per-thread + uniform parts the kernel needs 122 VGPRs and
+// no scratch there.  (Before that: 128 VGPRs with 44 bytes of scratch at four waves, 170 and none at two -- and the
+// scratch-free build at half the occupancy was 1.5 x slower, 100.8 vs 67.3 ms per 16 proofs at n = 2^19.)
+__global__ __launch_bounds__(256, 4) void k_ntt_pass1_r16(Pass1Args a) {
     extern __shared__ __align__(16) u64 lds[];
     const u32 T = 1u << a.log_T, t = threadIdx.x;
     const int log_n2 = a.logn - a.log_n1;

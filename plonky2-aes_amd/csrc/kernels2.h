@@ -188,6 +188,8 @@ __global__ __launch_bounds__(256, 4) void k_quotient(QuotientArgs a) {
             u32 j1 = min(a.R, (chunk + 1) * a.qdf);
             u64 w8[8];
             if (ONE_WALK) {
+                // chunks of exactly 8 columns, npp + 1 = 10 of them, k_is[8 chunk + k] < 80: R == 80 and qdf == 8, which
+                // p2_circuit_load requires of every circuit it accepts (npp follows from the two)
 #pragma unroll
                 for (int k = 0; k < 8; k++) {
                     const u32 j = 8 * chunk + k;
@@ -307,55 +309,10 @@ __global__ void k_zeta_pows(const u64* chal, u64* pows, size_t pows_batch_stride
     o[i] = r.a;
     o[n + i] = r.b;
 }
-// out[col] = sum_i coeffs[col][i] * pw[i]   (extension result), one workgroup per (column, proof)
-__global__ __launch_bounds__(256) void k_eval_polys(const u64* __restrict__ coeffs, size_t coeffs_batch_stride, const u64* __restrict__ pw /*[2][n]*/,
-                                                     size_t pw_batch_stride, u32 n, u64* __restrict__ out /*[cols][2]*/, size_t out_batch_stride) {
-    __shared__ u64 la[256], lb[256];
-    const u64* c = coeffs + (size_t)blockIdx.y * coeffs_batch_stride + (size_t)blockIdx.x * n;
-    const u64* pa = pw + (size_t)blockIdx.y * pw_batch_stride;
-    u64 sa = 0, sb = 0;
-    u32 i = threadIdx.x;
-    // four rows per trip, their twelve loads issued before the first product (loads_issued, kernels.h)
-    for (; i + 3 * blockDim.x < n; i += 4 * blockDim.x) {
-        u64 v[4], wa[4], wb[4];
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            v[k] = c[i + k * blockDim.x];
-            wa[k] = pa[i + k * blockDim.x];
-            wb[k] = pa[n + i + k * blockDim.x];
-        }
-        loads_issued();
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            sa = gl::add(sa, gl::mul(v[k], wa[k]));
-            sb = gl::add(sb, gl::mul(v[k], wb[k]));
-        }
-    }
-    for (; i < n; i += blockDim.x) {
-        u64 v = c[i];
-        sa = gl::add(sa, gl::mul(v, pa[i]));
-        sb = gl::add(sb, gl::mul(v, pa[n + i]));
-    }
-    la[threadIdx.x] = sa;
-    lb[threadIdx.x] = sb;
-    __syncthreads();
-    for (u32 off = blockDim.x / 2; off > 0; off >>= 1) {
-        if (threadIdx.x < off) {
-            la[threadIdx.x] = gl::add(la[threadIdx.x], la[threadIdx.x + off]);
-            lb[threadIdx.x] = gl::add(lb[threadIdx.x], lb[threadIdx.x + off]);
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        u64* o = out + (size_t)blockIdx.y * out_batch_stride + 2 * (size_t)blockIdx.x;
-        o[0] = la[0];
-        o[1] = lb[0];
-    }
-}
-
-// The same for a LIST of polynomials from several oracles in one launch (round 2 launched the kernel above once per oracle and
-// point: preprocessed, wires, Z at zeta, Z at g zeta, quotient): entry e = column `col` of the coefficient matrix `base`,
-// evaluated with power table pw_k (0: zeta, 1: g zeta), result to extension slot `out`.
+// out = sum_i coeffs[col][i] * pw[i] (extension result) for a LIST of polynomials from several oracles in one launch, one
+// workgroup per (entry, proof) (round 2 launched a kernel per oracle and point: preprocessed, wires, Z at zeta, Z at g zeta,
+// quotient): entry e = column `col` of the coefficient matrix `base`, evaluated with power table pw_k (0: zeta, 1: g zeta),
+// result to extension slot `out`.
 struct EvalRef {
     const u64* base;      // coefficient matrix of the oracle (proof 0)
     size_t batch_stride;  // 0 for the shared preprocessed oracle
@@ -565,22 +522,6 @@ __device__ __forceinline__ void store_u64_bytes(uint8_t* p, u64 v) {
 #pragma unroll
     for (int i = 0; i < 8; i++) p[i] = (uint8_t)(v >> (8 * i));
 }
-// copy `count` u64 words (src stride per proof) to byte offset `dst_off` of every proof
-__global__ void k_proof_copy(const u64* src, size_t src_batch_stride, u32 count, uint8_t* proofs, size_t proof_bytes, size_t dst_off) {
-    u32 i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= count) return;
-    store_u64_bytes(proofs + (size_t)blockIdx.y * proof_bytes + dst_off + 8 * (size_t)i, src[(size_t)blockIdx.y * src_batch_stride + i]);
-}
-// strided variant: word i comes from src[i * elem_stride]  (component-column -> interleaved extension elements)
-__global__ void k_proof_copy_ext(const u64* src, size_t src_batch_stride, size_t comp_stride, u32 count, uint8_t* proofs, size_t proof_bytes, size_t dst_off) {
-    u32 i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= count) return;
-    const u64* s = src + (size_t)blockIdx.y * src_batch_stride;
-    uint8_t* d = proofs + (size_t)blockIdx.y * proof_bytes + dst_off + 16 * (size_t)i;
-    store_u64_bytes(d, s[i]);
-    store_u64_bytes(d + 8, s[comp_stride + i]);
-}
-
 // dst[i] (extension) = src[map[i]]
 __global__ void k_gather_ext(const u64* src, size_t src_batch_stride, const u32* map, u32 count, u64* dst, size_t dst_batch_stride) {
     u32 i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -590,16 +531,8 @@ __global__ void k_gather_ext(const u64* src, size_t src_batch_stride, const u32*
     d[0] = s[0];
     d[1] = s[1];
 }
-__global__ void k_proof_gather_ext(const u64* src, size_t src_batch_stride, const u32* map, u32 count, uint8_t* proofs, size_t proof_bytes, size_t dst_off) {
-    u32 i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= count) return;
-    const u64* s = src + (size_t)blockIdx.y * src_batch_stride + 2 * (size_t)map[i];
-    uint8_t* d = proofs + (size_t)blockIdx.y * proof_bytes + dst_off + 16 * (size_t)i;
-    store_u64_bytes(d, s[0]);
-    store_u64_bytes(d + 8, s[1]);
-}
 // Every fixed-position piece of the proof -- the caps, the opening set, the final polynomial, the PoW witness -- in ONE launch
-// (round 2: nine launches of the three kernels above).  blockIdx.z = piece.
+// (round 2: nine launches of three copy kernels).  blockIdx.z = piece.
 struct ProofSeg {
     const u64* src;
     const u32* map;       // kind 2: gather map

@@ -117,11 +117,6 @@ struct p2_circuit {
     // phase timing of the host path on stderr
     size_t opt_chunk = 128, opt_streams = 2;
     std::map<const u64*, u64*> pass1_out_tw;  // two-pass NTT: output-twiddle table per full twiddle table (ensure_pass1_table)
-    bool opt_merkle_top = true;               // P2AES_MERKLE_TOP=0: every level its own launch (A/B measurements)
-    int opt_pass1_waves = 4;                  // P2AES_PASS1_WAVES=2: the 178-register, scratch-free build of the pass-1 kernel (A/B measurements)
-    bool opt_quotient_two_walks = false;      // P2AES_QUOTIENT_TWO_WALKS: round 2's form of the quotient kernel (A/B measurements)
-    bool opt_pass1_noswizzle = false;         // P2AES_PASS1_NOSWIZZLE: pass-1 workgroups in launch order (A/B measurements)
-    bool opt_pass1_radix2 = false;            // P2AES_PASS1_RADIX2: the round-2 pass-1 kernel (A/B measurements)
     // Longest chain of the witness schedule (P2AES_WITNESS_FUSE at load, 1..8).  Default 1 = no chains: measured on the 64 KiB
     // circuit, chains of 8 cut the levels from 12.4 k to 2.6 k and change nothing (73 vs 66 ms per 16 witnesses, 17.4 vs 17.6
     // proofs/s) -- the kernel is bound by one compute unit's address path, not by its depth -- and the chain executor costs
@@ -198,6 +193,16 @@ static int run_ntt(p2_circuit* C, const char* name, NttArgs a, u32 cols, u32 bat
     return 0;
 }
 static const u32 LDS_NTT_MAX_BITS = 14;  // whole transform in one workgroup's LDS up to 2^14 points
+// The NTT kernels are launched with more dynamic LDS than the default limit allows (p2_circuit_load, PrimCtx::init).
+static hipError_t raise_ntt_lds_limits() {
+    const std::pair<const void*, int> limits[] = {{(const void*)k_ntt_lds, 128 * 1024},
+                                                  {(const void*)k_ntt_r16<false>, (int)r16_lds_bytes(LDS_NTT_MAX_BITS)},
+                                                  {(const void*)k_ntt_r16<true>, (int)r16_lds_bytes(LDS_NTT_MAX_BITS - 1)},
+                                                  {(const void*)k_ntt_pass1_r16, 64 * 1024}};
+    for (const auto& l : limits)
+        if (hipError_t e = hipFuncSetAttribute(l.first, hipFuncAttributeMaxDynamicSharedMemorySize, l.second)) return e;
+    return hipSuccess;
+}
 // The output twiddles of pass 1 for the order-2^logn table `tw_full`, in output order (k_pass1_out_tw); built at load, never
 // while workspaces are open (allocations made then belong to the workspaces).
 static int ensure_pass1_table(p2_circuit* C, const u64* tw_full, u32 logn) {
@@ -235,14 +240,9 @@ static int ntt_big(p2_circuit* C, const char* name, const u64* in, u64* out, con
     auto it = C->pass1_out_tw.find(tw_full);
     if (it == C->pass1_out_tw.end()) return set_error("internal: no pass-1 twiddle table for this transform"), P2_ERR_INVALID;
     a.out_tw = it->second;
-    a.xcd_swizzle = (cosets > 1 && !in_coset_blocks && !C->opt_pass1_noswizzle) ? 1 : 0;  // only where workgroups share their input
+    a.xcd_swizzle = (cosets > 1 && !in_coset_blocks) ? 1 : 0;  // only where workgroups share their input
     const std::string name1 = std::string(name) + "_pass1";  // the two passes are timed apart
-    if (C->opt_pass1_radix2)
-        LAUNCH(C, name1, k_ntt_pass1, dim3(tiles * cols * cosets, batch), dim3(256), (size_t)8 << 12, a);
-    else if (C->opt_pass1_waves == 2)
-        LAUNCH(C, name1, k_ntt_pass1_r16<2>, dim3(tiles * cols * cosets, batch), dim3(256), r16_lds_bytes(12), a);
-    else
-        LAUNCH(C, name1, k_ntt_pass1_r16<4>, dim3(tiles * cols * cosets, batch), dim3(256), r16_lds_bytes(12), a);
+    LAUNCH(C, name1, k_ntt_pass1_r16, dim3(tiles * cols * cosets, batch), dim3(256), r16_lds_bytes(12), a);
     // pass 2: every row of n2 contiguous points, in place
     if (out_col_stride != ((size_t)cosets << logn)) return set_error("internal: two-pass NTT needs densely packed output blocks"), P2_ERR_INVALID;
     NttArgs b{};
@@ -325,7 +325,7 @@ static int merkle_levels(p2_circuit* C, Tree& t, u32 batch) {
     // the waves of a fused walk stay resident for all its levels and slow each other down, where separately launched levels
     // shrink to one wave per SIMD as they narrow (measured per 128-proof chunk: nine levels in 256-thread workgroups + 3.3 ms,
     // seven levels in one wave + 1.3 ms against 21.1 ms).  Launch count does not matter there: the chip is busy throughout.
-    const u32 fused = (C->opt_merkle_top && batch <= 16) ? std::min<u32>(levels, 9) : 0;
+    const u32 fused = batch <= 16 ? std::min<u32>(levels, 9) : 0;
     const u32 top_threads = 256;
     const size_t leaves = (size_t)1 << t.bits;
     for (u32 l = 0; l < levels - fused; l++) {
@@ -860,10 +860,7 @@ static int prove_chunk(p2_circuit* C, u32 B, u32 n_inputs, const u64* d_values, 
             LAUNCH(C, "alpha_pows", k_alpha_pows, g1(2 * B, 64), dim3(64), 0, C->cur->d_chal, C->cur->d_apow, B, nterms);
         }
         if (c.poseidon_rows.empty())
-            if (C->opt_quotient_two_walks)
-                LAUNCH(C, "quotient", (k_quotient<false, false>), g1(N, 256, B), dim3(256), 0, a);
-            else
-                LAUNCH(C, "quotient", (k_quotient<false, true>), g1(N, 256, B), dim3(256), 0, a);  // the wire columns read once
+            LAUNCH(C, "quotient", (k_quotient<false, true>), g1(N, 256, B), dim3(256), 0, a);  // the wire columns read once
         else
             LAUNCH(C, "quotient", k_quotient<true>, g1(N, 256, B), dim3(256), 0, a);
         // coset-wise inverse transform: residues r_j, then the 8-point cross-coset DFT
@@ -1419,11 +1416,6 @@ p2_circuit* p2_circuit_load(const uint8_t* blob, size_t len, int device) {
         // environment defaults for the options, read once here (never per call)
         if (const char* e = getenv("P2AES_CHUNK")) C->opt_chunk = (size_t)std::max(1, atoi(e));
         if (const char* e = getenv("P2AES_STREAMS")) C->opt_streams = (size_t)std::min(8, std::max(1, atoi(e)));
-        C->opt_pass1_radix2 = getenv("P2AES_PASS1_RADIX2") != nullptr;
-        C->opt_pass1_noswizzle = getenv("P2AES_PASS1_NOSWIZZLE") != nullptr;
-        C->opt_quotient_two_walks = getenv("P2AES_QUOTIENT_TWO_WALKS") != nullptr;
-        if (const char* e = getenv("P2AES_PASS1_WAVES")) C->opt_pass1_waves = atoi(e) == 2 ? 2 : 4;
-        if (const char* e = getenv("P2AES_MERKLE_TOP")) C->opt_merkle_top = atoi(e) != 0;
         if (const char* e = getenv("P2AES_WITNESS_FUSE")) C->opt_witness_fuse = (u32)std::min(1024, std::max(1, atoi(e)));
         C->opt_debug_timing = getenv("P2AES_DEBUG_TIMING") != nullptr;
         if (const char* e = getenv("P2AES_TEST_FAIL_ALLOC_AFTER")) C->fail_alloc_after = atol(e);
@@ -1431,14 +1423,7 @@ p2_circuit* p2_circuit_load(const uint8_t* blob, size_t len, int device) {
         if (hipSetDevice(device) != hipSuccess) throw std::runtime_error("hipSetDevice failed");
         if (hipStreamCreate(&C->stream) != hipSuccess) throw std::runtime_error("hipStreamCreate failed");
         if (hipEventCreateWithFlags(&C->ev_witness, hipEventDisableTiming) != hipSuccess) throw std::runtime_error("hipEventCreate failed");
-        if (hipFuncSetAttribute((const void*)k_ntt_lds, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024) != hipSuccess ||
-            hipFuncSetAttribute((const void*)k_ntt_r16<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)r16_lds_bytes(14)) != hipSuccess ||
-            hipFuncSetAttribute((const void*)k_ntt_r16<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)r16_lds_bytes(13)) != hipSuccess)
-            throw std::runtime_error("cannot raise the dynamic LDS limit for the NTT kernels");
-        if (hipFuncSetAttribute((const void*)k_ntt_pass1, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024) != hipSuccess ||
-            hipFuncSetAttribute((const void*)k_ntt_pass1_r16<2>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024) != hipSuccess ||
-            hipFuncSetAttribute((const void*)k_ntt_pass1_r16<4>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024) != hipSuccess)
-            throw std::runtime_error("cannot set the dynamic LDS limit of the pass-1 NTT");
+        if (raise_ntt_lds_limits() != hipSuccess) throw std::runtime_error("cannot raise the dynamic LDS limit for the NTT kernels");
         // opening maps
         const u32 np = c.num_preprocessed(), W = c.cfg.num_wires, zc = c.num_zs_cols(), qc = c.num_quotient_cols(), NC = c.cfg.num_challenges;
         const u32 ncc = c.num_constants_cols(), nzpp = c.num_zs_pp();
@@ -1982,9 +1967,7 @@ struct PrimCtx {
         C.lde_bits = C.logn + 3;
         C.N = C.n << 3;
         HIPCHECK(hipStreamCreate(&C.stream));
-        HIPCHECK(hipFuncSetAttribute((const void*)k_ntt_lds, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
-        HIPCHECK(hipFuncSetAttribute((const void*)k_ntt_r16<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)r16_lds_bytes(14)));
-        HIPCHECK(hipFuncSetAttribute((const void*)k_ntt_r16<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)r16_lds_bytes(13)));
+        HIPCHECK(raise_ntt_lds_limits());
         size_t n = C.n;
         std::vector<u64> twf(n), twi(n);
         u64 w = gl::root_of_unity(degree_bits), wi = gl::inv(w), x = 1, xi = 1;
@@ -1998,10 +1981,6 @@ struct PrimCtx {
         C.d_tw_fwd = C.d_tw_fwd_full;
         C.d_tw_inv = C.d_tw_inv_full;
         if (ensure_pass1_table(&C, C.d_tw_fwd_full, (u32)degree_bits) || ensure_pass1_table(&C, C.d_tw_inv_full, (u32)degree_bits)) return P2_ERR_HIP;
-        C.opt_pass1_radix2 = getenv("P2AES_PASS1_RADIX2") != nullptr;
-        if (const char* e = getenv("P2AES_PASS1_WAVES")) C.opt_pass1_waves = atoi(e) == 2 ? 2 : 4;
-        HIPCHECK(hipFuncSetAttribute((const void*)k_ntt_pass1_r16<2>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
-        HIPCHECK(hipFuncSetAttribute((const void*)k_ntt_pass1_r16<4>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
         std::vector<u64> bases(8);
         u64 wl = gl::root_of_unity(degree_bits + 3);
         for (u32 j = 0; j < 8; j++) bases[j] = gl::mul(gl::MULT_GEN, gl::pow(wl, j));

@@ -539,23 +539,20 @@ def test_options_change_scheduling_not_proofs(gpu):
 
 
 def test_schedule_switches_change_scheduling_not_proofs(gpu, monkeypatch):
-    """Round 3's load-time choices -- the witness schedule (no chains by default, or chains of up to 8 lookup-free ops on the critical path), the
-    fused Merkle top with its cooperative narrow levels (batches <= 16 only), the register-blocked first NTT pass -- must not
-    show in a single proof byte: the same 20 witnesses through a default handle (batch 20: one launch per Merkle level) and, one
-    by one and in small batches, through handles loaded with every switch flipped."""
+    """The witness schedule (no chains by default, or chains of up to 8 lookup-free ops on the critical path, chosen at load)
+    and the fused Merkle top with its cooperative narrow levels (batches <= 16 only) must not show in a single proof byte: the
+    same 20 witnesses through a default handle (batch 20: one launch per Merkle level) and, one by one and in small batches,
+    through handles loaded with chains of 8 and of 4."""
     data, pws, _ = circuits.encrypt(gpu, 4, 64, False, keys=[(bytes([i] * 16), bytes([i + 1] * 12), bytes((7 * i + j) & 0xFF for j in range(64))) for i in range(20)])
     ref, st = data.prove_batch(pws)
     assert st == [0] * 20 and len(set(ref)) == 20
     small, st = data.prove_batch(pws[:3])                       # batch <= 16: fused Merkle top
     assert st == [0] * 3 and small == ref[:3]
-    for env in ({"P2AES_WITNESS_FUSE": "8"}, {"P2AES_WITNESS_FUSE": "4", "P2AES_MERKLE_TOP": "0"}, {"P2AES_PASS1_RADIX2": "1", "P2AES_PASS1_NOSWIZZLE": "1"},
-                {"P2AES_PASS1_WAVES": "2", "P2AES_QUOTIENT_TWO_WALKS": "1"}):
-        for k, v in env.items():
-            monkeypatch.setenv(k, v)
+    for fuse in ("8", "4"):
+        monkeypatch.setenv("P2AES_WITNESS_FUSE", fuse)
         other = gpu.CircuitData(data.blob)
-        other.gpu()                                             # the switches are read when the handle is loaded
-        for k in env:
-            monkeypatch.delenv(k)
+        other.gpu()                                             # the schedule is built when the handle is loaded
+        monkeypatch.delenv("P2AES_WITNESS_FUSE")
         assert other.prove(pws[5]) == ref[5]
         got, st = other.prove_batch(pws[:18])
         assert st == [0] * 18 and got == ref[:18]
