@@ -169,9 +169,11 @@ pub mod plonk {
             pub fn standard_recursion_zk_config() -> Self { CircuitConfig { zero_knowledge: true } }
         }
 
-        /// Serialised proof exactly as the device writes it ("Proof layout").
+        /// Serialised proof exactly as the device writes it ("Proof layout"), and the values of the circuit's
+        /// public inputs in registration order, parsed from the proof's trailer (empty for a circuit without any).
         pub struct ProofWithPublicInputs<F, C, const D: usize> {
             pub bytes: Vec<u8>,
+            pub public_inputs: Vec<F>,
             pub(crate) _p: PhantomData<(F, C)>,
         }
         impl<F, C, const D: usize> ProofWithPublicInputs<F, C, D> {
@@ -183,6 +185,7 @@ pub mod plonk {
             pub(crate) handle: *mut ffi::P2Circuit,
             pub(crate) blob: Vec<u8>,
             pub(crate) verifier_data: Vec<u64>,
+            pub(crate) num_public_inputs: usize,   // read once at build: every proof of the circuit has this many
             pub(crate) _p: PhantomData<(F, C)>,
         }
         // `prove(&self)` takes a shared reference and the handle serialises its own enqueues (include/p2aes.h).
@@ -210,12 +213,27 @@ pub mod plonk {
                 let rc = unsafe { ffi::p2_prove_batch(self.handle, pws.len(), asg.as_ptr(), bytes.as_mut_ptr(), status.as_mut_ptr()) };
                 if rc != ffi::P2_OK { return Err(last_error()); }
                 Ok(status.iter().enumerate().map(|(i, st)| match *st {
-                    0 => Ok(ProofWithPublicInputs { bytes: bytes[i * pb..(i + 1) * pb].to_vec(), _p: PhantomData }),
+                    0 => {
+                        let proof = bytes[i * pb..(i + 1) * pb].to_vec();
+                        let public_inputs = self.parse_public_inputs(&proof)?;
+                        Ok(ProofWithPublicInputs { bytes: proof, public_inputs, _p: PhantomData })
+                    }
                     1 => Err(anyhow::anyhow!("witness generation failed: conflicting value or lookup input not in table")),
                     2 => Err(anyhow::anyhow!("witness generation failed: a generator never ran (an input target was not set)")),
                     3 => Err(anyhow::anyhow!("Opening point is in the subgroup.")),
                     s => Err(anyhow::anyhow!("prove failed with status {s}")),
                 }).collect())
+            }
+            /// The public-input trailer of a proof of this circuit: u64 k || k values, the last 8 (k + 1) bytes (none for k = 0).
+            /// Reads those bytes only, so it costs O(k) per proof of a batch.
+            fn parse_public_inputs(&self, proof: &[u8]) -> anyhow::Result<Vec<F>> {
+                let k = self.num_public_inputs;
+                if k == 0 { return Ok(Vec::new()); }
+                anyhow::ensure!(proof.len() >= 8 * (k + 1), "proof shorter than its public-input trailer");
+                let t = &proof[proof.len() - 8 * (k + 1)..];
+                let word = |i: usize| u64::from_le_bytes(t[8 * i..8 * i + 8].try_into().unwrap());
+                anyhow::ensure!(word(0) == k as u64, "wrong number of public inputs");
+                Ok((1..=k).map(|i| F::from_canonical_u64(word(i))).collect())
             }
             /// circuit_gcm.rs:782 (19 sites).
             pub fn verify(&self, proof: ProofWithPublicInputs<F, C, D>) -> anyhow::Result<()> {
@@ -265,6 +283,12 @@ pub mod plonk {
                 Target(unsafe { ffi::p2_builder_select(self.h, b.target.0, x.0, y.0) })
             }
             pub fn connect(&mut self, x: Target, y: Target) { unsafe { ffi::p2_builder_connect(self.h, x.0, y.0) } }              // :163
+            /// `register_public_input`: every proof carries the target's value (ProofWithPublicInputs::public_inputs).
+            pub fn register_public_input(&mut self, t: Target) {
+                let rc = unsafe { ffi::p2_builder_register_public_input(self.h, t.0) };
+                assert!(rc == ffi::P2_OK, "{}", last_error());
+            }
+            pub fn register_public_inputs(&mut self, ts: &[Target]) { for &t in ts { self.register_public_input(t) } }
             /// circuit_aes.rs:300,317,334; circuit_gcm.rs:396,415.  `(u16, u16)` is two adjacent u16 in memory.
             pub fn add_lookup_table_from_pairs(&mut self, table: Arc<Vec<(u16, u16)>>) -> usize {
                 // (u16, u16) has no guaranteed layout (repr(Rust)): flatten to the [in, out, in, out, ...] array the C ABI reads
@@ -302,7 +326,8 @@ pub mod plonk {
                 let rc = unsafe { ffi::p2_circuit_verifier_data(handle, vd.as_mut_ptr(), vd.len(), &mut n) };
                 assert!(rc == ffi::P2_OK, "{}", last_error());
                 vd.truncate(n);
-                CircuitData { handle, blob, verifier_data: vd, _p: PhantomData }
+                let num_public_inputs = unsafe { ffi::p2_circuit_num_public_inputs(handle) };
+                CircuitData { handle, blob, verifier_data: vd, num_public_inputs, _p: PhantomData }
             }
         }
     }

@@ -84,6 +84,11 @@ p2_target p2_builder_mul(p2_builder*, p2_target x, p2_target y);
 p2_target p2_builder_select(p2_builder*, p2_target b, p2_target x, p2_target y); /* if b {x} else {y} */
 p2_target p2_builder_is_equal(p2_builder*, p2_target x, p2_target y);
 void p2_builder_connect(p2_builder*, p2_target x, p2_target y);
+/* CircuitBuilder::register_public_input: the target's value becomes public input number (calls so far); duplicates allowed.
+ * build() hashes the public inputs in the circuit (hash_n_to_hash_no_pad) into the PublicInputGate, and every proof of the
+ * circuit ends with the trailer u64 k || k x u64 value.  A circuit with none is built exactly as before.  P2_ERR_INVALID
+ * for a target the builder never handed out. */
+int p2_builder_register_public_input(p2_builder*, p2_target t);
 /* pairs = n_pairs * (input u16, output u16); returns the LUT index (an identical table is re-used) */
 size_t p2_builder_add_lookup_table_from_pairs(p2_builder*, const uint16_t* pairs, size_t n_pairs);
 /* returns the looked-up output target; (size_t)-1 lut index is an error -> returns UINT64_MAX */
@@ -204,8 +209,9 @@ void p2_native_aes_gcm_encrypt(const uint8_t* key, int nk, int nr, const uint8_t
 typedef struct {
     uint32_t degree_bits, num_wires, num_routed_wires, num_constants_cols, num_zs_cols, num_quotient_cols, num_luts,
         num_ops, num_levels, num_slots, num_virtual_targets, num_fri_rounds;
-    uint64_t proof_bytes; /* exact serialised proof size */
+    uint64_t proof_bytes; /* exact serialised proof size, public-input trailer included */
     uint32_t zero_knowledge, num_gate_kinds; /* standard_recursion_zk_config(); distinct gate types in the circuit */
+    uint32_t num_public_inputs; /* targets registered with p2_builder_register_public_input */
 } p2_circuit_info;
 int p2_blob_info(const uint8_t* blob, size_t len, p2_circuit_info* out);
 /* The device-side schedule of a compiled circuit's witness program for macro size `fuse` (csrc/witness_schedule.h; the prover
@@ -217,6 +223,12 @@ int p2_witness_schedule_check(const uint8_t* blob, size_t len, uint32_t fuse, ui
 /* verifier_data = constants_sigmas_cap (16 digests) || circuit_digest, 68 u64 -- from p2_circuit_verifier_data */
 int p2_verify(const uint8_t* blob, size_t blob_len, const uint64_t* verifier_data, size_t verifier_data_len,
               const uint8_t* proof, size_t proof_len);
+/* ProofWithPublicInputs::public_inputs: the k values of the proof's public-input trailer (k = num_public_inputs of the
+ * circuit; *n_written = k, 0 for a circuit without public inputs).  P2_ERR_INVALID if proof_len is not the circuit's
+ * proof size, the count word is not k, or cap < k.  Parsing only: p2_verify checks that the values are the proven ones.
+ * Parses the whole blob on every call; with a loaded handle, p2_circuit_public_inputs reads the trailer alone. */
+int p2_proof_public_inputs(const uint8_t* blob, size_t blob_len, const uint8_t* proof, size_t proof_len, uint64_t* out, size_t cap,
+                           size_t* n_written);
 
 /* ------------------------------------------------------------------ GPU prover */
 typedef struct p2_circuit p2_circuit;
@@ -238,6 +250,10 @@ size_t p2_circuit_chunk_proofs(p2_circuit*);
 int p2_circuit_set_zk_key(p2_circuit*, const uint64_t key[4]);
 int p2_circuit_set_zk_seed(p2_circuit*, uint64_t seed);
 size_t p2_circuit_proof_bytes(const p2_circuit*);
+/* Public inputs of a loaded circuit: their number, and p2_proof_public_inputs on the handle -- it reads only the proof's
+ * trailer (O(k)), so it is the form to call once per proof of a batch. */
+size_t p2_circuit_num_public_inputs(const p2_circuit*);
+int p2_circuit_public_inputs(const p2_circuit*, const uint8_t* proof, size_t proof_len, uint64_t* out, size_t cap, size_t* n_written);
 /* One PartialWitness: (target, value) pairs, values canonical (< p). */
 typedef struct {
     const p2_target* targets;
@@ -310,7 +326,8 @@ int p2_gpu_intt(const uint64_t* values, size_t cols, int degree_bits, uint64_t* 
 /* column-major leaves [cols][num_leaves] -> cap digests (2^cap_height * 4 u64) */
 int p2_gpu_merkle_cap(const uint64_t* cols_major, size_t cols, size_t num_leaves, int cap_height, uint64_t* cap, int device);
 /* debug: copy a named intermediate buffer of proof `index` of the last batch to the host
- * ("wires", "wires_cap", "zs", "zs_cap", "quotient_coeffs", "quotient_cap", "challenges", "openings", ...) */
+ * ("wires", "wires_cap", "zs", "zs_cap", "quotient_coeffs", "quotient_cap", "challenges", "openings",
+ * "public_inputs_hash", ...) */
 int p2_circuit_debug_read(p2_circuit*, const char* name, size_t index, uint64_t* out, size_t cap, size_t* n_written);
 
 #ifdef __cplusplus

@@ -14,6 +14,7 @@ PyTorch is not needed here; `prove_batch_device` accepts raw device pointers (e.
 """
 import ctypes as C
 import os
+import struct
 
 P = 0xFFFFFFFF00000001
 
@@ -50,6 +51,7 @@ VERIFY_REASONS = {
     "FRI fold consistency check failed.": VERIFY_FRI_FOLD,
     "Invalid Merkle proof (FRI round).": VERIFY_MERKLE_FRI,
     "Final polynomial evaluation is invalid.": VERIFY_FINAL_POLY,
+    "wrong number of public inputs": VERIFY_SHAPE,
 }
 
 u32p = C.POINTER(C.c_uint32)
@@ -67,7 +69,8 @@ class _Info(C.Structure):
     _fields_ = [(n, C.c_uint32) for n in ("degree_bits", "num_wires", "num_routed_wires", "num_constants_cols", "num_zs_cols",
                                            "num_quotient_cols", "num_luts", "num_ops", "num_levels", "num_slots",
                                            "num_virtual_targets", "num_fri_rounds")] + [("proof_bytes", C.c_uint64), ("zero_knowledge", C.c_uint32),
-                                                                                      ("num_gate_kinds", C.c_uint32)]
+                                                                                      ("num_gate_kinds", C.c_uint32),
+                                                                                      ("num_public_inputs", C.c_uint32)]
 
 
 class _Assignment(C.Structure):
@@ -102,6 +105,8 @@ def lib():
         "p2_builder_add": (u64, [vp, u64, u64]), "p2_builder_sub": (u64, [vp, u64, u64]), "p2_builder_mul": (u64, [vp, u64, u64]),
         "p2_builder_select": (u64, [vp, u64, u64, u64]), "p2_builder_is_equal": (u64, [vp, u64, u64]),
         "p2_builder_connect": (None, [vp, u64, u64]),
+        "p2_builder_register_public_input": (C.c_int, [vp, u64]),
+        "p2_proof_public_inputs": (C.c_int, [C.c_char_p, sz, C.c_char_p, sz, u64p, sz, C.POINTER(sz)]),
         "p2_builder_add_lookup_table_from_pairs": (sz, [vp, u16p, sz]),
         "p2_builder_add_lookup_from_index": (u64, [vp, u64, sz]),
         "p2_builder_num_gates": (sz, [vp]),
@@ -155,6 +160,8 @@ def lib():
         "p2_circuit_load": (vp, [C.c_char_p, sz, C.c_int]), "p2_circuit_free": (None, [vp]),
         "p2_circuit_verifier_data": (C.c_int, [vp, u64p, sz, C.POINTER(sz)]),
         "p2_circuit_proof_bytes": (sz, [vp]),
+        "p2_circuit_num_public_inputs": (sz, [vp]),
+        "p2_circuit_public_inputs": (C.c_int, [vp, C.c_char_p, sz, u64p, sz, C.POINTER(sz)]),
         "p2_circuit_chunk_proofs": (sz, [vp]),
         "p2_prove_batch": (C.c_int, [vp, sz, C.POINTER(_Assignment), C.c_char_p, C.POINTER(C.c_int)]),
         "p2_prove_batch_device": (C.c_int, [vp, sz, u64p, sz, vp, vp, vp, vp]),
@@ -215,6 +222,15 @@ class CircuitBuilder:
     def select(self, b, x, y): return lib().p2_builder_select(self._h, b, x, y)
     def is_equal(self, x, y): return lib().p2_builder_is_equal(self._h, x, y)
     def connect(self, x, y): lib().p2_builder_connect(self._h, x, y)
+
+    def register_public_input(self, t):
+        """CircuitBuilder::register_public_input: every proof carries the target's value (in registration order)."""
+        if lib().p2_builder_register_public_input(self._h, t):
+            raise P2Error(_err())
+
+    def register_public_inputs(self, ts):
+        for t in ts:
+            self.register_public_input(t)
 
     def add_lookup_table_from_pairs(self, pairs):
         flat = (C.c_uint16 * (2 * len(pairs)))(*[v for p in pairs for v in p])
@@ -416,6 +432,22 @@ class CircuitData:
 
     @property
     def proof_bytes(self): return self.info["proof_bytes"]
+
+    @property
+    def num_public_inputs(self): return self.info["num_public_inputs"]
+
+    def public_inputs(self, proof):
+        """ProofWithPublicInputs::public_inputs: the values of the proof's public-input trailer, u64 k || k values (parsing
+        only; verify() checks that they are the ones the proof is about).  Reads the trailer alone: O(k) per proof."""
+        k, pb = self.num_public_inputs, self.proof_bytes
+        if len(proof) != pb:
+            raise P2Error("proof length differs from the circuit's proof size")
+        if k == 0:
+            return []
+        words = struct.unpack_from("<%dQ" % (k + 1), proof, pb - 8 * (k + 1))
+        if words[0] != k:
+            raise P2Error("wrong number of public inputs")
+        return list(words[1:])
 
     def witness_schedule(self, fuse=8):
         """Host-side check of the device's witness schedule for macro size `fuse` (csrc/witness_schedule.h):

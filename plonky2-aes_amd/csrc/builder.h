@@ -69,6 +69,14 @@ class CircuitBuilder {
 
     void connect(Target x, Target y) { copy_constraints_.push_back({x, y}); }
 
+    // plonky2 CircuitBuilder::register_public_input: the proof carries the target's value, in registration order
+    void register_public_input(Target t) {
+        const bool known = is_wire(t) ? (wire_row(t) < gate_instances_.size() && wire_col(t) < cfg_.num_routed_wires) : t < num_virtual_;
+        if (!known) throw std::runtime_error("register_public_input: no such target (or a wire that is not routed)");
+        public_inputs_.push_back(t);
+    }
+    size_t num_public_inputs() const { return public_inputs_.size(); }
+
     size_t num_gates() const { return gate_instances_.size(); }
 
     // ---- arithmetic (plonky2 gadgets/arithmetic.rs) -----------------------------------------------
@@ -274,6 +282,7 @@ class CircuitBuilder {
     std::vector<LookupRows> lookup_rows_;
     std::vector<std::pair<u32, u32>> constant_generators_;  // (row, index)
     std::vector<Gen> gens_;
+    std::vector<Target> public_inputs_;
 };
 
 // Adds, per LUT: LookupGate rows for the looking pairs, then the LookupTableGate rows (stored upside down),
@@ -309,14 +318,20 @@ inline Circuit CircuitBuilder::build() {
     c.cfg = cfg_;
     const u32 R = cfg_.num_routed_wires;
 
-    // Public inputs: the reference registers none (grep register_public_input -> 0 hits), so the public-input
-    // hash is hash_no_pad([]) = 0^4 and needs no PoseidonGate; route four zero constants to a PublicInputGate.
+    // Public inputs.  Without any (the reference registers none) the public-input hash is hash_no_pad([]) = 0^4 and needs
+    // no PoseidonGate: four zero constants go to the PublicInputGate, and the circuit is what it was before public inputs
+    // existed.  With some, as upstream: public_inputs_hash = hash_n_to_hash_no_pad(public_inputs) in the circuit (one
+    // PoseidonGate row per 8 inputs), its four elements connected to the gate's wires 0..3.
     // Upstream also attaches RandomValueGenerators to the gate's unused wires (randomize_unused_pi_wires);
     // here those wires stay 0 so that proofs are reproducible.
-    {
+    if (public_inputs_.empty()) {
         Target z = zero();
         u32 pi_gate = add_gate(G_PUBLIC_INPUT);
         for (u32 i = 0; i < 4; i++) connect(z, wire_target(pi_gate, i));
+    } else {
+        std::vector<Target> h = hash_n_to_m_no_pad(public_inputs_, 4);
+        u32 pi_gate = add_gate(G_PUBLIC_INPUT);
+        for (u32 i = 0; i < 4; i++) connect(h[i], wire_target(pi_gate, i));
     }
     add_all_lookups();
     while (constants_to_targets_.size() > constant_generators_.size()) add_gate(G_CONSTANT);
@@ -557,6 +572,7 @@ inline Circuit CircuitBuilder::build() {
     }
     c.vt_slot.resize(V);
     for (u64 v = 0; v < V; v++) c.vt_slot[v] = (int32_t)slot((Target)v);
+    for (Target t : public_inputs_) c.pi_slots.push_back(slot(t));  // routed PoseidonGate inputs: every one has a slot already
     c.num_slots = num_slots;
     c.wire_slot.resize((size_t)R * n);
     for (u64 idx = 0; idx < (u64)R * n; idx++) {

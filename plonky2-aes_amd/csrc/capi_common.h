@@ -34,10 +34,31 @@ inline size_t proof_words(const Circuit& c, size_t* n_merkle_proofs) {
     if (n_merkle_proofs) *n_merkle_proofs = mp * c.cfg.num_query_rounds;
     return w;
 }
-inline size_t proof_bytes(const Circuit& c) {
+// Public-input trailer after the PoW witness, only for a circuit with k >= 1 public inputs: u64 k || k x u64 value
+// (plonky2 writes the public inputs as a field vector after the proof).  Zero-PI proofs have none: their layout is unchanged.
+inline size_t pi_trailer_bytes(const Circuit& c) { return c.pi_slots.empty() ? 0 : 8 * (1 + c.pi_slots.size()); }
+// byte size of the proof up to and including the PoW witness: where the trailer starts
+inline size_t proof_body_bytes(const Circuit& c) {
     size_t mp;
     size_t w = proof_words(c, &mp);
     return 8 * w + mp;  // one u8 length prefix per Merkle proof
+}
+inline size_t proof_bytes(const Circuit& c) { return proof_body_bytes(c) + pi_trailer_bytes(c); }
+// ProofWithPublicInputs::public_inputs: the trailer of one proof of `c`, whose size is `pbytes` = proof_bytes(c).  O(k):
+// reads the last 8 (k + 1) bytes only.  *n_written = k (0 without public inputs).
+inline int read_public_inputs(const Circuit& c, size_t pbytes, const uint8_t* proof, size_t proof_len, uint64_t* out, size_t cap,
+                              size_t* n_written) {
+    const size_t k = c.pi_slots.size();
+    if (n_written) *n_written = k;
+    if (!proof || proof_len != pbytes) return set_error("proof length differs from the circuit's proof size"), P2_ERR_INVALID;
+    if (k == 0) return P2_OK;
+    const uint8_t* t = proof + pbytes - pi_trailer_bytes(c);
+    u64 cnt;
+    memcpy(&cnt, t, 8);
+    if (cnt != k) return set_error("wrong number of public inputs"), P2_ERR_INVALID;
+    if (!out || cap < k) return set_error("output buffer holds fewer than " + std::to_string(k) + " public inputs"), P2_ERR_INVALID;
+    memcpy(out, t + 8, 8 * k);
+    return P2_OK;
 }
 inline void fill_info(const Circuit& c, p2_circuit_info* o) {
     o->degree_bits = c.degree_bits;
@@ -55,5 +76,6 @@ inline void fill_info(const Circuit& c, p2_circuit_info* o) {
     o->proof_bytes = proof_bytes(c);
     o->zero_knowledge = c.cfg.zero_knowledge;
     o->num_gate_kinds = (uint32_t)c.gates.size();
+    o->num_public_inputs = (uint32_t)c.pi_slots.size();
 }
 }  // namespace p2

@@ -72,6 +72,7 @@ p2_target p2_builder_mul(p2_builder* b, p2_target x, p2_target y) { return guard
 p2_target p2_builder_select(p2_builder* b, p2_target c, p2_target x, p2_target y) { return guarded_t([&]() -> p2_target { return b->b.select(BoolTarget{c}, x, y); }); }
 p2_target p2_builder_is_equal(p2_builder* b, p2_target x, p2_target y) { return guarded_t([&]() -> p2_target { return b->b.is_equal(x, y).target; }); }
 void p2_builder_connect(p2_builder* b, p2_target x, p2_target y) { (void)guarded([&] { b->b.connect(x, y); }); }
+int p2_builder_register_public_input(p2_builder* b, p2_target t) { return guarded([&] { b->b.register_public_input(t); }); }
 size_t p2_builder_add_lookup_table_from_pairs(p2_builder* b, const uint16_t* pairs, size_t n) {
     return guarded_sz([&]() -> size_t {
         std::vector<std::pair<u16, u16>> t(n);
@@ -614,6 +615,14 @@ int p2_verify(const uint8_t* blob, size_t blob_len, const uint64_t* vd, size_t v
         std::string err = verify_proof(c, v, proof, proof_len);
         if (!err.empty()) return set_error(err), P2_ERR_VERIFY;
         return P2_OK;
+    } catch (std::exception& e) {
+        return set_error(e.what()), P2_ERR_INVALID;
+    }
+}
+int p2_proof_public_inputs(const uint8_t* blob, size_t blob_len, const uint8_t* proof, size_t proof_len, uint64_t* out, size_t cap, size_t* n_written) {
+    try {
+        Circuit c = deserialize(blob, blob_len);  // the whole blob: p2_circuit_public_inputs is the per-proof form
+        return read_public_inputs(c, proof_bytes(c), proof, proof_len, out, cap, n_written);
     } catch (std::exception& e) {
         return set_error(e.what()), P2_ERR_INVALID;
     }

@@ -122,6 +122,9 @@ struct Circuit {
     // routed wires carry the same random value (copy-constrained), for the Z polynomials
     std::vector<u32> blind_rows;
     std::vector<std::pair<u32, u32>> blind_zrows;
+    // public inputs (register_public_input), in registration order: the witness slot of each target; duplicates allowed.
+    // Empty for a circuit without public inputs, whose blob then ends at blind_zrows exactly as before the section existed.
+    std::vector<u32> pi_slots;
 
     u32 n() const { return 1u << degree_bits; }
     u32 num_selectors() const { return (u32)groups.size(); }
@@ -185,6 +188,10 @@ struct BlobReader {
 
 static const char BLOB_MAGIC[8] = {'P', '2', 'A', 'E', 'S', 'C', 'I', 'R'};
 static const u32 BLOB_VERSION = 4;  // 4: one gate type per lookup table (repeated G_LOOKUP / G_LOOKUP_TABLE entries in `gates`), row-major sigma cycles
+// Optional trailing section of a version-4 blob, written only for a circuit with public inputs: PI_TAG, then pi_slots as a
+// length-prefixed u32 array, then nothing.  A reader of version 4 that stops at blind_zrows still loads such a blob.
+static const u32 BLOB_PI_TAG = 0x49425550u;  // "PUBI"
+static const u64 MAX_PUBLIC_INPUTS = 1u << 24;
 
 static inline std::vector<uint8_t> serialize(const Circuit& c) {
     BlobWriter w;
@@ -212,6 +219,10 @@ static inline std::vector<uint8_t> serialize(const Circuit& c) {
     w.vec(c.poseidon_rows);
     w.vec(c.blind_rows);
     w.vec(c.blind_zrows);
+    if (!c.pi_slots.empty()) {
+        w.w32(BLOB_PI_TAG);
+        w.vec(c.pi_slots);
+    }
     return w.buf;
 }
 
@@ -251,6 +262,14 @@ static inline Circuit deserialize(const void* data, size_t len) {
     r.vec(c.poseidon_rows);
     r.vec(c.blind_rows);
     r.vec(c.blind_zrows);
+    if (r.pos != len) {
+        if (r.r32() != BLOB_PI_TAG) throw std::runtime_error("unknown section after blind_zrows");
+        const u64 k = r.r64();
+        if (k == 0 || k > MAX_PUBLIC_INPUTS || k > (len - r.pos) / 4) throw std::runtime_error("public input count");
+        c.pi_slots.resize(k);
+        r.raw(c.pi_slots.data(), k * 4);
+        if (r.pos != len) throw std::runtime_error("trailing bytes after the public input section");
+    }
     // shape checks: everything a kernel indexes with is validated here, once.
     size_t n = c.n();
     if (c.gates.empty() || c.gates.size() > MAX_GATE_TYPES || c.groups.empty() || c.groups.size() > c.gates.size()) throw std::runtime_error("gate list");
@@ -308,6 +327,8 @@ static inline Circuit deserialize(const void* data, size_t len) {
     for (auto s : c.vt_slot)
         if (s >= (int32_t)c.num_slots) throw std::runtime_error("vt slot range");
     if (c.level_offsets.empty() || c.level_offsets.back() != c.ops.size()) throw std::runtime_error("level offsets");
+    for (u32 s : c.pi_slots)
+        if (s >= c.num_slots) throw std::runtime_error("public input slot range");
     return c;
 }
 

@@ -1232,9 +1232,10 @@ struct ChalArgs {
     u32 aux;              // stage-specific (fri round, #queries, has_lookup)
     u64 mod;              // query index modulus
     const u64* digest;    // circuit digest (stage 0)
+    const u64* pi_hash;   // [batch][4] public-input hash (stage 0; k_pi_hash); null: no public inputs, the hash is 0^4
     int* status;
 };
-// stage 0: init; observe circuit digest, pi hash (0^4), wires cap; betas, gammas, deltas
+// stage 0: init; observe circuit digest, pi hash, wires cap; betas, gammas, deltas
 // stage 1: observe zs cap; alphas            stage 2: observe quotient cap; zeta
 // stage 3: observe openings; fri_alpha       stage 4: observe FRI cap (round aux); beta
 // stage 5: observe final poly                stage 6: observe pow witness; response; query indices
@@ -1252,7 +1253,7 @@ __global__ __launch_bounds__(64) void k_challenger(ChalArgs a) {
         c.w = c.inb = c.outb = 0;
         c.in_len = c.out_len = 0;
         for (int i = 0; i < 4; i++) c.observe(a.digest[i]);
-        for (int i = 0; i < 4; i++) c.observe(0);
+        for (int i = 0; i < 4; i++) c.observe(a.pi_hash ? a.pi_hash[(size_t)p * 4 + i] : 0);
     } else {
         c.load(a.st[p]);
     }
@@ -1301,6 +1302,38 @@ __global__ __launch_bounds__(64) void k_challenger(ChalArgs a) {
         if (writer) ch[CH_FRI_BETAS + 2 * a.aux] = b0, ch[CH_FRI_BETAS + 2 * a.aux + 1] = b1;
     }
     if (real) c.store(a.st[p]);
+}
+
+// Public inputs (circuits with k >= 1 only), once per proof right after the witness: the values of the k public-input slots
+// go into the proof's trailer (u64 k || k x u64, byte `trailer_off` of the proof; byte stores, the offset is not 8-aligned)
+// and hash_no_pad of them -- the sponge of the in-circuit hash_n_to_hash_no_pad, overwrite mode, rate 8 -- into pi_hash for
+// the transcript (k_challenger stage 0) and the PublicInputGate constraint (k_quotient).  The permutations are sequential,
+// one per 8 inputs (130 for a 1 KiB ciphertext with its tag): a 16-lane group per proof runs them cooperatively
+// (glf::poseidon_coop, as DevChallenger).  A failed proof's trailer is zeroed with the rest of its slot by k_finish.
+__global__ __launch_bounds__(64) void k_pi_hash(const u64* __restrict__ values, u32 num_slots, const u32* __restrict__ pi_slots, u32 k, u32 batch,
+                                                u64* __restrict__ pi_hash, uint8_t* __restrict__ proofs, size_t proof_bytes, size_t trailer_off) {
+    const u32 t = blockIdx.x * blockDim.x + threadIdx.x;
+    const bool real = (t >> 4) < batch;
+    const u32 p = real ? (t >> 4) : batch - 1;  // a group past the end replays the last proof without storing
+    const u32 i = t & 15;
+    const u64* v = values + (size_t)p * num_slots;
+    uint8_t* tr = proofs + (size_t)p * proof_bytes + trailer_off;
+    if (real) {
+        for (u32 j = i; j < k; j += 16) {
+            const u64 x = v[pi_slots[j]];
+#pragma unroll
+            for (int b = 0; b < 8; b++) tr[8 + 8 * (size_t)j + b] = (uint8_t)(x >> (8 * b));
+        }
+        if (i == 0)
+#pragma unroll
+            for (int b = 0; b < 8; b++) tr[b] = (uint8_t)((u64)k >> (8 * b));
+    }
+    u64 w = 0;  // this lane's state word; lanes 12..15 stay 0
+    for (u32 off = 0; off < k; off += 8) {
+        if (i < 8 && off + i < k) w = v[pi_slots[off + i]];  // overwrite mode: words past a short last chunk keep the state
+        w = glf::poseidon_coop(w, i);
+    }
+    if (real && i < 4) pi_hash[(size_t)p * 4 + i] = w;
 }
 
 // Proof-of-work grinding: smallest witness w such that the duplex response has >= pow_bits leading zeros.

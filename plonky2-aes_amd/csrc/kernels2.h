@@ -24,6 +24,7 @@ struct QuotientArgs {
     u32 lut_last_row[8];  // last_lut row per LUT: RE there equals get_lut_poly (read from the zs VALUES)
     const u64* zs_values;  // [zs_cols][n]
     size_t zs_values_batch_stride;
+    const u64* pi_hash;    // [batch][4] public-input hash (k_pi_hash); null: no public inputs, the hash is 0^4
 };
 
 // alpha^k for k < count, per proof and challenge: apow[(proof*2 + i)*APOW_STRIDE + k]
@@ -277,7 +278,11 @@ __global__ __launch_bounds__(256, 4) void k_quotient(QuotientArgs a) {
             }
             if (k < 4 && (f_const || f_pi)) w0 = W[(size_t)k * N];
             if (k < 2 && f_const) term = gl::add(term, gl::mul(f_const, gl::sub(k == 0 ? c0 : c1, w0)));
-            if (k < 4 && f_pi) term = gl::add(term, gl::mul(f_pi, w0));
+            if (k < 4 && f_pi) {
+                // PublicInputGate: wire k - h_k, h per proof (blockIdx.y) and k uniform: a scalar load
+                const u64 h = a.pi_hash ? a.pi_hash[(size_t)blockIdx.y * 4 + k] : 0;
+                term = gl::add(term, gl::mul(f_pi, gl::sub(w0, h)));
+            }
             return term;
         };
         if (HAS_POSEIDON) {

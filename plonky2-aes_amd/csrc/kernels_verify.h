@@ -59,6 +59,10 @@ struct VerifyArgs {
     const u32* lut_pairs;    // input | output << 16, LUT after LUT
     const u32* lut_offsets;  // [num_luts + 1]
     const u64* k_is;         // [R]
+    // public inputs (k >= 1 only): the count word's byte offset (compared with num_pi, never unpacked: it is not a field
+    // element) and the values' word index; the transcript leaves hash_no_pad(values) in pi_hash for the vanishing check
+    u32 num_pi, pi_cnt_byte, pi_off;
+    u64* pi_hash;            // [batch][4]
 };
 
 __device__ __forceinline__ u64 vfy_ld_bytes(const uint8_t* p) {
@@ -79,6 +83,7 @@ __global__ __launch_bounds__(256) void k_vfy_unpack(VerifyArgs a) {
         if (v >= gl::P) atomicOr(&a.flags[p], (u32)VF_NONCANON);
     }
     if (i < a.n_cnt && pr[a.cnt_off[i]] != a.cnt_exp[i]) atomicOr(&a.flags[p], (u32)VF_SHAPE);
+    if (i == 0 && a.num_pi && vfy_ld_bytes(pr + a.pi_cnt_byte) != (u64)a.num_pi) atomicOr(&a.flags[p], (u32)VF_SHAPE);  // "wrong number of public inputs"
 }
 
 // ------------------------------------------------------------------------------------------- 2. transcript
@@ -95,7 +100,21 @@ __global__ __launch_bounds__(64) void k_vfy_transcript(VerifyArgs a) {
     const u64* w = a.words + (size_t)p * a.W;
     u64* ch = a.chal + (size_t)p * CH_WORDS;
     for (int i = 0; i < 4; i++) c.observe(a.vd[a.cap_words + i]);  // circuit digest
-    for (int i = 0; i < 4; i++) c.observe(0);                       // hash of zero public inputs
+    if (a.num_pi) {
+        // public_inputs_hash = hash_no_pad(values) on the group's sponge (overwrite mode, rate 8), then observed
+        u64 s = 0;
+        for (u32 off = 0; off < a.num_pi; off += 8) {
+            if (c.i < 8 && off + c.i < a.num_pi) s = w[a.pi_off + off + c.i];
+            s = glf::poseidon_coop(s, c.i);
+        }
+        for (int i = 0; i < 4; i++) {
+            const u64 h = glf::shfl64(s, c.gbase + i);
+            c.observe(h);
+            if (writer) a.pi_hash[(size_t)p * 4 + i] = h;
+        }
+    } else {
+        for (int i = 0; i < 4; i++) c.observe(0);  // hash of zero public inputs
+    }
     for (u32 i = 0; i < a.cap_words; i++) c.observe(w[i]);          // wires cap
     u64 bg[4], dl[4];
     for (int i = 0; i < 4; i++) bg[i] = c.challenge();  // betas, gammas
@@ -365,7 +384,10 @@ __global__ __launch_bounds__(256) void k_vfy_vanishing(VerifyArgs a) {
         } else if (kind == p2::G_CONSTANT) {
             for (u32 k = 0; k < 2; k++) gate[k] = gl::add(gate[k], gl::mul(filter, gl::sub(vfy_e2(w, gc + 2 * k), wire(k))));
         } else if (kind == p2::G_PUBLIC_INPUT) {
-            for (u32 k = 0; k < 4; k++) gate[k] = gl::add(gate[k], gl::mul(filter, wire(k)));
+            for (u32 k = 0; k < 4; k++) {
+                const E2 h = gl::e2(a.num_pi ? a.pi_hash[(size_t)p * 4 + k] : 0);
+                gate[k] = gl::add(gate[k], gl::mul(filter, gl::sub(wire(k), h)));
+            }
         } else if (kind == p2::G_POSEIDON) {
             vfy_poseidon_gate(wire, [&](int k, E2 cst) { gate[k] = gl::add(gate[k], gl::mul(filter, cst)); }, pg_st, pg_tmp);
         }

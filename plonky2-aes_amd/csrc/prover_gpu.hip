@@ -46,6 +46,7 @@ struct Workspace {
     u32* d_mult = nullptr;
     int* d_status = nullptr;
     u64* d_advice = nullptr;
+    u64* d_pi_hash = nullptr;          // [chunk][4] public-input hash per proof (k_pi_hash; circuits with public inputs)
     u64 *d_wires = nullptr, *d_wcoef = nullptr, *d_wlde = nullptr;
     u64 *d_zs = nullptr, *d_zcoef = nullptr, *d_zlde = nullptr, *d_permq = nullptr, *d_perm_seg = nullptr, *d_fri_seg = nullptr, *d_lktmp = nullptr;
     u64 *d_qvals = nullptr, *d_qres = nullptr, *d_qcoef = nullptr, *d_qlde = nullptr;
@@ -78,6 +79,7 @@ struct p2_circuit {
     WChain* d_wchains = nullptr;
     u32 witness_levels = 0, witness_chains = 0;
     int32_t* d_wire_slot = nullptr;
+    u32* d_pi_slots = nullptr;  // witness slot of every public input (circuits with public inputs)
     u64* d_lut_ent = nullptr;
     u32 *d_lut_pairs = nullptr, *d_lut_offsets = nullptr, *d_num_lookups = nullptr;
     LookupRows* d_lookup_rows = nullptr;
@@ -364,6 +366,7 @@ static int challenger(p2_circuit* C, u32 stage, const u64* observe, size_t strid
     a.aux = aux;
     a.mod = mod;
     a.digest = C->d_digest;
+    a.pi_hash = C->c.pi_slots.empty() ? nullptr : C->cur->d_pi_hash;
     a.status = C->cur->d_status;
     LAUNCH(C, "challenger", k_challenger, g1((size_t)batch * 16, 64), dim3(64), 0, a);  // a 16-lane group per proof
     return 0;
@@ -387,6 +390,7 @@ static int circuit_setup(p2_circuit* C) {
         if (upload(C, &C->d_wchains, ws.chains.data(), ws.chains.size())) return P2_ERR_HIP;
     }
     if (upload(C, &C->d_wire_slot, c.wire_slot.data(), c.wire_slot.size())) return P2_ERR_HIP;
+    if (!c.pi_slots.empty() && upload(C, &C->d_pi_slots, c.pi_slots.data(), c.pi_slots.size())) return P2_ERR_HIP;
     {
         // witness generation resolves a lookup with ONE load: input value -> (flat entry index << 16) | output
         std::vector<u64> ent(c.luts.size() * 65536, ~0ull);
@@ -609,6 +613,7 @@ static int build_workspace(p2_circuit* C, Workspace* W, size_t chunk, u32 ws_inp
     WS_ALLOC(W->d_mult, chunk * std::max<size_t>(C->total_lut_entries, 1));
     WS_ALLOC(W->d_status, chunk);
     WS_ALLOC(W->d_advice, chunk * std::max<size_t>(c.poseidon_rows.size(), 1) * 55);
+    WS_ALLOC(W->d_pi_hash, chunk * 4);
     WS_ALLOC(W->d_wires, chunk * act * n);
     WS_ALLOC(W->d_wcoef, chunk * act * n);
     WS_ALLOC(W->d_wlde, chunk * (act + c.salt()) * N);
@@ -742,6 +747,9 @@ static int prove_chunk(p2_circuit* C, u32 B, u32 n_inputs, const u64* d_values, 
         HIPCHECK(hipEventRecord(C->ev_witness, C->cur->stream));
         C->witness_recorded = true;
     }
+    if (!c.pi_slots.empty())
+        LAUNCH(C, "pi_hash", k_pi_hash, g1((size_t)B * 16, 64), dim3(64), 0, C->cur->d_values, c.num_slots, C->d_pi_slots, (u32)c.pi_slots.size(), B,
+               C->cur->d_pi_hash, d_proofs, C->pbytes, proof_body_bytes(c));  // a 16-lane group per proof
     LAUNCH(C, "fill_wires", k_fill_wires, g1((size_t)R * n, 256, B), dim3(256), 0, C->d_wire_slot, C->cur->d_values, C->cur->d_wires, (size_t)R * n, c.num_slots, ws,
            C->cur->d_status);
     if (act > R)
@@ -852,6 +860,7 @@ static int prove_chunk(p2_circuit* C, u32 B, u32 n_inputs, const u64* d_values, 
         for (u32 l = 0; l < c.luts.size(); l++) a.lut_last_row[l] = c.lookup_rows[l].last_lut;
         a.zs_values = C->cur->d_zs;
         a.zs_values_batch_stride = zs_s;
+        a.pi_hash = c.pi_slots.empty() ? nullptr : C->cur->d_pi_hash;
         a.apow = C->cur->d_apow;
         {
             u32 nlk = nlp ? 4 + (u32)c.luts.size() + 2 * nsldc : 0;
@@ -1013,7 +1022,7 @@ static int prove_chunk(p2_circuit* C, u32 B, u32 n_inputs, const u64* d_values, 
         off += 16 * fl;
         segs.s[nseg++] = ProofSeg{C->cur->d_chal + CH_POW, nullptr, (size_t)CH_WORDS, 0, off, 1u, 0};
         off += 8;
-        if (off != pb) return set_error("internal: proof layout size mismatch"), P2_ERR_INVALID;
+        if (off + pi_trailer_bytes(c) != pb) return set_error("internal: proof layout size mismatch"), P2_ERR_INVALID;  // the trailer: k_pi_hash
         LAUNCH(C, "proof_segments", k_proof_segments, dim3(2, B, nseg), dim3(256), 0, segs);
     }
     LAUNCH(C, "finish", k_finish, g1(C->pbytes, 256, B), dim3(256), 0, C->cur->d_status, d_status_out, d_proofs, C->pbytes, B);
@@ -1123,12 +1132,12 @@ struct VerifyWs {
     hipStream_t stream = nullptr;
     hipEvent_t done = nullptr;
     size_t chunk = 0;
-    u64 *d_words = nullptr, *d_chal = nullptr, *d_vq = nullptr, *d_vd = nullptr;
+    u64 *d_words = nullptr, *d_chal = nullptr, *d_vq = nullptr, *d_vd = nullptr, *d_pi_hash = nullptr;
     u32 *d_flags = nullptr, *d_qfail = nullptr;
     uint8_t* d_proofs = nullptr;
     int *d_status = nullptr, *h_status = nullptr;
     void release() {
-        for (void* p : {(void*)d_words, (void*)d_chal, (void*)d_vq, (void*)d_vd, (void*)d_flags, (void*)d_qfail, (void*)d_proofs, (void*)d_status})
+        for (void* p : {(void*)d_words, (void*)d_chal, (void*)d_vq, (void*)d_vd, (void*)d_pi_hash, (void*)d_flags, (void*)d_qfail, (void*)d_proofs, (void*)d_status})
             if (p) (void)hipFree(p);
         if (h_status) (void)hipHostFree(h_status);
         if (stream) (void)hipStreamDestroy(stream);
@@ -1216,6 +1225,12 @@ static int verify_setup(p2_circuit* C) {
     a.final_len = (u32)(C->n >> (VFY_ARITY_BITS * C->arities.size()));
     a.final_off = words(2 * a.final_len);
     a.pow_off = words(1);
+    a.num_pi = (u32)c.pi_slots.size();
+    if (a.num_pi) {
+        a.pi_cnt_byte = (u32)pos;  // the count word: compared with num_pi by k_vfy_unpack, not unpacked
+        pos += 8;
+        a.pi_off = words(a.num_pi);
+    }
     if (pos != C->pbytes) return set_error("internal: verifier layout differs from the proof size"), P2_ERR_INVALID;
     // the opening batches in the order they are observed and reduced: constants, sigmas, wires, zs, partial products,
     // quotient, lookup zs | zs(g zeta), lookup zs(g zeta)
@@ -1288,6 +1303,7 @@ static VerifyWs* verify_lease(p2_circuit* C) {
     bool ok = hipStreamCreateWithFlags(&W->stream, hipStreamNonBlocking) == hipSuccess && hipEventCreateWithFlags(&W->done, hipEventDisableTiming) == hipSuccess &&
               hipMalloc((void**)&W->d_words, chunk * a.W * 8) == hipSuccess && hipMalloc((void**)&W->d_chal, chunk * CH_WORDS * 8) == hipSuccess &&
               hipMalloc((void**)&W->d_vq, chunk * VQ_WORDS * 8) == hipSuccess && hipMalloc((void**)&W->d_vd, sizeof(VdArg)) == hipSuccess &&
+              hipMalloc((void**)&W->d_pi_hash, chunk * 4 * 8) == hipSuccess &&
               hipMalloc((void**)&W->d_flags, chunk * 4) == hipSuccess && hipMalloc((void**)&W->d_qfail, chunk * 4) == hipSuccess &&
               hipMalloc((void**)&W->d_proofs, chunk * C->pbytes) == hipSuccess && hipMalloc((void**)&W->d_status, chunk * sizeof(int)) == hipSuccess &&
               hipHostMalloc((void**)&W->h_status, chunk * sizeof(int), hipHostMallocDefault) == hipSuccess;
@@ -1322,6 +1338,7 @@ static int verify_run(p2_circuit* C, VerifyWs* W, size_t batch, const uint8_t* p
         a.chal = W->d_chal;
         a.vq = W->d_vq;
         a.vd = W->d_vd;
+        a.pi_hash = W->d_pi_hash;
         if (host) {
             HIPCHECK(hipMemcpyAsync(W->d_proofs, proofs + done * pb, B * pb, hipMemcpyHostToDevice, st));
             a.proofs = W->d_proofs;
@@ -1491,6 +1508,11 @@ int p2_circuit_verifier_data(const p2_circuit* C, uint64_t* out, size_t cap, siz
     return P2_OK;
 }
 size_t p2_circuit_proof_bytes(const p2_circuit* C) { return C->pbytes; }
+size_t p2_circuit_num_public_inputs(const p2_circuit* C) { return C ? C->c.pi_slots.size() : 0; }
+int p2_circuit_public_inputs(const p2_circuit* C, const uint8_t* proof, size_t proof_len, uint64_t* out, size_t cap, size_t* n_written) {
+    if (!C) return set_error("p2_circuit_public_inputs: null circuit handle"), P2_ERR_INVALID;
+    return read_public_inputs(C->c, C->pbytes, proof, proof_len, out, cap, n_written);
+}
 size_t p2_circuit_chunk_proofs(p2_circuit* C) {
     std::lock_guard<std::mutex> lock(C->mu);
     return C->chunk;
@@ -1816,6 +1838,13 @@ int p2_circuit_debug_read(p2_circuit* C, const char* name_c, size_t index, uint6
     else if (name == "quotient_values") { src = C->cur->d_qvals + index * 2 * N; count = 2 * N; }
     else if (name == "quotient_coeffs") { src = C->cur->d_qcoef + index * qc * n; count = (size_t)qc * n; }
     else if (name == "quotient_cap") { src = C->cur->qtree.dig + index * C->cur->qtree.stride() + cap_off(C->cur->qtree, c.cfg.cap_height); count = cap_words; }
+    else if (name == "public_inputs_hash" && c.pi_slots.empty()) {
+        if (cap < 4) return set_error("debug buffer too small"), P2_ERR_INVALID;
+        for (int i = 0; i < 4; i++) out[i] = 0;  // hash_no_pad of zero public inputs
+        *n_written = 4;
+        return P2_OK;
+    }
+    else if (name == "public_inputs_hash") { src = C->cur->d_pi_hash + index * 4; count = 4; }
     else if (name == "challenges") { src = C->cur->d_chal + index * CH_WORDS; count = CH_WORDS; }
     else if (name == "openings") { src = C->cur->d_ev + index * 2 * C->ev_count; count = 2 * (size_t)C->ev_count; }
     else if (name == "fri_final_poly_in") { src = C->cur->d_fri_coef[0] + index * 2 * n; count = 2 * n; }

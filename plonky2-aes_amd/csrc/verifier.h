@@ -188,13 +188,24 @@ inline std::string verify_proof(const Circuit& C, const VerifierData& vd, const 
     for (u32 a : arities) final_len >>= a;
     auto final_poly = read_exts(final_len);
     u64 pow_witness = r.r64();
+    // public-input trailer (circuits with k >= 1 public inputs): u64 k || k values
+    const size_t num_pi = C.pi_slots.size();
+    u64 pi_count = 0;
+    std::vector<u64> pis(num_pi);
+    if (num_pi) {
+        pi_count = r.r64();
+        for (auto& v : pis) v = r.r64();
+    }
     if (r.fail) return "proof truncated";
     if (r.pos != len) return "trailing bytes in proof";
+    if (pi_count != num_pi) return "wrong number of public inputs";
     auto canonical = [&](u64 v) { return v < P; };
     for (auto* v : {&o_constants, &o_sigmas, &o_wires, &o_zs, &o_zs_next, &o_pp, &o_quot, &o_lk, &o_lk_next, &final_poly})
         for (auto& e : *v)
             if (!canonical(e.a) || !canonical(e.b)) return "non-canonical field element";
     if (!canonical(pow_witness)) return "non-canonical field element";
+    for (u64 v : pis)
+        if (!canonical(v)) return "non-canonical field element";
     auto canonical_hashes = [&](const std::vector<Hash4>& hs) {
         for (auto& h : hs)
             for (int i = 0; i < 4; i++)
@@ -224,7 +235,8 @@ inline std::string verify_proof(const Circuit& C, const VerifierData& vd, const 
     // ---- challenges (plonk/get_challenges.rs)
     HostChallenger ch;
     ch.observe_hash(vd.circuit_digest);
-    for (int i = 0; i < 4; i++) ch.observe(0);  // public_inputs_hash of zero public inputs
+    const Hash4 pi_hash = h_hash_no_pad(pis.data(), num_pi);  // 0^4 for zero public inputs
+    ch.observe_hash(pi_hash);
     for (auto& h : wires_cap) ch.observe_hash(h);
     std::vector<u64> betas, gammas, deltas, alphas;
     for (size_t i = 0; i < NC; i++) betas.push_back(ch.challenge());
@@ -346,7 +358,7 @@ inline std::string verify_proof(const Circuit& C, const VerifierData& vd, const 
             } else if (kind == G_CONSTANT) {
                 for (int k = 0; k < 2; k++) gate[k] = add(gate[k], mul(filter, sub(gc[k], o_wires[k])));
             } else if (kind == G_PUBLIC_INPUT) {
-                for (int k = 0; k < 4; k++) gate[k] = add(gate[k], mul(filter, o_wires[k]));
+                for (int k = 0; k < 4; k++) gate[k] = add(gate[k], mul(filter, sub(o_wires[k], e2(pi_hash.e[k]))));
             } else if (kind == G_POSEIDON) {
                 poseidon_gate_constraints<FExt>([&](u32 i) { return o_wires[i]; },
                                                 [&](int k, E2 cst) { gate[k] = add(gate[k], mul(filter, cst)); });
