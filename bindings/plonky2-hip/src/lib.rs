@@ -2,7 +2,7 @@
 //! prover `libp2aes.so` through the C ABI of `include/p2aes.h`.
 //!
 //! Only what the reference calls is here -- `CircuitBuilder`, `Target`/`BoolTarget`, `PartialWitness` + `WitnessWrite`,
-//! `CircuitConfig`, `CircuitData::{prove, verify}`, `GoldilocksField` with the `Field`/`Field64`/`Sample` methods used, the
+//! `CircuitConfig`, `CircuitData::{prove, verify, verify_compressed}`, proof compression, `GoldilocksField` with the `Field`/`Field64`/`Sample` methods used, the
 //! `PoseidonHash` sponge -- under the module paths the reference imports them from.  Each item cites the call site it serves.
 //! The module `pod2` at the bottom re-exports the handful of pod2 names the ecgfp5 / poseidon-cipher crates use.
 //!
@@ -179,6 +179,30 @@ pub mod plonk {
         impl<F, C, const D: usize> ProofWithPublicInputs<F, C, D> {
             pub fn to_bytes(&self) -> Vec<u8> { self.bytes.clone() }
         }
+        impl<F: Field, C, const D: usize> ProofWithPublicInputs<F, C, D> {
+            /// `ProofWithPublicInputs::compress`.  Upstream takes `(circuit_digest, common_data)`; here
+            /// the circuit data that holds both.
+            pub fn compress(self, data: &CircuitData<F, C, D>) -> anyhow::Result<CompressedProofWithPublicInputs<F, C, D>> {
+                let bytes = data.convert(ffi::p2_proof_compress, &self.bytes)?;
+                Ok(CompressedProofWithPublicInputs { bytes, public_inputs: self.public_inputs, _p: PhantomData })
+            }
+        }
+
+        /// A compressed proof: the full proof's caps, openings and tail, its query indices, and each Merkle sibling and FRI
+        /// evaluation that the indices do not already imply.
+        pub struct CompressedProofWithPublicInputs<F, C, const D: usize> {
+            pub bytes: Vec<u8>,
+            pub public_inputs: Vec<F>,
+            pub(crate) _p: PhantomData<(F, C)>,
+        }
+        impl<F: Field, C, const D: usize> CompressedProofWithPublicInputs<F, C, D> {
+            pub fn to_bytes(&self) -> Vec<u8> { self.bytes.clone() }
+            /// `CompressedProofWithPublicInputs::decompress`; upstream's `(circuit_digest, common_data)` as in `compress`.
+            pub fn decompress(self, data: &CircuitData<F, C, D>) -> anyhow::Result<ProofWithPublicInputs<F, C, D>> {
+                let bytes = data.convert(ffi::p2_proof_decompress, &self.bytes)?;
+                Ok(ProofWithPublicInputs { bytes, public_inputs: self.public_inputs, _p: PhantomData })
+            }
+        }
 
         /// Result of `builder.build::<PoseidonGoldilocksConfig>()`: the compiled circuit, resident on one MI355X.
         pub struct CircuitData<F, C, const D: usize> {
@@ -243,6 +267,30 @@ pub mod plonk {
                 };
                 if rc != ffi::P2_OK { return Err(last_error()); }
                 Ok(())
+            }
+            /// `CircuitData::verify_compressed`: verify of the decompressed proof, behind the checks of decompression.
+            pub fn verify_compressed(&self, compressed_proof_with_pis: CompressedProofWithPublicInputs<F, C, D>) -> anyhow::Result<()> {
+                let p = &compressed_proof_with_pis.bytes;
+                let rc = unsafe {
+                    ffi::p2_verify_compressed(self.blob.as_ptr(), self.blob.len(), self.verifier_data.as_ptr(), self.verifier_data.len(),
+                                              p.as_ptr(), p.len())
+                };
+                if rc != ffi::P2_OK { return Err(last_error()); }
+                Ok(())
+            }
+            /// p2_proof_compress / p2_proof_decompress into a buffer of the full proof size (never too small).
+            pub(crate) fn convert(&self, f: unsafe extern "C" fn(*const u8, usize, *const u64, usize, *const u8, usize, *mut u8, usize, *mut usize) -> std::os::raw::c_int,
+                                  input: &[u8]) -> anyhow::Result<Vec<u8>> {
+                let pb = unsafe { ffi::p2_circuit_proof_bytes(self.handle) };
+                let mut out = vec![0u8; pb];
+                let mut n = 0usize;
+                let rc = unsafe {
+                    f(self.blob.as_ptr(), self.blob.len(), self.verifier_data.as_ptr(), self.verifier_data.len(), input.as_ptr(), input.len(),
+                      out.as_mut_ptr(), out.len(), &mut n)
+                };
+                if rc != ffi::P2_OK { return Err(last_error()); }
+                out.truncate(n);
+                Ok(out)
             }
         }
     }

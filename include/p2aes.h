@@ -223,6 +223,20 @@ int p2_witness_schedule_check(const uint8_t* blob, size_t len, uint32_t fuse, ui
 /* verifier_data = constants_sigmas_cap (16 digests) || circuit_digest, 68 u64 -- from p2_circuit_verifier_data */
 int p2_verify(const uint8_t* blob, size_t blob_len, const uint64_t* verifier_data, size_t verifier_data_len,
               const uint8_t* proof, size_t proof_len);
+/* Compressed proofs: ProofWithPublicInputs::compress, CompressedProofWithPublicInputs::decompress and
+ * CircuitData::verify_compressed, on the host.  Same argument conventions as p2_verify; a compressed proof is never longer
+ * than the full one (p2_blob_info's proof_bytes), so cap = proof_bytes always suffices.  *n_written receives the output's
+ * length (also when cap is too small: P2_ERR_INVALID).  A proof that cannot be converted is P2_ERR_VERIFY with the reason in
+ * p2_last_error: compress checks the full proof's shape and canonicality and takes the query indices from the transcript;
+ * decompress checks, in this order, the shape (indices below the LDE size, exact length, sibling counts, public-input count),
+ * the canonicality of every word, and that the written indices are the ones the transcript draws.  verify_compressed is
+ * verify_proof of the decompressed proof and checks the proof-of-work between canonicality and the indices. */
+int p2_proof_compress(const uint8_t* blob, size_t blob_len, const uint64_t* verifier_data, size_t verifier_data_len, const uint8_t* proof,
+                      size_t proof_len, uint8_t* out, size_t cap, size_t* n_written);
+int p2_proof_decompress(const uint8_t* blob, size_t blob_len, const uint64_t* verifier_data, size_t verifier_data_len, const uint8_t* cproof,
+                        size_t cproof_len, uint8_t* out, size_t cap, size_t* n_written);
+int p2_verify_compressed(const uint8_t* blob, size_t blob_len, const uint64_t* verifier_data, size_t verifier_data_len,
+                         const uint8_t* cproof, size_t cproof_len);
 /* ProofWithPublicInputs::public_inputs: the k values of the proof's public-input trailer (k = num_public_inputs of the
  * circuit; *n_written = k, 0 for a circuit without public inputs).  P2_ERR_INVALID if proof_len is not the circuit's
  * proof size, the count word is not k, or cap < k.  Parsing only: p2_verify checks that the values are the proven ones.
@@ -301,6 +315,29 @@ int p2_verify_batch(p2_circuit*, size_t batch, const uint8_t* proofs, const uint
  * verify_batch_device on one stream needs no host round trip.  Asynchronous: synchronise `stream` before reading d_status. */
 int p2_verify_batch_device(p2_circuit*, size_t batch, const uint8_t* d_proofs, const uint64_t* verifier_data, size_t vd_len,
                            int* d_status, void* stream);
+/* Compressed proofs in GPU batches (the conversions of p2_proof_compress / p2_proof_decompress / p2_verify_compressed; layout
+ * and verdict order in DESIGN.md section 8).  Compressed proofs sit at a stride of p2_circuit_proof_bytes() (a compressed
+ * proof is never longer than the full one) with lengths[i] their actual lengths; the bytes of a slot past its length are
+ * zero in compress's output and ignored on input.  status[i] <- P2_VERIFY_*: compress gives OK, SHAPE or NON_CANONICAL (the
+ * full proof's shape and canonicality) and a zeroed slot of length 0 for a proof it rejects; decompress gives OK, SHAPE (the
+ * compressed shape, or written indices that differ from the drawn ones) or NON_CANONICAL and a zeroed slot for a proof it
+ * rejects; verify_compressed gives the verdict of p2_verify_compressed.  A zeroed slot or a zero length is SHAPE.  A length
+ * above the stride is P2_ERR_INVALID in the host forms and a SHAPE verdict in the device forms.  verifier_data as
+ * p2_verify_batch.  The workspaces, chunks and thread safety are p2_verify_batch's. */
+int p2_compress_batch(p2_circuit*, size_t batch, const uint8_t* proofs, const uint64_t* verifier_data, size_t vd_len, uint8_t* out,
+                      uint32_t* lengths, int* status);
+int p2_decompress_batch(p2_circuit*, size_t batch, const uint8_t* cproofs, const uint32_t* lengths, const uint64_t* verifier_data,
+                        size_t vd_len, uint8_t* out, int* status);
+int p2_verify_compressed_batch(p2_circuit*, size_t batch, const uint8_t* cproofs, const uint32_t* lengths, const uint64_t* verifier_data,
+                               size_t vd_len, int* status);
+/* The same with every buffer but verifier_data in device memory, ordered with `stream` like p2_verify_batch_device:
+ * prove_batch_device -> compress_batch_device -> verify_compressed_batch_device on one stream needs no host round trip. */
+int p2_compress_batch_device(p2_circuit*, size_t batch, const uint8_t* d_proofs, const uint64_t* verifier_data, size_t vd_len,
+                             uint8_t* d_out, uint32_t* d_lengths, int* d_status, void* stream);
+int p2_decompress_batch_device(p2_circuit*, size_t batch, const uint8_t* d_cproofs, const uint32_t* d_lengths,
+                               const uint64_t* verifier_data, size_t vd_len, uint8_t* d_out, int* d_status, void* stream);
+int p2_verify_compressed_batch_device(p2_circuit*, size_t batch, const uint8_t* d_cproofs, const uint32_t* d_lengths,
+                                      const uint64_t* verifier_data, size_t vd_len, int* d_status, void* stream);
 /* Tuning knobs of a handle: "chunk" (proofs per workspace, default 128), "streams" (proving streams, default 2),
  * "debug_timing" (host-path phase times on stderr), "verify_chunk" (proofs per p2_verify_batch chunk).  The environment
  * variables P2AES_CHUNK / P2AES_STREAMS / P2AES_DEBUG_TIMING / P2AES_VERIFY_CHUNK set the defaults and are read once, in

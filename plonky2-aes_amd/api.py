@@ -52,6 +52,10 @@ VERIFY_REASONS = {
     "Invalid Merkle proof (FRI round).": VERIFY_MERKLE_FRI,
     "Final polynomial evaluation is invalid.": VERIFY_FINAL_POLY,
     "wrong number of public inputs": VERIFY_SHAPE,
+    # compressed proofs (csrc/compress.h): their layout follows from the written query indices
+    "query index out of range": VERIFY_SHAPE,
+    "wrong sibling count in compressed proof": VERIFY_SHAPE,
+    "query indices differ from the transcript": VERIFY_SHAPE,
 }
 
 u32p = C.POINTER(C.c_uint32)
@@ -157,6 +161,9 @@ def lib():
         "p2_blob_info": (C.c_int, [C.c_char_p, sz, C.POINTER(_Info)]),
         "p2_witness_schedule_check": (C.c_int, [C.c_char_p, sz, C.c_uint32, u32p]),
         "p2_verify": (C.c_int, [C.c_char_p, sz, u64p, sz, C.c_char_p, sz]),
+        "p2_proof_compress": (C.c_int, [C.c_char_p, sz, u64p, sz, C.c_char_p, sz, C.c_char_p, sz, C.POINTER(sz)]),
+        "p2_proof_decompress": (C.c_int, [C.c_char_p, sz, u64p, sz, C.c_char_p, sz, C.c_char_p, sz, C.POINTER(sz)]),
+        "p2_verify_compressed": (C.c_int, [C.c_char_p, sz, u64p, sz, C.c_char_p, sz]),
         "p2_circuit_load": (vp, [C.c_char_p, sz, C.c_int]), "p2_circuit_free": (None, [vp]),
         "p2_circuit_verifier_data": (C.c_int, [vp, u64p, sz, C.POINTER(sz)]),
         "p2_circuit_proof_bytes": (sz, [vp]),
@@ -168,6 +175,12 @@ def lib():
         "p2_circuit_synchronize": (C.c_int, [vp]),
         "p2_verify_batch": (C.c_int, [vp, sz, C.c_char_p, u64p, sz, C.POINTER(C.c_int)]),
         "p2_verify_batch_device": (C.c_int, [vp, sz, vp, u64p, sz, vp, vp]),
+        "p2_compress_batch": (C.c_int, [vp, sz, C.c_char_p, u64p, sz, C.c_char_p, u32p, C.POINTER(C.c_int)]),
+        "p2_compress_batch_device": (C.c_int, [vp, sz, vp, u64p, sz, vp, vp, vp, vp]),
+        "p2_decompress_batch": (C.c_int, [vp, sz, C.c_char_p, u32p, u64p, sz, C.c_char_p, C.POINTER(C.c_int)]),
+        "p2_decompress_batch_device": (C.c_int, [vp, sz, vp, vp, u64p, sz, vp, vp, vp]),
+        "p2_verify_compressed_batch": (C.c_int, [vp, sz, C.c_char_p, u32p, u64p, sz, C.POINTER(C.c_int)]),
+        "p2_verify_compressed_batch_device": (C.c_int, [vp, sz, vp, vp, u64p, sz, vp, vp]),
         "p2_circuit_set_timing": (C.c_int, [vp, C.c_int]),
         "p2_circuit_get_timing": (sz, [vp, C.POINTER(_KernelTime), sz]),
         "p2_gpu_device_count": (C.c_int, []),
@@ -572,6 +585,99 @@ class CircuitData:
         vd, n = self._vd_arg(verifier_data)
         if lib().p2_verify_batch_device(self.gpu(), batch, d_proofs, vd, n, d_status, stream):
             raise P2Error("p2_verify_batch_device failed: " + _err())
+
+    # ---- compressed proofs: upstream's ProofWithPublicInputs::compress,
+    # CompressedProofWithPublicInputs::decompress and CircuitData::verify_compressed on the host, batches on the GPU
+    def _convert(self, fn, name, proof, verifier_data):
+        vd = verifier_data if verifier_data is not None else self.verifier_data()
+        proof = bytes(proof)
+        out = C.create_string_buffer(max(self.proof_bytes, 1))
+        n = sz()
+        if fn(self.blob, len(self.blob), _arr(vd), len(vd), proof, len(proof), out, self.proof_bytes, C.byref(n)):
+            raise P2Error(name + " failed: " + _err())
+        return out.raw[: n.value]
+
+    def compress(self, proof, verifier_data=None):
+        """ProofWithPublicInputs::compress (host): the compressed bytes of a full proof of this circuit."""
+        return self._convert(lib().p2_proof_compress, "compress", proof, verifier_data)
+
+    def decompress(self, cproof, verifier_data=None):
+        """CompressedProofWithPublicInputs::decompress (host): the full proof back."""
+        return self._convert(lib().p2_proof_decompress, "decompress", cproof, verifier_data)
+
+    def verify_compressed(self, cproof, verifier_data=None):
+        """CircuitData::verify_compressed (host): verify() of the decompressed proof, behind the checks of decompression."""
+        vd = verifier_data if verifier_data is not None else self.verifier_data()
+        cproof = bytes(cproof)
+        if lib().p2_verify_compressed(self.blob, len(self.blob), _arr(vd), len(vd), cproof, len(cproof)):
+            raise P2Error("verify_compressed failed: " + _err())
+
+    def _slots(self, items, name):
+        """A batch of at most proof_bytes-long byte strings (None = an empty slot) as one fixed-stride buffer and lengths."""
+        pb = self.proof_bytes
+        parts = [b"" if p is None else bytes(p) for p in items]
+        if any(len(p) > pb for p in parts):
+            raise P2Error("%s: a proof is longer than %d bytes" % (name, pb))
+        B = len(parts)
+        buf = C.create_string_buffer(max(B * pb, 1))
+        base = C.addressof(buf)
+        for i, p in enumerate(parts):
+            C.memmove(base + i * pb, p, len(p))
+        return B, buf, (C.c_uint32 * max(B, 1))(*[len(p) for p in parts])
+
+    def compress_batch(self, proofs, verifier_data=None):
+        """GPU compression (p2_compress_batch): (list of compressed proofs, list of VERIFY_* codes); a failed slot is None."""
+        B, buf, _ = self._slots(proofs, "compress_batch")
+        pb = self.proof_bytes
+        out = C.create_string_buffer(max(B * pb, 1))
+        lengths = (C.c_uint32 * max(B, 1))()
+        status = (C.c_int * max(B, 1))()
+        vd, n = self._vd_arg(verifier_data)
+        if lib().p2_compress_batch(self.gpu(), B, buf, vd, n, out, lengths, status):
+            raise P2Error("p2_compress_batch failed: " + _err())
+        base = C.addressof(out)
+        return [C.string_at(base + i * pb, lengths[i]) if status[i] == 0 else None for i in range(B)], list(status[:B])
+
+    def decompress_batch(self, cproofs, verifier_data=None):
+        """GPU decompression (p2_decompress_batch): (list of full proofs, list of VERIFY_* codes); a failed slot is None."""
+        B, buf, lengths = self._slots(cproofs, "decompress_batch")
+        pb = self.proof_bytes
+        out = C.create_string_buffer(max(B * pb, 1))
+        status = (C.c_int * max(B, 1))()
+        vd, n = self._vd_arg(verifier_data)
+        if lib().p2_decompress_batch(self.gpu(), B, buf, lengths, vd, n, out, status):
+            raise P2Error("p2_decompress_batch failed: " + _err())
+        base = C.addressof(out)
+        return [C.string_at(base + i * pb, pb) if status[i] == 0 else None for i in range(B)], list(status[:B])
+
+    def verify_compressed_batch(self, cproofs, verifier_data=None, lengths=None):
+        """GPU verification of compressed proofs (p2_verify_compressed_batch): one VERIFY_* code per proof, the reason class
+        verify_compressed(cproof) would report.  `lengths` overrides the byte strings' own lengths (tests)."""
+        B, buf, own = self._slots(cproofs, "verify_compressed_batch")
+        if lengths is not None:
+            own = (C.c_uint32 * max(B, 1))(*lengths)
+        status = (C.c_int * max(B, 1))()
+        vd, n = self._vd_arg(verifier_data)
+        if lib().p2_verify_compressed_batch(self.gpu(), B, buf, own, vd, n, status):
+            raise P2Error("p2_verify_compressed_batch failed: " + _err())
+        return list(status[:B])
+
+    def compress_batch_device(self, d_proofs, d_out, d_lengths, d_status, batch, verifier_data=None, stream=None):
+        """Device-resident form: full proofs in, compressed proofs at a stride of proof_bytes, uint32 lengths and int32 statuses
+        out (raw device pointers, e.g. torch tensors' data_ptr()); asynchronous on `stream` like verify_batch_device."""
+        vd, n = self._vd_arg(verifier_data)
+        if lib().p2_compress_batch_device(self.gpu(), batch, d_proofs, vd, n, d_out, d_lengths, d_status, stream):
+            raise P2Error("p2_compress_batch_device failed: " + _err())
+
+    def decompress_batch_device(self, d_cproofs, d_lengths, d_out, d_status, batch, verifier_data=None, stream=None):
+        vd, n = self._vd_arg(verifier_data)
+        if lib().p2_decompress_batch_device(self.gpu(), batch, d_cproofs, d_lengths, vd, n, d_out, d_status, stream):
+            raise P2Error("p2_decompress_batch_device failed: " + _err())
+
+    def verify_compressed_batch_device(self, d_cproofs, d_lengths, d_status, batch, verifier_data=None, stream=None):
+        vd, n = self._vd_arg(verifier_data)
+        if lib().p2_verify_compressed_batch_device(self.gpu(), batch, d_cproofs, d_lengths, vd, n, d_status, stream):
+            raise P2Error("p2_verify_compressed_batch_device failed: " + _err())
 
     def debug_read(self, name, index=0, cap=1 << 26):
         out = (u64 * cap)()

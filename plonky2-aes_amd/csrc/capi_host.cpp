@@ -5,6 +5,7 @@
 #include "../../include/p2aes.h"
 #include "aes_gadgets.h"
 #include "capi_common.h"
+#include "compress.h"
 #include "ecgfp5.h"
 #include "poseidon_cipher.h"
 #include "poseidon_fast.h"
@@ -49,6 +50,36 @@ static size_t guarded_sz(F f) {
     return r;
 }
 
+// verifier_data = constants_sigmas_cap || circuit_digest; false if vd_len does not fit the circuit
+static bool read_verifier_data(const Circuit& c, const uint64_t* vd, size_t vd_len, VerifierData& v) {
+    size_t cap_n = (size_t)1 << c.cfg.cap_height;
+    if (!vd || vd_len != 4 * cap_n + 4) return false;
+    v.constants_sigmas_cap.resize(cap_n);
+    for (size_t i = 0; i < cap_n; i++) memcpy(v.constants_sigmas_cap[i].e, vd + 4 * i, 32);
+    memcpy(v.circuit_digest.e, vd + 4 * cap_n, 32);
+    return true;
+}
+// p2_proof_compress / p2_proof_decompress: one conversion of compress.h, its output copied to `out` when it fits
+template <class F>
+static int convert_proof(const uint8_t* blob, size_t blob_len, const uint64_t* vd, size_t vd_len, const uint8_t* in, size_t in_len, uint8_t* out,
+                         size_t cap, size_t* n_written, F&& f) {
+    try {
+        if (n_written) *n_written = 0;
+        Circuit c = deserialize(blob, blob_len);
+        VerifierData v;
+        if (!read_verifier_data(c, vd, vd_len, v)) return set_error("verifier_data must be cap || circuit_digest"), P2_ERR_INVALID;
+        if (!in) return set_error("null proof"), P2_ERR_INVALID;
+        std::vector<uint8_t> res;
+        std::string err = f(c, v, in, in_len, res);
+        if (!err.empty()) return set_error(err), P2_ERR_VERIFY;
+        if (n_written) *n_written = res.size();
+        if (!out || cap < res.size()) return set_error("output buffer holds fewer than " + std::to_string(res.size()) + " bytes"), P2_ERR_INVALID;
+        memcpy(out, res.data(), res.size());
+        return P2_OK;
+    } catch (std::exception& e) {
+        return set_error(e.what()), P2_ERR_INVALID;
+    }
+}
 extern "C" {
 
 const char* p2_last_error(void) { return p2::g_last_error.c_str(); }
@@ -606,13 +637,34 @@ int p2_witness_schedule_check(const uint8_t* blob, size_t len, uint32_t fuse, ui
 int p2_verify(const uint8_t* blob, size_t blob_len, const uint64_t* vd, size_t vd_len, const uint8_t* proof, size_t proof_len) {
     try {
         Circuit c = deserialize(blob, blob_len);
-        size_t cap_n = (size_t)1 << c.cfg.cap_height;
-        if (vd_len != 4 * cap_n + 4) return set_error("verifier_data must be cap || circuit_digest"), P2_ERR_INVALID;
         VerifierData v;
-        v.constants_sigmas_cap.resize(cap_n);
-        for (size_t i = 0; i < cap_n; i++) memcpy(v.constants_sigmas_cap[i].e, vd + 4 * i, 32);
-        memcpy(v.circuit_digest.e, vd + 4 * cap_n, 32);
+        if (!read_verifier_data(c, vd, vd_len, v)) return set_error("verifier_data must be cap || circuit_digest"), P2_ERR_INVALID;
         std::string err = verify_proof(c, v, proof, proof_len);
+        if (!err.empty()) return set_error(err), P2_ERR_VERIFY;
+        return P2_OK;
+    } catch (std::exception& e) {
+        return set_error(e.what()), P2_ERR_INVALID;
+    }
+}
+int p2_proof_compress(const uint8_t* blob, size_t blob_len, const uint64_t* vd, size_t vd_len, const uint8_t* proof, size_t proof_len, uint8_t* out,
+                      size_t cap, size_t* n_written) {
+    return convert_proof(blob, blob_len, vd, vd_len, proof, proof_len, out, cap, n_written,
+                         [](const Circuit& c, const VerifierData& v, const uint8_t* p, size_t n, std::vector<uint8_t>& r) { return compress_proof(c, v, p, n, r); });
+}
+int p2_proof_decompress(const uint8_t* blob, size_t blob_len, const uint64_t* vd, size_t vd_len, const uint8_t* cproof, size_t cproof_len,
+                        uint8_t* out, size_t cap, size_t* n_written) {
+    return convert_proof(blob, blob_len, vd, vd_len, cproof, cproof_len, out, cap, n_written,
+                         [](const Circuit& c, const VerifierData& v, const uint8_t* p, size_t n, std::vector<uint8_t>& r) {
+                             return decompress_proof(c, v, p, n, r, false);
+                         });
+}
+int p2_verify_compressed(const uint8_t* blob, size_t blob_len, const uint64_t* vd, size_t vd_len, const uint8_t* cproof, size_t cproof_len) {
+    try {
+        Circuit c = deserialize(blob, blob_len);
+        VerifierData v;
+        if (!read_verifier_data(c, vd, vd_len, v)) return set_error("verifier_data must be cap || circuit_digest"), P2_ERR_INVALID;
+        if (!cproof) return set_error("null proof"), P2_ERR_INVALID;
+        std::string err = verify_compressed_proof(c, v, cproof, cproof_len);
         if (!err.empty()) return set_error(err), P2_ERR_VERIFY;
         return P2_OK;
     } catch (std::exception& e) {

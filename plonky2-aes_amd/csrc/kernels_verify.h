@@ -22,7 +22,8 @@
 
 namespace p2k {
 
-enum VerifyFlag : u32 { VF_SHAPE = 1, VF_NONCANON = 2, VF_POW = 4, VF_ZETA = 8, VF_VANISH = 16 };
+// VF_INDICES: a compressed proof's written query indices differ from the drawn ones (kernels_compress.h), SHAPE after POW
+enum VerifyFlag : u32 { VF_SHAPE = 1, VF_NONCANON = 2, VF_POW = 4, VF_ZETA = 8, VF_VANISH = 16, VF_INDICES = 32 };
 static const u32 VQ_WORDS = 8;        // per proof: red0, red1, g*zeta, fri_alpha^|e1| (extension elements)
 static const u32 VFY_MAX_ROUNDS = 8;  // as CH_FRI_BETAS
 static const u32 VFY_ARITY_BITS = 4;  // FriReductionStrategy::ConstantArityBits(4, 5): checked on the host
@@ -238,6 +239,18 @@ __device__ __forceinline__ void vfy_poseidon_gate(WireFn wire, EmitFn emit, E2* 
     for (int i = 0; i < 12; i++) emit(k++, gl::sub(st[i], wire(p2::PG_OUT + i)));
 }
 
+// The opening reductions fri_combine_initial needs: red0, red1, g*zeta, fri_alpha^|e1| into vq (also k_cmp_reductions)
+__device__ __forceinline__ void vfy_opening_reductions(const VerifyArgs& a, u32 p, const u64* w, const u64* ch, E2 zeta) {
+    const E2 fa = gl::e2(ch[CH_FRI_ALPHA], ch[CH_FRI_ALPHA + 1]);
+    E2 r0 = gl::e2(0), r1 = gl::e2(0);
+    for (u32 e = a.n_b0; e-- > 0;) r0 = gl::add(gl::mul(r0, fa), vfy_e2(w, a.obs_map[e]));
+    for (u32 e = a.n_b1; e-- > 0;) r1 = gl::add(gl::mul(r1, fa), vfy_e2(w, a.obs_map[a.n_b0 + e]));
+    const E2 gz = gl::mul(zeta, gl::root_of_unity((int)a.degree_bits));
+    const E2 ap = gl::pow(fa, (u64)(a.NC + a.zc - a.nzpp));
+    u64* o = a.vq + (size_t)p * VQ_WORDS;
+    o[0] = r0.a, o[1] = r0.b, o[2] = r1.a, o[3] = r1.b, o[4] = gz.a, o[5] = gz.b, o[6] = ap.a, o[7] = ap.b;
+}
+
 __global__ __launch_bounds__(256) void k_vfy_vanishing(VerifyArgs a) {
     __shared__ u64 red[256];
     __shared__ u64 lutacc[2][p2::MAX_LUTS];
@@ -279,17 +292,7 @@ __global__ __launch_bounds__(256) void k_vfy_vanishing(VerifyArgs a) {
     for (u32 k = tid; k < a.ngc; k += blockDim.x) gate[k] = gl::e2(0);
     __syncthreads();
     const E2 zeta = gl::e2(ch[CH_ZETA], ch[CH_ZETA + 1]);
-    if (tid == 64) {
-        // a second wave: the opening reductions fri_combine_initial needs (k_vfy_queries)
-        const E2 fa = gl::e2(ch[CH_FRI_ALPHA], ch[CH_FRI_ALPHA + 1]);
-        E2 r0 = gl::e2(0), r1 = gl::e2(0);
-        for (u32 e = a.n_b0; e-- > 0;) r0 = gl::add(gl::mul(r0, fa), vfy_e2(w, a.obs_map[e]));
-        for (u32 e = a.n_b1; e-- > 0;) r1 = gl::add(gl::mul(r1, fa), vfy_e2(w, a.obs_map[a.n_b0 + e]));
-        const E2 gz = gl::mul(zeta, gl::root_of_unity((int)a.degree_bits));
-        const E2 ap = gl::pow(fa, (u64)(a.NC + a.zc - a.nzpp));
-        u64* o = a.vq + (size_t)p * VQ_WORDS;
-        o[0] = r0.a, o[1] = r0.b, o[2] = r1.a, o[3] = r1.b, o[4] = gz.a, o[5] = gz.b, o[6] = ap.a, o[7] = ap.b;
-    }
+    if (tid == 64) vfy_opening_reductions(a, p, w, ch, zeta);  // a second wave: what fri_combine_initial needs (k_vfy_queries)
     if (tid != 0) return;
     const u32 NC = a.NC, R = a.R, npp = a.npp, qdf = a.qdf, nlp = a.nlp, nsldc = a.nsldc;
     const E2 zpn = gl::exp_pow2(zeta, (int)a.degree_bits);
@@ -547,6 +550,7 @@ __global__ void k_vfy_finish(VerifyArgs a, u32 slots) {
     if (f & VF_SHAPE) st = P2_VERIFY_SHAPE;
     else if (f & VF_NONCANON) st = P2_VERIFY_NON_CANONICAL;
     else if (f & VF_POW) st = P2_VERIFY_POW;
+    else if (f & VF_INDICES) st = P2_VERIFY_SHAPE;
     else if (f & VF_ZETA) st = P2_VERIFY_ZETA_IN_SUBGROUP;
     else if (f & VF_VANISH) st = P2_VERIFY_VANISHING;
     else if (key != ~0u) {

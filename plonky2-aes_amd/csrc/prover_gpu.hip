@@ -16,7 +16,7 @@
 #include "os_random.h"
 #include "kernels.h"
 #include "kernels2.h"
-#include "kernels_verify.h"
+#include "kernels_compress.h"
 
 using namespace p2;
 using namespace p2k;
@@ -134,6 +134,9 @@ struct p2_circuit {
     size_t vfy_chunk = 0;
     std::vector<struct VerifyWs*> vfy_free;
     std::mutex vfy_mu;
+    // compressed proofs (kernels_compress.h): the source of every word of the full layout, and the layout's fixed parts
+    u32* d_cmp_wmap = nullptr;
+    u32 cmp_prefix = 0, cmp_tail = 0, cmp_cols[4] = {0, 0, 0, 0};
     long fail_alloc_after = -1;            // test hook, see dalloc_ws
     // timing
     bool timing_on = false;
@@ -1136,10 +1139,16 @@ struct VerifyWs {
     u32 *d_flags = nullptr, *d_qfail = nullptr;
     uint8_t* d_proofs = nullptr;
     int *d_status = nullptr, *h_status = nullptr;
+    // compressed proofs, allocated by their first use (cmp_ensure)
+    CmpPlan* d_plan = nullptr;
+    uint8_t* d_cout = nullptr;
+    u32 *d_len = nullptr, *h_len = nullptr;
     void release() {
-        for (void* p : {(void*)d_words, (void*)d_chal, (void*)d_vq, (void*)d_vd, (void*)d_pi_hash, (void*)d_flags, (void*)d_qfail, (void*)d_proofs, (void*)d_status})
+        for (void* p : {(void*)d_words, (void*)d_chal, (void*)d_vq, (void*)d_vd, (void*)d_pi_hash, (void*)d_flags, (void*)d_qfail, (void*)d_proofs, (void*)d_status,
+                        (void*)d_plan, (void*)d_cout, (void*)d_len})
             if (p) (void)hipFree(p);
         if (h_status) (void)hipHostFree(h_status);
+        if (h_len) (void)hipHostFree(h_len);
         if (stream) (void)hipStreamDestroy(stream);
         if (done) (void)hipEventDestroy(done);
         *this = VerifyWs();
@@ -1275,6 +1284,34 @@ static int verify_setup(p2_circuit* C) {
     return 0;
 }
 
+// The compressed layout's per-circuit parts (compress.h::compress_shape): where each word of the full layout comes from.
+static int cmp_setup(p2_circuit* C) {
+    if (!C->vfy_error.empty()) return 0;
+    const Circuit& c = C->c;
+    const VerifyArgs& a = C->vfy_args;
+    if (c.cfg.num_query_rounds > CMP_MAXQ || a.init_depth > 31) {
+        C->vfy_error = "compressed proofs: more than 32 queries or an initial tree deeper than 31 levels";
+        return 0;
+    }
+    std::vector<u32> wmap(a.W, cmp_code(CW_PREFIX, 0, 0, 0));
+    for (u32 i = a.final_off; i < a.W; i++) wmap[i] = cmp_code(CW_TAIL, 0, 0, 0);
+    for (u32 q = 0; q < c.cfg.num_query_rounds; q++) {
+        const u32 base = a.q_off + q * a.q_stride;
+        for (u32 o = 0; o < 4; o++) {
+            for (u32 e = 0; e < a.init_width[o]; e++) wmap[base + a.init_eval_off[o] + e] = cmp_code(CW_LEAF, q, o, e);
+            for (u32 e = 0; e < 4 * a.init_depth; e++) wmap[base + a.init_sib_off[o] + e] = cmp_code(CW_SIB, q, o, e);
+        }
+        for (u32 r = 0; r < a.num_rounds; r++) {
+            for (u32 e = 0; e < 2 * VFY_ARITY; e++) wmap[base + a.step_eval_off[r] + e] = cmp_code(CW_EVAL, q, 4 + r, e);
+            for (u32 e = 0; e < 4 * a.step_depth[r]; e++) wmap[base + a.step_sib_off[r] + e] = cmp_code(CW_SIB, q, 4 + r, e);
+        }
+    }
+    C->cmp_prefix = 8 * a.q_off;
+    C->cmp_tail = (u32)(C->pbytes - 8 * (size_t)a.final_off - (size_t)a.n_cnt);  // the tail's byte offset: every count byte lies before it
+    for (u32 o = 0; o < 4; o++) C->cmp_cols[o] = a.init_width[o];
+    return upload(C, &C->d_cmp_wmap, wmap.data(), wmap.size());
+}
+
 static VerifyWs* verify_lease(p2_circuit* C) {
     VerifyWs* W = nullptr;
     std::vector<VerifyWs*> stale;  // made before the "verify_chunk" option changed: drained and freed after the lock is released
@@ -1394,6 +1431,143 @@ static int verify_batch_impl(p2_circuit* C, size_t batch, const uint8_t* proofs,
     return rc;
 }
 
+// ---------------------------------------------------------------------------------- compressed proofs (kernels_compress.h)
+enum CmpMode { CMP_COMPRESS, CMP_DECOMPRESS, CMP_VERIFY };
+static int cmp_ensure(p2_circuit* C, VerifyWs* W) {
+    if (W->d_plan) return P2_OK;
+    const size_t n = W->chunk;
+    if (hipMalloc((void**)&W->d_plan, n * sizeof(CmpPlan)) != hipSuccess || hipMalloc((void**)&W->d_cout, n * C->pbytes) != hipSuccess ||
+        hipMalloc((void**)&W->d_len, n * 4) != hipSuccess || hipHostMalloc((void**)&W->h_len, n * 4, hipHostMallocDefault) != hipSuccess)
+        return set_error("compression workspace could not be allocated"), P2_ERR_HIP;
+    return P2_OK;
+}
+
+// Enqueues one conversion of `batch` proofs on `st`; host / device memory as verify_run.  in: full proofs (compress) or
+// compressed ones at the same stride with `lengths`; out: compressed proofs (compress, with lengths_out) or full ones.
+static int cmp_run(p2_circuit* C, VerifyWs* W, CmpMode mode, size_t batch, const uint8_t* in, const u32* lengths, uint8_t* out, u32* lengths_out,
+                   const VdArg& vd, int* status, hipStream_t st, bool host) {
+    const size_t pb = C->pbytes;
+    HIPCHECK(hipStreamWaitEvent(st, W->done, 0));
+    hipLaunchKernelGGL(k_vfy_set_vd, dim3(1), dim3(128), 0, st, vd, W->d_vd, C->vfy_args.cap_words + 4);
+    HIPCHECK(hipGetLastError());
+    for (size_t done = 0; done < batch; done += W->chunk) {
+        const u32 B = (u32)std::min(W->chunk, batch - done);
+        CmpArgs a{};
+        a.v = C->vfy_args;
+        VerifyArgs& v = a.v;
+        v.batch = B;
+        v.words = W->d_words;
+        v.flags = W->d_flags;
+        v.qfail = W->d_qfail;
+        v.chal = W->d_chal;
+        v.vq = W->d_vq;
+        v.vd = W->d_vd;
+        v.pi_hash = W->d_pi_hash;
+        a.plan = W->d_plan;
+        a.wmap = C->d_cmp_wmap;
+        a.prefix = C->cmp_prefix;
+        a.tail = C->cmp_tail;
+        for (int o = 0; o < 4; o++) a.cols[o] = C->cmp_cols[o];
+        a.from_chal = mode == CMP_COMPRESS;
+        if (host) {
+            HIPCHECK(hipMemcpyAsync(W->d_proofs, in + done * pb, B * pb, hipMemcpyHostToDevice, st));
+            if (lengths) HIPCHECK(hipMemcpyAsync(W->d_len, lengths + done, B * 4, hipMemcpyHostToDevice, st));
+            v.status = W->d_status;
+            a.cout = W->d_cout;
+            a.lengths = W->d_len;
+            a.lengths_out = W->d_len;
+            v.proofs = a.cproofs = W->d_proofs;
+        } else {
+            v.status = status + done;
+            a.cout = out ? out + done * pb : nullptr;
+            a.lengths = lengths ? lengths + done : nullptr;
+            a.lengths_out = lengths_out ? lengths_out + done : nullptr;
+            v.proofs = a.cproofs = in + done * pb;
+        }
+        HIPCHECK(hipMemsetAsync(W->d_flags, 0, (size_t)B * 4, st));
+        HIPCHECK(hipMemsetAsync(W->d_qfail, 0xFF, (size_t)B * 4, st));
+        const dim3 words_grid((v.W + 255) / 256, B);
+        if (mode == CMP_COMPRESS) {
+            hipLaunchKernelGGL(k_vfy_unpack, words_grid, dim3(256), 0, st, v);
+            HIPCHECK(hipGetLastError());
+            hipLaunchKernelGGL(k_vfy_transcript, g1((size_t)B * 16, 64), dim3(64), 0, st, v);
+            HIPCHECK(hipGetLastError());
+            hipLaunchKernelGGL(k_cmp_plan, dim3(B), dim3(256), 0, st, a);
+            HIPCHECK(hipGetLastError());
+            HIPCHECK(hipMemsetAsync(a.cout, 0, (size_t)B * pb, st));
+            hipLaunchKernelGGL(k_cmp_emit, words_grid, dim3(256), 0, st, a);
+            HIPCHECK(hipGetLastError());
+            hipLaunchKernelGGL(k_cmp_finish, g1(B, 64), dim3(64), 0, st, a);
+            HIPCHECK(hipGetLastError());
+        } else {
+            hipLaunchKernelGGL(k_cmp_plan, dim3(B), dim3(256), 0, st, a);
+            HIPCHECK(hipGetLastError());
+            hipLaunchKernelGGL(k_cmp_scatter, words_grid, dim3(256), 0, st, a);
+            HIPCHECK(hipGetLastError());
+            hipLaunchKernelGGL(k_vfy_transcript, g1((size_t)B * 16, 64), dim3(64), 0, st, v);
+            HIPCHECK(hipGetLastError());
+            hipLaunchKernelGGL(k_cmp_reductions, g1(B, 64), dim3(64), 0, st, a);
+            HIPCHECK(hipGetLastError());
+            hipLaunchKernelGGL(k_cmp_infer, dim3(B), dim3(CMP_MAXQ), 0, st, a);
+            HIPCHECK(hipGetLastError());
+            hipLaunchKernelGGL(k_cmp_merkle, dim3(B, 4 + v.num_rounds), dim3(CMP_MAXQ), 0, st, a);
+            HIPCHECK(hipGetLastError());
+            if (mode == CMP_DECOMPRESS) {
+                hipLaunchKernelGGL(k_cmp_finish, g1(B, 64), dim3(64), 0, st, a);
+                HIPCHECK(hipGetLastError());
+                hipLaunchKernelGGL(k_cmp_pack, words_grid, dim3(256), 0, st, a);
+                HIPCHECK(hipGetLastError());
+            } else {
+                const u32 slots = 4 + v.num_rounds + 1;
+                hipLaunchKernelGGL(k_vfy_vanishing, dim3(B), dim3(256), 0, st, v);
+                HIPCHECK(hipGetLastError());
+                hipLaunchKernelGGL(k_vfy_queries, dim3((u32)(((size_t)B * v.num_queries + 63) / 64), slots), dim3(64), 0, st, v);
+                HIPCHECK(hipGetLastError());
+                hipLaunchKernelGGL(k_vfy_finish, g1(B, 64), dim3(64), 0, st, v, slots);
+                HIPCHECK(hipGetLastError());
+            }
+        }
+        if (host) {
+            HIPCHECK(hipMemcpyAsync(W->h_status, W->d_status, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, st));
+            if (mode == CMP_COMPRESS) HIPCHECK(hipMemcpyAsync(W->h_len, W->d_len, (size_t)B * 4, hipMemcpyDeviceToHost, st));
+            if (mode != CMP_VERIFY) HIPCHECK(hipMemcpyAsync(out + done * pb, W->d_cout, (size_t)B * pb, hipMemcpyDeviceToHost, st));
+            HIPCHECK(hipStreamSynchronize(st));
+            memcpy(status + done, W->h_status, (size_t)B * sizeof(int));
+            if (mode == CMP_COMPRESS) memcpy(lengths_out + done, W->h_len, (size_t)B * 4);
+        }
+    }
+    HIPCHECK(hipEventRecord(W->done, st));
+    return P2_OK;
+}
+
+static int cmp_batch_impl(p2_circuit* C, CmpMode mode, size_t batch, const uint8_t* in, const u32* lengths, const uint64_t* verifier_data, size_t vd_len,
+                          uint8_t* out, u32* lengths_out, int* status, hipStream_t st, bool host) {
+    static const char* names[3] = {"p2_compress_batch", "p2_decompress_batch", "p2_verify_compressed_batch"};
+    const std::string name = names[mode];
+    if (!C) return set_error(name + ": null circuit handle"), P2_ERR_INVALID;
+    const size_t vd_words = (size_t)C->vfy_args.cap_words + 4;
+    if (verifier_data && vd_len != vd_words) return set_error("verifier_data must be cap || circuit_digest (" + std::to_string(vd_words) + " words)"), P2_ERR_INVALID;
+    if (!C->vfy_error.empty()) return set_error(C->vfy_error), P2_ERR_INVALID;
+    if (batch == 0) return P2_OK;
+    if (!in || !status || (mode != CMP_VERIFY && !out) || (mode == CMP_COMPRESS ? !lengths_out : !lengths))
+        return set_error(name + ": null buffer"), P2_ERR_INVALID;
+    if (host && mode != CMP_COMPRESS)
+        for (size_t i = 0; i < batch; i++)
+            if (lengths[i] > C->pbytes)
+                return set_error(name + ": length " + std::to_string(lengths[i]) + " of proof " + std::to_string(i) + " exceeds the stride " + std::to_string(C->pbytes)),
+                       P2_ERR_INVALID;
+    VdArg vd{};
+    memcpy(vd.w, verifier_data ? verifier_data : C->verifier_data.data(), vd_words * 8);
+    HIPCHECK(hipSetDevice(C->device));
+    VerifyWs* W = verify_lease(C);
+    if (!W) return P2_ERR_HIP;
+    int rc = cmp_ensure(C, W);
+    if (rc == P2_OK) rc = cmp_run(C, W, mode, batch, in, lengths, out, lengths_out, vd, status, host ? W->stream : st, host);
+    if (rc != P2_OK) (void)hipStreamSynchronize(host ? W->stream : st);
+    verify_return(C, W);
+    return rc;
+}
+
 extern "C" {
 
 int p2_gpu_device_count(void) {
@@ -1473,7 +1647,7 @@ p2_circuit* p2_circuit_load(const uint8_t* blob, size_t len, int device) {
         if (fl > C->n_obs) throw std::runtime_error("final polynomial larger than the observation buffer");
         if (upload(C, &C->d_map_obs, obs.data(), obs.size()) || upload(C, &C->d_map_ser, ser.data(), ser.size())) throw std::runtime_error(g_last_error);
         if (circuit_setup(C)) throw std::runtime_error(g_last_error);
-        if (verify_setup(C)) throw std::runtime_error(g_last_error);
+        if (verify_setup(C) || cmp_setup(C)) throw std::runtime_error(g_last_error);
         return C;
     } catch (std::exception& e) {
         set_error(e.what());
@@ -2077,5 +2251,26 @@ int p2_verify_batch(p2_circuit* C, size_t batch, const uint8_t* proofs, const ui
 }
 int p2_verify_batch_device(p2_circuit* C, size_t batch, const uint8_t* d_proofs, const uint64_t* verifier_data, size_t vd_len, int* d_status, void* stream) {
     return guarded_rc([&] { return verify_batch_impl(C, batch, d_proofs, verifier_data, vd_len, d_status, (hipStream_t)stream, false); });
+}
+int p2_compress_batch(p2_circuit* C, size_t batch, const uint8_t* proofs, const uint64_t* vd, size_t vd_len, uint8_t* out, uint32_t* lengths, int* status) {
+    return guarded_rc([&] { return cmp_batch_impl(C, CMP_COMPRESS, batch, proofs, nullptr, vd, vd_len, out, lengths, status, nullptr, true); });
+}
+int p2_compress_batch_device(p2_circuit* C, size_t batch, const uint8_t* d_proofs, const uint64_t* vd, size_t vd_len, uint8_t* d_out, uint32_t* d_lengths,
+                             int* d_status, void* stream) {
+    return guarded_rc([&] { return cmp_batch_impl(C, CMP_COMPRESS, batch, d_proofs, nullptr, vd, vd_len, d_out, d_lengths, d_status, (hipStream_t)stream, false); });
+}
+int p2_decompress_batch(p2_circuit* C, size_t batch, const uint8_t* cproofs, const uint32_t* lengths, const uint64_t* vd, size_t vd_len, uint8_t* out, int* status) {
+    return guarded_rc([&] { return cmp_batch_impl(C, CMP_DECOMPRESS, batch, cproofs, lengths, vd, vd_len, out, nullptr, status, nullptr, true); });
+}
+int p2_decompress_batch_device(p2_circuit* C, size_t batch, const uint8_t* d_cproofs, const uint32_t* d_lengths, const uint64_t* vd, size_t vd_len, uint8_t* d_out,
+                               int* d_status, void* stream) {
+    return guarded_rc([&] { return cmp_batch_impl(C, CMP_DECOMPRESS, batch, d_cproofs, d_lengths, vd, vd_len, d_out, nullptr, d_status, (hipStream_t)stream, false); });
+}
+int p2_verify_compressed_batch(p2_circuit* C, size_t batch, const uint8_t* cproofs, const uint32_t* lengths, const uint64_t* vd, size_t vd_len, int* status) {
+    return guarded_rc([&] { return cmp_batch_impl(C, CMP_VERIFY, batch, cproofs, lengths, vd, vd_len, nullptr, nullptr, status, nullptr, true); });
+}
+int p2_verify_compressed_batch_device(p2_circuit* C, size_t batch, const uint8_t* d_cproofs, const uint32_t* d_lengths, const uint64_t* vd, size_t vd_len,
+                                      int* d_status, void* stream) {
+    return guarded_rc([&] { return cmp_batch_impl(C, CMP_VERIFY, batch, d_cproofs, d_lengths, vd, vd_len, nullptr, nullptr, d_status, (hipStream_t)stream, false); });
 }
 }

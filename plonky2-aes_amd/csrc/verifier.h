@@ -131,13 +131,38 @@ inline bool verify_merkle_to_cap(const u64* leaf, size_t width, size_t index, co
     return index < cap.size() && cur == cap[index];
 }
 
-// Returns "" on success, else the reason (anyhow-style error text).
-inline std::string verify_proof(const Circuit& C, const VerifierData& vd, const uint8_t* bytes, size_t len) {
+struct ProofQuery {
+    std::vector<std::vector<u64>> init_evals;
+    std::vector<std::vector<Hash4>> init_proofs;
+    std::vector<std::vector<gl::E2>> step_evals;
+    std::vector<std::vector<Hash4>> step_proofs;
+};
+// A proof as read by verify_proof, every field in the order of the byte layout.
+struct ParsedProof {
+    std::vector<Hash4> wires_cap, zs_cap, quot_cap;
+    std::vector<gl::E2> o_constants, o_sigmas, o_wires, o_zs, o_zs_next, o_lk, o_lk_next, o_pp, o_quot;
+    std::vector<std::vector<Hash4>> fri_caps;
+    std::vector<ProofQuery> queries;
+    std::vector<gl::E2> final_poly;
+    u64 pow_witness = 0;
+    std::vector<u64> pis;
+};
+// The Fiat-Shamir challenges of a proof (plonk/get_challenges.rs), and the opening batches they observe.
+struct Transcript {
+    Hash4 pi_hash;
+    std::vector<u64> betas, gammas, deltas, alphas;
+    gl::E2 zeta, fri_alpha;
+    std::vector<gl::E2> batch0, batch1, fri_betas;
+    u64 pow_response = 0;
+    std::vector<size_t> query_idx;
+};
+
+// The reader of verify_proof: shape and canonicality.  Returns "" on success, else the reason.
+inline std::string parse_proof(const Circuit& C, const uint8_t* bytes, size_t len, ParsedProof& pp) {
     using namespace gl;
     const size_t NC = C.cfg.num_challenges, R = C.cfg.num_routed_wires, npp = C.num_partial_products(), nlp = C.num_lookup_polys();
-    const size_t nsldc = C.num_sldc_polys(), qdf = C.cfg.quotient_degree_factor, ncc = C.num_constants_cols();
-    const size_t nsel = C.num_selectors(), nls = C.num_lookup_selectors;
-    const size_t n = C.n(), lde_bits = C.degree_bits + C.cfg.rate_bits, N = (size_t)1 << lde_bits;
+    const size_t qdf = C.cfg.quotient_degree_factor, ncc = C.num_constants_cols();
+    const size_t n = C.n(), lde_bits = C.degree_bits + C.cfg.rate_bits;
     const size_t cap_n = (size_t)1 << C.cfg.cap_height;
     const std::vector<u32> arities = C.reduction_arity_bits();
     // Proof shape (upstream: fri/validate_shape.rs + the fixed layout of ProofWithPublicInputs): the total length and the
@@ -156,22 +181,25 @@ inline std::string verify_proof(const Circuit& C, const VerifierData& vd, const 
         for (auto& e : v) e = r.ext();
         return v;
     };
-    auto wires_cap = read_cap(), zs_cap = read_cap(), quot_cap = read_cap();
-    auto o_constants = read_exts(ncc), o_sigmas = read_exts(R), o_wires = read_exts(C.cfg.num_wires);
+    auto& wires_cap = pp.wires_cap = read_cap();
+    auto& zs_cap = pp.zs_cap = read_cap();
+    auto& quot_cap = pp.quot_cap = read_cap();
+    auto& o_constants = pp.o_constants = read_exts(ncc);
+    auto& o_sigmas = pp.o_sigmas = read_exts(R);
+    auto& o_wires = pp.o_wires = read_exts(C.cfg.num_wires);
     // read_opening_set: ..., plonk_zs, plonk_zs_next, lookup_zs, lookup_zs_next, partial_products, quotient_polys
-    auto o_zs = read_exts(NC), o_zs_next = read_exts(NC);
-    auto o_lk = read_exts(NC * nlp), o_lk_next = read_exts(NC * nlp);
-    auto o_pp = read_exts(NC * npp), o_quot = read_exts(NC * qdf);
-    std::vector<std::vector<Hash4>> fri_caps;
+    auto& o_zs = pp.o_zs = read_exts(NC);
+    auto& o_zs_next = pp.o_zs_next = read_exts(NC);
+    auto& o_lk = pp.o_lk = read_exts(NC * nlp);
+    auto& o_lk_next = pp.o_lk_next = read_exts(NC * nlp);
+    auto& o_pp = pp.o_pp = read_exts(NC * npp);
+    auto& o_quot = pp.o_quot = read_exts(NC * qdf);
+    auto& fri_caps = pp.fri_caps;
+    fri_caps.clear();
     for (size_t i = 0; i < arities.size(); i++) fri_caps.push_back(read_cap());
-    struct Query {
-        std::vector<std::vector<u64>> init_evals;
-        std::vector<std::vector<Hash4>> init_proofs;
-        std::vector<std::vector<E2>> step_evals;
-        std::vector<std::vector<Hash4>> step_proofs;
-    };
     const size_t oracle_cols[4] = {C.num_preprocessed(), C.cfg.num_wires, C.num_zs_cols(), C.num_quotient_cols()};
-    std::vector<Query> queries(C.cfg.num_query_rounds);
+    auto& queries = pp.queries;
+    queries.assign(C.cfg.num_query_rounds, ProofQuery());
     for (auto& q : queries) {
         for (int o = 0; o < 4; o++) {
             std::vector<u64> ev(oracle_cols[o] + (o ? C.salt() : 0));  // blinded oracles carry SALT_SIZE extra leaf elements
@@ -186,12 +214,13 @@ inline std::string verify_proof(const Circuit& C, const VerifierData& vd, const 
     }
     size_t final_len = n;
     for (u32 a : arities) final_len >>= a;
-    auto final_poly = read_exts(final_len);
-    u64 pow_witness = r.r64();
+    auto& final_poly = pp.final_poly = read_exts(final_len);
+    u64 pow_witness = pp.pow_witness = r.r64();
     // public-input trailer (circuits with k >= 1 public inputs): u64 k || k values
     const size_t num_pi = C.pi_slots.size();
     u64 pi_count = 0;
-    std::vector<u64> pis(num_pi);
+    auto& pis = pp.pis;
+    pis.assign(num_pi, 0);
     if (num_pi) {
         pi_count = r.r64();
         for (auto& v : pis) v = r.r64();
@@ -231,14 +260,28 @@ inline std::string verify_proof(const Circuit& C, const VerifierData& vd, const 
             bits -= arities[k];
         }
     }
+    return "";
+}
 
-    // ---- challenges (plonk/get_challenges.rs)
+// Fiat-Shamir on a parsed proof: every challenge up to the query indices (the PoW response is left for the caller to check).
+inline Transcript fiat_shamir(const Circuit& C, const VerifierData& vd, const ParsedProof& pp) {
+    using namespace gl;
+    const size_t NC = C.cfg.num_challenges, nlp = C.num_lookup_polys();
+    const size_t lde_bits = C.degree_bits + C.cfg.rate_bits, N = (size_t)1 << lde_bits;
+    const size_t num_pi = C.pi_slots.size();
+    Transcript T;
+    auto& betas = T.betas;
+    auto& gammas = T.gammas;
+    auto& deltas = T.deltas;
+    auto& alphas = T.alphas;
+    auto& batch0 = T.batch0;
+    auto& batch1 = T.batch1;
+    auto& fri_betas = T.fri_betas;
     HostChallenger ch;
     ch.observe_hash(vd.circuit_digest);
-    const Hash4 pi_hash = h_hash_no_pad(pis.data(), num_pi);  // 0^4 for zero public inputs
-    ch.observe_hash(pi_hash);
-    for (auto& h : wires_cap) ch.observe_hash(h);
-    std::vector<u64> betas, gammas, deltas, alphas;
+    T.pi_hash = h_hash_no_pad(pp.pis.data(), num_pi);  // 0^4 for zero public inputs
+    ch.observe_hash(T.pi_hash);
+    for (auto& h : pp.wires_cap) ch.observe_hash(h);
     for (size_t i = 0; i < NC; i++) betas.push_back(ch.challenge());
     for (size_t i = 0; i < NC; i++) gammas.push_back(ch.challenge());
     if (nlp) {
@@ -246,28 +289,98 @@ inline std::string verify_proof(const Circuit& C, const VerifierData& vd, const 
         deltas.insert(deltas.end(), gammas.begin(), gammas.end());
         for (size_t i = 0; i < 2 * NC; i++) deltas.push_back(ch.challenge());
     }
-    for (auto& h : zs_cap) ch.observe_hash(h);
+    for (auto& h : pp.zs_cap) ch.observe_hash(h);
     for (size_t i = 0; i < NC; i++) alphas.push_back(ch.challenge());
-    for (auto& h : quot_cap) ch.observe_hash(h);
-    E2 zeta = ch.ext_challenge();
-    std::vector<E2> batch0, batch1;
-    for (auto* v : {&o_constants, &o_sigmas, &o_wires, &o_zs, &o_pp, &o_quot, &o_lk}) batch0.insert(batch0.end(), v->begin(), v->end());
-    for (auto* v : {&o_zs_next, &o_lk_next}) batch1.insert(batch1.end(), v->begin(), v->end());
+    for (auto& h : pp.quot_cap) ch.observe_hash(h);
+    T.zeta = ch.ext_challenge();
+    for (auto* v : {&pp.o_constants, &pp.o_sigmas, &pp.o_wires, &pp.o_zs, &pp.o_pp, &pp.o_quot, &pp.o_lk}) batch0.insert(batch0.end(), v->begin(), v->end());
+    for (auto* v : {&pp.o_zs_next, &pp.o_lk_next}) batch1.insert(batch1.end(), v->begin(), v->end());
     for (auto& e : batch0) ch.observe_ext(e);
     for (auto& e : batch1) ch.observe_ext(e);
-    E2 fri_alpha = ch.ext_challenge();
-    std::vector<E2> fri_betas;
-    for (auto& cap : fri_caps) {
+    T.fri_alpha = ch.ext_challenge();
+    for (auto& cap : pp.fri_caps) {
         for (auto& h : cap) ch.observe_hash(h);
         fri_betas.push_back(ch.ext_challenge());
     }
-    for (auto& e : final_poly) ch.observe_ext(e);
-    ch.observe(pow_witness);
-    u64 pow_response = ch.challenge();
-    if ((pow_response >> (64 - C.cfg.pow_bits)) != 0) return "Invalid proof-of-work witness.";
-    std::vector<size_t> query_idx;
-    for (size_t i = 0; i < queries.size(); i++) query_idx.push_back((size_t)(ch.challenge() % N));
+    for (auto& e : pp.final_poly) ch.observe_ext(e);
+    ch.observe(pp.pow_witness);
+    T.pow_response = ch.challenge();
+    for (size_t i = 0; i < pp.queries.size(); i++) T.query_idx.push_back((size_t)(ch.challenge() % N));
+    return T;
+}
 
+// fri_combine_initial: the opening batches (reduced to red0 at zeta, red1 at g*zeta) against a query's initial-tree leaves at
+// subgroup_x.  The salt elements at the end of a blinded leaf take no part in the combination (unsalted_eval).
+inline gl::E2 fri_combine_initial(const Circuit& C, const ProofQuery& q, u64 subgroup_x, const Transcript& T, gl::E2 red0, gl::E2 red1, gl::E2 g_zeta) {
+    using namespace gl;
+    const size_t NC = C.cfg.num_challenges, nzpp = C.num_zs_pp();
+    const E2 fri_alpha = T.fri_alpha, zeta = T.zeta;
+    std::vector<u64> e0, e1;
+    const size_t zc_ = C.num_zs_cols();
+    e0.insert(e0.end(), q.init_evals[0].begin(), q.init_evals[0].end());
+    e0.insert(e0.end(), q.init_evals[1].begin(), q.init_evals[1].begin() + C.cfg.num_wires);
+    e0.insert(e0.end(), q.init_evals[2].begin(), q.init_evals[2].begin() + nzpp);
+    e0.insert(e0.end(), q.init_evals[3].begin(), q.init_evals[3].begin() + C.num_quotient_cols());
+    e0.insert(e0.end(), q.init_evals[2].begin() + nzpp, q.init_evals[2].begin() + zc_);
+    e1.insert(e1.end(), q.init_evals[2].begin(), q.init_evals[2].begin() + NC);
+    e1.insert(e1.end(), q.init_evals[2].begin() + nzpp, q.init_evals[2].begin() + zc_);
+    auto reduce_base = [&](const std::vector<u64>& v) {
+        E2 acc = e2(0);
+        for (size_t k = v.size(); k-- > 0;) acc = add(mul(acc, fri_alpha), e2(v[k]));
+        return acc;
+    };
+    E2 sum = mul(sub(reduce_base(e0), red0), inv(sub(e2(subgroup_x), zeta)));
+    sum = mul(sum, pow(fri_alpha, e1.size()));
+    sum = add(sum, mul(sub(reduce_base(e1), red1), inv(sub(e2(subgroup_x), g_zeta))));
+    return sum;
+}
+// compute_evaluation: interpolate the coset {(coset_start*g^k, evals_rev[k])} that holds subgroup_x and evaluate it at beta
+inline gl::E2 fri_compute_evaluation(const std::vector<gl::E2>& evals, size_t x_index, u64 subgroup_x, u32 ab, gl::E2 beta) {
+    using namespace gl;
+    size_t arity = (size_t)1 << ab;
+    size_t within = x_index & (arity - 1);
+    u64 g = root_of_unity((int)ab);
+    u32 rev_within = bitrev((u32)within, (int)ab);
+    u64 coset_start = mul(subgroup_x, pow(g, arity - rev_within));
+    std::vector<u64> xs(arity);
+    std::vector<E2> ys(arity);
+    for (size_t t = 0; t < arity; t++) {
+        xs[t] = mul(coset_start, pow(g, t));
+        ys[t] = evals[bitrev((u32)t, (int)ab)];
+    }
+    E2 acc = e2(0);
+    for (size_t t = 0; t < arity; t++) {
+        E2 num = e2(1);
+        u64 den = 1;
+        for (size_t m = 0; m < arity; m++)
+            if (m != t) {
+                num = mul(num, sub(beta, e2(xs[m])));
+                den = mul(den, sub(xs[t], xs[m]));
+            }
+        acc = add(acc, mul(mul(ys[t], num), inv(den)));
+    }
+    return acc;
+}
+
+// The checks after the transcript: the vanishing identity at zeta, then FRI.
+inline std::string verify_parsed(const Circuit& C, const VerifierData& vd, const ParsedProof& pp, const Transcript& T) {
+    using namespace gl;
+    const size_t NC = C.cfg.num_challenges, R = C.cfg.num_routed_wires, npp = C.num_partial_products(), nlp = C.num_lookup_polys();
+    const size_t nsldc = C.num_sldc_polys(), qdf = C.cfg.quotient_degree_factor;
+    const size_t nsel = C.num_selectors(), nls = C.num_lookup_selectors;
+    const size_t n = C.n(), lde_bits = C.degree_bits + C.cfg.rate_bits;
+    const std::vector<u32> arities = C.reduction_arity_bits();
+    const auto &wires_cap = pp.wires_cap, &zs_cap = pp.zs_cap, &quot_cap = pp.quot_cap;
+    const auto &o_constants = pp.o_constants, &o_sigmas = pp.o_sigmas, &o_wires = pp.o_wires, &o_zs = pp.o_zs, &o_zs_next = pp.o_zs_next;
+    const auto &o_lk = pp.o_lk, &o_lk_next = pp.o_lk_next, &o_pp = pp.o_pp, &o_quot = pp.o_quot;
+    const auto& fri_caps = pp.fri_caps;
+    const auto& queries = pp.queries;
+    const auto& final_poly = pp.final_poly;
+    const auto &betas = T.betas, &gammas = T.gammas, &deltas = T.deltas, &alphas = T.alphas;
+    const auto &batch0 = T.batch0, &batch1 = T.batch1, &fri_betas = T.fri_betas;
+    const auto& query_idx = T.query_idx;
+    const E2 zeta = T.zeta, fri_alpha = T.fri_alpha;
+    const Hash4 pi_hash = T.pi_hash;
     // ---- vanishing polynomial at zeta (eval_vanishing_poly)
     E2 zeta_pow_n = exp_pow2(zeta, (int)C.degree_bits);
     E2 z_h_zeta = sub(zeta_pow_n, e2(1));
@@ -382,35 +495,16 @@ inline std::string verify_proof(const Circuit& C, const VerifierData& vd, const 
         return acc;
     };
     E2 red0 = reduce(batch0), red1 = reduce(batch1);
-    const size_t nzpp = C.num_zs_pp();
     const std::vector<Hash4>* init_caps[4] = {&vd.constants_sigmas_cap, &wires_cap, &zs_cap, &quot_cap};
     u64 w_lde = root_of_unity((int)lde_bits);
     for (size_t qi = 0; qi < queries.size(); qi++) {
-        const Query& q = queries[qi];
+        const ProofQuery& q = queries[qi];
         size_t x_index = query_idx[qi];
         for (int o = 0; o < 4; o++)
             if (!verify_merkle_to_cap(q.init_evals[o].data(), q.init_evals[o].size(), x_index, *init_caps[o], q.init_proofs[o]))
                 return "Invalid Merkle proof (initial tree).";
         u64 subgroup_x = mul(MULT_GEN, pow(w_lde, bitrev((u32)x_index, (int)lde_bits)));
-        // fri_combine_initial
-        std::vector<u64> e0, e1;
-        // unsalted_eval: the salt elements at the end of a blinded leaf take no part in the combination
-        const size_t zc_ = C.num_zs_cols();
-        e0.insert(e0.end(), q.init_evals[0].begin(), q.init_evals[0].end());
-        e0.insert(e0.end(), q.init_evals[1].begin(), q.init_evals[1].begin() + C.cfg.num_wires);
-        e0.insert(e0.end(), q.init_evals[2].begin(), q.init_evals[2].begin() + nzpp);
-        e0.insert(e0.end(), q.init_evals[3].begin(), q.init_evals[3].begin() + C.num_quotient_cols());
-        e0.insert(e0.end(), q.init_evals[2].begin() + nzpp, q.init_evals[2].begin() + zc_);
-        e1.insert(e1.end(), q.init_evals[2].begin(), q.init_evals[2].begin() + NC);
-        e1.insert(e1.end(), q.init_evals[2].begin() + nzpp, q.init_evals[2].begin() + zc_);
-        auto reduce_base = [&](const std::vector<u64>& v) {
-            E2 acc = e2(0);
-            for (size_t k = v.size(); k-- > 0;) acc = add(mul(acc, fri_alpha), e2(v[k]));
-            return acc;
-        };
-        E2 sum = mul(sub(reduce_base(e0), red0), inv(sub(e2(subgroup_x), zeta)));
-        sum = mul(sum, pow(fri_alpha, e1.size()));
-        sum = add(sum, mul(sub(reduce_base(e1), red1), inv(sub(e2(subgroup_x), g_zeta))));
+        E2 sum = fri_combine_initial(C, q, subgroup_x, T, red0, red1, g_zeta);
         E2 old_eval = sum;
         for (size_t k = 0; k < arities.size(); k++) {
             u32 ab = arities[k];
@@ -418,28 +512,7 @@ inline std::string verify_proof(const Circuit& C, const VerifierData& vd, const 
             const std::vector<E2>& evals = q.step_evals[k];
             size_t coset_index = x_index >> ab, within = x_index & (arity - 1);
             if (!eq(evals[within], old_eval)) return "FRI fold consistency check failed.";
-            // compute_evaluation: interpolate {(coset_start*g^k, evals_rev[k])} and evaluate at beta
-            u64 g = root_of_unity((int)ab);
-            u32 rev_within = bitrev((u32)within, (int)ab);
-            u64 coset_start = mul(subgroup_x, pow(g, arity - rev_within));
-            std::vector<u64> xs(arity);
-            std::vector<E2> ys(arity);
-            for (size_t t = 0; t < arity; t++) {
-                xs[t] = mul(coset_start, pow(g, t));
-                ys[t] = evals[bitrev((u32)t, (int)ab)];
-            }
-            E2 acc = e2(0);
-            for (size_t t = 0; t < arity; t++) {
-                E2 num = e2(1);
-                u64 den = 1;
-                for (size_t m = 0; m < arity; m++)
-                    if (m != t) {
-                        num = mul(num, sub(fri_betas[k], e2(xs[m])));
-                        den = mul(den, sub(xs[t], xs[m]));
-                    }
-                acc = add(acc, mul(mul(ys[t], num), inv(den)));
-            }
-            old_eval = acc;
+            old_eval = fri_compute_evaluation(evals, x_index, subgroup_x, ab, fri_betas[k]);
             std::vector<u64> flat;
             for (auto& e : evals) {
                 flat.push_back(e.a);
@@ -454,6 +527,25 @@ inline std::string verify_proof(const Circuit& C, const VerifierData& vd, const 
         if (!eq(fe, old_eval)) return "Final polynomial evaluation is invalid.";
     }
     return "";
+}
+
+// Shape reasons of compressed proofs (compress.h): their layout is a function of the written query
+// indices, so each of these is a SHAPE verdict, like a Merkle path of the wrong depth in a full proof.
+enum CompressedShape { CS_INDEX_RANGE, CS_SIBLING_COUNT, CS_INDICES };
+inline std::string compressed_shape_reason(CompressedShape s) {
+    if (s == CS_INDEX_RANGE) return "query index out of range";
+    if (s == CS_SIBLING_COUNT) return "wrong sibling count in compressed proof";
+    return "query indices differ from the transcript";
+}
+
+// Returns "" on success, else the reason (anyhow-style error text).
+inline std::string verify_proof(const Circuit& C, const VerifierData& vd, const uint8_t* bytes, size_t len) {
+    ParsedProof pp;
+    std::string err = parse_proof(C, bytes, len, pp);
+    if (!err.empty()) return err;
+    const Transcript T = fiat_shamir(C, vd, pp);
+    if ((T.pow_response >> (64 - C.cfg.pow_bits)) != 0) return "Invalid proof-of-work witness.";
+    return verify_parsed(C, vd, pp, T);
 }
 
 }  // namespace p2
