@@ -674,7 +674,7 @@ int p2_verify_compressed(const uint8_t* blob, size_t blob_len, const uint64_t* v
 int p2_proof_public_inputs(const uint8_t* blob, size_t blob_len, const uint8_t* proof, size_t proof_len, uint64_t* out, size_t cap, size_t* n_written) {
     try {
         Circuit c = deserialize(blob, blob_len);  // the whole blob: p2_circuit_public_inputs is the per-proof form
-        return read_public_inputs(c, proof_bytes(c), proof, proof_len, out, cap, n_written);
+        return read_public_inputs(make_proof_layout(c), proof, proof_len, out, cap, n_written);
     } catch (std::exception& e) {
         return set_error(e.what()), P2_ERR_INVALID;
     }

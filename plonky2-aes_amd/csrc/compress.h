@@ -21,43 +21,6 @@
 
 namespace p2 {
 
-// Sizes of a circuit's full proof that the compressed layout shares.
-struct CompressShape {
-    size_t Q = 0, prefix = 0, tail = 0, final_len = 0, cap_h = 0, lde_bits = 0;
-    size_t cols[4] = {0, 0, 0, 0};  // leaf widths of the initial trees (salt included)
-    std::vector<u32> arities;
-    std::vector<size_t> depth;      // [tree]: tree 0 = the initial trees, tree 1 + r = FRI round r
-    std::vector<size_t> shift;      // [tree]: leaf index of the tree = query index >> shift
-};
-inline CompressShape compress_shape(const Circuit& c) {
-    CompressShape s;
-    const size_t cap_n = (size_t)1 << c.cfg.cap_height, NC = c.cfg.num_challenges;
-    s.Q = c.cfg.num_query_rounds;
-    s.cap_h = c.cfg.cap_height;
-    s.lde_bits = c.degree_bits + c.cfg.rate_bits;
-    s.arities = c.reduction_arity_bits();
-    const size_t n_open = c.num_constants_cols() + c.cfg.num_routed_wires + c.cfg.num_wires + 2 * NC + NC * c.num_partial_products() +
-                          c.num_quotient_cols() + 2 * NC * c.num_lookup_polys();
-    s.prefix = 8 * (3 * 4 * cap_n + 2 * n_open + s.arities.size() * 4 * cap_n);
-    s.final_len = c.n();
-    for (u32 a : s.arities) s.final_len >>= a;
-    s.tail = 8 * (2 * s.final_len + 1) + pi_trailer_bytes(c);
-    s.cols[0] = c.num_preprocessed();
-    s.cols[1] = c.cfg.num_wires + c.salt();
-    s.cols[2] = c.num_zs_cols() + c.salt();
-    s.cols[3] = c.num_quotient_cols() + c.salt();
-    s.depth.push_back(s.lde_bits - s.cap_h);
-    s.shift.push_back(0);
-    size_t bits = s.lde_bits, sh = 0;
-    for (u32 a : s.arities) {
-        bits -= a;
-        sh += a;
-        s.depth.push_back(bits - s.cap_h);
-        s.shift.push_back(sh);
-    }
-    return s;
-}
-
 // The layout of one compressed proof, from its query indices.
 struct CompressLayout {
     std::vector<std::vector<size_t>> leaf, rep, off;  // [tree][query]: leaf index, first query with that leaf, byte offset of its block
@@ -65,21 +28,25 @@ struct CompressLayout {
     size_t len = 0;
 };
 inline size_t popcount(const std::vector<bool>& v) { return (size_t)std::count(v.begin(), v.end(), true); }
-inline size_t block_bytes(const CompressShape& s, size_t t, size_t kept) {
-    if (t == 0) return 8 * (s.cols[0] + s.cols[1] + s.cols[2] + s.cols[3]) + 4 * (1 + 32 * kept);
-    return 16 * (((size_t)1 << s.arities[t - 1]) - 1) + 1 + 32 * kept;
+// One stored opening of tree t: the leaf words (initial tree o's row, or a FRI coset without the evaluation left out), the
+// count byte, the kept siblings; an initial-tree block holds four of them.
+inline size_t leaf_bytes(const ProofLayout& s, size_t t, int o) { return t == 0 ? 8 * (size_t)s.init[o].width : 8 * (size_t)s.step[t - 1].width - 16; }
+inline size_t block_bytes(const ProofLayout& s, size_t t, size_t kept) {
+    size_t b = 0;
+    for (int o = 0; o < (t == 0 ? 4 : 1); o++) b += leaf_bytes(s, t, o) + 1 + 32 * kept;
+    return b;
 }
-inline CompressLayout compress_layout(const CompressShape& s, const std::vector<size_t>& idx) {
+inline CompressLayout compress_layout(const ProofLayout& s, const std::vector<size_t>& idx) {
     CompressLayout L;
-    const size_t T = 1 + s.arities.size();
-    L.leaf.assign(T, std::vector<size_t>(s.Q));
+    const size_t T = s.num_trees(), Q = s.num_queries;
+    L.leaf.assign(T, std::vector<size_t>(Q));
     L.rep = L.off = L.leaf;
     L.kept.resize(T);
-    size_t pos = s.prefix + 4 * s.Q;
+    size_t pos = s.queries_off + 4 * Q;
     for (size_t t = 0; t < T; t++) {
-        const size_t depth = s.depth[t], nl = (size_t)1 << (depth + s.cap_h);
-        for (size_t q = 0; q < s.Q; q++) {
-            L.leaf[t][q] = idx[q] >> s.shift[t];
+        const size_t depth = s.tree(t).depth, nl = (size_t)1 << (depth + s.cap_height);
+        for (size_t q = 0; q < Q; q++) {
+            L.leaf[t][q] = idx[q] >> s.tree(t).shift;
             L.rep[t][q] = q;
             for (size_t e = 0; e < q; e++)
                 if (L.leaf[t][e] == L.leaf[t][q]) {
@@ -90,25 +57,25 @@ inline CompressLayout compress_layout(const CompressShape& s, const std::vector<
         // compress_merkle_proofs: every node on a query's path below the cap is known; walking the queries in order, a
         // sibling that is not yet known is kept and becomes known
         std::set<size_t> known;
-        for (size_t q = 0; q < s.Q; q++)
+        for (size_t q = 0; q < Q; q++)
             for (size_t j = 0; j < depth; j++) known.insert((L.leaf[t][q] + nl) >> j);
-        L.kept[t].assign(s.Q, std::vector<bool>(depth, false));
-        for (size_t q = 0; q < s.Q; q++) {
+        L.kept[t].assign(Q, std::vector<bool>(depth, false));
+        for (size_t q = 0; q < Q; q++) {
             size_t node = L.leaf[t][q] + nl;
             for (size_t l = 0; l < depth; l++, node >>= 1)
                 if (known.insert(node ^ 1).second) L.kept[t][q][l] = true;
         }
         std::vector<size_t> order;
-        for (size_t q = 0; q < s.Q; q++)
+        for (size_t q = 0; q < Q; q++)
             if (L.rep[t][q] == q) order.push_back(q);
         std::sort(order.begin(), order.end(), [&](size_t a, size_t b) { return L.leaf[t][a] < L.leaf[t][b]; });
         for (size_t q : order) {
             L.off[t][q] = pos;
             pos += block_bytes(s, t, popcount(L.kept[t][q]));
         }
-        for (size_t q = 0; q < s.Q; q++) L.off[t][q] = L.off[t][L.rep[t][q]];
+        for (size_t q = 0; q < Q; q++) L.off[t][q] = L.off[t][L.rep[t][q]];
     }
-    L.len = pos + s.tail;
+    L.len = pos + s.tail_bytes();
     return L;
 }
 
@@ -167,17 +134,18 @@ inline std::string compress_proof(const Circuit& c, const VerifierData& vd, cons
     std::string err = parse_proof(c, bytes, len, pp);
     if (!err.empty()) return err;
     const Transcript T = fiat_shamir(c, vd, pp);
-    const CompressShape s = compress_shape(c);
+    const ProofLayout s = make_proof_layout(c);
+    const size_t Q = s.num_queries, prefix = s.queries_off, tail_len = s.tail_bytes();
     const CompressLayout L = compress_layout(s, T.query_idx);
     out.assign(L.len, 0);
-    memcpy(out.data(), bytes, s.prefix);
-    memcpy(out.data() + L.len - s.tail, bytes + len - s.tail, s.tail);
-    for (size_t q = 0; q < s.Q; q++) {
+    memcpy(out.data(), bytes, prefix);
+    memcpy(out.data() + L.len - tail_len, bytes + s.final_off, tail_len);
+    for (size_t q = 0; q < Q; q++) {
         const u32 v = (u32)T.query_idx[q];
-        memcpy(&out[s.prefix + 4 * q], &v, 4);
+        memcpy(&out[prefix + 4 * q], &v, 4);
     }
     for (size_t t = 0; t < L.leaf.size(); t++)
-        for (size_t q = 0; q < s.Q; q++) {
+        for (size_t q = 0; q < Q; q++) {
             if (L.rep[t][q] != q) continue;
             const ProofQuery& pq = pp.queries[q];
             ByteWriter w{out, L.off[t][q]};
@@ -192,8 +160,8 @@ inline std::string compress_proof(const Circuit& c, const VerifierData& vd, cons
                     siblings(pq.init_proofs[o]);
                 }
             } else {
-                const size_t r = t - 1, arity = (size_t)1 << s.arities[r];
-                const size_t left_out = (T.query_idx[q] >> s.shift[r]) & (arity - 1);  // what the fold check recomputes
+                const size_t r = t - 1, arity = s.step[r].width / 2;
+                const size_t left_out = (T.query_idx[q] >> s.tree(r).shift) & (arity - 1);  // what the fold check recomputes
                 for (size_t k = 0; k < arity; k++)
                     if (k != left_out) w.ext(pq.step_evals[r][k]);
                 siblings(pq.step_proofs[r]);
@@ -231,12 +199,13 @@ inline bool decompress_paths(const CompressLayout& L, size_t t, size_t depth, si
 inline std::string decompress_proof(const Circuit& c, const VerifierData& vd, const uint8_t* cb, size_t clen, std::vector<uint8_t>& out,
                                     bool check_pow) {
     using namespace gl;
-    const CompressShape s = compress_shape(c);
-    if (clen < s.prefix + 4 * s.Q) return "proof truncated";
-    std::vector<size_t> idx(s.Q);
-    for (size_t q = 0; q < s.Q; q++) {
+    const ProofLayout s = make_proof_layout(c);
+    const size_t Q = s.num_queries, prefix = s.queries_off, tail_len = s.tail_bytes();
+    if (clen < prefix + 4 * Q) return "proof truncated";
+    std::vector<size_t> idx(Q);
+    for (size_t q = 0; q < Q; q++) {
         u32 v;
-        memcpy(&v, cb + s.prefix + 4 * q, 4);
+        memcpy(&v, cb + prefix + 4 * q, 4);
         if ((v >> s.lde_bits) != 0) return compressed_shape_reason(CS_INDEX_RANGE);
         idx[q] = v;
     }
@@ -245,17 +214,17 @@ inline std::string decompress_proof(const Circuit& c, const VerifierData& vd, co
     if (clen > L.len) return "trailing bytes in proof";
     const size_t T = L.leaf.size();
     for (size_t t = 0; t < T; t++)
-        for (size_t q = 0; q < s.Q; q++) {
+        for (size_t q = 0; q < Q; q++) {
             if (L.rep[t][q] != q) continue;
             const size_t k = popcount(L.kept[t][q]);
             size_t at = L.off[t][q];
             for (int o = 0; o < (t == 0 ? 4 : 1); o++) {
-                at += t == 0 ? 8 * s.cols[o] : 16 * (((size_t)1 << s.arities[t - 1]) - 1);
+                at += leaf_bytes(s, t, o);
                 if (cb[at] != k) return compressed_shape_reason(CS_SIBLING_COUNT);
                 at += 1 + 32 * k;
             }
         }
-    const size_t tail = L.len - s.tail, pi_cnt = tail + 8 * (2 * s.final_len + 1);
+    const size_t tail = L.len - tail_len, pi_cnt = tail + (s.pi_cnt_off - s.final_off);
     if (!c.pi_slots.empty()) {
         u64 k;
         memcpy(&k, cb + pi_cnt, 8);
@@ -270,31 +239,26 @@ inline std::string decompress_proof(const Circuit& c, const VerifierData& vd, co
         }
         return true;
     };
-    if (!canon(0, s.prefix / 8) || !canon(tail, 2 * s.final_len + 1) || !canon(pi_cnt + 8, c.pi_slots.size())) return "non-canonical field element";
+    if (!canon(0, prefix / 8) || !canon(tail, 2 * s.final_len + 1) || !canon(pi_cnt + 8, c.pi_slots.size())) return "non-canonical field element";
     for (size_t t = 0; t < T; t++)
-        for (size_t q = 0; q < s.Q; q++) {
+        for (size_t q = 0; q < Q; q++) {
             if (L.rep[t][q] != q) continue;
             const size_t k = popcount(L.kept[t][q]);
             size_t at = L.off[t][q];
             for (int o = 0; o < (t == 0 ? 4 : 1); o++) {
-                const size_t ev = t == 0 ? s.cols[o] : 2 * (((size_t)1 << s.arities[t - 1]) - 1);
+                const size_t ev = leaf_bytes(s, t, o) / 8;
                 if (!canon(at, ev) || !canon(at + 8 * ev + 1, 4 * k)) return "non-canonical field element";
                 at += 8 * ev + 1 + 32 * k;
             }
         }
     // the transcript reads the prefix and the tail only: parse them as a full proof with empty query blocks
-    std::vector<uint8_t> full(proof_bytes(c), 0);
-    memcpy(full.data(), cb, s.prefix);
-    memcpy(full.data() + full.size() - s.tail, cb + tail, s.tail);
-    {
-        size_t at = s.prefix;
-        for (size_t q = 0; q < s.Q; q++)
-            for (size_t t = 0; t < T; t++)
-                for (int o = 0; o < (t == 0 ? 4 : 1); o++) {
-                    at += t == 0 ? 8 * s.cols[o] : 16 * ((size_t)1 << s.arities[t - 1]);
-                    full[at] = (uint8_t)s.depth[t];
-                    at += 1 + 32 * s.depth[t];
-                }
+    std::vector<uint8_t> full(s.bytes, 0);
+    memcpy(full.data(), cb, prefix);
+    memcpy(full.data() + s.final_off, cb + tail, tail_len);
+    for (size_t q = 0; q < Q; q++) {
+        uint8_t* qb = &full[s.queries_off + q * s.query_bytes];
+        for (auto& p : s.init) qb[p.cnt_off] = (uint8_t)p.depth;
+        for (auto& p : s.step) qb[p.cnt_off] = (uint8_t)p.depth;
     }
     ParsedProof pp;
     std::string err = parse_proof(c, full.data(), full.size(), pp);
@@ -314,35 +278,35 @@ inline std::string decompress_proof(const Circuit& c, const VerifierData& vd, co
         return h;
     };
     // initial trees: the leaf rows, then each tree's paths
-    for (size_t q = 0; q < s.Q; q++) {
+    for (size_t q = 0; q < Q; q++) {
         size_t at = L.off[0][q];
         const size_t k = popcount(L.kept[0][L.rep[0][q]]);
         for (int o = 0; o < 4; o++) {
             auto& ev = pp.queries[q].init_evals[o];
-            for (size_t i = 0; i < s.cols[o]; i++) ev[i] = rd64(at + 8 * i);
-            at += 8 * s.cols[o] + 1 + 32 * k;
+            for (size_t i = 0; i < s.init[o].width; i++) ev[i] = rd64(at + 8 * i);
+            at += leaf_bytes(s, 0, o) + 1 + 32 * k;
         }
     }
     auto rebuild = [&](size_t t, const std::vector<Hash4>& leaf_hash, const std::vector<size_t>& stored_at, std::vector<std::vector<Hash4>>& paths) {
-        std::vector<std::vector<Hash4>> stored(s.Q);
-        for (size_t q = 0; q < s.Q; q++)
+        std::vector<std::vector<Hash4>> stored(Q);
+        for (size_t q = 0; q < Q; q++)
             for (size_t i = 0; i < popcount(L.kept[t][q]); i++) stored[q].push_back(rdhash(stored_at[q] + 32 * i));
-        return decompress_paths(L, t, s.depth[t], s.cap_h, leaf_hash, stored, paths);
+        return decompress_paths(L, t, s.tree(t).depth, s.cap_height, leaf_hash, stored, paths);
     };
     for (int o = 0; o < 4; o++) {
-        std::vector<Hash4> lh(s.Q);
-        std::vector<size_t> stored_at(s.Q);
-        for (size_t q = 0; q < s.Q; q++) {
+        std::vector<Hash4> lh(Q);
+        std::vector<size_t> stored_at(Q);
+        for (size_t q = 0; q < Q; q++) {
             const auto& ev = pp.queries[q].init_evals[o];
             lh[q] = h_hash_or_noop(ev.data(), ev.size());
             size_t at = L.off[0][q];
             const size_t k = popcount(L.kept[0][L.rep[0][q]]);
-            for (int o2 = 0; o2 < o; o2++) at += 8 * s.cols[o2] + 1 + 32 * k;
-            stored_at[q] = at + 8 * s.cols[o] + 1;
+            for (int o2 = 0; o2 < o; o2++) at += leaf_bytes(s, 0, o2) + 1 + 32 * k;
+            stored_at[q] = at + leaf_bytes(s, 0, o) + 1;
         }
         std::vector<std::vector<Hash4>> paths;
         if (!rebuild(0, lh, stored_at, paths)) return "internal: Merkle path reconstruction";
-        for (size_t q = 0; q < s.Q; q++) pp.queries[q].init_proofs[o] = paths[q];
+        for (size_t q = 0; q < Q; q++) pp.queries[q].init_proofs[o] = paths[q];
     }
     // FRI rounds: the evaluation the first query of a coset leaves out is the value its fold check expects
     const E2 g_zeta = mul(Tr.zeta, root_of_unity((int)c.degree_bits));
@@ -353,20 +317,20 @@ inline std::string decompress_proof(const Circuit& c, const VerifierData& vd, co
     };
     const E2 red0 = reduce(Tr.batch0), red1 = reduce(Tr.batch1);
     const u64 w_lde = root_of_unity((int)s.lde_bits);
-    std::vector<u64> sx0(s.Q);
-    for (size_t q = 0; q < s.Q; q++) sx0[q] = mul(MULT_GEN, pow(w_lde, bitrev((u32)idx[q], (int)s.lde_bits)));
-    for (size_t r = 0; r < s.arities.size(); r++) {
-        const size_t t = 1 + r, arity = (size_t)1 << s.arities[r];
-        std::vector<Hash4> lh(s.Q);
-        std::vector<size_t> stored_at(s.Q);
-        for (size_t q = 0; q < s.Q; q++) {
+    std::vector<u64> sx0(Q);
+    for (size_t q = 0; q < Q; q++) sx0[q] = mul(MULT_GEN, pow(w_lde, bitrev((u32)idx[q], (int)s.lde_bits)));
+    for (size_t r = 0; r < s.step.size(); r++) {
+        const size_t t = 1 + r, arity = s.step[r].width / 2;
+        std::vector<Hash4> lh(Q);
+        std::vector<size_t> stored_at(Q);
+        for (size_t q = 0; q < Q; q++) {
             auto& ev = pp.queries[q].step_evals[r];
             const size_t rq = L.rep[t][q];
             if (rq == q) {
-                const size_t left_out = (idx[q] >> s.shift[r]) & (arity - 1);
+                const size_t left_out = (idx[q] >> s.tree(r).shift) & (arity - 1);
                 const E2 v = r == 0 ? fri_combine_initial(c, pp.queries[q], sx0[q], Tr, red0, red1, g_zeta)
-                                    : fri_compute_evaluation(pp.queries[q].step_evals[r - 1], idx[q] >> s.shift[r - 1],
-                                                             exp_pow2(sx0[q], (int)s.shift[r - 1]), s.arities[r - 1], Tr.fri_betas[r - 1]);
+                                    : fri_compute_evaluation(pp.queries[q].step_evals[r - 1], idx[q] >> s.tree(r - 1).shift,
+                                                             exp_pow2(sx0[q], (int)s.tree(r - 1).shift), s.arity_bits(r - 1), Tr.fri_betas[r - 1]);
                 for (size_t k = 0, i = 0; k < arity; k++) {
                     if (k == left_out) {
                         ev[k] = v;
@@ -381,11 +345,11 @@ inline std::string decompress_proof(const Circuit& c, const VerifierData& vd, co
             std::vector<u64> flat;
             for (auto& e : ev) flat.push_back(e.a), flat.push_back(e.b);
             lh[q] = h_hash_or_noop(flat.data(), flat.size());
-            stored_at[q] = L.off[t][q] + 16 * (arity - 1) + 1;
+            stored_at[q] = L.off[t][q] + leaf_bytes(s, t, 0) + 1;
         }
         std::vector<std::vector<Hash4>> paths;
         if (!rebuild(t, lh, stored_at, paths)) return "internal: Merkle path reconstruction";
-        for (size_t q = 0; q < s.Q; q++) pp.queries[q].step_proofs[r] = paths[q];
+        for (size_t q = 0; q < Q; q++) pp.queries[q].step_proofs[r] = paths[q];
     }
     out = serialize_proof(c, pp);
     return "";

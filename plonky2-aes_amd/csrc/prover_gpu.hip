@@ -71,7 +71,8 @@ struct p2_circuit {
     hipStream_t stream = nullptr;  // setup stream (= ws[0] once workspaces exist)
     size_t n = 0, N = 0;
     u32 logn = 0, lde_bits = 0, active_wires = 0;
-    size_t pbytes = 0;
+    ProofLayout layout;  // where every field of a proof sits (proof_layout.h), built at load
+    size_t pbytes = 0;   // = layout.bytes
     std::vector<u32> arities;
     // ---- static device data
     Op* d_ops = nullptr;
@@ -130,13 +131,12 @@ struct p2_circuit {
     std::mutex staging_mu;
     // batched verification (p2_verify_batch): layout tables built at load, workspaces leased per call like the staging sets
     std::string vfy_error;  // non-empty: a precondition of the verifier kernels does not hold for this circuit
-    VerifyArgs vfy_args{};  // layout and circuit fields; the per-call pointers are filled in by verify_run
+    VerifyArgs vfy_args{};  // layout and circuit fields; the per-call pointers are filled in by proof_run
     size_t vfy_chunk = 0;
     std::vector<struct VerifyWs*> vfy_free;
     std::mutex vfy_mu;
-    // compressed proofs (kernels_compress.h): the source of every word of the full layout, and the layout's fixed parts
+    // compressed proofs (kernels_compress.h): the source of every word of the full layout
     u32* d_cmp_wmap = nullptr;
-    u32 cmp_prefix = 0, cmp_tail = 0, cmp_cols[4] = {0, 0, 0, 0};
     long fail_alloc_after = -1;            // test hook, see dalloc_ws
     // timing
     bool timing_on = false;
@@ -176,6 +176,24 @@ static int upload(p2_circuit* C, T** p, const T* host, size_t count) {
         }                                                                                             \
         HIPCHECK(hipGetLastError());                                                                  \
     } while (0)
+
+// Launch outside the timing map (the verification / compression driver, whose kernels run on a caller's or a workspace's stream).
+#define LAUNCH_ON(st, kernel, grid, block, ...)                          \
+    do {                                                                 \
+        hipLaunchKernelGGL(kernel, grid, block, 0, st, __VA_ARGS__);     \
+        HIPCHECK(hipGetLastError());                                     \
+    } while (0)
+
+// The gate table of QuotientArgs and VerifyArgs: kind, selector column and selector group of every gate type.
+template <class Args>
+static void fill_gate_table(const Circuit& c, Args& a) {
+    for (u32 g = 0; g < c.gates.size(); g++) {
+        a.gate_kind[g] = c.gates[g];
+        a.gate_sel[g] = c.selector_index[g];
+        a.group_lo[g] = c.groups[c.selector_index[g]].first;
+        a.group_hi[g] = c.groups[c.selector_index[g]].second;
+    }
+}
 
 static inline dim3 g1(size_t work, u32 block, u32 y = 1, u32 z = 1) { return dim3((u32)((work + block - 1) / block), y, z); }
 
@@ -752,7 +770,7 @@ static int prove_chunk(p2_circuit* C, u32 B, u32 n_inputs, const u64* d_values, 
     }
     if (!c.pi_slots.empty())
         LAUNCH(C, "pi_hash", k_pi_hash, g1((size_t)B * 16, 64), dim3(64), 0, C->cur->d_values, c.num_slots, C->d_pi_slots, (u32)c.pi_slots.size(), B,
-               C->cur->d_pi_hash, d_proofs, C->pbytes, proof_body_bytes(c));  // a 16-lane group per proof
+               C->cur->d_pi_hash, d_proofs, C->pbytes, C->layout.body_bytes);  // a 16-lane group per proof
     LAUNCH(C, "fill_wires", k_fill_wires, g1((size_t)R * n, 256, B), dim3(256), 0, C->d_wire_slot, C->cur->d_values, C->cur->d_wires, (size_t)R * n, c.num_slots, ws,
            C->cur->d_status);
     if (act > R)
@@ -854,12 +872,7 @@ static int prove_chunk(p2_circuit* C, u32 B, u32 n_inputs, const u64* d_values, 
         a.nlp = nlp;
         a.num_gates = (u32)c.gates.size();
         a.num_gate_constraints = c.num_gate_constraints;
-        for (u32 g = 0; g < c.gates.size(); g++) {
-            a.gate_kind[g] = c.gates[g];
-            a.gate_sel[g] = c.selector_index[g];
-            a.group_lo[g] = c.groups[c.selector_index[g]].first;
-            a.group_hi[g] = c.groups[c.selector_index[g]].second;
-        }
+        fill_gate_table(c, a);
         for (u32 l = 0; l < c.luts.size(); l++) a.lut_last_row[l] = c.lookup_rows[l].last_lut;
         a.zs_values = C->cur->d_zs;
         a.zs_values_batch_stride = zs_s;
@@ -965,39 +978,31 @@ static int prove_chunk(p2_circuit* C, u32 B, u32 n_inputs, const u64* d_values, 
         LAUNCH(C, "pow_finish", k_pow_finish, g1(B, 64), dim3(64), 0, C->cur->d_chal, C->cur->d_pow_best, B, C->cur->d_status);
         if (challenger(C, 6, C->cur->d_obs, 0, 0, c.cfg.num_query_rounds, (u64)N, B)) return P2_ERR_HIP;
         // 10. proof assembly
-        size_t off = 0;
-        const size_t pb = C->pbytes;
+        const ProofLayout& L = C->layout;
         ProofSegs segs{};
         u32 nseg = 0;
         segs.proofs = d_proofs;
-        segs.proof_bytes = pb;
-        for (Tree* t : {&C->cur->wtree, &C->cur->ztree, &C->cur->qtree}) {
-            segs.s[nseg++] = ProofSeg{t->dig + cap_off(*t, cap_h), nullptr, t->stride(), 0, off, cap_words, 0};
-            off += 8 * (size_t)cap_words;
-        }
-        segs.s[nseg++] = ProofSeg{C->cur->d_ev, C->d_map_ser, 2 * (size_t)C->ev_count, 0, off, C->n_ser, 2};
-        off += 16 * (size_t)C->n_ser;
+        segs.proof_bytes = L.bytes;
+        const Tree* caps[3] = {&C->cur->wtree, &C->cur->ztree, &C->cur->qtree};
+        for (int i = 0; i < 3; i++) segs.s[nseg++] = ProofSeg{caps[i]->dig + cap_off(*caps[i], cap_h), nullptr, caps[i]->stride(), 0, L.caps_off[i], cap_words, 0};
+        segs.s[nseg++] = ProofSeg{C->cur->d_ev, C->d_map_ser, 2 * (size_t)C->ev_count, 0, L.open[0].off, C->n_ser, 2};
         if (R_ + 6 > 12) return set_error("internal: more FRI rounds than proof segments"), P2_ERR_INVALID;
         for (u32 r = 0; r < R_; r++) {
             Tree& t = C->cur->fri_tree[r];
-            segs.s[nseg++] = ProofSeg{t.dig + cap_off(t, cap_h), nullptr, t.stride(), 0, off, cap_words, 0};
-            off += 8 * (size_t)cap_words;
+            segs.s[nseg++] = ProofSeg{t.dig + cap_off(t, cap_h), nullptr, t.stride(), 0, L.fri_caps_off + r * L.cap_bytes, cap_words, 0};
         }
         QueryArgs q{};
         const u64* ldes[4] = {C->d_pre_lde, C->cur->d_wlde, C->cur->d_zlde, C->cur->d_qlde};
         const size_t lstr[4] = {0, wls, zl_s, ql_s};
         const Tree* trees[4] = {&C->pre_tree, &C->cur->wtree, &C->cur->ztree, &C->cur->qtree};
-        const u32 colsv[4] = {np, c.cfg.num_wires + salt, zc + salt, qc + salt};  // blinded leaves end with the salt
         const u32 actv[4] = {np, act + salt, zc + salt, qc + salt};
-        size_t qbytes = 0;
         for (int o = 0; o < 4; o++) {
             q.oracles[o].lde = ldes[o];
             q.oracles[o].lde_batch_stride = lstr[o];
             q.oracles[o].digests = trees[o]->dig;
             q.oracles[o].dig_batch_stride = o == 0 ? 0 : trees[o]->stride();
-            q.oracles[o].cols = colsv[o];
+            q.oracles[o].cols = L.init[o].width;  // blinded leaves end with the salt
             q.oracles[o].active_cols = actv[o];
-            qbytes += 8 * (size_t)colsv[o] + 1 + 32 * (size_t)(C->lde_bits - cap_h);
         }
         q.lde_bits = C->lde_bits;
         q.cap_height = cap_h;
@@ -1011,21 +1016,16 @@ static int prove_chunk(p2_circuit* C, u32 B, u32 n_inputs, const u64* d_values, 
             q.fri_bits[r] = lb;
             q.fri_digests[r] = C->cur->fri_tree[r].dig;
             q.fri_dig_batch_stride[r] = C->cur->fri_tree[r].stride();
-            qbytes += 16 * ((size_t)1 << C->arities[r]) + 1 + 32 * (size_t)(lb - C->arities[r] - cap_h);
             lb -= C->arities[r];
         }
         q.chal = C->cur->d_chal;
         q.proofs = d_proofs;
-        q.proof_bytes = pb;
-        q.queries_off = off;
-        q.query_bytes = qbytes;
+        q.proof_bytes = L.bytes;
+        q.queries_off = L.queries_off;
+        q.query_bytes = L.query_bytes;
         LAUNCH(C, "write_queries", k_write_queries, dim3(c.cfg.num_query_rounds, B), dim3(256), 0, q);
-        off += qbytes * c.cfg.num_query_rounds;
-        segs.s[nseg++] = ProofSeg{C->cur->d_fri_coef[R_], nullptr, 2 * fl, fl, off, (u32)fl, 1};
-        off += 16 * fl;
-        segs.s[nseg++] = ProofSeg{C->cur->d_chal + CH_POW, nullptr, (size_t)CH_WORDS, 0, off, 1u, 0};
-        off += 8;
-        if (off + pi_trailer_bytes(c) != pb) return set_error("internal: proof layout size mismatch"), P2_ERR_INVALID;  // the trailer: k_pi_hash
+        segs.s[nseg++] = ProofSeg{C->cur->d_fri_coef[R_], nullptr, 2 * fl, fl, L.final_off, (u32)fl, 1};
+        segs.s[nseg++] = ProofSeg{C->cur->d_chal + CH_POW, nullptr, (size_t)CH_WORDS, 0, L.pow_off, 1u, 0};  // the trailer: k_pi_hash
         LAUNCH(C, "proof_segments", k_proof_segments, dim3(2, B, nseg), dim3(256), 0, segs);
     }
     LAUNCH(C, "finish", k_finish, g1(C->pbytes, 256, B), dim3(256), 0, C->cur->d_status, d_status_out, d_proofs, C->pbytes, B);
@@ -1128,7 +1128,8 @@ static int guarded_rc(F&& f) {
         return set_error("unknown exception"), P2_ERR_INVALID;
     }
 }
-// ---------------------------------------------------------------------------------- batched verification (kernels_verify.h)
+// ---------------------------------------------------------------------------------- batched verification and compressed proofs
+// (kernels_verify.h, kernels_compress.h): the layout tables built at load, the leased workspaces and one driver for the four operations
 // Per-call workspace: device buffers for one chunk of proofs, a stream for the host path and an event that orders the next
 // user of the workspace behind the last kernel that read it (the device path returns before its kernels have run).
 struct VerifyWs {
@@ -1139,7 +1140,7 @@ struct VerifyWs {
     u32 *d_flags = nullptr, *d_qfail = nullptr;
     uint8_t* d_proofs = nullptr;
     int *d_status = nullptr, *h_status = nullptr;
-    // compressed proofs, allocated by their first use (cmp_ensure)
+    // compressed proofs, allocated by their first use (cmp_ensure); never by plain verification
     CmpPlan* d_plan = nullptr;
     uint8_t* d_cout = nullptr;
     u32 *d_len = nullptr, *h_len = nullptr;
@@ -1166,8 +1167,7 @@ __global__ void k_vfy_set_vd(VdArg v, u64* out, u32 count) {
 static int verify_setup(p2_circuit* C) {
     const Circuit& c = C->c;
     const u32 NC = c.cfg.num_challenges, R = c.cfg.num_routed_wires, NW = c.cfg.num_wires, qdf = c.cfg.quotient_degree_factor;
-    const u32 ncc = c.num_constants_cols(), nlp = c.num_lookup_polys(), npp = c.num_partial_products(), zc = c.num_zs_cols();
-    const u32 cap_n = 1u << c.cfg.cap_height, lde_bits = C->lde_bits;
+    const u32 nlp = c.num_lookup_polys(), npp = c.num_partial_products(), zc = c.num_zs_cols(), lde_bits = C->lde_bits;
     // preconditions of k_vfy_vanishing / k_vfy_queries: fixed shapes they index with (cf. the host verifier's fixed arrays)
     std::string why;
     if (NC != 2) why = "num_challenges != 2";
@@ -1185,71 +1185,58 @@ static int verify_setup(p2_circuit* C) {
         C->vfy_error = "p2_verify_batch does not support this circuit: " + why;
         return 0;
     }
+    // the unpacked words and the count bytes, in the order of the layout
+    const ProofLayout& L = C->layout;
     std::vector<u32> woff, coff, obs;
     std::vector<uint8_t> cexp;
-    size_t pos = 0;
-    auto words = [&](size_t k) {
+    auto words = [&](size_t at, size_t k) {
         u32 first = (u32)woff.size();
-        for (size_t i = 0; i < k; i++, pos += 8) woff.push_back((u32)pos);
+        for (size_t i = 0; i < k; i++) woff.push_back((u32)(at + 8 * i));
         return first;
     };
-    auto count = [&](u32 depth) {
-        coff.push_back((u32)pos++);
-        cexp.push_back((uint8_t)depth);
-    };
     VerifyArgs& a = C->vfy_args;
-    a.cap_words = 4 * cap_n;
-    words(3 * a.cap_words);
-    a.o_const = words(2 * ncc);
-    a.o_sig = words(2 * R);
-    a.o_wires = words(2 * NW);
-    a.o_zs = words(2 * NC);
-    a.o_zsn = words(2 * NC);
-    a.o_lk = words(2 * NC * nlp);
-    a.o_lkn = words(2 * NC * nlp);
-    a.o_pp = words(2 * NC * npp);
-    a.o_quot = words(2 * NC * qdf);
-    a.fri_caps_off = words(C->arities.size() * a.cap_words);
-    const u32 cols[4] = {c.num_preprocessed(), NW + c.salt(), zc + c.salt(), c.num_quotient_cols() + c.salt()};
-    a.init_depth = lde_bits - c.cfg.cap_height;
-    for (u32 q = 0; q < c.cfg.num_query_rounds; q++) {
+    a.cap_words = (u32)(L.cap_bytes / 8);
+    words(L.caps_off[0], 3 * a.cap_words);
+    u32 open_word[OG_GROUPS];
+    for (u32 k = 0; k < OG_GROUPS; k++) open_word[k] = words(L.open[k].off, 2 * L.open[k].len);
+    a.o_const = open_word[OG_CONSTANTS], a.o_sig = open_word[OG_SIGMAS], a.o_wires = open_word[OG_WIRES];
+    a.o_zs = open_word[OG_ZS], a.o_zsn = open_word[OG_ZS_NEXT], a.o_lk = open_word[OG_LOOKUP_ZS], a.o_lkn = open_word[OG_LOOKUP_ZS_NEXT];
+    a.o_pp = open_word[OG_PARTIAL_PRODUCTS], a.o_quot = open_word[OG_QUOTIENT];
+    a.fri_caps_off = words(L.fri_caps_off, L.step.size() * a.cap_words);
+    a.init_depth = L.init[0].depth;
+    a.q_off = (u32)woff.size();
+    for (u32 q = 0; q < L.num_queries; q++) {
+        const size_t at = L.queries_off + q * L.query_bytes;
         const u32 base = (u32)woff.size();
-        if (q == 0) a.q_off = base;
+        auto path = [&](const ProofLayout::Path& p, u32& eval_off, u32& sib_off) {
+            eval_off = words(at + p.leaf_off, p.width) - base;
+            coff.push_back((u32)(at + p.cnt_off));
+            cexp.push_back((uint8_t)p.depth);
+            sib_off = words(at + p.sib_off, 4 * p.depth) - base;
+        };
         for (int o = 0; o < 4; o++) {
-            a.init_eval_off[o] = words(cols[o]) - base;
-            a.init_width[o] = cols[o];
-            count(a.init_depth);
-            a.init_sib_off[o] = words(4 * a.init_depth) - base;
+            path(L.init[o], a.init_eval_off[o], a.init_sib_off[o]);
+            a.init_width[o] = L.init[o].width;
         }
-        u32 bits = lde_bits;
-        for (u32 k = 0; k < C->arities.size(); k++) {
-            a.step_eval_off[k] = words(2 * VFY_ARITY) - base;
-            a.step_depth[k] = bits - c.cfg.cap_height - C->arities[k];
-            count(a.step_depth[k]);
-            a.step_sib_off[k] = words(4 * a.step_depth[k]) - base;
-            bits -= C->arities[k];
+        for (u32 k = 0; k < L.step.size(); k++) {
+            path(L.step[k], a.step_eval_off[k], a.step_sib_off[k]);
+            a.step_depth[k] = L.step[k].depth;
         }
-        if (q == 0) a.q_stride = (u32)woff.size() - base;
+        a.q_stride = (u32)woff.size() - base;
     }
-    a.final_len = (u32)(C->n >> (VFY_ARITY_BITS * C->arities.size()));
-    a.final_off = words(2 * a.final_len);
-    a.pow_off = words(1);
-    a.num_pi = (u32)c.pi_slots.size();
+    a.final_len = L.final_len;
+    a.final_off = words(L.final_off, 2 * L.final_len);
+    a.pow_off = words(L.pow_off, 1);
+    a.num_pi = L.num_pi;
     if (a.num_pi) {
-        a.pi_cnt_byte = (u32)pos;  // the count word: compared with num_pi by k_vfy_unpack, not unpacked
-        pos += 8;
-        a.pi_off = words(a.num_pi);
+        a.pi_cnt_byte = (u32)L.pi_cnt_off;  // the count word: compared with num_pi by k_vfy_unpack, not unpacked
+        a.pi_off = words(L.pi_off, a.num_pi);
     }
-    if (pos != C->pbytes) return set_error("internal: verifier layout differs from the proof size"), P2_ERR_INVALID;
-    // the opening batches in the order they are observed and reduced: constants, sigmas, wires, zs, partial products,
-    // quotient, lookup zs | zs(g zeta), lookup zs(g zeta)
-    auto ext = [&](u32 off, u32 k) {
-        for (u32 i = 0; i < k; i++) obs.push_back(off + 2 * i);
-    };
-    ext(a.o_const, ncc), ext(a.o_sig, R), ext(a.o_wires, NW), ext(a.o_zs, NC), ext(a.o_pp, NC * npp), ext(a.o_quot, NC * qdf), ext(a.o_lk, NC * nlp);
-    a.n_b0 = (u32)obs.size();
-    ext(a.o_zsn, NC), ext(a.o_lkn, NC * nlp);
-    a.n_b1 = (u32)obs.size() - a.n_b0;
+    // the opening batches in the order they are observed and reduced
+    for (OpenGroup g : OPEN_OBSERVED)
+        for (u32 i = 0; i < L.open[g].len; i++) obs.push_back(open_word[g] + 2 * i);
+    a.n_b0 = L.set.n_b0;
+    a.n_b1 = L.set.n_b1;
     a.W = (u32)woff.size();
     a.n_cnt = (u32)coff.size();
     if (upload(C, (u32**)&a.word_off, woff.data(), woff.size()) || upload(C, (u32**)&a.cnt_off, coff.data(), coff.size()) ||
@@ -1267,12 +1254,7 @@ static int verify_setup(p2_circuit* C) {
     a.lut_deg = nlp ? c.lut_degree() : 0;
     a.nsel = c.num_selectors(), a.nls = c.num_lookup_selectors, a.ngc = c.num_gate_constraints, a.nzpp = c.num_zs_pp(), a.zc = zc;
     a.num_gates = (u32)c.gates.size();
-    for (u32 g = 0; g < c.gates.size(); g++) {
-        a.gate_kind[g] = c.gates[g];
-        a.gate_sel[g] = c.selector_index[g];
-        a.group_lo[g] = c.groups[c.selector_index[g]].first;
-        a.group_hi[g] = c.groups[c.selector_index[g]].second;
-    }
+    fill_gate_table(c, a);
     a.num_luts = (u32)c.luts.size();
     a.lut_pairs = C->d_lut_pairs;
     a.lut_offsets = C->d_lut_offsets;
@@ -1284,7 +1266,7 @@ static int verify_setup(p2_circuit* C) {
     return 0;
 }
 
-// The compressed layout's per-circuit parts (compress.h::compress_shape): where each word of the full layout comes from.
+// The compressed layout's per-circuit table: where each word of the full layout comes from.
 static int cmp_setup(p2_circuit* C) {
     if (!C->vfy_error.empty()) return 0;
     const Circuit& c = C->c;
@@ -1306,9 +1288,6 @@ static int cmp_setup(p2_circuit* C) {
             for (u32 e = 0; e < 4 * a.step_depth[r]; e++) wmap[base + a.step_sib_off[r] + e] = cmp_code(CW_SIB, q, 4 + r, e);
         }
     }
-    C->cmp_prefix = 8 * a.q_off;
-    C->cmp_tail = (u32)(C->pbytes - 8 * (size_t)a.final_off - (size_t)a.n_cnt);  // the tail's byte offset: every count byte lies before it
-    for (u32 o = 0; o < 4; o++) C->cmp_cols[o] = a.init_width[o];
     return upload(C, &C->d_cmp_wmap, wmap.data(), wmap.size());
 }
 
@@ -1357,82 +1336,8 @@ static void verify_return(p2_circuit* C, VerifyWs* W) {
     C->vfy_free.push_back(W);
 }
 
-// Enqueues the verification of `batch` proofs on `st`.  host: proofs / status are host memory (staged through the workspace,
-// and the call waits for the statuses); otherwise both are device memory and the call returns once everything is enqueued.
-static int verify_run(p2_circuit* C, VerifyWs* W, size_t batch, const uint8_t* proofs, const VdArg& vd, int* status, hipStream_t st, bool host) {
-    const size_t pb = C->pbytes;
-    HIPCHECK(hipStreamWaitEvent(st, W->done, 0));  // the workspace's previous user
-    const u32 vd_words = C->vfy_args.cap_words + 4;
-    hipLaunchKernelGGL(k_vfy_set_vd, dim3(1), dim3(128), 0, st, vd, W->d_vd, vd_words);
-    HIPCHECK(hipGetLastError());
-    for (size_t done = 0; done < batch; done += W->chunk) {
-        const u32 B = (u32)std::min(W->chunk, batch - done);
-        VerifyArgs a = C->vfy_args;
-        a.batch = B;
-        a.words = W->d_words;
-        a.flags = W->d_flags;
-        a.qfail = W->d_qfail;
-        a.chal = W->d_chal;
-        a.vq = W->d_vq;
-        a.vd = W->d_vd;
-        a.pi_hash = W->d_pi_hash;
-        if (host) {
-            HIPCHECK(hipMemcpyAsync(W->d_proofs, proofs + done * pb, B * pb, hipMemcpyHostToDevice, st));
-            a.proofs = W->d_proofs;
-            a.status = W->d_status;
-        } else {
-            a.proofs = proofs + done * pb;
-            a.status = status + done;
-        }
-        HIPCHECK(hipMemsetAsync(W->d_flags, 0, (size_t)B * 4, st));
-        HIPCHECK(hipMemsetAsync(W->d_qfail, 0xFF, (size_t)B * 4, st));
-        const u32 slots = 4 + a.num_rounds + 1;
-        hipLaunchKernelGGL(k_vfy_unpack, dim3((a.W + 255) / 256, B), dim3(256), 0, st, a);
-        HIPCHECK(hipGetLastError());
-        hipLaunchKernelGGL(k_vfy_transcript, g1((size_t)B * 16, 64), dim3(64), 0, st, a);
-        HIPCHECK(hipGetLastError());
-        hipLaunchKernelGGL(k_vfy_vanishing, dim3(B), dim3(256), 0, st, a);
-        HIPCHECK(hipGetLastError());
-        hipLaunchKernelGGL(k_vfy_queries, dim3((u32)(((size_t)B * a.num_queries + 63) / 64), slots), dim3(64), 0, st, a);
-        HIPCHECK(hipGetLastError());
-        hipLaunchKernelGGL(k_vfy_finish, g1(B, 64), dim3(64), 0, st, a, slots);
-        HIPCHECK(hipGetLastError());
-        if (host) {
-            HIPCHECK(hipMemcpyAsync(W->h_status, W->d_status, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, st));
-            HIPCHECK(hipStreamSynchronize(st));
-            memcpy(status + done, W->h_status, (size_t)B * sizeof(int));
-        }
-    }
-    HIPCHECK(hipEventRecord(W->done, st));
-    return P2_OK;
-}
-
-static int verify_batch_impl(p2_circuit* C, size_t batch, const uint8_t* proofs, const uint64_t* verifier_data, size_t vd_len, int* status, hipStream_t st,
-                             bool host) {
-    if (!C) return set_error("p2_verify_batch: null circuit handle"), P2_ERR_INVALID;
-    const size_t vd_words = (size_t)C->vfy_args.cap_words + 4;
-    if (verifier_data && vd_len != vd_words) return set_error("verifier_data must be cap || circuit_digest (" + std::to_string(vd_words) + " words)"), P2_ERR_INVALID;
-    if (!C->vfy_error.empty()) return set_error(C->vfy_error), P2_ERR_INVALID;
-    if (batch == 0) return P2_OK;
-    if (!proofs || !status) return set_error("p2_verify_batch: null proofs or status"), P2_ERR_INVALID;
-    VdArg vd{};
-    const u64* src = verifier_data ? verifier_data : C->verifier_data.data();
-    if (vd_words > sizeof(vd.w) / 8) return set_error("internal: verifier data larger than the kernel argument"), P2_ERR_INVALID;
-    memcpy(vd.w, src, vd_words * 8);
-    HIPCHECK(hipSetDevice(C->device));
-    VerifyWs* W = verify_lease(C);
-    if (!W) return P2_ERR_HIP;
-    int rc = verify_run(C, W, batch, proofs, vd, status, host ? W->stream : st, host);
-    if (rc != P2_OK) {
-        // the workspace may still be in use by what was enqueued before the failure: drain before handing it out again
-        (void)hipStreamSynchronize(host ? W->stream : st);
-    }
-    verify_return(C, W);
-    return rc;
-}
-
-// ---------------------------------------------------------------------------------- compressed proofs (kernels_compress.h)
-enum CmpMode { CMP_COMPRESS, CMP_DECOMPRESS, CMP_VERIFY };
+// ---- the driver: verify, compress, decompress, verify compressed
+enum ProofOp { OP_VERIFY, OP_COMPRESS, OP_DECOMPRESS, OP_VERIFY_COMPRESSED };
 static int cmp_ensure(p2_circuit* C, VerifyWs* W) {
     if (W->d_plan) return P2_OK;
     const size_t n = W->chunk;
@@ -1442,14 +1347,17 @@ static int cmp_ensure(p2_circuit* C, VerifyWs* W) {
     return P2_OK;
 }
 
-// Enqueues one conversion of `batch` proofs on `st`; host / device memory as verify_run.  in: full proofs (compress) or
-// compressed ones at the same stride with `lengths`; out: compressed proofs (compress, with lengths_out) or full ones.
-static int cmp_run(p2_circuit* C, VerifyWs* W, CmpMode mode, size_t batch, const uint8_t* in, const u32* lengths, uint8_t* out, u32* lengths_out,
-                   const VdArg& vd, int* status, hipStream_t st, bool host) {
-    const size_t pb = C->pbytes;
-    HIPCHECK(hipStreamWaitEvent(st, W->done, 0));
-    hipLaunchKernelGGL(k_vfy_set_vd, dim3(1), dim3(128), 0, st, vd, W->d_vd, C->vfy_args.cap_words + 4);
-    HIPCHECK(hipGetLastError());
+// Enqueues one operation on `batch` proofs on `st`, a chunk of the workspace at a time.  host: every buffer is host memory
+// (staged through the workspace, and the call waits for the results); otherwise all are device memory and the call returns
+// once everything is enqueued.  in: full proofs (verify, compress) or compressed ones at the same stride with `lengths`;
+// out: compressed proofs (compress, with lengths_out) or full ones (decompress).
+static int proof_run(p2_circuit* C, VerifyWs* W, ProofOp op, size_t batch, const uint8_t* in, const u32* lengths, uint8_t* out, u32* lengths_out,
+                     const VdArg& vd, int* status, hipStream_t st, bool host) {
+    const ProofLayout& L = C->layout;
+    const size_t pb = L.bytes;
+    const bool full_in = op == OP_VERIFY || op == OP_COMPRESS, verdict = op == OP_VERIFY || op == OP_VERIFY_COMPRESSED;
+    HIPCHECK(hipStreamWaitEvent(st, W->done, 0));  // the workspace's previous user
+    LAUNCH_ON(st, k_vfy_set_vd, dim3(1), dim3(128), vd, W->d_vd, C->vfy_args.cap_words + 4);
     for (size_t done = 0; done < batch; done += W->chunk) {
         const u32 B = (u32)std::min(W->chunk, batch - done);
         CmpArgs a{};
@@ -1465,10 +1373,10 @@ static int cmp_run(p2_circuit* C, VerifyWs* W, CmpMode mode, size_t batch, const
         v.pi_hash = W->d_pi_hash;
         a.plan = W->d_plan;
         a.wmap = C->d_cmp_wmap;
-        a.prefix = C->cmp_prefix;
-        a.tail = C->cmp_tail;
-        for (int o = 0; o < 4; o++) a.cols[o] = C->cmp_cols[o];
-        a.from_chal = mode == CMP_COMPRESS;
+        a.prefix = (u32)L.queries_off;
+        a.tail = (u32)L.tail_bytes();
+        for (int o = 0; o < 4; o++) a.cols[o] = L.init[o].width;
+        a.from_chal = op == OP_COMPRESS;
         if (host) {
             HIPCHECK(hipMemcpyAsync(W->d_proofs, in + done * pb, B * pb, hipMemcpyHostToDevice, st));
             if (lengths) HIPCHECK(hipMemcpyAsync(W->d_len, lengths + done, B * 4, hipMemcpyHostToDevice, st));
@@ -1486,83 +1394,71 @@ static int cmp_run(p2_circuit* C, VerifyWs* W, CmpMode mode, size_t batch, const
         }
         HIPCHECK(hipMemsetAsync(W->d_flags, 0, (size_t)B * 4, st));
         HIPCHECK(hipMemsetAsync(W->d_qfail, 0xFF, (size_t)B * 4, st));
-        const dim3 words_grid((v.W + 255) / 256, B);
-        if (mode == CMP_COMPRESS) {
-            hipLaunchKernelGGL(k_vfy_unpack, words_grid, dim3(256), 0, st, v);
-            HIPCHECK(hipGetLastError());
-            hipLaunchKernelGGL(k_vfy_transcript, g1((size_t)B * 16, 64), dim3(64), 0, st, v);
-            HIPCHECK(hipGetLastError());
-            hipLaunchKernelGGL(k_cmp_plan, dim3(B), dim3(256), 0, st, a);
-            HIPCHECK(hipGetLastError());
+        const dim3 words_grid((v.W + 255) / 256, B), proofs_grid = g1(B, 64), transcript_grid = g1((size_t)B * 16, 64);
+        if (full_in) {  // the words of a full proof and its challenges
+            LAUNCH_ON(st, k_vfy_unpack, words_grid, dim3(256), v);
+            LAUNCH_ON(st, k_vfy_transcript, transcript_grid, dim3(64), v);
+        } else {  // the same from a compressed proof: what it stores, then what its Merkle caps and fold checks imply
+            LAUNCH_ON(st, k_cmp_plan, dim3(B), dim3(256), a);
+            LAUNCH_ON(st, k_cmp_scatter, words_grid, dim3(256), a);
+            LAUNCH_ON(st, k_vfy_transcript, transcript_grid, dim3(64), v);
+            LAUNCH_ON(st, k_cmp_reductions, proofs_grid, dim3(64), a);
+            LAUNCH_ON(st, k_cmp_infer, dim3(B), dim3(CMP_MAXQ), a);
+            LAUNCH_ON(st, k_cmp_merkle, dim3(B, 4 + v.num_rounds), dim3(CMP_MAXQ), a);
+        }
+        if (op == OP_COMPRESS) {
+            LAUNCH_ON(st, k_cmp_plan, dim3(B), dim3(256), a);
             HIPCHECK(hipMemsetAsync(a.cout, 0, (size_t)B * pb, st));
-            hipLaunchKernelGGL(k_cmp_emit, words_grid, dim3(256), 0, st, a);
-            HIPCHECK(hipGetLastError());
-            hipLaunchKernelGGL(k_cmp_finish, g1(B, 64), dim3(64), 0, st, a);
-            HIPCHECK(hipGetLastError());
+            LAUNCH_ON(st, k_cmp_emit, words_grid, dim3(256), a);
+            LAUNCH_ON(st, k_cmp_finish, proofs_grid, dim3(64), a);
+        } else if (op == OP_DECOMPRESS) {
+            LAUNCH_ON(st, k_cmp_finish, proofs_grid, dim3(64), a);
+            LAUNCH_ON(st, k_cmp_pack, words_grid, dim3(256), a);
         } else {
-            hipLaunchKernelGGL(k_cmp_plan, dim3(B), dim3(256), 0, st, a);
-            HIPCHECK(hipGetLastError());
-            hipLaunchKernelGGL(k_cmp_scatter, words_grid, dim3(256), 0, st, a);
-            HIPCHECK(hipGetLastError());
-            hipLaunchKernelGGL(k_vfy_transcript, g1((size_t)B * 16, 64), dim3(64), 0, st, v);
-            HIPCHECK(hipGetLastError());
-            hipLaunchKernelGGL(k_cmp_reductions, g1(B, 64), dim3(64), 0, st, a);
-            HIPCHECK(hipGetLastError());
-            hipLaunchKernelGGL(k_cmp_infer, dim3(B), dim3(CMP_MAXQ), 0, st, a);
-            HIPCHECK(hipGetLastError());
-            hipLaunchKernelGGL(k_cmp_merkle, dim3(B, 4 + v.num_rounds), dim3(CMP_MAXQ), 0, st, a);
-            HIPCHECK(hipGetLastError());
-            if (mode == CMP_DECOMPRESS) {
-                hipLaunchKernelGGL(k_cmp_finish, g1(B, 64), dim3(64), 0, st, a);
-                HIPCHECK(hipGetLastError());
-                hipLaunchKernelGGL(k_cmp_pack, words_grid, dim3(256), 0, st, a);
-                HIPCHECK(hipGetLastError());
-            } else {
-                const u32 slots = 4 + v.num_rounds + 1;
-                hipLaunchKernelGGL(k_vfy_vanishing, dim3(B), dim3(256), 0, st, v);
-                HIPCHECK(hipGetLastError());
-                hipLaunchKernelGGL(k_vfy_queries, dim3((u32)(((size_t)B * v.num_queries + 63) / 64), slots), dim3(64), 0, st, v);
-                HIPCHECK(hipGetLastError());
-                hipLaunchKernelGGL(k_vfy_finish, g1(B, 64), dim3(64), 0, st, v, slots);
-                HIPCHECK(hipGetLastError());
-            }
+            const u32 slots = 4 + v.num_rounds + 1;
+            LAUNCH_ON(st, k_vfy_vanishing, dim3(B), dim3(256), v);
+            LAUNCH_ON(st, k_vfy_queries, dim3((u32)(((size_t)B * v.num_queries + 63) / 64), slots), dim3(64), v);
+            LAUNCH_ON(st, k_vfy_finish, proofs_grid, dim3(64), v, slots);
         }
         if (host) {
             HIPCHECK(hipMemcpyAsync(W->h_status, W->d_status, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, st));
-            if (mode == CMP_COMPRESS) HIPCHECK(hipMemcpyAsync(W->h_len, W->d_len, (size_t)B * 4, hipMemcpyDeviceToHost, st));
-            if (mode != CMP_VERIFY) HIPCHECK(hipMemcpyAsync(out + done * pb, W->d_cout, (size_t)B * pb, hipMemcpyDeviceToHost, st));
+            if (op == OP_COMPRESS) HIPCHECK(hipMemcpyAsync(W->h_len, W->d_len, (size_t)B * 4, hipMemcpyDeviceToHost, st));
+            if (!verdict) HIPCHECK(hipMemcpyAsync(out + done * pb, W->d_cout, (size_t)B * pb, hipMemcpyDeviceToHost, st));
             HIPCHECK(hipStreamSynchronize(st));
             memcpy(status + done, W->h_status, (size_t)B * sizeof(int));
-            if (mode == CMP_COMPRESS) memcpy(lengths_out + done, W->h_len, (size_t)B * 4);
+            if (op == OP_COMPRESS) memcpy(lengths_out + done, W->h_len, (size_t)B * 4);
         }
     }
     HIPCHECK(hipEventRecord(W->done, st));
     return P2_OK;
 }
 
-static int cmp_batch_impl(p2_circuit* C, CmpMode mode, size_t batch, const uint8_t* in, const u32* lengths, const uint64_t* verifier_data, size_t vd_len,
-                          uint8_t* out, u32* lengths_out, int* status, hipStream_t st, bool host) {
-    static const char* names[3] = {"p2_compress_batch", "p2_decompress_batch", "p2_verify_compressed_batch"};
-    const std::string name = names[mode];
+static int proof_batch_impl(p2_circuit* C, ProofOp op, size_t batch, const uint8_t* in, const u32* lengths, const uint64_t* verifier_data, size_t vd_len,
+                            uint8_t* out, u32* lengths_out, int* status, hipStream_t st, bool host) {
+    static const char* names[4] = {"p2_verify_batch", "p2_compress_batch", "p2_decompress_batch", "p2_verify_compressed_batch"};
+    const std::string name = names[op];
+    const bool full_in = op == OP_VERIFY || op == OP_COMPRESS, verdict = op == OP_VERIFY || op == OP_VERIFY_COMPRESSED;
     if (!C) return set_error(name + ": null circuit handle"), P2_ERR_INVALID;
     const size_t vd_words = (size_t)C->vfy_args.cap_words + 4;
     if (verifier_data && vd_len != vd_words) return set_error("verifier_data must be cap || circuit_digest (" + std::to_string(vd_words) + " words)"), P2_ERR_INVALID;
     if (!C->vfy_error.empty()) return set_error(C->vfy_error), P2_ERR_INVALID;
     if (batch == 0) return P2_OK;
-    if (!in || !status || (mode != CMP_VERIFY && !out) || (mode == CMP_COMPRESS ? !lengths_out : !lengths))
-        return set_error(name + ": null buffer"), P2_ERR_INVALID;
-    if (host && mode != CMP_COMPRESS)
+    if (!in || !status || (!verdict && !out) || (op == OP_COMPRESS && !lengths_out) || (!full_in && !lengths))
+        return set_error(name + (op == OP_VERIFY ? ": null proofs or status" : ": null buffer")), P2_ERR_INVALID;
+    if (host && !full_in)
         for (size_t i = 0; i < batch; i++)
             if (lengths[i] > C->pbytes)
                 return set_error(name + ": length " + std::to_string(lengths[i]) + " of proof " + std::to_string(i) + " exceeds the stride " + std::to_string(C->pbytes)),
                        P2_ERR_INVALID;
     VdArg vd{};
+    if (vd_words > sizeof(vd.w) / 8) return set_error("internal: verifier data larger than the kernel argument"), P2_ERR_INVALID;
     memcpy(vd.w, verifier_data ? verifier_data : C->verifier_data.data(), vd_words * 8);
     HIPCHECK(hipSetDevice(C->device));
     VerifyWs* W = verify_lease(C);
     if (!W) return P2_ERR_HIP;
-    int rc = cmp_ensure(C, W);
-    if (rc == P2_OK) rc = cmp_run(C, W, mode, batch, in, lengths, out, lengths_out, vd, status, host ? W->stream : st, host);
+    int rc = op == OP_VERIFY ? P2_OK : cmp_ensure(C, W);  // plain verification never allocates the compression buffers
+    if (rc == P2_OK) rc = proof_run(C, W, op, batch, in, lengths, out, lengths_out, vd, status, host ? W->stream : st, host);
+    // the workspace may still be in use by what was enqueued before the failure: drain before handing it out again
     if (rc != P2_OK) (void)hipStreamSynchronize(host ? W->stream : st);
     verify_return(C, W);
     return rc;
@@ -1610,41 +1506,18 @@ p2_circuit* p2_circuit_load(const uint8_t* blob, size_t len, int device) {
         if (const char* e = getenv("P2AES_WITNESS_FUSE")) C->opt_witness_fuse = (u32)std::min(1024, std::max(1, atoi(e)));
         C->opt_debug_timing = getenv("P2AES_DEBUG_TIMING") != nullptr;
         if (const char* e = getenv("P2AES_TEST_FAIL_ALLOC_AFTER")) C->fail_alloc_after = atol(e);
-        C->pbytes = proof_bytes(c);
+        C->layout = make_proof_layout(c);
+        C->pbytes = C->layout.bytes;
         if (hipSetDevice(device) != hipSuccess) throw std::runtime_error("hipSetDevice failed");
         if (hipStreamCreate(&C->stream) != hipSuccess) throw std::runtime_error("hipStreamCreate failed");
         if (hipEventCreateWithFlags(&C->ev_witness, hipEventDisableTiming) != hipSuccess) throw std::runtime_error("hipEventCreate failed");
         if (raise_ntt_lds_limits() != hipSuccess) throw std::runtime_error("cannot raise the dynamic LDS limit for the NTT kernels");
-        // opening maps
-        const u32 np = c.num_preprocessed(), W = c.cfg.num_wires, zc = c.num_zs_cols(), qc = c.num_quotient_cols(), NC = c.cfg.num_challenges;
-        const u32 ncc = c.num_constants_cols(), nzpp = c.num_zs_pp();
-        const u32 E_PRE = 0, E_W = np, E_Z = np + W, E_ZN = E_Z + zc, E_Q = E_ZN + zc;
-        C->ev_count = E_Q + qc;
-        std::vector<u32> obs, ser;
-        auto range = [](std::vector<u32>& v, u32 base, u32 a, u32 b) {
-            for (u32 i = a; i < b; i++) v.push_back(base + i);
-        };
-        range(obs, E_PRE, 0, np);
-        range(obs, E_W, 0, W);
-        range(obs, E_Z, 0, nzpp);
-        range(obs, E_Q, 0, qc);
-        range(obs, E_Z, nzpp, zc);
-        range(obs, E_ZN, 0, NC);
-        range(obs, E_ZN, nzpp, zc);
-        range(ser, E_PRE, 0, ncc);
-        range(ser, E_PRE, ncc, np);
-        range(ser, E_W, 0, W);
-        range(ser, E_Z, 0, NC);
-        range(ser, E_ZN, 0, NC);
-        range(ser, E_Z, nzpp, zc);   // write_opening_set puts lookup_zs / lookup_zs_next between plonk_zs_next and the
-        range(ser, E_ZN, nzpp, zc);  // partial products (the OpeningSet struct itself lists them last)
-        range(ser, E_Z, NC, nzpp);
-        range(ser, E_Q, 0, qc);
+        // opening maps: the evaluation slots in observed and in serialised order
+        const std::vector<u32> obs = C->layout.set.slots_in(true), ser = C->layout.set.slots_in(false);
+        C->ev_count = C->layout.set.slots;
         C->n_obs = (u32)obs.size();
         C->n_ser = (u32)ser.size();
-        size_t fl = C->n;
-        for (u32 a : C->arities) fl >>= a;
-        if (fl > C->n_obs) throw std::runtime_error("final polynomial larger than the observation buffer");
+        if (C->layout.final_len > C->n_obs) throw std::runtime_error("final polynomial larger than the observation buffer");
         if (upload(C, &C->d_map_obs, obs.data(), obs.size()) || upload(C, &C->d_map_ser, ser.data(), ser.size())) throw std::runtime_error(g_last_error);
         if (circuit_setup(C)) throw std::runtime_error(g_last_error);
         if (verify_setup(C) || cmp_setup(C)) throw std::runtime_error(g_last_error);
@@ -1685,7 +1558,7 @@ size_t p2_circuit_proof_bytes(const p2_circuit* C) { return C->pbytes; }
 size_t p2_circuit_num_public_inputs(const p2_circuit* C) { return C ? C->c.pi_slots.size() : 0; }
 int p2_circuit_public_inputs(const p2_circuit* C, const uint8_t* proof, size_t proof_len, uint64_t* out, size_t cap, size_t* n_written) {
     if (!C) return set_error("p2_circuit_public_inputs: null circuit handle"), P2_ERR_INVALID;
-    return read_public_inputs(C->c, C->pbytes, proof, proof_len, out, cap, n_written);
+    return read_public_inputs(C->layout, proof, proof_len, out, cap, n_written);
 }
 size_t p2_circuit_chunk_proofs(p2_circuit* C) {
     std::lock_guard<std::mutex> lock(C->mu);
@@ -1712,25 +1585,27 @@ int p2_circuit_set_zk_seed(p2_circuit* C, uint64_t seed) {
 
 static int setup_polyrefs(p2_circuit* C) {
     const Circuit& c = C->c;
-    const u32 np = c.num_preprocessed(), W = c.cfg.num_wires, zc = c.num_zs_cols(), qc = c.num_quotient_cols(), NC = c.cfg.num_challenges, nzpp = c.num_zs_pp();
+    const u32 np = c.num_preprocessed(), zc = c.num_zs_cols(), qc = c.num_quotient_cols();
     const size_t n = C->n;
+    // the two FRI batches: the coefficient column behind every opening, in observed order
+    const OpeningSet& os = C->layout.set;
+    const PolyRef oracle[OS_SLOTS] = {{C->d_pre_coeffs, 0, 0, 0}, {C->cur->d_wcoef, (size_t)C->active_wires * n, 0, 0}, {C->cur->d_zcoef, (size_t)zc * n, 0, 0},
+                                      {C->cur->d_zcoef, (size_t)zc * n, 0, 0}, {C->cur->d_qcoef, (size_t)qc * n, 0, 0}};
     std::vector<PolyRef> v;
-    for (u32 i = 0; i < np; i++) v.push_back({C->d_pre_coeffs, 0, i, 0});
-    for (u32 i = 0; i < W; i++) v.push_back({i < C->active_wires ? C->cur->d_wcoef : nullptr, (size_t)C->active_wires * n, i, 0});
-    for (u32 i = 0; i < nzpp; i++) v.push_back({C->cur->d_zcoef, (size_t)zc * n, i, 0});
-    for (u32 i = 0; i < qc; i++) v.push_back({C->cur->d_qcoef, (size_t)qc * n, i, 0});
-    for (u32 i = nzpp; i < zc; i++) v.push_back({C->cur->d_zcoef, (size_t)zc * n, i, 0});
-    C->n_b0 = (u32)v.size();
-    for (u32 i = 0; i < NC; i++) v.push_back({C->cur->d_zcoef, (size_t)zc * n, i, 0});
-    for (u32 i = nzpp; i < zc; i++) v.push_back({C->cur->d_zcoef, (size_t)zc * n, i, 0});
-    C->n_b1 = (u32)v.size() - C->n_b0;
-    // the opening set: every polynomial at zeta, the Z columns at g zeta as well (slots: preprocessed | wires | Z(zeta) | Z(g zeta) | quotient)
+    for (OpenGroup k : OPEN_OBSERVED)
+        for (u32 i = os.g[k].lo; i < os.g[k].hi; i++) {
+            PolyRef r = oracle[os.g[k].slot];
+            r.col = i;
+            if (os.g[k].slot == OS_WIRES && i >= C->active_wires) r.base = nullptr;  // identically zero, never materialised
+            v.push_back(r);
+        }
+    C->n_b0 = os.n_b0;
+    C->n_b1 = os.n_b1;
+    // the opening set: every materialised column of every oracle at zeta, the Z columns at g zeta as well
     std::vector<EvalRef> e;
-    for (u32 i = 0; i < np; i++) e.push_back({C->d_pre_coeffs, 0, i, 0, i, 0});
-    for (u32 i = 0; i < C->active_wires; i++) e.push_back({C->cur->d_wcoef, (size_t)C->active_wires * n, i, 0, np + i, 0});
-    for (u32 i = 0; i < zc; i++) e.push_back({C->cur->d_zcoef, (size_t)zc * n, i, 0, np + W + i, 0});
-    for (u32 i = 0; i < zc; i++) e.push_back({C->cur->d_zcoef, (size_t)zc * n, i, 1, np + W + zc + i, 0});
-    for (u32 i = 0; i < qc; i++) e.push_back({C->cur->d_qcoef, (size_t)qc * n, i, 0, np + W + 2 * zc + i, 0});
+    const u32 cols[OS_SLOTS] = {np, C->active_wires, zc, zc, qc};
+    for (u32 b = 0; b < OS_SLOTS; b++)
+        for (u32 i = 0; i < cols[b]; i++) e.push_back({oracle[b].base, oracle[b].batch_stride, i, b == OS_Z_NEXT, os.slot_base[b] + i, 0});
     C->n_evalrefs = (u32)e.size();
     if (upload(C, &C->cur->d_evalrefs, e.data(), e.size())) return P2_ERR_HIP;
     return upload(C, &C->cur->d_polyrefs, v.data(), v.size());
@@ -2247,30 +2122,30 @@ int p2_gpu_merkle_cap(const uint64_t* cols_major, size_t cols, size_t num_leaves
 
 // ---- batched verification
 int p2_verify_batch(p2_circuit* C, size_t batch, const uint8_t* proofs, const uint64_t* verifier_data, size_t vd_len, int* status) {
-    return guarded_rc([&] { return verify_batch_impl(C, batch, proofs, verifier_data, vd_len, status, nullptr, true); });
+    return guarded_rc([&] { return proof_batch_impl(C, OP_VERIFY, batch, proofs, nullptr, verifier_data, vd_len, nullptr, nullptr, status, nullptr, true); });
 }
 int p2_verify_batch_device(p2_circuit* C, size_t batch, const uint8_t* d_proofs, const uint64_t* verifier_data, size_t vd_len, int* d_status, void* stream) {
-    return guarded_rc([&] { return verify_batch_impl(C, batch, d_proofs, verifier_data, vd_len, d_status, (hipStream_t)stream, false); });
+    return guarded_rc([&] { return proof_batch_impl(C, OP_VERIFY, batch, d_proofs, nullptr, verifier_data, vd_len, nullptr, nullptr, d_status, (hipStream_t)stream, false); });
 }
 int p2_compress_batch(p2_circuit* C, size_t batch, const uint8_t* proofs, const uint64_t* vd, size_t vd_len, uint8_t* out, uint32_t* lengths, int* status) {
-    return guarded_rc([&] { return cmp_batch_impl(C, CMP_COMPRESS, batch, proofs, nullptr, vd, vd_len, out, lengths, status, nullptr, true); });
+    return guarded_rc([&] { return proof_batch_impl(C, OP_COMPRESS, batch, proofs, nullptr, vd, vd_len, out, lengths, status, nullptr, true); });
 }
 int p2_compress_batch_device(p2_circuit* C, size_t batch, const uint8_t* d_proofs, const uint64_t* vd, size_t vd_len, uint8_t* d_out, uint32_t* d_lengths,
                              int* d_status, void* stream) {
-    return guarded_rc([&] { return cmp_batch_impl(C, CMP_COMPRESS, batch, d_proofs, nullptr, vd, vd_len, d_out, d_lengths, d_status, (hipStream_t)stream, false); });
+    return guarded_rc([&] { return proof_batch_impl(C, OP_COMPRESS, batch, d_proofs, nullptr, vd, vd_len, d_out, d_lengths, d_status, (hipStream_t)stream, false); });
 }
 int p2_decompress_batch(p2_circuit* C, size_t batch, const uint8_t* cproofs, const uint32_t* lengths, const uint64_t* vd, size_t vd_len, uint8_t* out, int* status) {
-    return guarded_rc([&] { return cmp_batch_impl(C, CMP_DECOMPRESS, batch, cproofs, lengths, vd, vd_len, out, nullptr, status, nullptr, true); });
+    return guarded_rc([&] { return proof_batch_impl(C, OP_DECOMPRESS, batch, cproofs, lengths, vd, vd_len, out, nullptr, status, nullptr, true); });
 }
 int p2_decompress_batch_device(p2_circuit* C, size_t batch, const uint8_t* d_cproofs, const uint32_t* d_lengths, const uint64_t* vd, size_t vd_len, uint8_t* d_out,
                                int* d_status, void* stream) {
-    return guarded_rc([&] { return cmp_batch_impl(C, CMP_DECOMPRESS, batch, d_cproofs, d_lengths, vd, vd_len, d_out, nullptr, d_status, (hipStream_t)stream, false); });
+    return guarded_rc([&] { return proof_batch_impl(C, OP_DECOMPRESS, batch, d_cproofs, d_lengths, vd, vd_len, d_out, nullptr, d_status, (hipStream_t)stream, false); });
 }
 int p2_verify_compressed_batch(p2_circuit* C, size_t batch, const uint8_t* cproofs, const uint32_t* lengths, const uint64_t* vd, size_t vd_len, int* status) {
-    return guarded_rc([&] { return cmp_batch_impl(C, CMP_VERIFY, batch, cproofs, lengths, vd, vd_len, nullptr, nullptr, status, nullptr, true); });
+    return guarded_rc([&] { return proof_batch_impl(C, OP_VERIFY_COMPRESSED, batch, cproofs, lengths, vd, vd_len, nullptr, nullptr, status, nullptr, true); });
 }
 int p2_verify_compressed_batch_device(p2_circuit* C, size_t batch, const uint8_t* d_cproofs, const uint32_t* d_lengths, const uint64_t* vd, size_t vd_len,
                                       int* d_status, void* stream) {
-    return guarded_rc([&] { return cmp_batch_impl(C, CMP_VERIFY, batch, d_cproofs, d_lengths, vd, vd_len, nullptr, nullptr, d_status, (hipStream_t)stream, false); });
+    return guarded_rc([&] { return proof_batch_impl(C, OP_VERIFY_COMPRESSED, batch, d_cproofs, d_lengths, vd, vd_len, nullptr, nullptr, d_status, (hipStream_t)stream, false); });
 }
 }
