@@ -151,8 +151,15 @@ pub mod iop {
 
 pub mod plonk {
     pub mod config {
-        /// `PoseidonGoldilocksConfig` -- the only configuration the backend implements.
+        /// The hash configuration `build::<C>()` compiles a circuit for (upstream `GenericConfig`'s `Hasher`).
+        pub trait GenericConfig { const HASHER: std::os::raw::c_int; }
+        /// `PoseidonGoldilocksConfig`: Poseidon Merkle trees, challenger and circuit digest.
         pub struct PoseidonGoldilocksConfig;
+        impl GenericConfig for PoseidonGoldilocksConfig { const HASHER: std::os::raw::c_int = crate::ffi::P2_HASHER_POSEIDON; }
+        /// `KeccakGoldilocksConfig`: Merkle trees and circuit digest by Keccak-256 truncated to 25 bytes (`KeccakHash<25>`), the
+        /// challenger still Poseidon -- the configuration for proofs that are not verified inside another circuit.
+        pub struct KeccakGoldilocksConfig;
+        impl GenericConfig for KeccakGoldilocksConfig { const HASHER: std::os::raw::c_int = crate::ffi::P2_HASHER_KECCAK; }
     }
     pub mod circuit_data {
         use crate::field::types::Field;
@@ -358,9 +365,11 @@ pub mod plonk {
                 out.into_iter().map(Target).collect()
             }
             pub fn num_gates(&self) -> usize { unsafe { ffi::p2_builder_num_gates(self.h) } }
-            /// `build::<PoseidonGoldilocksConfig>()` (19 sites): compile on the host, then upload the circuit
+            /// `build::<PoseidonGoldilocksConfig>()` (19 sites) or `build::<KeccakGoldilocksConfig>()`: compile on the host, then upload the circuit
             /// to HIP device P2AES_DEVICE (default 0) and commit constants | sigmas there.
-            pub fn build<C>(self) -> CircuitData<F, C, D> {
+            pub fn build<C: crate::plonk::config::GenericConfig>(self) -> CircuitData<F, C, D> {
+                let rc = unsafe { ffi::p2_builder_set_hasher(self.h, C::HASHER) };
+                assert!(rc == ffi::P2_OK, "{}", last_error());
                 let (mut blob_ptr, mut len) = (core::ptr::null_mut::<u8>(), 0usize);
                 let rc = unsafe { ffi::p2_builder_build(self.h, &mut blob_ptr, &mut len) };
                 assert!(rc == ffi::P2_OK, "{}", last_error());

@@ -51,7 +51,7 @@ enum {
 enum {
     P2_VERIFY_OK = 0,
     P2_VERIFY_SHAPE = 1,             /* "proof truncated", "trailing bytes in proof", "Merkle path of the wrong depth (...)" */
-    P2_VERIFY_NON_CANONICAL = 2,     /* "non-canonical field element" */
+    P2_VERIFY_NON_CANONICAL = 2,     /* "non-canonical field element", "hash word out of range" (Keccak circuits) */
     P2_VERIFY_POW = 3,               /* "Invalid proof-of-work witness." */
     P2_VERIFY_ZETA_IN_SUBGROUP = 4,  /* "Opening point is in the subgroup." */
     P2_VERIFY_VANISHING = 5,         /* "vanishing polynomial identity does not hold at zeta" */
@@ -70,6 +70,19 @@ typedef uint64_t p2_target;
 
 p2_builder* p2_builder_new(void);    /* CircuitConfig::standard_recursion_config() */
 p2_builder* p2_builder_new_zk(void); /* CircuitConfig::standard_recursion_zk_config() (examples/aes_gcm_128.rs:36) */
+/* The hash configuration of a circuit.  P2_HASHER_POSEIDON is PoseidonGoldilocksConfig (what p2_builder_new / _new_zk build).
+ * P2_HASHER_KECCAK is KeccakGoldilocksConfig: Merkle trees and circuit digest hashed with Keccak-256 truncated to 25 bytes
+ * (KeccakHash<25>); the Fiat-Shamir challenger, the proof-of-work and the public-input hash stay Poseidon.  A 25-byte digest
+ * is carried everywhere as four field elements holding bytes 0-6, 7-13, 14-20 and 21-24, so proof size
+ * and layout do not depend on the hasher; a proof whose hash words leave these ranges is P2_VERIFY_NON_CANONICAL.  Every
+ * call that takes a blob or a handle reads the hasher from it. */
+enum { P2_HASHER_POSEIDON = 0, P2_HASHER_KECCAK = 1 };
+/* standard_recursion_config() (zero_knowledge == 0) or standard_recursion_zk_config() with the given hasher; NULL for an
+ * unknown hasher.  (0, P2_HASHER_POSEIDON) is p2_builder_new(). */
+p2_builder* p2_builder_new_config(int zero_knowledge, int hasher);
+/* The hasher of an existing builder, any time before p2_builder_build (upstream chooses it there: build::<C>()); the gates
+ * and targets added so far do not depend on it. */
+int p2_builder_set_hasher(p2_builder*, int hasher);
 void p2_builder_free(p2_builder*);
 p2_target p2_builder_add_virtual_target(p2_builder*);
 p2_target p2_builder_constant(p2_builder*, uint64_t c);
@@ -204,6 +217,11 @@ void p2_native_gctr(const uint8_t* key, int nk, int nr, const uint8_t* icb16, co
 void p2_native_aes_gcm_encrypt(const uint8_t* key, int nk, int nr, const uint8_t* nonce12, const uint8_t* pt, size_t len,
                                uint8_t* ct, uint8_t* tag16);
 
+/* The tree hasher of P2_HASHER_KECCAK on the host (csrc/keccak_hash.h): hash_no_pad of n words, and two_to_one of two digests
+ * in the four-word form (each word in its range).  out4 is in the four-word form. */
+void p2_native_keccak_hash_no_pad(const uint64_t* in, size_t n, uint64_t out4[4]);
+void p2_native_keccak_two_to_one(const uint64_t l4[4], const uint64_t r4[4], uint64_t out4[4]);
+
 /* ------------------------------------------------------------------ circuit info / verification (host) */
 /* Shape of a compiled circuit without touching a device. */
 typedef struct {
@@ -212,6 +230,7 @@ typedef struct {
     uint64_t proof_bytes; /* exact serialised proof size, public-input trailer included */
     uint32_t zero_knowledge, num_gate_kinds; /* standard_recursion_zk_config(); distinct gate types in the circuit */
     uint32_t num_public_inputs; /* targets registered with p2_builder_register_public_input */
+    uint32_t hasher;            /* P2_HASHER_* */
 } p2_circuit_info;
 int p2_blob_info(const uint8_t* blob, size_t len, p2_circuit_info* out);
 /* The device-side schedule of a compiled circuit's witness program for macro size `fuse` (csrc/witness_schedule.h; the prover
@@ -362,6 +381,8 @@ int p2_gpu_lde(const uint64_t* coeffs, size_t cols, int degree_bits, int rate_bi
 int p2_gpu_intt(const uint64_t* values, size_t cols, int degree_bits, uint64_t* coeffs, int device);
 /* column-major leaves [cols][num_leaves] -> cap digests (2^cap_height * 4 u64) */
 int p2_gpu_merkle_cap(const uint64_t* cols_major, size_t cols, size_t num_leaves, int cap_height, uint64_t* cap, int device);
+/* the same with the tree hasher chosen (P2_HASHER_*); Keccak needs cols >= 4 (every leaf is hashed, there is no no-op case) */
+int p2_gpu_merkle_cap_hasher(const uint64_t* cols_major, size_t cols, size_t num_leaves, int cap_height, int hasher, uint64_t* cap, int device);
 /* debug: copy a named intermediate buffer of proof `index` of the last batch to the host
  * ("wires", "wires_cap", "zs", "zs_cap", "quotient_coeffs", "quotient_cap", "challenges", "openings",
  * "public_inputs_hash", ...) */

@@ -8,6 +8,7 @@ from .api import (  # noqa: F401
     CircuitBuilder,
     CircuitData,
     ECGFP5SecretKey,
+    HASHERS,
     P2Error,
     PartialWitness,
     PoseidonEncryptTarget,
@@ -24,6 +25,7 @@ from .api import (  # noqa: F401
     VERIFY_VANISHING,
     VERIFY_ZETA_IN_SUBGROUP,
     ecgfp5,
+    keccak_native,
     lib,
     lib_path,
     native,

@@ -44,6 +44,7 @@ VERIFY_REASONS = {
     "Merkle path of the wrong depth (initial tree).": VERIFY_SHAPE,
     "Merkle path of the wrong depth (FRI round).": VERIFY_SHAPE,
     "non-canonical field element": VERIFY_NON_CANONICAL,
+    "hash word out of range": VERIFY_NON_CANONICAL,  # Keccak circuits: a hash word >= 2^56 (the fourth >= 2^32)
     "Invalid proof-of-work witness.": VERIFY_POW,
     "Opening point is in the subgroup.": VERIFY_ZETA_IN_SUBGROUP,
     "vanishing polynomial identity does not hold at zeta": VERIFY_VANISHING,
@@ -74,7 +75,12 @@ class _Info(C.Structure):
                                            "num_quotient_cols", "num_luts", "num_ops", "num_levels", "num_slots",
                                            "num_virtual_targets", "num_fri_rounds")] + [("proof_bytes", C.c_uint64), ("zero_knowledge", C.c_uint32),
                                                                                       ("num_gate_kinds", C.c_uint32),
-                                                                                      ("num_public_inputs", C.c_uint32)]
+                                                                                      ("num_public_inputs", C.c_uint32),
+                                                                                      ("hasher", C.c_uint32)]
+
+
+# the tree hasher of a circuit (include/p2aes.h P2_HASHER_*): PoseidonGoldilocksConfig / KeccakGoldilocksConfig
+HASHERS = {"poseidon": 0, "keccak": 1}
 
 
 class _Assignment(C.Structure):
@@ -98,6 +104,9 @@ def lib():
     sig = {
         "p2_last_error": (C.c_char_p, []),
         "p2_builder_new": (vp, []), "p2_builder_new_zk": (vp, []), "p2_builder_free": (None, [vp]),
+        "p2_builder_new_config": (vp, [C.c_int, C.c_int]), "p2_builder_set_hasher": (C.c_int, [vp, C.c_int]),
+        "p2_native_keccak_hash_no_pad": (None, [u64p, sz, u64p]), "p2_native_keccak_two_to_one": (None, [u64p, u64p, u64p]),
+        "p2_gpu_merkle_cap_hasher": (C.c_int, [u64p, sz, sz, C.c_int, C.c_int, u64p, C.c_int]),
         "p2_circuit_set_zk_seed": (C.c_int, [vp, u64]),
         "p2_circuit_set_zk_key": (C.c_int, [vp, C.POINTER(u64)]),
         "p2_circuit_set_option": (C.c_int, [vp, C.c_char_p, C.c_long]),
@@ -213,9 +222,18 @@ def _arr(vals):
 
 
 class CircuitBuilder:
-    def __init__(self, zero_knowledge=False):
-        """CircuitBuilder::<F, D>::new(standard_recursion_config()) or, with zero_knowledge, standard_recursion_zk_config()."""
-        self._h = lib().p2_builder_new_zk() if zero_knowledge else lib().p2_builder_new()
+    def __init__(self, zero_knowledge=False, hasher="poseidon"):
+        """CircuitBuilder::<F, D>::new(standard_recursion_config()) or, with zero_knowledge, standard_recursion_zk_config().
+        hasher: "poseidon" (build::<PoseidonGoldilocksConfig>()) or "keccak" (build::<KeccakGoldilocksConfig>(): Keccak-256
+        Merkle trees and circuit digest); everything made from the circuit afterwards takes the hasher from it."""
+        if hasher not in HASHERS:
+            raise P2Error("unknown hasher %r (known: %s)" % (hasher, ", ".join(sorted(HASHERS))))
+        if hasher == "poseidon":
+            self._h = lib().p2_builder_new_zk() if zero_knowledge else lib().p2_builder_new()
+        else:
+            self._h = lib().p2_builder_new_config(1 if zero_knowledge else 0, HASHERS[hasher])
+        if not self._h:
+            raise P2Error(_err())
 
     def __del__(self):
         if getattr(self, "_h", None):
@@ -429,6 +447,7 @@ class CircuitData:
         if lib().p2_blob_info(blob, len(blob), C.byref(info)):
             raise P2Error(_err())
         self.info = {n: getattr(info, n) for n, _ in _Info._fields_}
+        self.info["hasher"] = {v: k for k, v in HASHERS.items()}[info.hasher]
 
     def __del__(self):
         if getattr(self, "_gpu", None):
@@ -742,6 +761,23 @@ class PoseidonEncryptTarget:
         pw.set_target_arr(self.m, [v for fq in m for v in fq])
         pw.set_target_arr(self.nonce, nonce)
         pw.set_target_arr(self.ct, [v for fq in ct for v in fq])
+
+
+class keccak_native:
+    """The tree hasher of hasher="keccak" on the host (csrc/keccak_hash.h): digests in the four-word form (bytes 0-6, 7-13,
+    14-20, 21-24 of the 25-byte Keccak-256 prefix)."""
+
+    @staticmethod
+    def hash_no_pad(words):
+        out = (u64 * 4)()
+        lib().p2_native_keccak_hash_no_pad(_arr(words), len(words), out)
+        return list(out)
+
+    @staticmethod
+    def two_to_one(l, r):
+        out = (u64 * 4)()
+        lib().p2_native_keccak_two_to_one(_arr(l), _arr(r), out)
+        return list(out)
 
 
 class poseidon_native:

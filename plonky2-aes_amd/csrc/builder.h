@@ -42,6 +42,7 @@ struct GateInstance {
 class CircuitBuilder {
    public:
     explicit CircuitBuilder(const Config& cfg = Config()) : cfg_(cfg) {}
+    void set_hasher(u32 hasher) { cfg_.hasher = hasher; }  // the tree hasher is a property of build::<C>(), not of the gates
 
     // ---- targets ------------------------------------------------------------------------------------
     Target add_virtual_target() { return (Target)num_virtual_++; }

@@ -43,5 +43,6 @@ inline void fill_info(const Circuit& c, p2_circuit_info* o) {
     o->zero_knowledge = c.cfg.zero_knowledge;
     o->num_gate_kinds = (uint32_t)c.gates.size();
     o->num_public_inputs = (uint32_t)c.pi_slots.size();
+    o->hasher = c.cfg.hasher;
 }
 }  // namespace p2

@@ -90,6 +90,18 @@ p2_builder* p2_builder_new_zk(void) {
     cfg.zero_knowledge = 1;
     return new p2_builder{CircuitBuilder(cfg)};
 }
+p2_builder* p2_builder_new_config(int zero_knowledge, int hasher) {
+    if (hasher != P2_HASHER_POSEIDON && hasher != P2_HASHER_KECCAK) return set_error("p2_builder_new_config: unknown hasher"), nullptr;
+    Config cfg;
+    cfg.zero_knowledge = zero_knowledge ? 1 : 0;
+    cfg.hasher = (u32)hasher;
+    return new p2_builder{CircuitBuilder(cfg)};
+}
+int p2_builder_set_hasher(p2_builder* b, int hasher) {
+    if (!b || (hasher != P2_HASHER_POSEIDON && hasher != P2_HASHER_KECCAK)) return set_error("p2_builder_set_hasher: unknown hasher"), P2_ERR_INVALID;
+    b->b.set_hasher((u32)hasher);
+    return P2_OK;
+}
 void p2_builder_free(p2_builder* b) { delete b; }
 p2_target p2_builder_add_virtual_target(p2_builder* b) { return guarded_t([&]() -> p2_target { return b->b.add_virtual_target(); }); }
 p2_target p2_builder_constant(p2_builder* b, uint64_t c) { return guarded_t([&]() -> p2_target { return b->b.constant(c); }); }
@@ -280,6 +292,8 @@ void p2_native_hash_n_to_m_no_pad(const uint64_t* in, size_t n, uint64_t* out, s
         std::copy(o.begin(), o.end(), out);
     });
 }
+void p2_native_keccak_hash_no_pad(const uint64_t* in, size_t n, uint64_t out[4]) { kc::hash_no_pad(in, (u32)n, out); }
+void p2_native_keccak_two_to_one(const uint64_t l[4], const uint64_t r[4], uint64_t out[4]) { kc::two_to_one(l, r, out); }
 static pcipher::Fq fq_at(const uint64_t* p) { return pcipher::Fq{p[0], p[1], p[2], p[3], p[4]}; }
 void p2_native_poseidon_encrypt(const uint64_t* ks, const uint64_t* msg, size_t n_msg, const uint64_t* nonce, uint64_t* ct) {
     (void)guarded([&] {

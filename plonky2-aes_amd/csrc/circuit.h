@@ -36,7 +36,11 @@ struct Config {
     u32 arity_bits = 4;       // FriReductionStrategy::ConstantArityBits(4, 5)
     u32 final_poly_bits = 5;
     u32 zero_knowledge = 0;   // standard_recursion_zk_config(): blinding rows + salted Merkle leaves
+    // Not part of the blob's fixed config record (CONFIG_BLOB_BYTES): a Keccak circuit carries it in the trailing HASH section.
+    u32 hasher = 0;           // HASHER_POSEIDON: PoseidonGoldilocksConfig; HASHER_KECCAK: KeccakGoldilocksConfig (keccak_hash.h)
 };
+enum Hasher : u32 { HASHER_POSEIDON = 0, HASHER_KECCAK = 1 };
+static const size_t CONFIG_BLOB_BYTES = 12 * sizeof(u32);  // num_wires .. zero_knowledge
 static const u32 SALT_SIZE = 4;  // plonky2 fri::oracle SALT_SIZE: random elements appended to every leaf of a blinded oracle
 
 // Blinding randomness.  Upstream draws every blinding element from the OS RNG.  Here the handle holds a 256-bit key
@@ -192,12 +196,15 @@ static const u32 BLOB_VERSION = 4;  // 4: one gate type per lookup table (repeat
 // length-prefixed u32 array, then nothing.  A reader of version 4 that stops at blind_zrows still loads such a blob.
 static const u32 BLOB_PI_TAG = 0x49425550u;  // "PUBI"
 static const u64 MAX_PUBLIC_INPUTS = 1u << 24;
+// Optional trailing section, written only for a Keccak circuit, after the PUBI section if both are present: HASH_TAG, one u32
+// (the hasher).  Every Poseidon blob is byte for byte what it was before the section existed.
+static const u32 BLOB_HASH_TAG = 0x48534148u;  // "HASH"
 
 static inline std::vector<uint8_t> serialize(const Circuit& c) {
     BlobWriter w;
     w.raw(BLOB_MAGIC, 8);
     w.w32(BLOB_VERSION);
-    w.raw(&c.cfg, sizeof(Config));
+    w.raw(&c.cfg, CONFIG_BLOB_BYTES);
     w.w32(c.degree_bits);
     w.vec(c.gates);
     w.vec(c.selector_index);
@@ -223,6 +230,10 @@ static inline std::vector<uint8_t> serialize(const Circuit& c) {
         w.w32(BLOB_PI_TAG);
         w.vec(c.pi_slots);
     }
+    if (c.cfg.hasher != HASHER_POSEIDON) {
+        w.w32(BLOB_HASH_TAG);
+        w.w32(c.cfg.hasher);
+    }
     return w.buf;
 }
 
@@ -233,7 +244,7 @@ static inline Circuit deserialize(const void* data, size_t len) {
     if (memcmp(magic, BLOB_MAGIC, 8) != 0) throw std::runtime_error("bad circuit blob magic");
     if (r.r32() != BLOB_VERSION) throw std::runtime_error("unsupported circuit blob version");
     Circuit c;
-    r.raw(&c.cfg, sizeof(Config));
+    r.raw(&c.cfg, CONFIG_BLOB_BYTES);
     c.degree_bits = r.r32();
     if (c.degree_bits < 2 || c.degree_bits > 26) throw std::runtime_error("degree_bits out of range");
     if (c.cfg.num_wires != 135 || c.cfg.num_routed_wires != 80 || c.cfg.num_constants != 2 || c.cfg.num_challenges != 2 ||
@@ -263,12 +274,21 @@ static inline Circuit deserialize(const void* data, size_t len) {
     r.vec(c.blind_rows);
     r.vec(c.blind_zrows);
     if (r.pos != len) {
-        if (r.r32() != BLOB_PI_TAG) throw std::runtime_error("unknown section after blind_zrows");
-        const u64 k = r.r64();
-        if (k == 0 || k > MAX_PUBLIC_INPUTS || k > (len - r.pos) / 4) throw std::runtime_error("public input count");
-        c.pi_slots.resize(k);
-        r.raw(c.pi_slots.data(), k * 4);
-        if (r.pos != len) throw std::runtime_error("trailing bytes after the public input section");
+        u32 tag = r.r32();
+        if (tag == BLOB_PI_TAG) {
+            const u64 k = r.r64();
+            if (k == 0 || k > MAX_PUBLIC_INPUTS || k > (len - r.pos) / 4) throw std::runtime_error("public input count");
+            c.pi_slots.resize(k);
+            r.raw(c.pi_slots.data(), k * 4);
+            tag = r.pos != len ? r.r32() : 0;
+        }
+        if (tag == BLOB_HASH_TAG) {
+            c.cfg.hasher = r.r32();
+            if (c.cfg.hasher != HASHER_KECCAK) throw std::runtime_error("hasher section: unknown hasher");
+        } else if (tag != 0 || c.pi_slots.empty()) {
+            throw std::runtime_error(c.pi_slots.empty() ? "unknown section after blind_zrows" : "trailing bytes after the public input section");
+        }
+        if (r.pos != len) throw std::runtime_error(c.cfg.hasher ? "trailing bytes after the hasher section" : "trailing bytes after the public input section");
     }
     // shape checks: everything a kernel indexes with is validated here, once.
     size_t n = c.n();

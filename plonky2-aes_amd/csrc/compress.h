@@ -173,7 +173,7 @@ inline std::string compress_proof(const Circuit& c, const VerifierData& vd, cons
 // decompress_merkle_proofs: the leaves' digests, then level by level every query's parent, taking a sibling from the query's
 // own block where the layout keeps one and from the nodes already seen otherwise.  siblings[q] receives the full path.
 inline bool decompress_paths(const CompressLayout& L, size_t t, size_t depth, size_t cap_h, const std::vector<Hash4>& leaf_hash,
-                             const std::vector<std::vector<Hash4>>& stored, std::vector<std::vector<Hash4>>& siblings) {
+                             const std::vector<std::vector<Hash4>>& stored, std::vector<std::vector<Hash4>>& siblings, u32 hasher) {
     const size_t Q = leaf_hash.size(), nl = (size_t)1 << (depth + cap_h);
     std::map<size_t, Hash4> seen;
     for (size_t q = 0; q < Q; q++) seen[L.leaf[t][q] + nl] = leaf_hash[q];
@@ -185,7 +185,7 @@ inline bool decompress_paths(const CompressLayout& L, size_t t, size_t depth, si
             auto s = seen.find(node ^ 1);
             if (s == seen.end()) return false;
             const Hash4& cur = seen[node];
-            seen[node >> 1] = (node & 1) ? h_two_to_one(s->second, cur) : h_two_to_one(cur, s->second);
+            seen[node >> 1] = (node & 1) ? h_two_to_one(s->second, cur, hasher) : h_two_to_one(cur, s->second, hasher);
         }
     siblings.assign(Q, std::vector<Hash4>(depth));
     for (size_t q = 0; q < Q; q++)
@@ -251,6 +251,30 @@ inline std::string decompress_proof(const Circuit& c, const VerifierData& vd, co
                 at += 8 * ev + 1 + 32 * k;
             }
         }
+    // Keccak circuits: the range of every hash word (caps of the prefix, kept siblings), with the precedence of canonicality
+    if (c.cfg.hasher == HASHER_KECCAK) {
+        auto ranged = [&](size_t at, size_t hashes) {
+            for (size_t i = 0; i < hashes; i++) {
+                u64 h[4];
+                memcpy(h, cb + at + 32 * i, 32);
+                if (!kc::in_range(h)) return false;
+            }
+            return true;
+        };
+        const size_t cap_hashes = s.cap_bytes / 32;
+        bool ok = ranged(s.caps_off[0], 3 * cap_hashes) && ranged(s.fri_caps_off, s.step.size() * cap_hashes);
+        for (size_t t = 0; t < T && ok; t++)
+            for (size_t q = 0; q < Q && ok; q++) {
+                if (L.rep[t][q] != q) continue;
+                const size_t k = popcount(L.kept[t][q]);
+                size_t at = L.off[t][q];
+                for (int o = 0; o < (t == 0 ? 4 : 1); o++) {
+                    ok = ok && ranged(at + leaf_bytes(s, t, o) + 1, k);
+                    at += leaf_bytes(s, t, o) + 1 + 32 * k;
+                }
+            }
+        if (!ok) return "hash word out of range";
+    }
     // the transcript reads the prefix and the tail only: parse them as a full proof with empty query blocks
     std::vector<uint8_t> full(s.bytes, 0);
     memcpy(full.data(), cb, prefix);
@@ -291,14 +315,14 @@ inline std::string decompress_proof(const Circuit& c, const VerifierData& vd, co
         std::vector<std::vector<Hash4>> stored(Q);
         for (size_t q = 0; q < Q; q++)
             for (size_t i = 0; i < popcount(L.kept[t][q]); i++) stored[q].push_back(rdhash(stored_at[q] + 32 * i));
-        return decompress_paths(L, t, s.tree(t).depth, s.cap_height, leaf_hash, stored, paths);
+        return decompress_paths(L, t, s.tree(t).depth, s.cap_height, leaf_hash, stored, paths, c.cfg.hasher);
     };
     for (int o = 0; o < 4; o++) {
         std::vector<Hash4> lh(Q);
         std::vector<size_t> stored_at(Q);
         for (size_t q = 0; q < Q; q++) {
             const auto& ev = pp.queries[q].init_evals[o];
-            lh[q] = h_hash_or_noop(ev.data(), ev.size());
+            lh[q] = h_hash_or_noop(ev.data(), ev.size(), c.cfg.hasher);
             size_t at = L.off[0][q];
             const size_t k = popcount(L.kept[0][L.rep[0][q]]);
             for (int o2 = 0; o2 < o; o2++) at += leaf_bytes(s, 0, o2) + 1 + 32 * k;
@@ -344,7 +368,7 @@ inline std::string decompress_proof(const Circuit& c, const VerifierData& vd, co
             }
             std::vector<u64> flat;
             for (auto& e : ev) flat.push_back(e.a), flat.push_back(e.b);
-            lh[q] = h_hash_or_noop(flat.data(), flat.size());
+            lh[q] = h_hash_or_noop(flat.data(), flat.size(), c.cfg.hasher);
             stored_at[q] = L.off[t][q] + leaf_bytes(s, t, 0) + 1;
         }
         std::vector<std::vector<Hash4>> paths;

@@ -17,6 +17,7 @@
 #include "kernels.h"
 #include "kernels2.h"
 #include "kernels_compress.h"
+#include "kernels_keccak.h"
 
 using namespace p2;
 using namespace p2k;
@@ -137,6 +138,9 @@ struct p2_circuit {
     std::mutex vfy_mu;
     // compressed proofs (kernels_compress.h): the source of every word of the full layout
     u32* d_cmp_wmap = nullptr;
+    // Keccak circuits: the word index of every hash of the unpacked proof, the caps first (k_kcv_range)
+    u32* d_kc_hash_idx = nullptr;
+    u32 kc_cap_hashes = 0, kc_hashes = 0;
     long fail_alloc_after = -1;            // test hook, see dalloc_ws
     // timing
     bool timing_on = false;
@@ -342,6 +346,17 @@ static int merkle_levels(p2_circuit* C, Tree& t, u32 batch) {
     const u32 cap_h = C->c.cfg.cap_height;
     if (t.bits <= cap_h) return 0;
     const u32 levels = t.bits - cap_h;                       // level l: 2^(bits-l-1) parents
+    if (C->c.cfg.hasher == HASHER_KECCAK) {
+        // one launch per level for every batch size: a Keccak level is one permutation of 24 short rounds, and the fused top of
+        // the Poseidon path exists for the latency of a single proof only
+        for (u32 l = 0; l < levels; l++) {
+            size_t parents = ((size_t)1 << t.bits) >> (l + 1);
+            size_t off_c = 4 * (((size_t)2 << t.bits) - ((size_t)2 << (t.bits - l)));
+            size_t off_p = 4 * (((size_t)2 << t.bits) - ((size_t)2 << (t.bits - l - 1)));
+            LAUNCH(C, "merkle_level", k_kc_level, g1(parents, 256, batch), dim3(256), 0, t.dig + off_c, t.dig + off_p, parents, t.stride());
+        }
+        return 0;
+    }
     // The last `fused` levels (parents per cap subtree 2^(fused-1) .. 1) run as ONE launch of a workgroup per cap node -- for
     // SMALL batches only.  These levels are latency bound either way (a level is one permutation deep whatever its width), so
     // what the fusion buys is launches: 54 -> 18 per chunk, 118 -> 70 for the whole pipeline.  For a full chunk it costs time:
@@ -367,6 +382,10 @@ static int merkle_levels(p2_circuit* C, Tree& t, u32 batch) {
 }
 static int merkle_build(p2_circuit* C, const u64* data, u32 cols, u32 active, size_t col_stride, size_t batch_stride, Tree& t, u32 batch) {
     size_t leaves = (size_t)1 << t.bits;
+    if (C->c.cfg.hasher == HASHER_KECCAK) {
+        LAUNCH(C, "hash_leaves", k_kc_leaves, g1(leaves, 256, batch), dim3(256), 0, data, (int)cols, (int)active, col_stride, batch_stride, leaves, t.dig, t.stride());
+        return merkle_levels(C, t, batch);
+    }
     LAUNCH(C, "hash_leaves", k_hash_leaves, g1(leaves, 256, batch), dim3(256), 0, data, (int)cols, (int)active, col_stride, batch_stride, leaves, t.dig,
            t.stride());
     return merkle_levels(C, t, batch);
@@ -560,6 +579,18 @@ static int circuit_setup(p2_circuit* C) {
         HIPCHECK(hipMemcpy(cap.data(), C->pre_tree.dig + cap_off(C->pre_tree, c.cfg.cap_height), cap.size() * 8, hipMemcpyDeviceToHost));
         // circuit digest = hash_no_pad(cap || hash_pad([]) || degree_bits)   (a dozen host permutations)
         std::vector<u64> parts(cap);
+        if (c.cfg.hasher == HASHER_KECCAK) {
+            // the same word sequence, both hashes by the tree hasher (upstream C::Hasher)
+            const u64 padded[12] = {1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1};
+            u64 h[4];
+            kc::hash_no_pad(padded, 12, h);
+            parts.insert(parts.end(), h, h + 4);
+            parts.push_back(c.degree_bits);
+            kc::hash_no_pad(parts.data(), (u32)parts.size(), h);
+            C->verifier_data = cap;
+            C->verifier_data.insert(C->verifier_data.end(), h, h + 4);
+            return upload(C, &C->d_digest, h, 4);
+        }
         {
             u64 st[12] = {1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1};  // hash_pad of the empty domain separator
             u64 s2[12] = {0};
@@ -949,7 +980,10 @@ static int prove_chunk(p2_circuit* C, u32 B, u32 n_inputs, const u64* d_values, 
             if (lde_cols(C, C->cur->d_fri_coef[r], 2 * n_r, C->cur->d_fri_vals[r], 2 * len, 2, r, B)) return P2_ERR_HIP;
             Tree& t = C->cur->fri_tree[r];
             size_t leaves = len / arity;
-            LAUNCH(C, "hash_fri_leaves", k_hash_fri_leaves, g1(leaves, 256, B), dim3(256), 0, C->cur->d_fri_vals[r], len, 2 * len, (int)arity, t.dig, t.stride());
+            if (c.cfg.hasher == HASHER_KECCAK)
+                LAUNCH(C, "hash_fri_leaves", k_kc_fri_leaves, g1(leaves, 256, B), dim3(256), 0, C->cur->d_fri_vals[r], len, 2 * len, (int)arity, t.dig, t.stride());
+            else
+                LAUNCH(C, "hash_fri_leaves", k_hash_fri_leaves, g1(leaves, 256, B), dim3(256), 0, C->cur->d_fri_vals[r], len, 2 * len, (int)arity, t.dig, t.stride());
             if (merkle_levels(C, t, B)) return P2_ERR_HIP;
             if (challenger(C, 4, t.dig + cap_off(t, cap_h), t.stride(), cap_words, r, 0, B)) return P2_ERR_HIP;
             size_t n_next = n_r >> C->arities[r];
@@ -1242,6 +1276,21 @@ static int verify_setup(p2_circuit* C) {
     if (upload(C, (u32**)&a.word_off, woff.data(), woff.size()) || upload(C, (u32**)&a.cnt_off, coff.data(), coff.size()) ||
         upload(C, (uint8_t**)&a.cnt_exp, cexp.data(), cexp.size()) || upload(C, (u32**)&a.obs_map, obs.data(), obs.size()))
         return P2_ERR_HIP;
+    if (c.cfg.hasher == HASHER_KECCAK) {
+        std::vector<u32> hidx;
+        for (u32 i = 0; i < 3 * a.cap_words; i += 4) hidx.push_back(i);
+        for (u32 i = 0; i < L.step.size() * a.cap_words; i += 4) hidx.push_back(a.fri_caps_off + i);
+        C->kc_cap_hashes = (u32)hidx.size();
+        for (u32 q = 0; q < L.num_queries; q++) {
+            const u32 base = a.q_off + q * a.q_stride;
+            for (int o = 0; o < 4; o++)
+                for (u32 l = 0; l < a.init_depth; l++) hidx.push_back(base + a.init_sib_off[o] + 4 * l);
+            for (u32 k = 0; k < L.step.size(); k++)
+                for (u32 l = 0; l < a.step_depth[k]; l++) hidx.push_back(base + a.step_sib_off[k] + 4 * l);
+        }
+        C->kc_hashes = (u32)hidx.size();
+        if (upload(C, &C->d_kc_hash_idx, hidx.data(), hidx.size())) return P2_ERR_HIP;
+    }
     a.proof_bytes = C->pbytes;
     a.degree_bits = c.degree_bits;
     a.lde_bits = lde_bits;
@@ -1356,6 +1405,7 @@ static int proof_run(p2_circuit* C, VerifyWs* W, ProofOp op, size_t batch, const
     const ProofLayout& L = C->layout;
     const size_t pb = L.bytes;
     const bool full_in = op == OP_VERIFY || op == OP_COMPRESS, verdict = op == OP_VERIFY || op == OP_VERIFY_COMPRESSED;
+    const bool keccak = C->c.cfg.hasher == HASHER_KECCAK;
     HIPCHECK(hipStreamWaitEvent(st, W->done, 0));  // the workspace's previous user
     LAUNCH_ON(st, k_vfy_set_vd, dim3(1), dim3(128), vd, W->d_vd, C->vfy_args.cap_words + 4);
     for (size_t done = 0; done < batch; done += W->chunk) {
@@ -1397,14 +1447,18 @@ static int proof_run(p2_circuit* C, VerifyWs* W, ProofOp op, size_t batch, const
         const dim3 words_grid((v.W + 255) / 256, B), proofs_grid = g1(B, 64), transcript_grid = g1((size_t)B * 16, 64);
         if (full_in) {  // the words of a full proof and its challenges
             LAUNCH_ON(st, k_vfy_unpack, words_grid, dim3(256), v);
+            if (keccak) LAUNCH_ON(st, k_kcv_range, g1(C->kc_hashes, 256, B), dim3(256), v, (const u32*)C->d_kc_hash_idx, C->kc_hashes);
             LAUNCH_ON(st, k_vfy_transcript, transcript_grid, dim3(64), v);
         } else {  // the same from a compressed proof: what it stores, then what its Merkle caps and fold checks imply
             LAUNCH_ON(st, k_cmp_plan, dim3(B), dim3(256), a);
             LAUNCH_ON(st, k_cmp_scatter, words_grid, dim3(256), a);
+            // (the caps of the prefix; a proof without a layout keeps its SHAPE flag, which comes first.  Stored siblings: k_kcc_merkle)
+            if (keccak) LAUNCH_ON(st, k_kcv_range, g1(C->kc_cap_hashes, 256, B), dim3(256), v, (const u32*)C->d_kc_hash_idx, C->kc_cap_hashes);
             LAUNCH_ON(st, k_vfy_transcript, transcript_grid, dim3(64), v);
             LAUNCH_ON(st, k_cmp_reductions, proofs_grid, dim3(64), a);
             LAUNCH_ON(st, k_cmp_infer, dim3(B), dim3(CMP_MAXQ), a);
-            LAUNCH_ON(st, k_cmp_merkle, dim3(B, 4 + v.num_rounds), dim3(CMP_MAXQ), a);
+            if (keccak) LAUNCH_ON(st, k_kcc_merkle, dim3(B, 4 + v.num_rounds), dim3(CMP_MAXQ), a);
+            else LAUNCH_ON(st, k_cmp_merkle, dim3(B, 4 + v.num_rounds), dim3(CMP_MAXQ), a);
         }
         if (op == OP_COMPRESS) {
             LAUNCH_ON(st, k_cmp_plan, dim3(B), dim3(256), a);
@@ -1417,7 +1471,9 @@ static int proof_run(p2_circuit* C, VerifyWs* W, ProofOp op, size_t batch, const
         } else {
             const u32 slots = 4 + v.num_rounds + 1;
             LAUNCH_ON(st, k_vfy_vanishing, dim3(B), dim3(256), v);
-            LAUNCH_ON(st, k_vfy_queries, dim3((u32)(((size_t)B * v.num_queries + 63) / 64), slots), dim3(64), v);
+            const dim3 queries_grid((u32)(((size_t)B * v.num_queries + 63) / 64), slots);
+            if (keccak) LAUNCH_ON(st, k_kcv_queries, queries_grid, dim3(64), v);
+            else LAUNCH_ON(st, k_vfy_queries, queries_grid, dim3(64), v);
             LAUNCH_ON(st, k_vfy_finish, proofs_grid, dim3(64), v, slots);
         }
         if (host) {
@@ -2103,6 +2159,11 @@ int p2_gpu_lde(const uint64_t* coeffs, size_t cols, int degree_bits, int rate_bi
     return P2_OK;
 }
 int p2_gpu_merkle_cap(const uint64_t* cols_major, size_t cols, size_t num_leaves, int cap_height, uint64_t* cap, int device) {
+    return p2_gpu_merkle_cap_hasher(cols_major, cols, num_leaves, cap_height, P2_HASHER_POSEIDON, cap, device);
+}
+int p2_gpu_merkle_cap_hasher(const uint64_t* cols_major, size_t cols, size_t num_leaves, int cap_height, int hasher, uint64_t* cap, int device) {
+    if (hasher != P2_HASHER_POSEIDON && hasher != P2_HASHER_KECCAK) return set_error("unknown hasher"), P2_ERR_INVALID;
+    if (hasher == P2_HASHER_KECCAK && cols < 4) return set_error("Keccak trees hash every leaf: at least 4 columns"), P2_ERR_INVALID;
     u32 bits = 0;
     while (((size_t)1 << bits) < num_leaves) bits++;
     if (((size_t)1 << bits) != num_leaves || (int)bits < cap_height) return set_error("num_leaves must be a power of two >= 2^cap_height"), P2_ERR_INVALID;
@@ -2110,6 +2171,7 @@ int p2_gpu_merkle_cap(const uint64_t* cols_major, size_t cols, size_t num_leaves
     if (int rc = ctx.init(device, 4)) return rc;
     p2_circuit* C = &ctx.C;
     C->c.cfg.cap_height = (u32)cap_height;
+    C->c.cfg.hasher = (u32)hasher;
     u64* d_in;
     Tree t;
     t.bits = bits;

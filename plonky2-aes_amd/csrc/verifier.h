@@ -8,6 +8,7 @@
 
 #include "circuit.h"
 #include "gl.h"
+#include "keccak_hash.h"
 #include "poseidon_gate.h"
 
 namespace p2 {
@@ -28,7 +29,13 @@ inline Hash4 h_hash_no_pad(const u64* in, size_t len) {
     memcpy(h.e, st, 32);
     return h;
 }
-inline Hash4 h_hash_or_noop(const u64* in, size_t len) {
+// The tree hasher of the circuit (Config::hasher).  Every Merkle leaf of a Keccak circuit is wider than 4 words.
+inline Hash4 h_hash_or_noop(const u64* in, size_t len, u32 hasher) {
+    if (hasher == HASHER_KECCAK) {
+        Hash4 h;
+        kc::hash_no_pad(in, (u32)len, h.e);
+        return h;
+    }
     if (len <= 4) {
         Hash4 h = {{0, 0, 0, 0}};
         for (size_t i = 0; i < len; i++) h.e[i] = in[i];
@@ -36,9 +43,10 @@ inline Hash4 h_hash_or_noop(const u64* in, size_t len) {
     }
     return h_hash_no_pad(in, len);
 }
-inline Hash4 h_two_to_one(const Hash4& l, const Hash4& r) {
+inline Hash4 h_two_to_one(const Hash4& l, const Hash4& r, u32 hasher) {
     Hash4 h;
-    gl::two_to_one(l.e, r.e, h.e);
+    if (hasher == HASHER_KECCAK) kc::two_to_one(l.e, r.e, h.e);
+    else gl::two_to_one(l.e, r.e, h.e);
     return h;
 }
 
@@ -122,10 +130,10 @@ struct ProofReader {
     }
 };
 
-inline bool verify_merkle_to_cap(const u64* leaf, size_t width, size_t index, const std::vector<Hash4>& cap, const std::vector<Hash4>& siblings) {
-    Hash4 cur = h_hash_or_noop(leaf, width);
+inline bool verify_merkle_to_cap(const u64* leaf, size_t width, size_t index, const std::vector<Hash4>& cap, const std::vector<Hash4>& siblings, u32 hasher) {
+    Hash4 cur = h_hash_or_noop(leaf, width, hasher);
     for (auto& s : siblings) {
-        cur = (index & 1) ? h_two_to_one(s, cur) : h_two_to_one(cur, s);
+        cur = (index & 1) ? h_two_to_one(s, cur, hasher) : h_two_to_one(cur, s, hasher);
         index >>= 1;
     }
     return index < cap.size() && cur == cap[index];
@@ -259,6 +267,21 @@ inline std::string parse_proof(const Circuit& C, const uint8_t* bytes, size_t le
                 if (!canonical(e.a) || !canonical(e.b)) return "non-canonical field element";
             bits -= arities[k];
         }
+    }
+    // Keccak circuits: two_to_one reads the low 7 (4) bytes of a hash word, so a word outside its range is rejected, not ignored
+    if (C.cfg.hasher == HASHER_KECCAK) {
+        auto ranged = [&](const std::vector<Hash4>& hs) {
+            for (auto& h : hs)
+                if (!kc::in_range(h.e)) return false;
+            return true;
+        };
+        bool ok = ranged(wires_cap) && ranged(zs_cap) && ranged(quot_cap);
+        for (auto& cap : fri_caps) ok = ok && ranged(cap);
+        for (auto& q : queries) {
+            for (auto& p : q.init_proofs) ok = ok && ranged(p);
+            for (auto& p : q.step_proofs) ok = ok && ranged(p);
+        }
+        if (!ok) return "hash word out of range";
     }
     return "";
 }
@@ -501,7 +524,7 @@ inline std::string verify_parsed(const Circuit& C, const VerifierData& vd, const
         const ProofQuery& q = queries[qi];
         size_t x_index = query_idx[qi];
         for (int o = 0; o < 4; o++)
-            if (!verify_merkle_to_cap(q.init_evals[o].data(), q.init_evals[o].size(), x_index, *init_caps[o], q.init_proofs[o]))
+            if (!verify_merkle_to_cap(q.init_evals[o].data(), q.init_evals[o].size(), x_index, *init_caps[o], q.init_proofs[o], C.cfg.hasher))
                 return "Invalid Merkle proof (initial tree).";
         u64 subgroup_x = mul(MULT_GEN, pow(w_lde, bitrev((u32)x_index, (int)lde_bits)));
         E2 sum = fri_combine_initial(C, q, subgroup_x, T, red0, red1, g_zeta);
@@ -518,7 +541,7 @@ inline std::string verify_parsed(const Circuit& C, const VerifierData& vd, const
                 flat.push_back(e.a);
                 flat.push_back(e.b);
             }
-            if (!verify_merkle_to_cap(flat.data(), flat.size(), coset_index, fri_caps[k], q.step_proofs[k])) return "Invalid Merkle proof (FRI round).";
+            if (!verify_merkle_to_cap(flat.data(), flat.size(), coset_index, fri_caps[k], q.step_proofs[k], C.cfg.hasher)) return "Invalid Merkle proof (FRI round).";
             subgroup_x = exp_pow2(subgroup_x, (int)ab);
             x_index = coset_index;
         }
