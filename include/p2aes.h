@@ -221,6 +221,8 @@ void p2_native_aes_gcm_encrypt(const uint8_t* key, int nk, int nr, const uint8_t
  * in the four-word form (each word in its range).  out4 is in the four-word form. */
 void p2_native_keccak_hash_no_pad(const uint64_t* in, size_t n, uint64_t out4[4]);
 void p2_native_keccak_two_to_one(const uint64_t l4[4], const uint64_t r4[4], uint64_t out4[4]);
+/* Keccak-256 (original padding) of a byte string, on the same permutation: the hash in a lookup gate's id. */
+void p2_native_keccak256(const uint8_t* data, size_t len, uint8_t out32[32]);
 
 /* ------------------------------------------------------------------ circuit info / verification (host) */
 /* Shape of a compiled circuit without touching a device. */

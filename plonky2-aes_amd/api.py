@@ -106,6 +106,7 @@ def lib():
         "p2_builder_new": (vp, []), "p2_builder_new_zk": (vp, []), "p2_builder_free": (None, [vp]),
         "p2_builder_new_config": (vp, [C.c_int, C.c_int]), "p2_builder_set_hasher": (C.c_int, [vp, C.c_int]),
         "p2_native_keccak_hash_no_pad": (None, [u64p, sz, u64p]), "p2_native_keccak_two_to_one": (None, [u64p, u64p, u64p]),
+        "p2_native_keccak256": (None, [C.c_char_p, sz, C.c_char_p]),
         "p2_gpu_merkle_cap_hasher": (C.c_int, [u64p, sz, sz, C.c_int, C.c_int, u64p, C.c_int]),
         "p2_circuit_set_zk_seed": (C.c_int, [vp, u64]),
         "p2_circuit_set_zk_key": (C.c_int, [vp, C.POINTER(u64)]),
@@ -778,6 +779,12 @@ class keccak_native:
         out = (u64 * 4)()
         lib().p2_native_keccak_two_to_one(_arr(l), _arr(r), out)
         return list(out)
+
+    @staticmethod
+    def keccak256(data):
+        out = C.create_string_buffer(32)
+        lib().p2_native_keccak256(bytes(data), len(data), out)
+        return out.raw
 
 
 class poseidon_native:

@@ -18,7 +18,7 @@
 
 #include "circuit.h"
 #include "gl.h"
-#include "keccak.h"
+#include "keccak_hash.h"
 
 namespace p2 {
 
@@ -403,7 +403,7 @@ inline Circuit CircuitBuilder::build() {
                     bytes.push_back((uint8_t)(v & 0xFF));
                     bytes.push_back((uint8_t)(v >> 8));
                 }
-            auto h = keccak256(bytes.data(), bytes.size());
+            auto h = kc::keccak256(bytes.data(), bytes.size());
             std::string hs = "[";
             for (size_t i = 0; i < h.size(); i++) hs += (i ? ", " : "") + std::to_string((unsigned)h[i]);
             hs += "]";

@@ -294,6 +294,7 @@ void p2_native_hash_n_to_m_no_pad(const uint64_t* in, size_t n, uint64_t* out, s
 }
 void p2_native_keccak_hash_no_pad(const uint64_t* in, size_t n, uint64_t out[4]) { kc::hash_no_pad(in, (u32)n, out); }
 void p2_native_keccak_two_to_one(const uint64_t l[4], const uint64_t r[4], uint64_t out[4]) { kc::two_to_one(l, r, out); }
+void p2_native_keccak256(const uint8_t* data, size_t len, uint8_t out[32]) { memcpy(out, kc::keccak256(data, len).data(), 32); }
 static pcipher::Fq fq_at(const uint64_t* p) { return pcipher::Fq{p[0], p[1], p[2], p[3], p[4]}; }
 void p2_native_poseidon_encrypt(const uint64_t* ks, const uint64_t* msg, size_t n_msg, const uint64_t* nonce, uint64_t* ct) {
     (void)guarded([&] {

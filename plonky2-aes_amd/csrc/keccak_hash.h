@@ -9,8 +9,15 @@
 // 21-24, little-endian (each below 2^56, the last below 2^32), so a hash stays four words everywhere a Poseidon hash is four
 // words.  two_to_one reads only the low 7 (4) bytes of each word: a verifier must reject a word outside its range (in_range)
 // or one proof would have many accepted encodings.
+//
+// The same permutation serves keccak256(bytes) on the host: plonky2 tags every LookupGate / LookupTableGate with the Keccak-256
+// of its table and the hash is part of the gate's id(), which builder.h needs to sort the gate types as upstream does.
 #pragma once
+#include <string.h>
+
+#include <array>
 #include <utility>
+#include <vector>
 
 #include "gl.h"
 
@@ -143,6 +150,27 @@ GL_HD void two_to_one(const u64* l, const u64* r, u64* out) {
     s[16] = 0x80ull << 56;
     permute(s);
     pack_digest(s, out);
+}
+
+// Keccak-256 of a byte string (host; lanes are little-endian words of the message, as everywhere above)
+static inline std::array<uint8_t, 32> keccak256(const uint8_t* data, size_t len) {
+    const size_t RATE = 8 * RATE_WORDS;
+    std::vector<uint8_t> msg(data, data + len);
+    msg.push_back(0x01);
+    msg.resize((msg.size() + RATE - 1) / RATE * RATE, 0);
+    msg.back() |= 0x80;
+    u64 s[25] = {0};
+    for (size_t off = 0; off < msg.size(); off += RATE) {
+        for (size_t i = 0; i < RATE_WORDS; i++) {
+            u64 w;
+            memcpy(&w, &msg[off + 8 * i], 8);
+            s[i] ^= w;
+        }
+        permute(s);
+    }
+    std::array<uint8_t, 32> out;
+    memcpy(out.data(), s, 32);
+    return out;
 }
 
 }  // namespace kc

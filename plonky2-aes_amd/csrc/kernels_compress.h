@@ -237,7 +237,9 @@ __global__ __launch_bounds__(CMP_MAXQ) void k_cmp_infer(CmpArgs a) {
 }
 
 // ------------------------------------------------------------------------------------------- 5. Merkle paths
-__global__ __launch_bounds__(CMP_MAXQ) void k_cmp_merkle(CmpArgs a) {
+// H: the tree hasher (PoseidonTree, KeccakTree).  A stored sibling that is not an accepted encoding of a hash is NON_CANONICAL.
+template <class H>
+__device__ __forceinline__ void cmp_merkle(const CmpArgs& a) {
     __shared__ u32 s_node[CMP_MAXQ], s_mask[CMP_MAXQ];
     __shared__ u64 s_cur[CMP_MAXQ][4], s_sib[CMP_MAXQ][4];
     const VerifyArgs& v = a.v;
@@ -252,8 +254,8 @@ __global__ __launch_bounds__(CMP_MAXQ) void k_cmp_merkle(CmpArgs a) {
     const u32 leaf = mine ? pl.idx[q] >> cmp_shift(t) : 0xFFFFFFFFu;
     const uint8_t* stored = a.cproofs + (size_t)p * v.proof_bytes + (mine ? pl.off[t][q] + cmp_sib_at(a, slot, __popc(mask)) : 0);
     u64 cur[4];
-    if (slot < 4) vfy_hash_or_noop(qw + v.init_eval_off[slot], v.init_width[slot], cur);
-    else vfy_hash_or_noop(qw + v.step_eval_off[slot - 4], 2 * VFY_ARITY, cur);
+    if (slot < 4) H::hash_or_noop(qw + v.init_eval_off[slot], v.init_width[slot], cur);
+    else H::hash_or_noop(qw + v.step_eval_off[slot - 4], 2 * VFY_ARITY, cur);
     s_mask[q] = mask;
     for (u32 l = 0; l < depth; l++) {
         const u32 node = leaf >> l;
@@ -261,11 +263,12 @@ __global__ __launch_bounds__(CMP_MAXQ) void k_cmp_merkle(CmpArgs a) {
         for (int i = 0; i < 4; i++) s_cur[q][i] = cur[i];
         if ((mask >> l) & 1) {
             const uint8_t* b = stored + 32 * __popc(mask & ((1u << l) - 1));
+            u64 y[4];
             for (int i = 0; i < 4; i++) {
-                const u64 y = vfy_ld_bytes(b + 8 * i);
-                if (y >= gl::P) atomicOr(&v.flags[p], (u32)VF_NONCANON);
-                s_sib[q][i] = y;
+                y[i] = vfy_ld_bytes(b + 8 * i);
+                s_sib[q][i] = y[i];
             }
+            if (!H::valid(y)) atomicOr(&v.flags[p], (u32)VF_NONCANON);
         }
         __syncthreads();
         u64 sb[4] = {0, 0, 0, 0};
@@ -283,19 +286,12 @@ __global__ __launch_bounds__(CMP_MAXQ) void k_cmp_merkle(CmpArgs a) {
                     for (int i = 0; i < 4; i++) sb[i] = on_path ? s_cur[from][i] : s_sib[from][i];
             }
             for (int i = 0; i < 4; i++) sib_out[4 * l + i] = sb[i];
-            u64 st[12];
-            const bool right = node & 1;
-            for (int i = 0; i < 4; i++) {
-                st[i] = right ? sb[i] : cur[i];
-                st[4 + i] = right ? cur[i] : sb[i];
-                st[8 + i] = 0;
-            }
-            glf::poseidon(st);
-            for (int i = 0; i < 4; i++) cur[i] = st[i];
+            H::compress(cur, sb, node & 1);
         }
         __syncthreads();
     }
 }
+__global__ __launch_bounds__(CMP_MAXQ) void k_cmp_merkle(CmpArgs a) { cmp_merkle<PoseidonTree>(a); }
 
 // ------------------------------------------------------------------------------------------- 6. outputs
 // decompression: the full byte layout of every proof whose status is OK, zeros otherwise

@@ -1,8 +1,10 @@
-// HIP kernels of the Keccak configuration (Config::hasher == HASHER_KECCAK; keccak_hash.h defines the hasher): the Merkle trees
-// of the prover, the path walk of the batched verifier and the tree reconstruction of the compressor.  Each is the Keccak
-// sibling of a Poseidon kernel and is launched in its place; the Poseidon kernels are untouched (their code generation is
-// pinned by tests/test_codegen.py and tests/test_public_inputs_host.py, which select kernels by name fragments -- none of the
-// fragments occurs in a name below).
+// HIP kernels of the Keccak configuration (Config::hasher == HASHER_KECCAK; keccak_hash.h defines the hasher), each launched in
+// place of a Poseidon kernel.  The prover's tree kernels and the range check are kernels of their own: the Poseidon ones are
+// hand-scheduled around their sponge and share nothing with a 25-lane state.  The path walk of the batched verifier and the
+// tree reconstruction of the compressor are the bodies of kernels_verify.h / kernels_compress.h instantiated with the
+// KeccakTree policy below.  The code generation of the Poseidon kernels is pinned by tests/test_codegen.py and
+// tests/test_public_inputs_host.py, which select kernels by name fragments: none of the fragments may occur in a kernel name
+// below, so the two instantiations are non-template kernels with names of their own.
 //
 // One thread = one sponge: 25 lanes = 50 VGPRs of state, a round is 32-bit logic throughout (xor, v_bfi_b32 for chi,
 // v_alignbit_b32 for rho), the round loop is not unrolled.  All stores are vector stores; the round constants come from
@@ -94,124 +96,23 @@ __global__ __launch_bounds__(256) void k_kcv_range(VerifyArgs a, const u32* __re
     if (!kc::in_range(a.words + (size_t)p * a.W + hash_idx[i])) atomicOr(&a.flags[p], (u32)VF_NONCANON);
 }
 
-__device__ __forceinline__ bool kcv_merkle(const u64* leaf, u32 width, u32 index, const u64* cap, u32 cap_n, const u64* sib, u32 depth) {
-    u64 cur[4];
-    kc::hash_no_pad(leaf, width, cur);
-    for (u32 l = 0; l < depth; l++) {
-        const u64* s = sib + 4 * (size_t)l;
-        const bool right = index & 1;
+// The tree hasher as the path walks use it: the members of PoseidonTree (kernels_verify.h)
+struct KeccakTree {
+    static __device__ __forceinline__ void hash_or_noop(const u64* in, u32 len, u64* out) { kc::hash_no_pad(in, len, out); }
+    static __device__ __forceinline__ void compress(u64* cur, const u64* sib, bool right) {
         u64 lr[8];
 #pragma unroll
         for (int i = 0; i < 4; i++) {
-            lr[i] = right ? s[i] : cur[i];
-            lr[4 + i] = right ? cur[i] : s[i];
+            lr[i] = right ? sib[i] : cur[i];
+            lr[4 + i] = right ? cur[i] : sib[i];
         }
         kc::two_to_one(lr, lr + 4, cur);
-        index >>= 1;
     }
-    const u64* c = cap + 4 * (size_t)(index & (cap_n - 1));
-    return index < cap_n && cur[0] == c[0] && cur[1] == c[1] && cur[2] == c[2] && cur[3] == c[3];
-}
+    static __device__ __forceinline__ bool valid(const u64* h) { return kc::in_range(h); }
+};
 
-// k_vfy_queries with the Keccak path walk: same slots, same checks, same failure keys.
-__global__ __launch_bounds__(64) void k_kcv_queries(VerifyArgs a) {
-    const u32 t = blockIdx.x * blockDim.x + threadIdx.x, slot = blockIdx.y, slots = gridDim.y;
-    if (t >= a.batch * a.num_queries) return;
-    const u32 p = t / a.num_queries, q = t % a.num_queries;
-    const u64* w = a.words + (size_t)p * a.W;
-    const u64* ch = a.chal + (size_t)p * CH_WORDS;
-    const u64* vq = a.vq + (size_t)p * VQ_WORDS;
-    const u64* qw = w + a.q_off + (size_t)q * a.q_stride;
-    const u32 cap_n = 1u << a.cap_height;
-    const u32 x_index = (u32)(ch[CH_QUERY + q] & (((u64)1 << a.lde_bits) - 1));
-    const u32 key = (q * slots + slot) << 1;
-    const u64 *leaf = nullptr, *cap = nullptr, *sib = nullptr;
-    u32 width = 0, index = 0, depth = 0, mkey = key;
-    if (slot < 4) {
-        cap = slot == 0 ? a.vd : w + (size_t)(slot - 1) * a.cap_words;
-        leaf = qw + a.init_eval_off[slot], width = a.init_width[slot], index = x_index, sib = qw + a.init_sib_off[slot], depth = a.init_depth;
-    } else {
-        const u64 subgroup_x0 = gl::mul(gl::MULT_GEN, gl::pow(gl::root_of_unity((int)a.lde_bits), gl::bitrev(x_index, (int)a.lde_bits)));
-        const u32 k = slot - 4;
-        const E2 expect = vfy_expected(a, w, qw, k, x_index, subgroup_x0, ch, vq);
-        if (k == a.num_rounds) {
-            const u64 sx = gl::exp_pow2(subgroup_x0, (int)(VFY_ARITY_BITS * a.num_rounds));
-            E2 fe = gl::e2(0);
-            for (u32 i = a.final_len; i-- > 0;) fe = gl::add(gl::mul(fe, sx), vfy_e2(w, a.final_off + 2 * i));
-            if (!gl::eq(fe, expect)) atomicMin(&a.qfail[p], key);
-            return;
-        }
-        const u32 xk = x_index >> (VFY_ARITY_BITS * k), within = xk & (VFY_ARITY - 1);
-        leaf = qw + a.step_eval_off[k];
-        if (!gl::eq(vfy_e2(leaf, 2 * within), expect)) {
-            atomicMin(&a.qfail[p], key);
-            return;
-        }
-        cap = w + a.fri_caps_off + (size_t)k * a.cap_words, width = 2 * VFY_ARITY, index = xk >> VFY_ARITY_BITS;
-        sib = qw + a.step_sib_off[k], depth = a.step_depth[k], mkey = key | 1;
-    }
-    if (!kcv_merkle(leaf, width, index, cap, cap_n, sib, depth)) atomicMin(&a.qfail[p], mkey);
-}
-
-// ------------------------------------------------------------------------------------------- compressed proofs
-// k_cmp_merkle with the Keccak hasher; a stored sibling outside its range is NON_CANONICAL like one that is not below p.
-__global__ __launch_bounds__(CMP_MAXQ) void k_kcc_merkle(CmpArgs a) {
-    __shared__ u32 s_node[CMP_MAXQ], s_mask[CMP_MAXQ];
-    __shared__ u64 s_cur[CMP_MAXQ][4], s_sib[CMP_MAXQ][4];
-    const VerifyArgs& v = a.v;
-    const u32 p = blockIdx.x, slot = blockIdx.y, q = threadIdx.x, Q = v.num_queries;
-    const CmpPlan& pl = a.plan[p];
-    if (pl.len == 0) return;  // (uniform over the workgroup)
-    const bool mine = q < Q;
-    const u32 t = slot < 4 ? 0 : slot - 3, depth = cmp_depth(v, t);
-    u64* qw = v.words + (size_t)p * v.W + v.q_off + (size_t)(mine ? q : 0) * v.q_stride;
-    u64* sib_out = qw + (slot < 4 ? v.init_sib_off[slot] : v.step_sib_off[slot - 4]);
-    const u32 mask = mine ? pl.mask[t][q] : 0;
-    const u32 leaf = mine ? pl.idx[q] >> cmp_shift(t) : 0xFFFFFFFFu;
-    const uint8_t* stored = a.cproofs + (size_t)p * v.proof_bytes + (mine ? pl.off[t][q] + cmp_sib_at(a, slot, __popc(mask)) : 0);
-    u64 cur[4];
-    if (slot < 4) kc::hash_no_pad(qw + v.init_eval_off[slot], v.init_width[slot], cur);
-    else kc::hash_no_pad(qw + v.step_eval_off[slot - 4], 2 * VFY_ARITY, cur);
-    s_mask[q] = mask;
-    for (u32 l = 0; l < depth; l++) {
-        const u32 node = leaf >> l;
-        s_node[q] = mine ? node : 0xFFFFFFFFu;
-        for (int i = 0; i < 4; i++) s_cur[q][i] = cur[i];
-        if ((mask >> l) & 1) {
-            const uint8_t* b = stored + 32 * __popc(mask & ((1u << l) - 1));
-            u64 y[4];
-            for (int i = 0; i < 4; i++) {
-                y[i] = vfy_ld_bytes(b + 8 * i);
-                s_sib[q][i] = y[i];
-            }
-            if (!kc::in_range(y)) atomicOr(&v.flags[p], (u32)VF_NONCANON);
-        }
-        __syncthreads();
-        u64 sb[4] = {0, 0, 0, 0};
-        if (mine) {
-            if ((mask >> l) & 1) {
-                for (int i = 0; i < 4; i++) sb[i] = s_sib[q][i];
-            } else {
-                u32 from = CMP_MAXQ;
-                bool on_path = false;
-                for (u32 e = 0; e < Q && from == CMP_MAXQ; e++)
-                    if (s_node[e] == (node ^ 1)) from = e, on_path = true;
-                for (u32 e = 0; e < q && from == CMP_MAXQ; e++)
-                    if (s_node[e] == node && ((s_mask[e] >> l) & 1)) from = e;
-                if (from < CMP_MAXQ)
-                    for (int i = 0; i < 4; i++) sb[i] = on_path ? s_cur[from][i] : s_sib[from][i];
-            }
-            for (int i = 0; i < 4; i++) sib_out[4 * l + i] = sb[i];
-            u64 lr[8];
-            const bool right = node & 1;
-            for (int i = 0; i < 4; i++) {
-                lr[i] = right ? sb[i] : cur[i];
-                lr[4 + i] = right ? cur[i] : sb[i];
-            }
-            kc::two_to_one(lr, lr + 4, cur);
-        }
-        __syncthreads();
-    }
-}
+// k_vfy_queries and k_cmp_merkle with the Keccak hasher
+__global__ __launch_bounds__(64) void k_kcv_queries(VerifyArgs a) { vfy_queries<KeccakTree>(a); }
+__global__ __launch_bounds__(CMP_MAXQ) void k_kcc_merkle(CmpArgs a) { cmp_merkle<KeccakTree>(a); }
 
 }  // namespace p2k

@@ -404,42 +404,53 @@ __global__ __launch_bounds__(256) void k_vfy_vanishing(VerifyArgs a) {
 }
 
 // ------------------------------------------------------------------------------------------- 4. queries
-__device__ __forceinline__ void vfy_hash_or_noop(const u64* in, u32 len, u64* out) {
-    if (len <= 4) {
+// The tree hasher of the circuit's configuration, as the path walks of the verifier (vfy_merkle) and of the compressor
+// (cmp_merkle, kernels_compress.h) use it: a policy type per hasher, KeccakTree (kernels_keccak.h) with the same members.
+struct PoseidonTree {
+    // the digest of a leaf: the leaf itself if it fits in a digest, else the overwrite-mode sponge
+    static __device__ __forceinline__ void hash_or_noop(const u64* in, u32 len, u64* out) {
+        if (len <= 4) {
 #pragma unroll
-        for (int i = 0; i < 4; i++) out[i] = (u32)i < len ? in[i] : 0;
-        return;
+            for (int i = 0; i < 4; i++) out[i] = (u32)i < len ? in[i] : 0;
+            return;
+        }
+        u64 st[12];
+#pragma unroll
+        for (int i = 0; i < 12; i++) st[i] = 0;
+        for (u32 off = 0; off < len; off += 8) {
+            const u32 k = min(8u, len - off);
+#pragma unroll
+            for (u32 i = 0; i < 8; i++)
+                if (i < k) st[i] = in[off + i];  // overwrite mode: a short last chunk keeps the state's other rate words
+            glf::poseidon(st);
+        }
+#pragma unroll
+        for (int i = 0; i < 4; i++) out[i] = st[i];
     }
-    u64 st[12];
-#pragma unroll
-    for (int i = 0; i < 12; i++) st[i] = 0;
-    for (u32 off = 0; off < len; off += 8) {
-        const u32 k = min(8u, len - off);
-#pragma unroll
-        for (u32 i = 0; i < 8; i++)
-            if (i < k) st[i] = in[off + i];  // overwrite mode: a short last chunk keeps the state's other rate words
-        glf::poseidon(st);
-    }
-#pragma unroll
-    for (int i = 0; i < 4; i++) out[i] = st[i];
-}
-// verify_merkle_to_cap: the leaf's digest climbed with `depth` siblings and compared with cap entry index >> depth
-__device__ __forceinline__ bool vfy_merkle(const u64* leaf, u32 width, u32 index, const u64* cap, u32 cap_n, const u64* sib, u32 depth) {
-    u64 cur[4];
-    vfy_hash_or_noop(leaf, width, cur);
-    for (u32 l = 0; l < depth; l++) {
-        const u64* s = sib + 4 * (size_t)l;
-        const bool right = index & 1;
+    // cur = two_to_one(cur, sib), or two_to_one(sib, cur) for a right child
+    static __device__ __forceinline__ void compress(u64* cur, const u64* sib, bool right) {
         u64 st[12];
 #pragma unroll
         for (int i = 0; i < 4; i++) {
-            st[i] = right ? s[i] : cur[i];
-            st[4 + i] = right ? cur[i] : s[i];
+            st[i] = right ? sib[i] : cur[i];
+            st[4 + i] = right ? cur[i] : sib[i];
             st[8 + i] = 0;
         }
         glf::poseidon(st);
 #pragma unroll
         for (int i = 0; i < 4; i++) cur[i] = st[i];
+    }
+    // whether a stored hash is an accepted encoding: four canonical field elements
+    static __device__ __forceinline__ bool valid(const u64* h) { return h[0] < gl::P && h[1] < gl::P && h[2] < gl::P && h[3] < gl::P; }
+};
+
+// verify_merkle_to_cap: the leaf's digest climbed with `depth` siblings and compared with cap entry index >> depth
+template <class H>
+__device__ __forceinline__ bool vfy_merkle(const u64* leaf, u32 width, u32 index, const u64* cap, u32 cap_n, const u64* sib, u32 depth) {
+    u64 cur[4];
+    H::hash_or_noop(leaf, width, cur);
+    for (u32 l = 0; l < depth; l++) {
+        H::compress(cur, sib + 4 * (size_t)l, index & 1);
         index >>= 1;
     }
     const u64* c = cap + 4 * (size_t)(index & (cap_n - 1));
@@ -501,7 +512,8 @@ __device__ __forceinline__ E2 vfy_expected(const VerifyArgs& a, const u64* w, co
 
 // slot s of query q: s < 4 initial tree s; 4 <= s < 4 + rounds: FRI round s - 4 (fold check, then Merkle); the last: final poly.
 // Failure key ((q * slots + s) << 1 | check): the smallest key is the check verify_proof reports first.
-__global__ __launch_bounds__(64) void k_vfy_queries(VerifyArgs a) {
+template <class H>
+__device__ __forceinline__ void vfy_queries(const VerifyArgs& a) {
     const u32 t = blockIdx.x * blockDim.x + threadIdx.x, slot = blockIdx.y, slots = gridDim.y;
     if (t >= a.batch * a.num_queries) return;
     const u32 p = t / a.num_queries, q = t % a.num_queries;
@@ -538,8 +550,9 @@ __global__ __launch_bounds__(64) void k_vfy_queries(VerifyArgs a) {
         cap = w + a.fri_caps_off + (size_t)k * a.cap_words, width = 2 * VFY_ARITY, index = xk >> VFY_ARITY_BITS;
         sib = qw + a.step_sib_off[k], depth = a.step_depth[k], mkey = key | 1;
     }
-    if (!vfy_merkle(leaf, width, index, cap, cap_n, sib, depth)) atomicMin(&a.qfail[p], mkey);
+    if (!vfy_merkle<H>(leaf, width, index, cap, cap_n, sib, depth)) atomicMin(&a.qfail[p], mkey);
 }
+__global__ __launch_bounds__(64) void k_vfy_queries(VerifyArgs a) { vfy_queries<PoseidonTree>(a); }
 
 // ------------------------------------------------------------------------------------------- 5. one status per proof
 __global__ void k_vfy_finish(VerifyArgs a, u32 slots) {

@@ -9,37 +9,19 @@ The same cross-compile also emits the gfx950 assembly, which tests/isa_lint.py w
 gl.h manages by hand (two wait states between a VALU write of an SGPR and a VALU read of it), and the asm strings of csrc/ are
 checked for scalar-ALU instructions (which clobber SCC behind the compiler's back)."""
 import os
-import re
-import subprocess
 
 import pytest
 
+import device_build as device
 import isa_lint
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
 
 @pytest.fixture(scope="module")
-def device_build(tmp_path_factory):
-    """One cross-compile of the product's device code: (resource remarks per function, assembly text)."""
-    if not os.path.exists(HIPCC):
-        pytest.skip("hipcc not available")
-    out = tmp_path_factory.mktemp("codegen") / "prover.s"
-    r = subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-S", "--cuda-device-only", "-Rpass-analysis=kernel-resource-usage",
-                        "-o", str(out), os.path.join(ROOT, "plonky2-aes_amd", "csrc", "prover_gpu.hip")], capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stderr[-2000:]
-    info = {}
-    cur = None
-    for line in r.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            cur = info.setdefault(m.group(1), {})
-            continue
-        m = re.search(r"remark:\s+(VGPRs|AGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|LDS Size \[bytes/block\]): (\d+)", line)
-        if m and cur is not None:
-            cur[m.group(1).split(" [")[0]] = int(m.group(2))
-    return info, open(out).read()
+def device_build():
+    """The cross-compile of the product's device code: (resource remarks per function, assembly text)."""
+    return device.cross_compile()
 
 
 @pytest.fixture(scope="module")

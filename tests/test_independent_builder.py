@@ -26,11 +26,14 @@ import oracle_builder as OB  # noqa: E402
 CASES = [(4, 13, False), (4, 13, True), (8, 40, False), (6, 16, False), (4, 1024, False)]
 
 
-def test_keccak_256_known_answers():
+def test_keccak_256_known_answers(pkg):
     # the Keccak team's published digests of the empty string and of "abc" (original padding, not SHA3-256)
     assert OB.keccak256(b"").hex() == "c5d2460186f7233c927e7db2dcc703c0e500b653ca82273b7bfad8045d85a470"
     assert OB.keccak256(b"abc").hex() == "4e03657aea45a94fc7d47ba826c8d667c0d1e6e33a64a036ec44f58fa12d6c45"
     assert OB.keccak256(bytes(200)) != OB.keccak256(bytes(201))            # spans two rate blocks
+    # the product's keccak256 (the lut_hash of a gate id): around the rate of 136 bytes, and a table of 256 pairs (eight blocks)
+    for msg in (b"", b"abc", bytes(range(135)), bytes(range(136)), bytes(range(137)), bytes(i * 7 & 255 for i in range(1024))):
+        assert pkg.keccak_native.keccak256(msg) == OB.keccak256(msg), len(msg)
 
 
 def _both(pkg, nk, L, tag):

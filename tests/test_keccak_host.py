@@ -2,22 +2,17 @@
 tests/keccak_ref.py (itself pinned by the published Keccak-256 vectors), the blob's HASH section, and the code generation of the
 Keccak kernels (gfx950 cross-compile)."""
 import ctypes as C
-import os
 import random
-import re
 import struct
-import subprocess
 
 import numpy as np
 import pytest
 
+import device_build
 import keccak_circuits
 import keccak_ref
 import oracle_lib
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "plonky2-aes_amd", "csrc")
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 P = 0xFFFFFFFF00000001
 HASH_TAG = 0x48534148  # csrc/circuit.h BLOB_HASH_TAG
 
@@ -110,22 +105,8 @@ PINNED_FRAGMENTS = ["k_hash_leaves", "k_hash_fri_leaves", "k_merkle_level", "k_q
                     "k_finish", "k_proof_segments"]
 
 
-def test_keccak_kernels_cross_compile_without_scratch(tmp_path):
-    if not os.path.exists(HIPCC):
-        pytest.skip("hipcc not available")
-    out = tmp_path / "p.s"
-    r = subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-S", "--cuda-device-only", "-Rpass-analysis=kernel-resource-usage",
-                        "-o", str(out), os.path.join(CSRC, "prover_gpu.hip")], capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stderr[-2000:]
-    info, cur = {}, None
-    for line in r.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            cur = info.setdefault(m.group(1), {})
-            continue
-        m = re.search(r"remark:\s+(VGPRs|AGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]): (\d+)", line)
-        if m and cur is not None:
-            cur[m.group(1).split(" [")[0]] = int(m.group(2))
+def test_keccak_kernels_cross_compile_without_scratch():
+    info, asm = device_build.cross_compile()
     for fragment, vgprs, waves in [(k, 102, 5) for k in TREE_KERNELS] + [(k, 128, 4) for k in VERIFY_KERNELS]:
         names = [n for n in info if fragment in n]
         assert len(names) == 1, (fragment, names)
@@ -134,7 +115,6 @@ def test_keccak_kernels_cross_compile_without_scratch(tmp_path):
         assert k["VGPRs"] + k.get("AGPRs", 0) <= vgprs and k["Occupancy"] >= waves, (fragment, k)
         assert not any(p in names[0] for p in PINNED_FRAGMENTS), names[0]  # the name fragments the other codegen tests select by
     # the rounds are 32-bit logic: chi as v_bfi_b32, rho as v_alignbit_b32
-    asm = open(out).read()
     body = asm[asm.index("k_kc_leaves"):]
     body = body[:body.index(".Lfunc_end")]
     assert body.count("v_bfi_b32") >= 50 and body.count("v_alignbit_b32") >= 48, (body.count("v_bfi_b32"), body.count("v_alignbit_b32"))

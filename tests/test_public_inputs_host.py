@@ -1,19 +1,15 @@
 """Public inputs on the host (no GPU): registration, the blob's public-input section and its validation, the proof layout with
 the public-input trailer, the in-circuit hash as the CPU oracle's witness computes it, and the new kernel's code generation."""
 import ctypes as C
-import os
-import re
 import struct
-import subprocess
 
 import pytest
 
+import device_build as device
 import isa_lint
 import pi_circuits
 import verify_layout
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 KS = [1, 7, 8, 9, 17]  # around the sponge rate (8); 7 and more also hold a duplicate, a constant and two computed targets
 
 
@@ -153,23 +149,8 @@ def test_host_verifier_checks_the_trailer_with_the_shape(pkg):
 
 
 @pytest.fixture(scope="module")
-def device_build(tmp_path_factory):
-    if not os.path.exists(HIPCC):
-        pytest.skip("hipcc not available")
-    out = tmp_path_factory.mktemp("pi_codegen") / "prover.s"
-    r = subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-S", "--cuda-device-only", "-Rpass-analysis=kernel-resource-usage",
-                        "-o", str(out), os.path.join(ROOT, "plonky2-aes_amd", "csrc", "prover_gpu.hip")], capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stderr[-2000:]
-    info, cur = {}, None
-    for line in r.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            cur = info.setdefault(m.group(1), {})
-            continue
-        m = re.search(r"remark:\s+(VGPRs|AGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]): (\d+)", line)
-        if m and cur is not None:
-            cur[m.group(1).split(" [")[0]] = int(m.group(2))
-    return info, open(out).read()
+def device_build():
+    return device.cross_compile()
 
 
 def test_pi_hash_kernel_cross_compiles_without_scratch(device_build):

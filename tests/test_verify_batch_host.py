@@ -3,13 +3,11 @@ header and api.py agree, the kernels cross-compile for gfx950 without scratch, a
 import ctypes as C
 import os
 import re
-import subprocess
 
-import pytest
+import device_build
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "plonky2-aes_amd", "csrc")
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 KERNELS = ["k_vfy_unpack", "k_vfy_transcript", "k_vfy_vanishing", "k_vfy_queries", "k_vfy_finish"]
 VGPR_BUDGET = 128  # four waves per SIMD or more; the largest of the five (k_vfy_transcript) takes 96
 
@@ -49,21 +47,8 @@ def test_null_handle_and_bad_arguments_are_errors(pkg):
     assert L.p2_verify_batch_device(None, 4, None, None, 0, None, None) == 1
 
 
-def test_verifier_kernels_cross_compile_without_scratch(tmp_path):
-    if not os.path.exists(HIPCC):
-        pytest.skip("hipcc not available")
-    r = subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-S", "--cuda-device-only", "-Rpass-analysis=kernel-resource-usage",
-                        "-o", str(tmp_path / "p.s"), os.path.join(CSRC, "prover_gpu.hip")], capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stderr[-2000:]
-    info, cur = {}, None
-    for line in r.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            cur = info.setdefault(m.group(1), {})
-            continue
-        m = re.search(r"remark:\s+(VGPRs|ScratchSize \[bytes/lane\]): (\d+)", line)
-        if m and cur is not None:
-            cur[m.group(1).split(" [")[0]] = int(m.group(2))
+def test_verifier_kernels_cross_compile_without_scratch():
+    info, _ = device_build.cross_compile()
     for k in KERNELS:
         names = [n for n in info if k in n]
         assert names, k
