@@ -1,7 +1,9 @@
 """The Keccak configuration (hasher="keccak") on the GPU.  The CPU oracle hashes with Poseidon and cannot follow, so the trees
 are pinned from outside by the Python Keccak / Merkle restatement of tests/keccak_ref.py; the wire matrix is pinned by the
-Poseidon build of the same circuit (whose witness the oracle checks elsewhere); everything after the wires commitment is
-checked by the two verifiers (host and GPU), which must agree verdict for verdict."""
+Poseidon build of the same circuit (whose witness the oracle checks elsewhere); here, everything after the wires commitment
+is checked by the two verifiers (host and GPU), which must agree verdict for verdict.  Those stages -- transcript, caps, Merkle
+paths, openings, FRI -- are pinned from outside by the Python proof replay in tests/test_gpu_proof_replay.py; only the
+vanishing identity at zeta is left to the verifiers alone."""
 import ctypes as C
 import random
 import struct
