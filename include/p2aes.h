@@ -206,6 +206,12 @@ int p2_selftest_host(uint64_t seed, size_t n_reductions, size_t n_permutations);
  * textbook forms as the reference): guards against code-generation regressions such as the add-with-carry fold described
  * in DESIGN.md.  Returns the number of mismatches, or a negative P2_ERR_* code. */
 int p2_selftest_device(uint64_t seed, size_t threads, int device);
+/* The host build of the hash kernels' permutation: kind 0 = twelve unknown words, 1 = words 8..11 enter as 0, 2 = words 0..7 enter
+ * as 0 (the words declared zero are not read); rows bit r = output word r is kept (canonical), the others are unspecified;
+ * parts 0 = the round loops as the kernels run them, 1 = first round, middle and last round as separate functions. */
+int p2_host_poseidon_known(uint64_t* states, size_t n_perm, int kind, uint32_t rows, int parts);
+/* k_hash_leaves' sponge on the host: data [min(active_cols, cols)][num_leaves] -> digests [num_leaves][4] */
+int p2_host_hash_leaves(const uint64_t* data, size_t cols, size_t active_cols, size_t num_leaves, uint64_t* digests);
 
 /* ------------------------------------------------------------------ native cipher (host; witness values) */
 uint8_t p2_native_gf_2_8_mul(uint8_t a, uint8_t b);
@@ -385,6 +391,13 @@ int p2_gpu_intt(const uint64_t* values, size_t cols, int degree_bits, uint64_t* 
 int p2_gpu_merkle_cap(const uint64_t* cols_major, size_t cols, size_t num_leaves, int cap_height, uint64_t* cap, int device);
 /* the same with the tree hasher chosen (P2_HASHER_*); Keccak needs cols >= 4 (every leaf is hashed, there is no no-op case) */
 int p2_gpu_merkle_cap_hasher(const uint64_t* cols_major, size_t cols, size_t num_leaves, int cap_height, int hasher, uint64_t* cap, int device);
+/* the tree kernels on their own, one launch each (tests/test_gpu_sponge.py):
+ * data [batch][min(active_cols, cols)][num_leaves], columns >= active_cols are zero and not stored -> digests [batch][num_leaves][4] */
+int p2_gpu_hash_leaves(const uint64_t* data, size_t cols, size_t active_cols, size_t num_leaves, size_t batch, uint64_t* digests, int device);
+/* child [batch][2 * num_parents][4] -> parent [batch][num_parents][4] */
+int p2_gpu_merkle_level(const uint64_t* child, size_t num_parents, size_t batch, uint64_t* parent, int device);
+/* vals [batch][2][len] -> digests [batch][len / arity][4] */
+int p2_gpu_hash_fri_leaves(const uint64_t* vals, size_t len, int arity, size_t batch, uint64_t* digests, int device);
 /* debug: copy a named intermediate buffer of proof `index` of the last batch to the host
  * ("wires", "wires_cap", "zs", "zs_cap", "quotient_coeffs", "quotient_cap", "challenges", "openings",
  * "public_inputs_hash", ...) */

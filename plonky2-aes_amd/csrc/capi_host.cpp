@@ -509,6 +509,42 @@ int p2_selftest_host(uint64_t seed, size_t n_reductions, size_t n_permutations) 
     return (int)std::min<size_t>(bad, 0x7FFFFFFF);
 }
 
+// The host build of the permutation with known-zero inputs and a mask of output words (poseidon_fast.h): FR_* kind, rows bit r =
+// word r is kept.  parts = 0: the two round loops the kernels run; 1: first_round / middle / last_round one after the other.
+int p2_host_poseidon_known(uint64_t* states, size_t n_perm, int kind, uint32_t rows, int parts) {
+    if (kind < 0 || kind > (int)glf::FR_ZERO_RATE || rows == 0 || rows > glf::ROWS_ALL) return set_error("kind must be 0..2 and rows a mask of words 0..11"), P2_ERR_INVALID;
+    for (size_t i = 0; i < n_perm; i++) {
+        u64* s = states + 12 * i;
+        if (parts) {
+            glf::first_round_any(s, (u32)kind);
+            glf::middle(s);
+            glf::last_round_any(s, rows);
+        } else {
+            glf::permute_known_any(s, (u32)kind, rows);
+        }
+    }
+    return P2_OK;
+}
+// k_hash_leaves on the host, with the same sponge steps (glf::sponge_permute): data [active][num_leaves] column-major, columns
+// >= active_cols are zero and not stored; digests [num_leaves][4].
+int p2_host_hash_leaves(const uint64_t* data, size_t cols, size_t active_cols, size_t num_leaves, uint64_t* digests) {
+    if (cols == 0 || cols > (1u << 20)) return set_error("cols out of range"), P2_ERR_INVALID;
+    for (size_t leaf = 0; leaf < num_leaves; leaf++) {
+        u64 st[12] = {0};
+        u64* out = digests + 4 * leaf;
+        if (cols <= 4) {
+            for (size_t c = 0; c < 4; c++) out[c] = (c < cols && c < active_cols) ? data[c * num_leaves + leaf] : 0;
+            continue;
+        }
+        for (size_t c0 = 0; c0 < cols; c0 += 8) {
+            for (size_t k = 0; k < 8 && c0 + k < cols; k++) st[k] = c0 + k < active_cols ? data[(c0 + k) * num_leaves + leaf] : 0;
+            glf::sponge_permute(st, (int)c0, (int)cols, (int)std::min(active_cols, cols));
+        }
+        for (int i = 0; i < 4; i++) out[i] = st[i];
+    }
+    return P2_OK;
+}
+
 // ---- native cipher
 uint8_t p2_native_gf_2_8_mul(uint8_t a, uint8_t b) { return aes::gf_2_8_mul(a, b); }
 void p2_native_aes_key_expansion(const uint8_t* key, int nk, int nr, uint8_t* out) {

@@ -32,7 +32,8 @@ static const u64 UNSET = ~0ull;
 #define P2_HASH_WAVES __attribute__((amdgpu_waves_per_eu(P2_HASH_WAVES_PER_EU, P2_HASH_WAVES_PER_EU)))
 // 12 lanes of state live in registers of ONE thread; one thread = one sponge.  (Leaf hashing has ~10^5..10^6
 // independent sponges per tree, so thread-per-sponge already fills the chip with coalesced column reads.)
-__device__ __forceinline__ void sponge_absorb_permute(u64* st) { glf::poseidon(st); }
+// Every permutation of these kernels is glf::first_round / middle / last_round with the words a sponge knows to be zero and
+// the outputs it never reads left out (glf::sponge_permute, glf::two_to_one_permute); one copy of the middle per kernel.
 
 // Leaf digests of a column-major batch: digest[leaf] = hash_or_noop(row leaf of `cols` columns).
 // Columns >= active_cols are known-zero (never materialised).
@@ -58,7 +59,7 @@ __global__ __launch_bounds__(256) P2_HASH_WAVES void k_hash_leaves(const u64* __
             if (c < cols) st[k] = c < active_cols ? d[(size_t)k * col_stride] : 0;
         }
         d += 8 * col_stride;
-        glf::poseidon(st);
+        glf::sponge_permute(st, c0, cols, active_cols);
     }
     u64* out = digests + (size_t)blockIdx.y * dig_batch_stride + ((size_t)blockIdx.x * blockDim.x + threadIdx.x) * 4;
 #pragma unroll
@@ -83,7 +84,7 @@ __global__ __launch_bounds__(256) P2_HASH_WAVES void k_hash_fri_leaves(const u64
             int e = e0 + k;
             if (e < width) st[k] = v[(size_t)(e & 1) * len + leaf * arity + (e >> 1)];
         }
-        glf::poseidon(st);
+        glf::sponge_permute(st, e0, width, width);
     }
     u64* out = digests + (size_t)blockIdx.y * dig_batch_stride + leaf * 4;
 #pragma unroll
@@ -100,13 +101,9 @@ __global__ __launch_bounds__(256) P2_HASH_WAVES void k_merkle_level(const u64* _
 #pragma unroll
         for (int k = 0; k < 8; k++) st[k] = c[k];
     }
-    {
-        u64 zero = 0;
-        asm("" : "+v"(zero));  // opaque: a known-zero capacity makes the first round a special case and costs 9 more registers
 #pragma unroll
-        for (int k = 8; k < 12; k++) st[k] = zero;
-    }
-    glf::poseidon(st);
+    for (int k = 8; k < 12; k++) st[k] = 0;  // the zero capacity: never read (first_round<FR_ZERO_CAP>)
+    glf::two_to_one_permute(st);
     u64* o = parent + (size_t)blockIdx.y * batch_stride + 4 * ((size_t)blockIdx.x * blockDim.x + threadIdx.x);  // formed late: see k_hash_leaves
 #pragma unroll
     for (int k = 0; k < 4; k++) o[k] = st[k];
@@ -138,13 +135,9 @@ __global__ __launch_bounds__(256) P2_HASH_WAVES void k_merkle_top(u64* __restric
 #pragma unroll
                 for (int q = 0; q < 8; q++) st[q] = c[q];
             }
-            {
-                u64 zero = 0;
-                asm("" : "+v"(zero));  // see k_merkle_level
 #pragma unroll
-                for (int q = 8; q < 12; q++) st[q] = zero;
-            }
-            glf::poseidon(st);
+            for (int q = 8; q < 12; q++) st[q] = 0;  // see k_merkle_level
+            glf::two_to_one_permute(st);
             u64* o = base + off_p + 4 * idx;
 #pragma unroll
             for (int q = 0; q < 4; q++) o[q] = st[q];

@@ -10,6 +10,9 @@
 //   * the 22 partial rounds use the sparse-matrix form derived by tools/gen_poseidon_fast.py: 23 multiply-accumulates per
 //     round instead of a 144-term MDS, the 12-term dot product in a carry-counting accumulator reduced once, and the dense
 //     11x11 layer that opens them merged into the fourth full round's linear step (PF_E);
+//   * the tree kernels never run the whole of it: permute_known / sponge_permute leave out the S-boxes and MDS terms of words
+//     that enter as 0 (the capacity in front of a first chunk, a chunk of known-zero columns) and the last round's MDS rows
+//     of outputs the sponge overwrites or never reads;
 //   * poseidon_coop: one state over 12 lanes of a 16-lane group, for the sequential Fiat-Shamir chain.
 // The host build of the same functions (plain 128-bit arithmetic) is what p2_selftest_host and the CPU tests exercise.
 #pragma once
@@ -25,6 +28,7 @@ using gl::u64;
 #define P2F_DECL static
 #endif
 #include "poseidon_fast.inc"
+P2F_DECL const unsigned long long PF_ZERO12[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // the addends of the last round's rows
 
 GL_HD void mul128(u64 a, u64 b, u64& hi, u64& lo) {
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -239,7 +243,8 @@ GL_HD u64 fold_al_ah(u64 al, u64 ah) {
 // MDS layer of a full round, with the NEXT round's constants folded into the accumulators (rc == nullptr: none):
 //   out[r] = rc[r] + sum_i circ[i] * s[(i + r) % 12] + 8 * s[0] (r == 0)      as some u64 representative.
 // Evaluated on 32-bit halves: every accumulator stays below 2^43, one fold per output word.
-GL_HD void mds_full(u64* s, const unsigned long long* rc) {
+// Only the rows whose bit is set in `rows` are evaluated; the other words keep their input (nobody reads them: last_round).
+GL_HD void mds_full(u64* s, const unsigned long long* rc, const u32 rows = 0xFFF) {
 #if defined(__HIP_DEVICE_COMPILE__)
     // Every term is one v_mad_u64_u32 with the coefficient as an inline constant (gl::madk: the coefficients 2, 8 and 16 must
     // not become shift-adds on zero-extended operands), and the round constant is the ADDEND of the first one, read from its
@@ -265,6 +270,8 @@ GL_HD void mds_full(u64* s, const unsigned long long* rc) {
         [l10] "v"(l[(10 + r) % 12]), [h10] "v"(h[(10 + r) % 12]), [l11] "v"(l[(11 + r) % 12]), [h11] "v"(h[(11 + r) % 12])
 #pragma unroll
     for (int r = 0; r < 12; r++) {
+        res[r] = s[r];
+        if (!((rows >> r) & 1)) continue;
         u64 al, ah;
         gl::sg dead;
         if (rc) {
@@ -307,6 +314,8 @@ GL_HD void mds_full(u64* s, const unsigned long long* rc) {
     }
 #pragma unroll
     for (int r = 0; r < 12; r++) {
+        out[r] = s[r];
+        if (!((rows >> r) & 1)) continue;
         u64 al = rc ? (u64)(u32)rc[r] : 0, ah = rc ? (u64)(rc[r] >> 32) : 0;
 #pragma unroll
         for (int i = 0; i < 12; i++) {
@@ -376,18 +385,157 @@ GL_HD u64 mulr_add_k(u64 k, u64 b, u64 c) {
 #endif
 }
 
-// In: canonical or not; out: canonical.
-GL_HD void poseidon(u64* s) {
+// ---- The permutation in three parts.  A sponge never needs all of it: the capacity words 8..11 are 0 in front of the first
+// permutation of every hash, an absorbed chunk of known-zero columns puts 0 into the rate words 0..7, and of the twelve outputs
+// only the words that the next chunk does not overwrite (or the digest words 0..3) are read.
+//   first_round    + constants, S-box, MDS, with the words known to be 0 left out: such a word leaves the S-box as the constant
+//                  RC[k]^7, and its MDS terms are part of the row's addend (RC1_ZCAP / RC1_ZRATE, tools/gen_poseidon_fast.py);
+//   middle         full rounds 1..3 (the dense layer merged into the last of them), the 22 partial rounds, full rounds 26..28;
+//   last_round     S-box, then only the MDS rows somebody reads, canonicalised.
+// `kind` and `rows` are compile-time constants (first_round<KIND>, last_round<ROWS>) or WAVE-UNIFORM run-time values (the leaf
+// kernels, whose chunks differ): then every group of terms sits behind a scalar branch and there is still one copy of each.
+enum : u32 { FR_GENERAL = 0, FR_ZERO_CAP = 1, FR_ZERO_RATE = 2 };           // which words enter as 0: none, 8..11, 0..7
+enum : u32 { ROWS_ALL = 0xFFF, ROWS_DIGEST = 0x00F, ROWS_CAPACITY = 0xF00 };  // bit r = output word r is read
+
+// The output words a sponge still needs when the NEXT chunk overwrites words 0..m-1 (overwrite mode, hash_n_to_hash_no_pad):
+// no next chunk (m <= 0): the digest; a full chunk: the capacity; a partial one: the rate words it leaves, and the capacity.
+GL_HD constexpr u32 rows_before_chunk(int m) { return m <= 0 ? 0x00Fu : m >= 8 ? 0xF00u : (0xFFFu & ~((1u << m) - 1u)); }
+
+// coefficient of state word j in MDS row r (circulant + the diagonal 8 at (0, 0)); at most 25: an inline constant
+GL_HD constexpr u32 mds_coef(int r, int j) {
+    constexpr u32 C[12] = {17, 15, 41, 16, 2, 28, 13, 13, 39, 18, 34, 20};
+    return C[(j - r + 12) % 12] + ((r == 0 && j == 0) ? 8u : 0u);
+}
+
 #if defined(__HIP_DEVICE_COMPILE__)
-    const unsigned long long* RC = (const unsigned long long*)gl::D_POSEIDON_RC;
-#else
-    const unsigned long long* RC = (const unsigned long long*)gl::H_POSEIDON_RC;
+// MDS row R split at the rate / capacity boundary, the per-term form of mds_full's blocks: the terms of words 0..7 on a
+// uniform addend (SGPR pairs), and the terms of words 8..11 on top of running accumulators.
+#define P2_FR_T(n) "v_mad_u64_u32 %[al], %[d], %[l" #n "], %[k" #n "], %[al]\n\tv_mad_u64_u32 %[ah], %[d], %[h" #n "], %[k" #n "], %[ah]\n\t"
+template <int R>
+GL_D void mds_rate_terms(u64& al, u64& ah, const u32* l, const u32* h, u64 rl, u64 rh) {
+    gl::sg dead;
+    asm("v_mad_u64_u32 %[al], %[d], %[l0], %[k0], %[rl]\n\tv_mad_u64_u32 %[ah], %[d], %[h0], %[k0], %[rh]\n\t"  //
+        P2_FR_T(1) P2_FR_T(2) P2_FR_T(3) P2_FR_T(4) P2_FR_T(5) P2_FR_T(6) "v_mad_u64_u32 %[al], %[d], %[l7], %[k7], %[al]\n\t"
+        "v_mad_u64_u32 %[ah], %[d], %[h7], %[k7], %[ah]"
+        : [al] "=&v"(al), [ah] "=&v"(ah), [d] "=&s"(dead)
+        : [rl] "s"(rl), [rh] "s"(rh), [l0] "v"(l[0]), [h0] "v"(h[0]), [l1] "v"(l[1]), [h1] "v"(h[1]), [l2] "v"(l[2]), [h2] "v"(h[2]),
+          [l3] "v"(l[3]), [h3] "v"(h[3]), [l4] "v"(l[4]), [h4] "v"(h[4]), [l5] "v"(l[5]), [h5] "v"(h[5]), [l6] "v"(l[6]), [h6] "v"(h[6]),
+          [l7] "v"(l[7]), [h7] "v"(h[7]), [k0] "n"(mds_coef(R, 0)), [k1] "n"(mds_coef(R, 1)), [k2] "n"(mds_coef(R, 2)),
+          [k3] "n"(mds_coef(R, 3)), [k4] "n"(mds_coef(R, 4)), [k5] "n"(mds_coef(R, 5)), [k6] "n"(mds_coef(R, 6)), [k7] "n"(mds_coef(R, 7)));
+}
+// ADDEND: the capacity terms open the row (a zero rate) and start from the addend themselves
+template <int R, bool ADDEND>
+GL_D void mds_cap_terms(u64& al, u64& ah, const u32* l, const u32* h, u64 rl, u64 rh) {
+    gl::sg dead;
+#define P2_FR_CAP_IN                                                                                                                      \
+    [l8] "v"(l[8]), [h8] "v"(h[8]), [l9] "v"(l[9]), [h9] "v"(h[9]), [l10] "v"(l[10]), [h10] "v"(h[10]), [l11] "v"(l[11]), [h11] "v"(h[11]), \
+        [k8] "n"(mds_coef(R, 8)), [k9] "n"(mds_coef(R, 9)), [k10] "n"(mds_coef(R, 10)), [k11] "n"(mds_coef(R, 11))
+    if (ADDEND)
+        asm("v_mad_u64_u32 %[al], %[d], %[l8], %[k8], %[rl]\n\tv_mad_u64_u32 %[ah], %[d], %[h8], %[k8], %[rh]\n\t"  //
+            P2_FR_T(9) P2_FR_T(10) "v_mad_u64_u32 %[al], %[d], %[l11], %[k11], %[al]\n\t"
+            "v_mad_u64_u32 %[ah], %[d], %[h11], %[k11], %[ah]"
+            : [al] "=&v"(al), [ah] "=&v"(ah), [d] "=&s"(dead)
+            : [rl] "s"(rl), [rh] "s"(rh), P2_FR_CAP_IN);
+    else
+        asm(P2_FR_T(8) P2_FR_T(9) P2_FR_T(10) "v_mad_u64_u32 %[al], %[d], %[l11], %[k11], %[al]\n\t"
+            "v_mad_u64_u32 %[ah], %[d], %[h11], %[k11], %[ah]"
+            : [al] "+v"(al), [ah] "+v"(ah), [d] "=&s"(dead)
+            : P2_FR_CAP_IN);
+#undef P2_FR_CAP_IN
+}
+#undef P2_FR_T
+template <int R>
+GL_D u64 first_round_row(const u32 kind, const u32* l, const u32* h, const u64 add) {  // kind != FR_ZERO_RATE
+    u64 al, ah;
+    mds_rate_terms<R>(al, ah, l, h, (u64)(u32)add, add >> 32);
+    if (kind != FR_ZERO_CAP) mds_cap_terms<R, false>(al, ah, l, h, 0, 0);
+    return fold_al_ah(al, ah);
+}
+template <int R>
+GL_D u64 zero_rate_row(const u32* l, const u32* h, const u64 add) {
+    u64 al, ah;
+    mds_cap_terms<R, true>(al, ah, l, h, (u64)(u32)add, add >> 32);
+    return fold_al_ah(al, ah);
+}
 #endif
-    // Round constants are never added on their own (except the very first ones): each layer's linear step starts its
-    // accumulators from the constants of the layer that follows.
+
+// One full round with the words that `kind` (FR_*) declares zero left out; they are not read.  pre: the constants the S-box
+// inputs still lack (the first round) or nullptr (the state carries them); add: the addend of every MDS row.
+GL_HD void full_round_known(u64* s, const u32 kind, const unsigned long long* pre, const unsigned long long* add) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    // A zero rate is a region of its own (four S-boxes, twelve rows of eight terms) and not a third arm of every row below:
+    // with three arms per row the register allocator needed 22 more VGPRs in k_hash_leaves and spilled.
+    u32 l[12], h[12];
+    if (kind == FR_ZERO_RATE) {
 #pragma unroll
-    for (int i = 0; i < 12; i++) s[i] = add_wrap(s[i], RC[i]);
-    for (int r = 0; r < 3; r++) full_round(s, RC + 12 * (r + 1));
+        for (int i = 8; i < 12; i++) {
+            const u64 z = sbox7(pre ? add_wrap(s[i], pre[i]) : s[i]);
+            l[i] = (u32)z;
+            h[i] = (u32)(z >> 32);
+        }
+#define P2_FR_ROW(r) s[r] = zero_rate_row<r>(l, h, add[r]);
+        P2_FR_ROW(0) P2_FR_ROW(1) P2_FR_ROW(2) P2_FR_ROW(3) P2_FR_ROW(4) P2_FR_ROW(5) P2_FR_ROW(6) P2_FR_ROW(7) P2_FR_ROW(8) P2_FR_ROW(9)
+        P2_FR_ROW(10) P2_FR_ROW(11)
+#undef P2_FR_ROW
+        return;
+    }
+    if (pre) {
+#pragma unroll
+        for (int i = 0; i < 8; i++) s[i] = add_wrap(s[i], pre[i]);
+    }
+#pragma unroll
+    for (int i = 0; i < 8; i++) s[i] = sbox7(s[i]);
+    if (kind != FR_ZERO_CAP) {
+        if (pre) {
+#pragma unroll
+            for (int i = 8; i < 12; i++) s[i] = add_wrap(s[i], pre[i]);
+        }
+#pragma unroll
+        for (int i = 8; i < 12; i++) s[i] = sbox7(s[i]);
+    }
+#pragma unroll
+    for (int i = 0; i < 12; i++) {
+        l[i] = (u32)s[i];
+        h[i] = (u32)(s[i] >> 32);
+    }
+#define P2_FR_ROW(r) s[r] = first_round_row<r>(kind, l, h, add[r]);
+    P2_FR_ROW(0) P2_FR_ROW(1) P2_FR_ROW(2) P2_FR_ROW(3) P2_FR_ROW(4) P2_FR_ROW(5) P2_FR_ROW(6) P2_FR_ROW(7) P2_FR_ROW(8) P2_FR_ROW(9)
+    P2_FR_ROW(10) P2_FR_ROW(11)
+#undef P2_FR_ROW
+#else
+    const int j0 = kind == FR_ZERO_RATE ? 8 : 0, j1 = kind == FR_ZERO_CAP ? 8 : 12;
+    u64 out[12];
+    for (int j = j0; j < j1; j++) s[j] = sbox7(pre ? add_wrap(s[j], pre[j]) : s[j]);
+    for (int r = 0; r < 12; r++) {
+        u64 al = (u32)add[r], ah = add[r] >> 32;
+        for (int j = j0; j < j1; j++) {
+            al += (s[j] & gl::EPS) * mds_coef(r, j);
+            ah += (s[j] >> 32) * mds_coef(r, j);
+        }
+        out[r] = fold_al_ah(al, ah);
+    }
+    for (int i = 0; i < 12; i++) s[i] = out[i];
+#endif
+}
+GL_HD const unsigned long long* poseidon_rc() {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return (const unsigned long long*)gl::D_POSEIDON_RC;
+#else
+    return (const unsigned long long*)gl::H_POSEIDON_RC;
+#endif
+}
+// Out: the state in front of the second round's S-boxes.
+GL_HD void first_round_any(u64* s, const u32 kind) {
+    full_round_known(s, kind, poseidon_rc(), kind == FR_ZERO_CAP ? RC1_ZCAP : kind == FR_ZERO_RATE ? RC1_ZRATE : poseidon_rc() + 12);
+}
+template <u32 KIND>
+GL_HD void first_round(u64* s) {
+    static_assert(KIND <= FR_ZERO_RATE, "FR_GENERAL, FR_ZERO_CAP or FR_ZERO_RATE");
+    first_round_any(s, KIND);
+}
+
+// The partial-round block: the fourth full round with the dense layer merged in, the 22 partial rounds, round 26's constants.
+GL_HD void partial_block(u64* s) {
     {
         // 4th full round with the dense 11x11 layer of the partial-round block merged into its linear step: lane 0 is the
         // MDS row (+ a_0, the first partial S-box's constant), lanes 1.. are rows of E = D0 . MDS[1.., :] (gen_poseidon_fast.py)
@@ -418,10 +566,83 @@ GL_HD void poseidon(u64* s) {
     }
 #pragma unroll
     for (int j = 1; j < 12; j++) s[j] = add_wrap(s[j], PF_RC26[j]);
+}
+// Everything between the first and the last full round; the same for every use of the permutation.
+GL_HD void middle(u64* s) {
+    const unsigned long long* RC = poseidon_rc();
+    for (int r = 1; r < 3; r++) full_round(s, RC + 12 * (r + 1));
+    partial_block(s);
+    for (int r = 26; r < 29; r++) full_round(s, RC + 12 * (r + 1));
+}
+
+// The words whose bit is set in `rows` come out canonical; the others are unspecified.
+GL_HD void last_round_any(u64* s, const u32 rows) {
+#pragma unroll
+    for (int i = 0; i < 12; i++) s[i] = sbox7(s[i]);
+    mds_full(s, PF_ZERO12, rows);
+#pragma unroll
+    for (int i = 0; i < 12; i++)
+        if ((rows >> i) & 1) s[i] = canon(s[i]);
+}
+template <u32 ROWS>
+GL_HD void last_round(u64* s) {
+    static_assert(ROWS != 0 && ROWS <= ROWS_ALL, "a mask of output words 0..11");
+    last_round_any(s, ROWS);
+}
+
+// first_round(kind), middle, last_round(rows) as the kernels run them: the first round is the first trip of the loop over
+// rounds 0..2 and the last round the last trip of the loop over rounds 26..29, so a kernel holds ONE copy of each loop body
+// whatever it knows about its inputs (the hash kernels are larger than the instruction cache as it is).
+GL_HD void permute_known_any(u64* s, const u32 kind, const u32 rows) {
+    const unsigned long long* RC = poseidon_rc();
+    const unsigned long long* add0 = kind == FR_ZERO_CAP ? RC1_ZCAP : kind == FR_ZERO_RATE ? RC1_ZRATE : RC + 12;
+#pragma nounroll
+    for (int r = 0; r < 3; r++) full_round_known(s, r == 0 ? kind : (u32)FR_GENERAL, r == 0 ? RC : nullptr, r == 0 ? add0 : RC + 12 * (r + 1));
+    partial_block(s);
+#pragma nounroll
+    for (int r = 26; r < 30; r++) {
+#pragma unroll
+        for (int i = 0; i < 12; i++) s[i] = sbox7(s[i]);
+        mds_full(s, r < 29 ? RC + 12 * (r + 1) : PF_ZERO12, r < 29 ? (u32)ROWS_ALL : rows);
+    }
+#pragma unroll
+    for (int i = 0; i < 12; i++)
+        if ((rows >> i) & 1) s[i] = canon(s[i]);
+}
+template <u32 KIND, u32 ROWS>
+GL_HD void permute_known(u64* s) {
+    static_assert(KIND <= FR_ZERO_RATE && ROWS != 0 && ROWS <= ROWS_ALL, "FR_* and a mask of output words 0..11");
+    permute_known_any(s, KIND, ROWS);
+}
+
+// The whole permutation on twelve unknown words.  In: canonical or not; out: canonical.
+// Round constants are never added on their own (except the very first ones): each layer's linear step starts its
+// accumulators from the constants of the layer that follows.
+GL_HD void poseidon(u64* s) {
+    const unsigned long long* RC = poseidon_rc();
+#pragma unroll
+    for (int i = 0; i < 12; i++) s[i] = add_wrap(s[i], RC[i]);
+    for (int r = 0; r < 3; r++) full_round(s, RC + 12 * (r + 1));
+    partial_block(s);
     for (int r = 26; r < 29; r++) full_round(s, RC + 12 * (r + 1));
     full_round(s, nullptr);
 #pragma unroll
     for (int i = 0; i < 12; i++) s[i] = canon(s[i]);
+}
+
+// One absorb-and-permute step of an overwrite-mode sponge (hash_n_to_hash_no_pad) over `width` input words of which the
+// words >= `live` are known to be 0: the chunk at word c0 is already in s[0..7] (a chunk of known zeros need not be).  The
+// first chunk meets a zero capacity, a whole chunk of known zeros behind it is a zero rate, anything else is general; the
+// outputs kept are those the chunk at c0 + 8 leaves standing.  c0, width, live: wave-uniform on the device.
+GL_HD u32 sponge_first_kind(int c0, int width, int live) {
+    return c0 == 0 ? (u32)FR_ZERO_CAP : (c0 >= live && c0 + 8 <= width) ? (u32)FR_ZERO_RATE : (u32)FR_GENERAL;
+}
+GL_HD void sponge_permute(u64* s, int c0, int width, int live) {
+    permute_known_any(s, sponge_first_kind(c0, width, live), rows_before_chunk(width - (c0 + 8)));
+}
+// two_to_one(a, b): words 0..7 = a || b, zero capacity, digest out
+GL_HD void two_to_one_permute(u64* s) {
+    permute_known<FR_ZERO_CAP, ROWS_DIGEST>(s);
 }
 
 #if defined(__HIPCC__)

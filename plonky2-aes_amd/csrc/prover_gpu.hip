@@ -2089,6 +2089,56 @@ int p2_gpu_poseidon(uint64_t* states, size_t n_perm, int device) {
     (void)hipFree(d);
     return P2_OK;
 }
+// The three tree kernels on their own (tests): host arrays in, host arrays out, one launch each.
+//   data [batch][min(active_cols, cols)][num_leaves] -> digests [batch][num_leaves][4]
+int p2_gpu_hash_leaves(const uint64_t* data, size_t cols, size_t active_cols, size_t num_leaves, size_t batch, uint64_t* digests, int device) {
+    if (cols == 0 || cols > (1u << 20) || num_leaves == 0 || batch == 0 || batch > 65535) return set_error("shape out of range"), P2_ERR_INVALID;
+    if (int rc = pick_device(device)) return rc;
+    const size_t stored = std::min(active_cols, cols), in_words = std::max<size_t>(stored, 1) * num_leaves;
+    u64 *d_in, *d_out;
+    HIPCHECK(hipMalloc((void**)&d_in, batch * in_words * 8));
+    HIPCHECK(hipMalloc((void**)&d_out, batch * num_leaves * 32));
+    HIPCHECK(hipMemcpy(d_in, data, batch * stored * num_leaves * 8, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_hash_leaves, g1(num_leaves, 256, (u32)batch), dim3(256), 0, 0, d_in, (int)cols, (int)active_cols, num_leaves, stored * num_leaves, num_leaves,
+                       d_out, num_leaves * 4);
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipMemcpy(digests, d_out, batch * num_leaves * 32, hipMemcpyDeviceToHost));
+    (void)hipFree(d_in);
+    (void)hipFree(d_out);
+    return P2_OK;
+}
+//   child [batch][2 * num_parents][4] -> parent [batch][num_parents][4]
+int p2_gpu_merkle_level(const uint64_t* child, size_t num_parents, size_t batch, uint64_t* parent, int device) {
+    if (num_parents == 0 || batch == 0 || batch > 65535) return set_error("shape out of range"), P2_ERR_INVALID;
+    if (int rc = pick_device(device)) return rc;
+    const size_t stride = 8 * num_parents;  // the kernel strides children and parents alike (levels of one digest buffer)
+    u64 *d_in, *d_out;
+    HIPCHECK(hipMalloc((void**)&d_in, batch * stride * 8));
+    HIPCHECK(hipMalloc((void**)&d_out, batch * stride * 8));
+    HIPCHECK(hipMemcpy(d_in, child, batch * stride * 8, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_merkle_level, g1(num_parents, 256, (u32)batch), dim3(256), 0, 0, d_in, d_out, num_parents, stride);
+    HIPCHECK(hipGetLastError());
+    for (size_t b = 0; b < batch; b++) HIPCHECK(hipMemcpy(parent + b * 4 * num_parents, d_out + b * stride, num_parents * 32, hipMemcpyDeviceToHost));
+    (void)hipFree(d_in);
+    (void)hipFree(d_out);
+    return P2_OK;
+}
+//   vals [batch][2][len] (the two components of len extension values) -> digests [batch][len / arity][4]
+int p2_gpu_hash_fri_leaves(const uint64_t* vals, size_t len, int arity, size_t batch, uint64_t* digests, int device) {
+    if (arity < 1 || arity > 64 || len == 0 || len % (size_t)arity || batch == 0 || batch > 65535) return set_error("shape out of range"), P2_ERR_INVALID;
+    if (int rc = pick_device(device)) return rc;
+    const size_t leaves = len / (size_t)arity;
+    u64 *d_in, *d_out;
+    HIPCHECK(hipMalloc((void**)&d_in, batch * 2 * len * 8));
+    HIPCHECK(hipMalloc((void**)&d_out, batch * leaves * 32));
+    HIPCHECK(hipMemcpy(d_in, vals, batch * 2 * len * 8, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_hash_fri_leaves, g1(leaves, 256, (u32)batch), dim3(256), 0, 0, d_in, len, 2 * len, arity, d_out, leaves * 4);
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipMemcpy(digests, d_out, batch * leaves * 32, hipMemcpyDeviceToHost));
+    (void)hipFree(d_in);
+    (void)hipFree(d_out);
+    return P2_OK;
+}
 // A throw-away circuit-less context for the NTT / Merkle primitives
 struct PrimCtx {
     p2_circuit C;

@@ -75,6 +75,15 @@ def derive():
     return rc, a, what, v, D0, L, E
 
 
+def first_round_addends(rc, known):
+    """Addends of the first full round's MDS rows when the state words in `known` enter the permutation as 0: such a word
+    leaves the S-box as the constant rc[k]^7, and its MDS terms join the row's own constant (the second round's rc[12 + r]):
+        addend[r] = rc[12 + r] + sum_{k in known} M[r][k] * rc[k]^7      (canonical)."""
+    M = [[(MDS_CIRC[(c - r) % W] + (MDS_DIAG[r] if r == c else 0)) % P for c in range(W)] for r in range(W)]
+    z = {k: pow(rc[k], 7, P) for k in known}
+    return [(rc[12 + r] + sum(M[r][k] * z[k] for k in known)) % P for r in range(W)]
+
+
 def permute_fast(state, rc, a, what, v, D0, L, E=None):
     s = list(state)
 
@@ -110,6 +119,16 @@ if __name__ == "__main__":
         assert permute(st, rc) == permute_fast(st, rc, a, what, v, D0, L)
         assert permute(st, rc) == permute_fast(st, rc, a, what, v, D0, L, E)
     print("sparse partial rounds == naive permutation on 20 states")
+    zcap, zrate = first_round_addends(rc, range(8, 12)), first_round_addends(rc, range(0, 8))
+    for t in range(20):   # the two addend tables against a plain first round on states with the known words at 0
+        for known, tab in ((range(8, 12), zcap), (range(0, 8), zrate)):
+            st = [0 if k in known else rnd.randrange(P) for k in range(12)]
+            z = [pow((st[k] + rc[k]) % P, 7, P) for k in range(12)]
+            plain = [(sum(z[(i + r) % W] * MDS_CIRC[i] for i in range(W)) + z[r] * MDS_DIAG[r] + rc[12 + r]) % P for r in range(W)]
+            live = [(tab[r] + sum((MDS_CIRC[(k - r) % W] + (MDS_DIAG[r] if k == r else 0)) * z[k] for k in range(W) if k not in known)) % P
+                    for r in range(W)]
+            assert plain == live
+    print("first-round addends for known-zero capacity / rate == plain first round on 20 states each")
     if len(sys.argv) > 1:
         with open(sys.argv[1], "w") as f:
             f.write("// Generated by tools/gen_poseidon_fast.py; equivalence with the naive permutation checked at generation time.\n")
@@ -125,4 +144,6 @@ if __name__ == "__main__":
             arr("PF_D0", [x for row in D0 for x in row], "[11 * 11]")
             arr("PF_E", [x for row in E for x in row], "[11 * 12]")
             arr("PF_RC26", [(rc[12 * 26 + k] + L[k]) % P for k in range(12)], "[12]")
+            arr("RC1_ZCAP", zcap, "[12]")
+            arr("RC1_ZRATE", zrate, "[12]")
         print("wrote", sys.argv[1])
