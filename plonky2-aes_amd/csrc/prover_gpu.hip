@@ -18,6 +18,7 @@
 #include "kernels2.h"
 #include "kernels_compress.h"
 #include "kernels_keccak.h"
+#include "verifier.h"
 
 using namespace p2;
 using namespace p2k;
@@ -36,9 +37,81 @@ struct Tree {
     u32 bits = 0;        // log2(#leaves)
     size_t stride() const { return (size_t)8 << bits; }
 };
+// first word of level l of a tree's digest buffer (level 0: the 2^bits leaf digests)
+static size_t level_off(u32 bits, u32 l) { return 4 * (((size_t)2 << bits) - ((size_t)2 << (bits - l))); }
+static size_t cap_off(const Tree& t, u32 cap_height) { return level_off(t.bits, t.bits - cap_height); }
+
+// Device allocations with one owner -- a handle, a PrimCtx, one call of a primitive -- freed when it goes, on every path out.
+struct Allocs : std::vector<void*> {
+    ~Allocs() { for (void* p : *this) (void)hipFree(p); }
+};
+template <class T>
+static int dalloc(Allocs& mem, T** p, size_t count) {
+    void* q = nullptr;
+    HIPCHECK(hipMalloc(&q, std::max<size_t>(count, 1) * sizeof(T)));
+    mem.push_back(q);
+    *p = (T*)q;
+    return 0;
+}
+template <class T>
+static int upload(Allocs& mem, T** p, const T* host, size_t count) {
+    if (dalloc(mem, p, count)) return P2_ERR_HIP;
+    if (count) HIPCHECK(hipMemcpy(*p, host, count * sizeof(T), hipMemcpyHostToDevice));
+    return 0;
+}
+
+// What a launch needs: its stream and, while per-kernel timing is on, the event pairs that collect_timing has yet to read.
+struct Lane {
+    hipStream_t stream = nullptr;
+    bool timing = false;  // follows p2_circuit::timing_on (p2_circuit_set_timing, build_workspace)
+    std::vector<std::pair<std::string, std::pair<hipEvent_t, hipEvent_t>>> pending;
+};
+// Launch on a lane, with optional per-kernel event timing under `name`.
+#define LAUNCH(lane, name, kernel, grid, block, shmem, ...)                                  \
+    do {                                                                                     \
+        Lane& _l = (lane);                                                                   \
+        hipEvent_t _e0 = nullptr, _e1 = nullptr;                                             \
+        if (_l.timing) {                                                                     \
+            (void)hipEventCreate(&_e0);                                                      \
+            (void)hipEventCreate(&_e1);                                                      \
+            (void)hipEventRecord(_e0, _l.stream);                                            \
+        }                                                                                    \
+        hipLaunchKernelGGL(kernel, grid, block, shmem, _l.stream, __VA_ARGS__);              \
+        if (_l.timing) {                                                                     \
+            (void)hipEventRecord(_e1, _l.stream);                                            \
+            _l.pending.push_back({name, {_e0, _e1}});                                        \
+        }                                                                                    \
+        HIPCHECK(hipGetLastError());                                                         \
+    } while (0)
+
+// What the transform and tree building blocks read: the size, the twiddle and shift tables and three words of the config.
+struct Domain {
+    u32 logn = 0;
+    std::vector<u32> arities;
+    u64 *d_tw_fwd = nullptr, *d_tw_inv = nullptr;  // w^k / w^-k for k < n_max/2, n_max = n
+    u64 *d_tw_fwd_full = nullptr, *d_tw_inv_full = nullptr;  // w^k / w^-k for k < n (two-pass NTT, n > 2^14)
+    u64* d_tw_fwd_round[9] = {nullptr};                       // order n_r tables for FRI rounds that still need two passes
+    u64* d_shift_pows[9] = {nullptr};              // per FRI round r (0 = main LDE): [8][n_r] (s_r w^j)^i
+    u64* d_shift_tw = nullptr;                     // main LDE, 2^13 <= n <= 2^14: [8][n/2] d_shift_pows[0][j][i] * w^i
+    std::map<const u64*, u64*> pass1_out_tw;       // two-pass NTT: output-twiddle table per full twiddle table (ensure_pass1_table)
+    u32 rate_bits = 3, cap_height = 0, hasher = HASHER_POSEIDON;
+    size_t n() const { return (size_t)1 << logn; }
+};
+
+// One committed oracle: column values -> coefficients -> LDE (the salt columns of a zk circuit last) -> Merkle tree.
+struct Oracle {
+    u64* vals = nullptr;  // [cols][n] per proof; null where the values never exist in this form (the quotient)
+    u64 *coef = nullptr, *lde = nullptr;  // [cols][n], [cols + salt][8 n]
+    Tree tree;
+    u32 cols = 0;       // materialised columns
+    u32 tree_cols = 0;  // columns of a leaf before the salt: more than `cols` where the rest are identically zero (wires)
+    u32 salt = 0;
+    size_t coef_stride = 0, lde_stride = 0;  // per proof; 0 for the preprocessed oracle, which every proof shares
+    size_t dig_stride() const { return lde_stride ? tree.stride() : 0; }
+};
 
 struct Workspace {
-    hipStream_t stream = nullptr;
+    Lane lane;                  // the proving stream
     hipEvent_t done = nullptr;  // recorded after the last kernel of a call; the caller's stream waits on it
     u32* d_input_slots = nullptr;      // slot of every input target, as last uploaded to this workspace
     std::vector<u32> h_input_slots;    // host copy: re-uploaded only when a call brings a different target list
@@ -48,10 +121,9 @@ struct Workspace {
     int* d_status = nullptr;
     u64* d_advice = nullptr;
     u64* d_pi_hash = nullptr;          // [chunk][4] public-input hash per proof (k_pi_hash; circuits with public inputs)
-    u64 *d_wires = nullptr, *d_wcoef = nullptr, *d_wlde = nullptr;
-    u64 *d_zs = nullptr, *d_zcoef = nullptr, *d_zlde = nullptr, *d_permq = nullptr, *d_perm_seg = nullptr, *d_fri_seg = nullptr, *d_lktmp = nullptr;
-    u64 *d_qvals = nullptr, *d_qres = nullptr, *d_qcoef = nullptr, *d_qlde = nullptr;
-    Tree wtree, ztree, qtree;
+    Oracle wires, zs, quot;
+    u64 *d_permq = nullptr, *d_perm_seg = nullptr, *d_fri_seg = nullptr, *d_lktmp = nullptr;
+    u64 *d_qvals = nullptr, *d_qres = nullptr;
     ChalState* d_chal_state = nullptr;
     u64* d_chal = nullptr;
     u64 *d_pows = nullptr, *d_ev = nullptr, *d_obs = nullptr, *d_comp = nullptr, *d_apow = nullptr;
@@ -63,18 +135,17 @@ struct Workspace {
     uint8_t* d_proofs = nullptr;
     PolyRef* d_polyrefs = nullptr;
     EvalRef* d_evalrefs = nullptr;
-    std::vector<std::pair<std::string, std::pair<hipEvent_t, hipEvent_t>>> pending;
 };
 
 struct p2_circuit {
     Circuit c;
     int device = 0;
-    hipStream_t stream = nullptr;  // setup stream (= ws[0] once workspaces exist)
+    Lane setup;  // load-time work (preprocessing); the proving lanes are the workspaces'
+    Domain dom;
     size_t n = 0, N = 0;
-    u32 logn = 0, lde_bits = 0, active_wires = 0;
+    u32 lde_bits = 0, active_wires = 0;
     ProofLayout layout;  // where every field of a proof sits (proof_layout.h), built at load
     size_t pbytes = 0;   // = layout.bytes
-    std::vector<u32> arities;
     // ---- static device data
     Op* d_ops = nullptr;
     WLevel* d_wlevels = nullptr;
@@ -91,15 +162,9 @@ struct p2_circuit {
     u64 zk_counter = 0;  // proofs attempted under this key; never reused, also when a batch fails
     size_t total_lut_entries = 0;
     u64 *d_sigmas = nullptr, *d_k_is = nullptr, *d_subgroup = nullptr;
-    u64 *d_tw_fwd = nullptr, *d_tw_inv = nullptr;  // w^k / w^-k for k < n_max/2, n_max = n
-    u64 *d_tw_fwd_full = nullptr, *d_tw_inv_full = nullptr;  // w^k / w^-k for k < n (two-pass NTT, n > 2^14)
-    u64* d_tw_fwd_round[9] = {nullptr};                       // order n_r tables for FRI rounds that still need two passes
-    u64* d_shift_pows[9] = {nullptr};              // per FRI round r (0 = main LDE): [8][n_r] (s_r w^j)^i
-    u64* d_shift_tw = nullptr;                     // main LDE, 2^13 <= n <= 2^14: [8][n/2] d_shift_pows[0][j][i] * w^i
     u64* d_shift_inv_pows = nullptr;               // [8][n] (g w^j)^-i / n   (quotient inverse)
     u64 *d_xs = nullptr, *d_l0 = nullptr, *d_zh_inv = nullptr, *d_w8inv = nullptr, *d_qscale = nullptr;
-    u64 *d_pre_coeffs = nullptr, *d_pre_lde = nullptr;
-    Tree pre_tree;
+    Oracle pre;               // constants | sigmas, committed at load
     u64* d_digest = nullptr;  // circuit digest (4)
     std::vector<u64> verifier_data;
     u32 n_b0 = 0, n_b1 = 0, n_evalrefs = 0;
@@ -108,10 +173,6 @@ struct p2_circuit {
     // ---- per-stream workspaces: chunks are dealt round-robin to streams so that the latency-bound stages of one
     // chunk (witness levels, Fiat-Shamir, PoW tail) overlap with the Poseidon-heavy stages of another
     std::vector<struct Workspace*> ws;
-    Workspace* cur = nullptr;  // workspace the host thread is currently enqueueing into (under `mu`)
-    Workspace setup_ws;        // used before any per-chunk workspace exists (preprocessing, primitives)
-    hipStream_t cur_stream() { return cur ? cur->stream : stream; }
-    std::vector<std::pair<std::string, std::pair<hipEvent_t, hipEvent_t>>>& cur_pending() { return cur ? cur->pending : setup_ws.pending; }
     hipEvent_t ev_witness = nullptr;  // end of the latest witness kernel on any proving stream
     bool witness_recorded = false;
     u32 ws_inputs = 0;
@@ -120,7 +181,6 @@ struct p2_circuit {
     // tuning options (p2_circuit_set_option; the environment is read ONCE, at load): proofs per chunk, proving streams,
     // phase timing of the host path on stderr
     size_t opt_chunk = 128, opt_streams = 2;
-    std::map<const u64*, u64*> pass1_out_tw;  // two-pass NTT: output-twiddle table per full twiddle table (ensure_pass1_table)
     // Longest chain of the witness schedule (P2AES_WITNESS_FUSE at load, 1..8).  Default 1 = no chains: measured on the 64 KiB
     // circuit, chains of 8 cut the levels from 12.4 k to 2.6 k and change nothing (73 vs 66 ms per 16 witnesses, 17.4 vs 17.6
     // proofs/s) -- the kernel is bound by one compute unit's address path, not by its depth -- and the chain executor costs
@@ -145,41 +205,9 @@ struct p2_circuit {
     // timing
     bool timing_on = false;
     std::map<std::string, std::pair<float, u32>> times;
-    std::vector<void*> allocs;
+    Allocs allocs;
     std::mutex mu;
 };
-
-template <class T>
-static int dalloc(p2_circuit* C, T** p, size_t count) {
-    void* q = nullptr;
-    HIPCHECK(hipMalloc(&q, std::max<size_t>(count, 1) * sizeof(T)));
-    C->allocs.push_back(q);
-    *p = (T*)q;
-    return 0;
-}
-template <class T>
-static int upload(p2_circuit* C, T** p, const T* host, size_t count) {
-    if (dalloc(C, p, count)) return P2_ERR_HIP;
-    if (count) HIPCHECK(hipMemcpy(*p, host, count * sizeof(T), hipMemcpyHostToDevice));
-    return 0;
-}
-
-// Launch with optional per-kernel event timing on the proving stream.
-#define LAUNCH(C, name, kernel, grid, block, shmem, ...)                                              \
-    do {                                                                                              \
-        hipEvent_t _e0 = nullptr, _e1 = nullptr;                                                      \
-        if ((C)->timing_on) {                                                                         \
-            (void)hipEventCreate(&_e0);                                                                     \
-            (void)hipEventCreate(&_e1);                                                                     \
-            (void)hipEventRecord(_e0, (C)->cur_stream());                                                         \
-        }                                                                                             \
-        hipLaunchKernelGGL(kernel, grid, block, shmem, (C)->cur_stream(), __VA_ARGS__);                     \
-        if ((C)->timing_on) {                                                                         \
-            (void)hipEventRecord(_e1, (C)->cur_stream());                                                         \
-            (C)->cur_pending().push_back({name, {_e0, _e1}});                                               \
-        }                                                                                             \
-        HIPCHECK(hipGetLastError());                                                                  \
-    } while (0)
 
 // Launch outside the timing map (the verification / compression driver, whose kernels run on a caller's or a workspace's stream).
 #define LAUNCH_ON(st, kernel, grid, block, ...)                          \
@@ -204,19 +232,19 @@ static inline dim3 g1(size_t work, u32 block, u32 y = 1, u32 z = 1) { return dim
 // ---------------------------------------------------------------------------------- building blocks
 static const u32 R16_MIN_BITS = 8;  // the register-blocked kernel needs n / 16 threads >= a few waves; smaller transforms keep k_ntt_lds
 static size_t r16_lds_bytes(int logn) { return 8 * (((size_t)1 << logn) + ((size_t)1 << (logn - 4))); }
-static int run_ntt(p2_circuit* C, const char* name, NttArgs a, u32 cols, u32 batch) {
-    a.log_nmax = (int)C->logn;
+static int run_ntt(Lane& L, const Domain& D, const char* name, NttArgs a, u32 cols, u32 batch) {
+    a.log_nmax = (int)D.logn;
     if ((u32)a.logn >= 13 && !a.bitrev_in && !a.bitrev_out && !a.post) {
         // half a column per workgroup: two (or more) workgroups per compute unit overlap each other's memory phases
-        LAUNCH(C, name, k_ntt_r16<true>, dim3(2 * cols * a.cosets, batch), dim3(1u << (a.logn - 5)), r16_lds_bytes(a.logn - 1), a);
+        LAUNCH(L, name, k_ntt_r16<true>, dim3(2 * cols * a.cosets, batch), dim3(1u << (a.logn - 5)), r16_lds_bytes(a.logn - 1), a);
         return 0;
     }
     if ((u32)a.logn >= R16_MIN_BITS) {
-        LAUNCH(C, name, k_ntt_r16<false>, dim3(cols * a.cosets, batch), dim3(1u << (a.logn - 4)), r16_lds_bytes(a.logn), a);
+        LAUNCH(L, name, k_ntt_r16<false>, dim3(cols * a.cosets, batch), dim3(1u << (a.logn - 4)), r16_lds_bytes(a.logn), a);
         return 0;
     }
     size_t shmem = (size_t)8 << a.logn;
-    LAUNCH(C, name, k_ntt_lds, dim3(cols * a.cosets, batch), dim3(1024), shmem, a);
+    LAUNCH(L, name, k_ntt_lds, dim3(cols * a.cosets, batch), dim3(1024), shmem, a);
     return 0;
 }
 static const u32 LDS_NTT_MAX_BITS = 14;  // whole transform in one workgroup's LDS up to 2^14 points
@@ -232,17 +260,17 @@ static hipError_t raise_ntt_lds_limits() {
 }
 // The output twiddles of pass 1 for the order-2^logn table `tw_full`, in output order (k_pass1_out_tw); built at load, never
 // while workspaces are open (allocations made then belong to the workspaces).
-static int ensure_pass1_table(p2_circuit* C, const u64* tw_full, u32 logn) {
-    if (logn <= LDS_NTT_MAX_BITS || C->pass1_out_tw.count(tw_full)) return 0;
+static int ensure_pass1_table(Lane& L, Domain& D, Allocs& mem, const u64* tw_full, u32 logn) {
+    if (logn <= LDS_NTT_MAX_BITS || D.pass1_out_tw.count(tw_full)) return 0;
     u64* t = nullptr;
-    if (dalloc(C, &t, (size_t)1 << logn)) return P2_ERR_HIP;
-    hipLaunchKernelGGL(k_pass1_out_tw, g1((size_t)1 << logn, 256), dim3(256), 0, C->stream, tw_full, t, (int)logn, (int)(logn - 12));
+    if (dalloc(mem, &t, (size_t)1 << logn)) return P2_ERR_HIP;
+    hipLaunchKernelGGL(k_pass1_out_tw, g1((size_t)1 << logn, 256), dim3(256), 0, L.stream, tw_full, t, (int)logn, (int)(logn - 12));
     HIPCHECK(hipGetLastError());
-    C->pass1_out_tw[tw_full] = t;
+    D.pass1_out_tw[tw_full] = t;
     return 0;
 }
 // two-pass transform of `cols*cosets` blocks: natural order in `in`, bit-reversed order in `out`
-static int ntt_big(p2_circuit* C, const char* name, const u64* in, u64* out, const u64* tw_full, const u64* pre, u32 logn, u32 cols, u32 cosets,
+static int ntt_big(Lane& L, const Domain& D, const char* name, const u64* in, u64* out, const u64* tw_full, const u64* pre, u32 logn, u32 cols, u32 cosets,
                    const u32* block_of_coset, int in_coset_blocks, size_t in_col_stride, size_t out_col_stride, size_t in_batch_stride,
                    size_t out_batch_stride, u64 post_scalar, u32 batch) {
     const u32 log_n2 = 12, log_n1 = logn - log_n2;
@@ -264,12 +292,12 @@ static int ntt_big(p2_circuit* C, const char* name, const u64* in, u64* out, con
     a.in_coset_blocks = in_coset_blocks;
     for (u32 j = 0; j < 8; j++) a.block_of_coset[j] = block_of_coset ? block_of_coset[j] : 0;
     u32 tiles = (1u << log_n2) >> log_T;
-    auto it = C->pass1_out_tw.find(tw_full);
-    if (it == C->pass1_out_tw.end()) return set_error("internal: no pass-1 twiddle table for this transform"), P2_ERR_INVALID;
+    auto it = D.pass1_out_tw.find(tw_full);
+    if (it == D.pass1_out_tw.end()) return set_error("internal: no pass-1 twiddle table for this transform"), P2_ERR_INVALID;
     a.out_tw = it->second;
     a.xcd_swizzle = (cosets > 1 && !in_coset_blocks) ? 1 : 0;  // only where workgroups share their input
     const std::string name1 = std::string(name) + "_pass1";  // the two passes are timed apart
-    LAUNCH(C, name1, k_ntt_pass1_r16, dim3(tiles * cols * cosets, batch), dim3(256), r16_lds_bytes(12), a);
+    LAUNCH(L, name1, k_ntt_pass1_r16, dim3(tiles * cols * cosets, batch), dim3(256), r16_lds_bytes(12), a);
     // pass 2: every row of n2 contiguous points, in place
     if (out_col_stride != ((size_t)cosets << logn)) return set_error("internal: two-pass NTT needs densely packed output blocks"), P2_ERR_INVALID;
     NttArgs b{};
@@ -284,120 +312,113 @@ static int ntt_big(p2_circuit* C, const char* name, const u64* in, u64* out, con
     b.cosets = 1;
     size_t rows = ((size_t)cols * cosets) << log_n1;
     // grid.x is limited to 2^31-1; rows*1 fits for every supported size
-    LAUNCH(C, name, k_ntt_r16<false>, dim3((u32)rows, batch), dim3(1u << (log_n2 - 4)), r16_lds_bytes((int)log_n2), b);
+    LAUNCH(L, name, k_ntt_r16<false>, dim3((u32)rows, batch), dim3(1u << (log_n2 - 4)), r16_lds_bytes((int)log_n2), b);
     return 0;
 }
 // values [cols][n] -> coeffs [cols][n].  `scratch` ([cols][n] per proof, same batch stride) is needed when n > 2^14.
-static int intt_cols(p2_circuit* C, const u64* vals, u64* coeffs, u32 cols, size_t batch_stride, u32 batch, u64* scratch = nullptr,
+static int intt_cols(Lane& L, const Domain& D, const u64* vals, u64* coeffs, u32 cols, size_t batch_stride, u32 batch, u64* scratch = nullptr,
                      size_t scratch_batch_stride = 0) {
-    if (C->logn > LDS_NTT_MAX_BITS) {
+    const size_t n = D.n();
+    if (D.logn > LDS_NTT_MAX_BITS) {
         if (!scratch) return set_error("internal: large iNTT needs scratch"), P2_ERR_INVALID;
-        if (ntt_big(C, "intt", vals, scratch, C->d_tw_inv_full, nullptr, C->logn, cols, 1, nullptr, 0, C->n, C->n, batch_stride, scratch_batch_stride,
-                    gl::inv((u64)C->n % gl::P), batch))
+        if (ntt_big(L, D, "intt", vals, scratch, D.d_tw_inv_full, nullptr, D.logn, cols, 1, nullptr, 0, n, n, batch_stride, scratch_batch_stride,
+                    gl::inv((u64)n % gl::P), batch))
             return P2_ERR_HIP;
-        LAUNCH(C, "bitrev_copy", k_bitrev_copy, g1(C->n, 256, batch, cols), dim3(256), 0, scratch, C->n, scratch_batch_stride, coeffs, C->n, batch_stride,
-               (int)C->logn, 1u, (const u64*)nullptr, 0u);
+        LAUNCH(L, "bitrev_copy", k_bitrev_copy, g1(n, 256, batch, cols), dim3(256), 0, scratch, n, scratch_batch_stride, coeffs, n, batch_stride,
+               (int)D.logn, 1u, (const u64*)nullptr, 0u);
         return 0;
     }
     NttArgs a{};
     a.in = vals;
     a.out = coeffs;
-    a.tw = C->d_tw_inv;
-    a.post_scalar = gl::inv((u64)C->n % gl::P);
-    a.in_col_stride = a.out_col_stride = C->n;
+    a.tw = D.d_tw_inv;
+    a.post_scalar = gl::inv((u64)n % gl::P);
+    a.in_col_stride = a.out_col_stride = n;
     a.in_batch_stride = a.out_batch_stride = batch_stride;
-    a.logn = (int)C->logn;
+    a.logn = (int)D.logn;
     a.cosets = 1;
     a.bitrev_out = 1;
-    return run_ntt(C, "intt", a, cols, batch);
+    return run_ntt(L, D, "intt", a, cols, batch);
 }
 // coeffs [cols][n_r] -> lde [cols][8 n_r] (bit-reversed order)
-static int lde_cols(p2_circuit* C, const u64* coeffs, size_t in_batch_stride, u64* lde, size_t out_batch_stride, u32 cols, u32 round, u32 batch) {
-    u32 logn_r = C->logn;
-    for (u32 r = 0; r < round; r++) logn_r -= C->arities[r];
+static int lde_cols(Lane& L, const Domain& D, const u64* coeffs, size_t in_batch_stride, u64* lde, size_t out_batch_stride, u32 cols, u32 round, u32 batch) {
+    u32 logn_r = D.logn;
+    for (u32 r = 0; r < round; r++) logn_r -= D.arities[r];
     u32 blocks[8];
-    for (u32 j = 0; j < 8; j++) blocks[j] = gl::bitrev(j, (int)C->c.cfg.rate_bits);
+    for (u32 j = 0; j < 8; j++) blocks[j] = gl::bitrev(j, (int)D.rate_bits);
     if (logn_r > LDS_NTT_MAX_BITS) {
         // twiddles of order n_r are a stride of the order-n table
-        if (round != 0 && C->d_tw_fwd_round[round] == nullptr) return set_error("internal: missing round twiddles"), P2_ERR_INVALID;
-        const u64* tw = round == 0 ? C->d_tw_fwd_full : C->d_tw_fwd_round[round];
-        return ntt_big(C, "lde", coeffs, lde, tw, C->d_shift_pows[round], logn_r, cols, 8, blocks, 0, (size_t)1 << logn_r, (size_t)8 << logn_r,
+        if (round != 0 && D.d_tw_fwd_round[round] == nullptr) return set_error("internal: missing round twiddles"), P2_ERR_INVALID;
+        const u64* tw = round == 0 ? D.d_tw_fwd_full : D.d_tw_fwd_round[round];
+        return ntt_big(L, D, "lde", coeffs, lde, tw, D.d_shift_pows[round], logn_r, cols, 8, blocks, 0, (size_t)1 << logn_r, (size_t)8 << logn_r,
                        in_batch_stride, out_batch_stride, 1, batch);
     }
     NttArgs a{};
     a.in = coeffs;
     a.out = lde;
-    a.tw = C->d_tw_fwd;
-    a.pre = C->d_shift_pows[round];
-    a.pre_tw = round == 0 ? C->d_shift_tw : nullptr;
+    a.tw = D.d_tw_fwd;
+    a.pre = D.d_shift_pows[round];
+    a.pre_tw = round == 0 ? D.d_shift_tw : nullptr;
     a.post_scalar = 1;
     a.in_col_stride = (size_t)1 << logn_r;
     a.out_col_stride = (size_t)8 << logn_r;
     a.in_batch_stride = in_batch_stride;
     a.out_batch_stride = out_batch_stride;
     a.logn = (int)logn_r;
-    a.cosets = 1 << C->c.cfg.rate_bits;
+    a.cosets = 1 << D.rate_bits;
     for (u32 j = 0; j < 8; j++) a.block_of_coset[j] = blocks[j];
-    return run_ntt(C, "lde", a, cols, batch);
+    return run_ntt(L, D, "lde", a, cols, batch);
+}
+// The three tree kernels of a hasher (one parameter list each for both hashers), and whether the top of a tree may be fused.
+struct TreeKernels {
+    decltype(&k_hash_leaves) leaves;
+    decltype(&k_hash_fri_leaves) fri_leaves;
+    decltype(&k_merkle_level) level;
+    // Keccak: one launch per level for every batch size: a Keccak level is one permutation of 24 short rounds, and the fused top of
+    // the Poseidon path exists for the latency of a single proof only
+    bool fused_top;
+};
+static TreeKernels tree_kernels(u32 hasher) {
+    if (hasher == HASHER_KECCAK) return {k_kc_leaves, k_kc_fri_leaves, k_kc_level, false};
+    return {k_hash_leaves, k_hash_fri_leaves, k_merkle_level, true};
 }
 // The levels above the leaf digests, up to the cap: wide levels one launch each, the top (at most 256 parents per cap
 // subtree, up to nine levels) in one launch of a workgroup per cap node.
-static int merkle_levels(p2_circuit* C, Tree& t, u32 batch) {
-    const u32 cap_h = C->c.cfg.cap_height;
+static int merkle_levels(Lane& L, const Domain& D, Tree& t, u32 batch) {
+    const u32 cap_h = D.cap_height;
     if (t.bits <= cap_h) return 0;
     const u32 levels = t.bits - cap_h;                       // level l: 2^(bits-l-1) parents
-    if (C->c.cfg.hasher == HASHER_KECCAK) {
-        // one launch per level for every batch size: a Keccak level is one permutation of 24 short rounds, and the fused top of
-        // the Poseidon path exists for the latency of a single proof only
-        for (u32 l = 0; l < levels; l++) {
-            size_t parents = ((size_t)1 << t.bits) >> (l + 1);
-            size_t off_c = 4 * (((size_t)2 << t.bits) - ((size_t)2 << (t.bits - l)));
-            size_t off_p = 4 * (((size_t)2 << t.bits) - ((size_t)2 << (t.bits - l - 1)));
-            LAUNCH(C, "merkle_level", k_kc_level, g1(parents, 256, batch), dim3(256), 0, t.dig + off_c, t.dig + off_p, parents, t.stride());
-        }
-        return 0;
-    }
+    const TreeKernels k = tree_kernels(D.hasher);
     // The last `fused` levels (parents per cap subtree 2^(fused-1) .. 1) run as ONE launch of a workgroup per cap node -- for
     // SMALL batches only.  These levels are latency bound either way (a level is one permutation deep whatever its width), so
     // what the fusion buys is launches: 54 -> 18 per chunk, 118 -> 70 for the whole pipeline.  For a full chunk it costs time:
     // the waves of a fused walk stay resident for all its levels and slow each other down, where separately launched levels
     // shrink to one wave per SIMD as they narrow (measured per 128-proof chunk: nine levels in 256-thread workgroups + 3.3 ms,
     // seven levels in one wave + 1.3 ms against 21.1 ms).  Launch count does not matter there: the chip is busy throughout.
-    const u32 fused = batch <= 16 ? std::min<u32>(levels, 9) : 0;
+    const u32 fused = k.fused_top && batch <= 16 ? std::min<u32>(levels, 9) : 0;
     const u32 top_threads = 256;
-    const size_t leaves = (size_t)1 << t.bits;
     for (u32 l = 0; l < levels - fused; l++) {
-        size_t parents = leaves >> (l + 1);
-        size_t off_c = 4 * (((size_t)2 << t.bits) - ((size_t)2 << (t.bits - l)));
-        size_t off_p = 4 * (((size_t)2 << t.bits) - ((size_t)2 << (t.bits - l - 1)));
-        LAUNCH(C, "merkle_level", k_merkle_level, g1(parents, 256, batch), dim3(256), 0, t.dig + off_c, t.dig + off_p, parents, t.stride());
+        size_t parents = ((size_t)1 << t.bits) >> (l + 1);
+        LAUNCH(L, "merkle_level", k.level, g1(parents, 256, batch), dim3(256), 0, t.dig + level_off(t.bits, l), t.dig + level_off(t.bits, l + 1), parents, t.stride());
     }
     if (fused) {
         // parents per cap subtree at the fused levels: 2^(fused-1) .. 1; those with more than 32 one thread per node, the rest cooperative
         const u32 direct = fused > 6 ? fused - 6 : 0;
-        if (direct) LAUNCH(C, "merkle_top", k_merkle_top, dim3(1u << cap_h, batch), dim3(top_threads), 0, t.dig, t.stride(), t.bits, levels - fused, direct);
-        LAUNCH(C, "merkle_top", k_merkle_top_coop, dim3(1u << cap_h, batch), dim3(256), 0, t.dig, t.stride(), t.bits, levels - fused + direct, fused - direct);
+        if (direct) LAUNCH(L, "merkle_top", k_merkle_top, dim3(1u << cap_h, batch), dim3(top_threads), 0, t.dig, t.stride(), t.bits, levels - fused, direct);
+        LAUNCH(L, "merkle_top", k_merkle_top_coop, dim3(1u << cap_h, batch), dim3(256), 0, t.dig, t.stride(), t.bits, levels - fused + direct, fused - direct);
     }
     return 0;
 }
-static int merkle_build(p2_circuit* C, const u64* data, u32 cols, u32 active, size_t col_stride, size_t batch_stride, Tree& t, u32 batch) {
+static int merkle_build(Lane& L, const Domain& D, const u64* data, u32 cols, u32 active, size_t col_stride, size_t batch_stride, Tree& t, u32 batch) {
     size_t leaves = (size_t)1 << t.bits;
-    if (C->c.cfg.hasher == HASHER_KECCAK) {
-        LAUNCH(C, "hash_leaves", k_kc_leaves, g1(leaves, 256, batch), dim3(256), 0, data, (int)cols, (int)active, col_stride, batch_stride, leaves, t.dig, t.stride());
-        return merkle_levels(C, t, batch);
-    }
-    LAUNCH(C, "hash_leaves", k_hash_leaves, g1(leaves, 256, batch), dim3(256), 0, data, (int)cols, (int)active, col_stride, batch_stride, leaves, t.dig,
+    LAUNCH(L, "hash_leaves", tree_kernels(D.hasher).leaves, g1(leaves, 256, batch), dim3(256), 0, data, (int)cols, (int)active, col_stride, batch_stride, leaves, t.dig,
            t.stride());
-    return merkle_levels(C, t, batch);
+    return merkle_levels(L, D, t, batch);
 }
-static size_t cap_off(const Tree& t, u32 cap_height) {
-    u32 l = t.bits - cap_height;
-    return 4 * (((size_t)2 << t.bits) - ((size_t)2 << (t.bits - l)));
-}
-static int challenger(p2_circuit* C, u32 stage, const u64* observe, size_t stride, u32 len, u32 aux, u64 mod, u32 batch) {
+static int challenger(p2_circuit* C, Workspace& W, u32 stage, const u64* observe, size_t stride, u32 len, u32 aux, u64 mod, u32 batch) {
     ChalArgs a{};
-    a.st = C->cur->d_chal_state;
-    a.chal = C->cur->d_chal;
+    a.st = W.d_chal_state;
+    a.chal = W.d_chal;
     a.observe = observe;
     a.observe_stride = stride;
     a.observe_len = len;
@@ -406,15 +427,16 @@ static int challenger(p2_circuit* C, u32 stage, const u64* observe, size_t strid
     a.aux = aux;
     a.mod = mod;
     a.digest = C->d_digest;
-    a.pi_hash = C->c.pi_slots.empty() ? nullptr : C->cur->d_pi_hash;
-    a.status = C->cur->d_status;
-    LAUNCH(C, "challenger", k_challenger, g1((size_t)batch * 16, 64), dim3(64), 0, a);  // a 16-lane group per proof
+    a.pi_hash = C->c.pi_slots.empty() ? nullptr : W.d_pi_hash;
+    a.status = W.d_status;
+    LAUNCH(W.lane, "challenger", k_challenger, g1((size_t)batch * 16, 64), dim3(64), 0, a);  // a 16-lane group per proof
     return 0;
 }
 
 // ---------------------------------------------------------------------------------- load / preprocess
 static int circuit_setup(p2_circuit* C) {
     const Circuit& c = C->c;
+    Domain& D = C->dom;
     const size_t n = C->n, N = C->N;
     const u32 R = c.cfg.num_routed_wires, ncc = c.num_constants_cols(), np = c.num_preprocessed();
     if (c.cfg.num_challenges > 2) return set_error("k_perm_chunks handles at most two challenges"), P2_ERR_INVALID;
@@ -425,12 +447,12 @@ static int circuit_setup(p2_circuit* C) {
         if (ws.max_chain > (u32)WITNESS_KMAX) return set_error("internal: witness chain longer than the kernel is unrolled for"), P2_ERR_INVALID;
         C->witness_levels = (u32)ws.levels.size();
         C->witness_chains = (u32)ws.chains.size();
-        if (upload(C, &C->d_ops, ws.ops.data(), ws.ops.size())) return P2_ERR_HIP;
-        if (upload(C, &C->d_wlevels, ws.levels.data(), ws.levels.size())) return P2_ERR_HIP;
-        if (upload(C, &C->d_wchains, ws.chains.data(), ws.chains.size())) return P2_ERR_HIP;
+        if (upload(C->allocs, &C->d_ops, ws.ops.data(), ws.ops.size())) return P2_ERR_HIP;
+        if (upload(C->allocs, &C->d_wlevels, ws.levels.data(), ws.levels.size())) return P2_ERR_HIP;
+        if (upload(C->allocs, &C->d_wchains, ws.chains.data(), ws.chains.size())) return P2_ERR_HIP;
     }
-    if (upload(C, &C->d_wire_slot, c.wire_slot.data(), c.wire_slot.size())) return P2_ERR_HIP;
-    if (!c.pi_slots.empty() && upload(C, &C->d_pi_slots, c.pi_slots.data(), c.pi_slots.size())) return P2_ERR_HIP;
+    if (upload(C->allocs, &C->d_wire_slot, c.wire_slot.data(), c.wire_slot.size())) return P2_ERR_HIP;
+    if (!c.pi_slots.empty() && upload(C->allocs, &C->d_pi_slots, c.pi_slots.data(), c.pi_slots.size())) return P2_ERR_HIP;
     {
         // witness generation resolves a lookup with ONE load: input value -> (flat entry index << 16) | output
         std::vector<u64> ent(c.luts.size() * 65536, ~0ull);
@@ -444,78 +466,78 @@ static int circuit_setup(p2_circuit* C) {
             offs.push_back((u32)pairs.size());
         }
         C->total_lut_entries = pairs.size();
-        if (upload(C, &C->d_lut_ent, ent.data(), ent.size())) return P2_ERR_HIP;
-        if (upload(C, &C->d_lut_pairs, pairs.data(), pairs.size())) return P2_ERR_HIP;
-        if (upload(C, &C->d_lut_offsets, offs.data(), offs.size())) return P2_ERR_HIP;
-        if (upload(C, &C->d_num_lookups, c.num_lookups.data(), c.num_lookups.size())) return P2_ERR_HIP;
-        if (upload(C, &C->d_lookup_rows, c.lookup_rows.data(), c.lookup_rows.size())) return P2_ERR_HIP;
+        if (upload(C->allocs, &C->d_lut_ent, ent.data(), ent.size())) return P2_ERR_HIP;
+        if (upload(C->allocs, &C->d_lut_pairs, pairs.data(), pairs.size())) return P2_ERR_HIP;
+        if (upload(C->allocs, &C->d_lut_offsets, offs.data(), offs.size())) return P2_ERR_HIP;
+        if (upload(C->allocs, &C->d_num_lookups, c.num_lookups.data(), c.num_lookups.size())) return P2_ERR_HIP;
+        if (upload(C->allocs, &C->d_lookup_rows, c.lookup_rows.data(), c.lookup_rows.size())) return P2_ERR_HIP;
     }
     {
         std::vector<int32_t> pi(n, -1);
         for (size_t k = 0; k < c.poseidon_rows.size(); k++) pi[c.poseidon_rows[k]] = (int32_t)k;
-        if (upload(C, &C->d_pos_index, pi.data(), n)) return P2_ERR_HIP;
+        if (upload(C->allocs, &C->d_pos_index, pi.data(), n)) return P2_ERR_HIP;
     }
-    if (upload(C, &C->d_blind_rows, c.blind_rows.data(), c.blind_rows.size())) return P2_ERR_HIP;
-    if (upload(C, &C->d_blind_zrows, (const u32*)c.blind_zrows.data(), 2 * c.blind_zrows.size())) return P2_ERR_HIP;
-    if (upload(C, &C->d_sigmas, c.sigmas.data(), c.sigmas.size())) return P2_ERR_HIP;
-    if (upload(C, &C->d_k_is, c.k_is.data(), c.k_is.size())) return P2_ERR_HIP;
+    if (upload(C->allocs, &C->d_blind_rows, c.blind_rows.data(), c.blind_rows.size())) return P2_ERR_HIP;
+    if (upload(C->allocs, &C->d_blind_zrows, (const u32*)c.blind_zrows.data(), 2 * c.blind_zrows.size())) return P2_ERR_HIP;
+    if (upload(C->allocs, &C->d_sigmas, c.sigmas.data(), c.sigmas.size())) return P2_ERR_HIP;
+    if (upload(C->allocs, &C->d_k_is, c.k_is.data(), c.k_is.size())) return P2_ERR_HIP;
     // twiddles, subgroup, coset tables (host-computed once; O(n) field ops)
     {
         std::vector<u64> sub(n), twi(n);
-        u64 w = gl::root_of_unity((int)C->logn), wi = gl::inv(w), x = 1, xi = 1;
+        u64 w = gl::root_of_unity((int)D.logn), wi = gl::inv(w), x = 1, xi = 1;
         for (size_t i = 0; i < n; i++) {
             sub[i] = x;
             twi[i] = xi;
             x = gl::mul(x, w);
             xi = gl::mul(xi, wi);
         }
-        if (upload(C, &C->d_subgroup, sub.data(), n)) return P2_ERR_HIP;
-        if (upload(C, &C->d_tw_inv_full, twi.data(), n)) return P2_ERR_HIP;
-        C->d_tw_fwd_full = C->d_subgroup;  // w^k, k < n
-        C->d_tw_fwd = C->d_tw_fwd_full;    // the single-pass kernel only indexes k < n/2
-        C->d_tw_inv = C->d_tw_inv_full;
-        if (ensure_pass1_table(C, C->d_tw_fwd_full, C->logn) || ensure_pass1_table(C, C->d_tw_inv_full, C->logn)) return P2_ERR_HIP;
+        if (upload(C->allocs, &C->d_subgroup, sub.data(), n)) return P2_ERR_HIP;
+        if (upload(C->allocs, &D.d_tw_inv_full, twi.data(), n)) return P2_ERR_HIP;
+        D.d_tw_fwd_full = C->d_subgroup;  // w^k, k < n
+        D.d_tw_fwd = D.d_tw_fwd_full;    // the single-pass kernel only indexes k < n/2
+        D.d_tw_inv = D.d_tw_inv_full;
+        if (ensure_pass1_table(C->setup, D, C->allocs, D.d_tw_fwd_full, D.logn) || ensure_pass1_table(C->setup, D, C->allocs, D.d_tw_inv_full, D.logn)) return P2_ERR_HIP;
         // FRI rounds whose polynomial is still > 2^14 need their own order-n_r table
-        u32 logn_r = C->logn;
-        for (u32 r = 0; r < C->arities.size(); r++) {
-            logn_r -= C->arities[r];
+        u32 logn_r = D.logn;
+        for (u32 r = 0; r < D.arities.size(); r++) {
+            logn_r -= D.arities[r];
             if (logn_r > LDS_NTT_MAX_BITS) {
                 size_t n_r = (size_t)1 << logn_r;
                 std::vector<u64> t(n_r);
-                for (size_t i = 0; i < n_r; i++) t[i] = sub[i << (C->logn - logn_r)];
-                if (upload(C, &C->d_tw_fwd_round[r + 1], t.data(), n_r)) return P2_ERR_HIP;
-                if (ensure_pass1_table(C, C->d_tw_fwd_round[r + 1], logn_r)) return P2_ERR_HIP;
+                for (size_t i = 0; i < n_r; i++) t[i] = sub[i << (D.logn - logn_r)];
+                if (upload(C->allocs, &D.d_tw_fwd_round[r + 1], t.data(), n_r)) return P2_ERR_HIP;
+                if (ensure_pass1_table(C->setup, D, C->allocs, D.d_tw_fwd_round[r + 1], logn_r)) return P2_ERR_HIP;
             }
         }
     }
     {
         // LDE shift tables for round r: bases s_{r,j} = g^(16^r) * w_{8 n_r}^j
-        u32 logn_r = C->logn;
+        u32 logn_r = D.logn;
         u64 shift = gl::MULT_GEN;
-        for (u32 r = 0; r <= C->arities.size(); r++) {
+        for (u32 r = 0; r <= D.arities.size(); r++) {
             size_t n_r = (size_t)1 << logn_r;
             std::vector<u64> bases(8);
             u64 wl = gl::root_of_unity((int)(logn_r + c.cfg.rate_bits));
             for (u32 j = 0; j < 8; j++) bases[j] = gl::mul(shift, gl::pow(wl, j));
             u64* d_b;
-            if (upload(C, &d_b, bases.data(), 8)) return P2_ERR_HIP;
-            if (dalloc(C, &C->d_shift_pows[r], 8 * n_r)) return P2_ERR_HIP;
-            hipLaunchKernelGGL(k_pow_table, g1(n_r, 256, 8), dim3(256), 0, C->stream, C->d_shift_pows[r], d_b, (u32)n_r, (u64)1);
-            if (r == 0 && C->logn >= 13 && C->logn <= LDS_NTT_MAX_BITS) {
-                if (dalloc(C, &C->d_shift_tw, 8 * (n_r / 2))) return P2_ERR_HIP;
-                hipLaunchKernelGGL(k_mul_tables, g1(n_r / 2, 256, 8), dim3(256), 0, C->stream, C->d_shift_tw, C->d_shift_pows[0], n_r, C->d_tw_fwd, 0, (u32)(n_r / 2));
+            if (upload(C->allocs, &d_b, bases.data(), 8)) return P2_ERR_HIP;
+            if (dalloc(C->allocs, &D.d_shift_pows[r], 8 * n_r)) return P2_ERR_HIP;
+            hipLaunchKernelGGL(k_pow_table, g1(n_r, 256, 8), dim3(256), 0, C->setup.stream, D.d_shift_pows[r], d_b, (u32)n_r, (u64)1);
+            if (r == 0 && D.logn >= 13 && D.logn <= LDS_NTT_MAX_BITS) {
+                if (dalloc(C->allocs, &D.d_shift_tw, 8 * (n_r / 2))) return P2_ERR_HIP;
+                hipLaunchKernelGGL(k_mul_tables, g1(n_r / 2, 256, 8), dim3(256), 0, C->setup.stream, D.d_shift_tw, D.d_shift_pows[0], n_r, D.d_tw_fwd, 0, (u32)(n_r / 2));
             }
             if (r == 0) {
                 std::vector<u64> ib(8);
                 for (u32 j = 0; j < 8; j++) ib[j] = gl::inv(bases[j]);
                 u64* d_ib;
-                if (upload(C, &d_ib, ib.data(), 8)) return P2_ERR_HIP;
-                if (dalloc(C, &C->d_shift_inv_pows, 8 * n_r)) return P2_ERR_HIP;
-                hipLaunchKernelGGL(k_pow_table, g1(n_r, 256, 8), dim3(256), 0, C->stream, C->d_shift_inv_pows, d_ib, (u32)n_r, gl::inv((u64)n % gl::P));
+                if (upload(C->allocs, &d_ib, ib.data(), 8)) return P2_ERR_HIP;
+                if (dalloc(C->allocs, &C->d_shift_inv_pows, 8 * n_r)) return P2_ERR_HIP;
+                hipLaunchKernelGGL(k_pow_table, g1(n_r, 256, 8), dim3(256), 0, C->setup.stream, C->d_shift_inv_pows, d_ib, (u32)n_r, gl::inv((u64)n % gl::P));
             }
-            if (r < C->arities.size()) {
-                shift = gl::pow(shift, (u64)1 << C->arities[r]);
-                logn_r -= C->arities[r];
+            if (r < D.arities.size()) {
+                shift = gl::pow(shift, (u64)1 << D.arities[r]);
+                logn_r -= D.arities[r];
             }
         }
         HIPCHECK(hipGetLastError());
@@ -554,76 +576,70 @@ static int circuit_setup(p2_circuit* C) {
             xs[p] = nat[i];
             l0[p] = gl::mul(zh[i & 7], di);
         }
-        if (upload(C, &C->d_xs, xs.data(), N)) return P2_ERR_HIP;
-        if (upload(C, &C->d_l0, l0.data(), N)) return P2_ERR_HIP;
-        if (upload(C, &C->d_zh_inv, zh_inv.data(), 8)) return P2_ERR_HIP;
-        if (upload(C, &C->d_w8inv, w8inv.data(), 8)) return P2_ERR_HIP;
-        if (upload(C, &C->d_qscale, qscale.data(), 8)) return P2_ERR_HIP;
+        if (upload(C->allocs, &C->d_xs, xs.data(), N)) return P2_ERR_HIP;
+        if (upload(C->allocs, &C->d_l0, l0.data(), N)) return P2_ERR_HIP;
+        if (upload(C->allocs, &C->d_zh_inv, zh_inv.data(), 8)) return P2_ERR_HIP;
+        if (upload(C->allocs, &C->d_w8inv, w8inv.data(), 8)) return P2_ERR_HIP;
+        if (upload(C->allocs, &C->d_qscale, qscale.data(), 8)) return P2_ERR_HIP;
     }
     // constants | sigmas commitment on the device
     {
-        u64* d_vals;
-        if (dalloc(C, &d_vals, (size_t)np * n)) return P2_ERR_HIP;
-        HIPCHECK(hipMemcpy(d_vals, c.constants.data(), (size_t)ncc * n * 8, hipMemcpyHostToDevice));
-        HIPCHECK(hipMemcpy(d_vals + (size_t)ncc * n, c.sigmas.data(), (size_t)R * n * 8, hipMemcpyHostToDevice));
-        if (dalloc(C, &C->d_pre_coeffs, (size_t)np * n)) return P2_ERR_HIP;
-        if (dalloc(C, &C->d_pre_lde, (size_t)np * N)) return P2_ERR_HIP;
-        C->pre_tree.bits = C->lde_bits;
-        if (dalloc(C, &C->pre_tree.dig, C->pre_tree.stride())) return P2_ERR_HIP;
-        if (intt_cols(C, d_vals, C->d_pre_coeffs, np, 0, 1, C->d_pre_lde, 0)) return P2_ERR_HIP;
-        if (lde_cols(C, C->d_pre_coeffs, 0, C->d_pre_lde, 0, np, 0, 1)) return P2_ERR_HIP;
-        if (merkle_build(C, C->d_pre_lde, np, np, N, 0, C->pre_tree, 1)) return P2_ERR_HIP;
-        HIPCHECK(hipStreamSynchronize(C->stream));
+        Oracle& o = C->pre;
+        o.cols = o.tree_cols = np;
+        o.tree.bits = C->lde_bits;
+        if (dalloc(C->allocs, &o.vals, (size_t)np * n) || dalloc(C->allocs, &o.coef, (size_t)np * n) || dalloc(C->allocs, &o.lde, (size_t)np * N) ||
+            dalloc(C->allocs, &o.tree.dig, o.tree.stride()))
+            return P2_ERR_HIP;
+        HIPCHECK(hipMemcpy(o.vals, c.constants.data(), (size_t)ncc * n * 8, hipMemcpyHostToDevice));
+        HIPCHECK(hipMemcpy(o.vals + (size_t)ncc * n, c.sigmas.data(), (size_t)R * n * 8, hipMemcpyHostToDevice));
+        if (intt_cols(C->setup, D, o.vals, o.coef, np, 0, 1, o.lde, 0)) return P2_ERR_HIP;
+        if (lde_cols(C->setup, D, o.coef, 0, o.lde, 0, np, 0, 1)) return P2_ERR_HIP;
+        if (merkle_build(C->setup, D, o.lde, np, np, N, 0, o.tree, 1)) return P2_ERR_HIP;
+        HIPCHECK(hipStreamSynchronize(C->setup.stream));
         size_t cap_n = (size_t)1 << c.cfg.cap_height;
         std::vector<u64> cap(4 * cap_n);
-        HIPCHECK(hipMemcpy(cap.data(), C->pre_tree.dig + cap_off(C->pre_tree, c.cfg.cap_height), cap.size() * 8, hipMemcpyDeviceToHost));
-        // circuit digest = hash_no_pad(cap || hash_pad([]) || degree_bits)   (a dozen host permutations)
+        HIPCHECK(hipMemcpy(cap.data(), o.tree.dig + cap_off(o.tree, c.cfg.cap_height), cap.size() * 8, hipMemcpyDeviceToHost));
+        // circuit digest = hash_no_pad(cap || hash_pad([]) || degree_bits), both hashes by the tree hasher (upstream C::Hasher)
+        const u64 padded[12] = {1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1};  // hash_pad of the empty domain separator
+        const Hash4 dom_sep = h_hash_or_noop(padded, 12, c.cfg.hasher);
         std::vector<u64> parts(cap);
-        if (c.cfg.hasher == HASHER_KECCAK) {
-            // the same word sequence, both hashes by the tree hasher (upstream C::Hasher)
-            const u64 padded[12] = {1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1};
-            u64 h[4];
-            kc::hash_no_pad(padded, 12, h);
-            parts.insert(parts.end(), h, h + 4);
-            parts.push_back(c.degree_bits);
-            kc::hash_no_pad(parts.data(), (u32)parts.size(), h);
-            C->verifier_data = cap;
-            C->verifier_data.insert(C->verifier_data.end(), h, h + 4);
-            return upload(C, &C->d_digest, h, 4);
-        }
-        {
-            u64 st[12] = {1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1};  // hash_pad of the empty domain separator
-            u64 s2[12] = {0};
-            for (int i = 0; i < 8; i++) s2[i] = st[i];
-            gl::poseidon(s2);
-            for (int i = 0; i < 4; i++) s2[i] = st[8 + i];
-            gl::poseidon(s2);
-            for (int i = 0; i < 4; i++) parts.push_back(s2[i]);
-        }
+        parts.insert(parts.end(), dom_sep.e, dom_sep.e + 4);
         parts.push_back(c.degree_bits);
-        u64 st[12] = {0};
-        for (size_t off = 0; off < parts.size(); off += 8) {
-            for (size_t i = 0; i < std::min<size_t>(8, parts.size() - off); i++) st[i] = parts[off + i];
-            gl::poseidon(st);
-        }
+        const Hash4 digest = h_hash_or_noop(parts.data(), parts.size(), c.cfg.hasher);
         C->verifier_data = cap;
-        for (int i = 0; i < 4; i++) C->verifier_data.push_back(st[i]);
-        if (upload(C, &C->d_digest, st, 4)) return P2_ERR_HIP;
+        C->verifier_data.insert(C->verifier_data.end(), digest.e, digest.e + 4);
+        if (upload(C->allocs, &C->d_digest, digest.e, 4)) return P2_ERR_HIP;
     }
     return 0;
 }
 
-static int setup_polyrefs(p2_circuit* C);
-static void collect_timing(p2_circuit* C);
-// Drains and releases every per-stream workspace; the handle is left with none (chunk == 0), ready to allocate again.
-static void release_workspaces(p2_circuit* C) {
-    for (Workspace* W : C->ws) {
-        if (W->stream) (void)hipStreamSynchronize(W->stream);
-        for (auto& pe : W->pending) {
+// Reads the event pairs of every lane into the timing map (waits for the launches they bracket).
+static void collect_timing(p2_circuit* C) {
+    std::vector<Lane*> lanes{&C->setup};
+    for (Workspace* W : C->ws) lanes.push_back(&W->lane);
+    for (Lane* L : lanes) {
+        for (auto& pe : L->pending) {
+            float ms = 0;
+            (void)hipEventSynchronize(pe.second.second);
+            (void)hipEventElapsedTime(&ms, pe.second.first, pe.second.second);
+            auto& t = C->times[pe.first];
+            t.first += ms;
+            t.second++;
             (void)hipEventDestroy(pe.second.first);
             (void)hipEventDestroy(pe.second.second);
         }
-        if (W->stream) (void)hipStreamDestroy(W->stream);
+        L->pending.clear();
+    }
+}
+// Drains and releases every per-stream workspace; the handle is left with none (chunk == 0), ready to allocate again.
+static void release_workspaces(p2_circuit* C) {
+    for (Workspace* W : C->ws) {
+        if (W->lane.stream) (void)hipStreamSynchronize(W->lane.stream);
+        for (auto& pe : W->lane.pending) {
+            (void)hipEventDestroy(pe.second.first);
+            (void)hipEventDestroy(pe.second.second);
+        }
+        if (W->lane.stream) (void)hipStreamDestroy(W->lane.stream);
         if (W->done) (void)hipEventDestroy(W->done);
         delete W;
     }
@@ -635,8 +651,28 @@ static void release_workspaces(p2_circuit* C) {
     }
     C->chunk = 0;
     C->ws_inputs = 0;
-    C->cur = nullptr;
     C->witness_recorded = false;
+}
+// The reference tables of a workspace: the coefficient column behind every opening (the two FRI batches, in observed order)
+// and the opening set itself.
+static int setup_polyrefs(p2_circuit* C, Workspace& W) {
+    const OpeningSet& os = C->layout.set;
+    const Oracle* oracle[OS_SLOTS] = {&C->pre, &W.wires, &W.zs, &W.zs, &W.quot};
+    std::vector<PolyRef> v;
+    for (OpenGroup k : OPEN_OBSERVED)
+        for (u32 i = os.g[k].lo; i < os.g[k].hi; i++) {
+            const Oracle& o = *oracle[os.g[k].slot];
+            v.push_back({i < o.cols ? o.coef : nullptr, o.coef_stride, i, 0});  // past `cols`: identically zero, never materialised
+        }
+    C->n_b0 = os.n_b0;
+    C->n_b1 = os.n_b1;
+    // the opening set: every materialised column of every oracle at zeta, the Z columns at g zeta as well
+    std::vector<EvalRef> e;
+    for (u32 b = 0; b < OS_SLOTS; b++)
+        for (u32 i = 0; i < oracle[b]->cols; i++) e.push_back({oracle[b]->coef, oracle[b]->coef_stride, i, b == OS_Z_NEXT, os.slot_base[b] + i, 0});
+    C->n_evalrefs = (u32)e.size();
+    if (upload(C->allocs, &W.d_evalrefs, e.data(), e.size())) return P2_ERR_HIP;
+    return upload(C->allocs, &W.d_polyrefs, v.data(), v.size());
 }
 // Test hook (P2AES_TEST_FAIL_ALLOC_AFTER=k in the environment when the handle is loaded): the k-th workspace allocation
 // fails as if the device were out of memory.  Exercises the roll-back below without needing a full HBM.
@@ -654,8 +690,9 @@ static int dalloc_ws(p2_circuit* C, size_t& counter, void** p, size_t bytes) {
 static int build_workspace(p2_circuit* C, Workspace* W, size_t chunk, u32 ws_inputs, size_t& counter) {
     const Circuit& c = C->c;
     const size_t n = C->n, N = C->N;
-    const u32 zc = c.num_zs_cols(), qc = c.num_quotient_cols(), NC = c.cfg.num_challenges, act = C->active_wires;
-    if (hipStreamCreateWithFlags(&W->stream, hipStreamNonBlocking) != hipSuccess) return set_error("hipStreamCreate failed"), P2_ERR_HIP;
+    const u32 NC = c.cfg.num_challenges;
+    W->lane.timing = C->timing_on;
+    if (hipStreamCreateWithFlags(&W->lane.stream, hipStreamNonBlocking) != hipSuccess) return set_error("hipStreamCreate failed"), P2_ERR_HIP;
     if (hipEventCreateWithFlags(&W->done, hipEventDisableTiming) != hipSuccess) return set_error("hipEventCreate failed"), P2_ERR_HIP;
 #define WS_ALLOC(field, count)                                                                       \
     if (dalloc_ws(C, counter, (void**)&(field), (size_t)(count) * sizeof(*(field)))) return P2_ERR_HIP
@@ -666,24 +703,25 @@ static int build_workspace(p2_circuit* C, Workspace* W, size_t chunk, u32 ws_inp
     WS_ALLOC(W->d_status, chunk);
     WS_ALLOC(W->d_advice, chunk * std::max<size_t>(c.poseidon_rows.size(), 1) * 55);
     WS_ALLOC(W->d_pi_hash, chunk * 4);
-    WS_ALLOC(W->d_wires, chunk * act * n);
-    WS_ALLOC(W->d_wcoef, chunk * act * n);
-    WS_ALLOC(W->d_wlde, chunk * (act + c.salt()) * N);
-    WS_ALLOC(W->d_zs, chunk * zc * n);
-    WS_ALLOC(W->d_zcoef, chunk * zc * n);
-    WS_ALLOC(W->d_zlde, chunk * (zc + c.salt()) * N);
+    W->wires.cols = C->active_wires, W->wires.tree_cols = c.cfg.num_wires;
+    W->zs.cols = W->zs.tree_cols = c.num_zs_cols();
+    W->quot.cols = W->quot.tree_cols = c.num_quotient_cols();
+    for (Oracle* o : {&W->wires, &W->zs, &W->quot}) {
+        o->salt = c.salt();
+        o->coef_stride = (size_t)o->cols * n;
+        o->lde_stride = (size_t)(o->cols + o->salt) * N;
+        o->tree.bits = C->lde_bits;
+        if (o != &W->quot) WS_ALLOC(o->vals, chunk * o->coef_stride);  // the quotient is evaluated on the LDE domain: d_qvals
+        WS_ALLOC(o->coef, chunk * o->coef_stride);
+        WS_ALLOC(o->lde, chunk * o->lde_stride);
+        WS_ALLOC(o->tree.dig, chunk * o->tree.stride());
+    }
     WS_ALLOC(W->d_permq, chunk * NC * (c.num_partial_products() + 1) * n);
     WS_ALLOC(W->d_perm_seg, chunk * NC * PERM_MAX_SEGS);
     WS_ALLOC(W->d_fri_seg, chunk * 4 * FRI_MAX_SEGS);
     WS_ALLOC(W->d_lktmp, chunk * NC * (c.num_sldc_polys() + 1) * n);
     WS_ALLOC(W->d_qvals, chunk * NC * N);
     WS_ALLOC(W->d_qres, chunk * NC * N);
-    WS_ALLOC(W->d_qcoef, chunk * qc * n);
-    WS_ALLOC(W->d_qlde, chunk * (qc + c.salt()) * N);
-    for (Tree* t : {&W->wtree, &W->ztree, &W->qtree}) {
-        t->bits = C->lde_bits;
-        WS_ALLOC(t->dig, chunk * t->stride());
-    }
     WS_ALLOC(W->d_chal_state, chunk);
     WS_ALLOC(W->d_chal, chunk * CH_WORDS);
     WS_ALLOC(W->d_pows, chunk * 8 * n);
@@ -691,25 +729,22 @@ static int build_workspace(p2_circuit* C, Workspace* W, size_t chunk, u32 ws_inp
     WS_ALLOC(W->d_obs, chunk * 2 * C->n_obs);
     WS_ALLOC(W->d_comp, chunk * 4 * n);
     WS_ALLOC(W->d_apow, chunk * 2 * APOW_STRIDE);
-    u32 logn_r = C->logn;
-    for (u32 r = 0; r <= C->arities.size(); r++) {
+    u32 logn_r = C->dom.logn;
+    for (u32 r = 0; r <= C->dom.arities.size(); r++) {
         size_t n_r = (size_t)1 << logn_r;
         WS_ALLOC(W->d_fri_coef[r], chunk * 2 * n_r);
-        if (r < C->arities.size()) {
+        if (r < C->dom.arities.size()) {
             WS_ALLOC(W->d_fri_vals[r], chunk * 2 * 8 * n_r);
-            W->fri_tree[r].bits = logn_r + c.cfg.rate_bits - C->arities[r];
+            W->fri_tree[r].bits = logn_r + c.cfg.rate_bits - C->dom.arities[r];
             WS_ALLOC(W->fri_tree[r].dig, chunk * W->fri_tree[r].stride());
-            logn_r -= C->arities[r];
+            logn_r -= C->dom.arities[r];
         }
     }
     WS_ALLOC(W->d_pow_best, chunk);
     WS_ALLOC(W->d_pow_list, chunk + 1);
     WS_ALLOC(W->d_proofs, chunk * C->pbytes);
 #undef WS_ALLOC
-    C->cur = W;
-    int e = setup_polyrefs(C);
-    C->cur = nullptr;
-    return e;
+    return setup_polyrefs(C, *W);
 }
 // Makes sure `nstreams` workspaces of `chunk` proofs and `n_inputs` input targets exist.  All-or-nothing: the new shape
 // (C->chunk, C->ws_inputs, C->ws) is published only after every allocation has succeeded; on failure whatever was
@@ -746,18 +781,30 @@ static int alloc_workspace(p2_circuit* C, size_t chunk, u32 n_inputs, size_t nst
 }
 
 // ---------------------------------------------------------------------------------- the pipeline
-// the target slots are already in the current workspace (d_input_slots); d_values: [batch][n_inputs] device; proofs/status: device.
-static int prove_chunk(p2_circuit* C, u32 B, u32 n_inputs, const u64* d_values, uint8_t* d_proofs, int* d_status_out, u64 proof_base) {
+// Commits one oracle and feeds its cap to the transcript: inverse transform of the values (where the oracle has them: the
+// quotient arrives as coefficients), LDE, salt columns (zk), Merkle tree, challenger stage `stage` (0, 1, 2 = wires, Z, quotient).
+static int commit_oracle(p2_circuit* C, Workspace& W, Oracle& o, u32 stage, u32 aux, u64 proof_base, u32 B) {
+    const size_t N = C->N;
+    const u32 cap_h = C->dom.cap_height;
+    if (o.vals && intt_cols(W.lane, C->dom, o.vals, o.coef, o.cols, o.coef_stride, B, o.lde, o.lde_stride)) return P2_ERR_HIP;
+    if (lde_cols(W.lane, C->dom, o.coef, o.coef_stride, o.lde, o.lde_stride, o.cols, 0, B)) return P2_ERR_HIP;
+    if (o.salt)
+        LAUNCH(W.lane, "fill_salt", k_fill_salt, g1((size_t)o.salt * N / 8, 256, B), dim3(256), 0, o.lde + (size_t)o.cols * N, o.lde_stride, N, C->zk_key, proof_base,
+               (u64)ZK_SALT + 1 + stage);
+    if (merkle_build(W.lane, C->dom, o.lde, o.tree_cols + o.salt, o.cols + o.salt, N, o.lde_stride, o.tree, B)) return P2_ERR_HIP;
+    return challenger(C, W, stage, o.tree.dig + cap_off(o.tree, cap_h), o.tree.stride(), 4u << cap_h, aux, 0, B);
+}
+// the target slots are already in the workspace (d_input_slots); d_values: [batch][n_inputs] device; proofs/status: device.
+static int prove_chunk(p2_circuit* C, Workspace& W, u32 B, u32 n_inputs, const u64* d_values, uint8_t* d_proofs, int* d_status_out, u64 proof_base) {
     const Circuit& c = C->c;
     const size_t n = C->n, N = C->N;
     const u32 R = c.cfg.num_routed_wires, NC = c.cfg.num_challenges, npp = c.num_partial_products(), nlp = c.num_lookup_polys();
-    const u32 zc = c.num_zs_cols(), qc = c.num_quotient_cols(), act = C->active_wires, ncc = c.num_constants_cols(), np = c.num_preprocessed();
+    const u32 qc = c.num_quotient_cols(), act = C->active_wires, ncc = c.num_constants_cols();
     const u32 cap_h = c.cfg.cap_height, cap_words = 4u << cap_h, nsldc = c.num_sldc_polys();
-    const u32 salt = c.salt();
-    const size_t ws = (size_t)act * n, wls = (size_t)(act + salt) * N, zs_s = (size_t)zc * n, zl_s = (size_t)(zc + salt) * N, ql_s = (size_t)(qc + salt) * N;
-    hipStream_t st = C->cur_stream();
+    const size_t ws = W.wires.coef_stride, wls = W.wires.lde_stride, zs_s = W.zs.coef_stride, zl_s = W.zs.lde_stride;
+    hipStream_t st = W.lane.stream;
     // 1. witness
-    HIPCHECK(hipMemsetAsync(C->cur->d_mult, 0, (size_t)B * std::max<size_t>(C->total_lut_entries, 1) * 4, st));
+    HIPCHECK(hipMemsetAsync(W.d_mult, 0, (size_t)B * std::max<size_t>(C->total_lut_entries, 1) * 4, st));
     {
         WitnessArgs a{};
         a.ops = C->d_ops;
@@ -766,15 +813,15 @@ static int prove_chunk(p2_circuit* C, u32 B, u32 n_inputs, const u64* d_values, 
         a.num_levels = C->witness_levels;
         a.num_slots = c.num_slots;
         a.n_inputs = n_inputs;
-        a.input_slots = C->cur->d_input_slots;
+        a.input_slots = W.d_input_slots;
         a.input_values = d_values;
-        a.values = C->cur->d_values;
+        a.values = W.d_values;
         a.lut_ent = C->d_lut_ent;
-        a.mult = C->cur->d_mult;
+        a.mult = W.d_mult;
         a.total_lut_entries = C->total_lut_entries;
-        a.status = C->cur->d_status;
+        a.status = W.d_status;
         a.wire_slot = C->d_wire_slot;
-        a.advice = C->cur->d_advice;
+        a.advice = W.d_advice;
         a.n = (u32)n;
         a.num_poseidon_rows = (u32)c.poseidon_rows.size();
         // 512 threads (8 waves, <= 128 VGPRs each) leave room on the compute unit: a 1024-thread workgroup needs a
@@ -784,33 +831,33 @@ static int prove_chunk(p2_circuit* C, u32 B, u32 n_inputs, const u64* d_values, 
         // this the two proving streams stay in lockstep -- both in witness generation with the chip idle, then both in
         // the wide kernels -- and a deep circuit's witness time is never hidden.  Chained, chunk k+1's witness runs
         // under chunk k's commitments.
-        if (C->witness_recorded) HIPCHECK(hipStreamWaitEvent(C->cur->stream, C->ev_witness, 0));
+        if (C->witness_recorded) HIPCHECK(hipStreamWaitEvent(W.lane.stream, C->ev_witness, 0));
         if (c.poseidon_rows.empty()) {
             if (C->witness_chains)
-                LAUNCH(C, "witness", (k_witness<false, true>), dim3(B), dim3(WITNESS_THREADS), 0, a);
+                LAUNCH(W.lane, "witness", (k_witness<false, true>), dim3(B), dim3(WITNESS_THREADS), 0, a);
             else
-                LAUNCH(C, "witness", (k_witness<false, false>), dim3(B), dim3(WITNESS_THREADS), 0, a);
+                LAUNCH(W.lane, "witness", (k_witness<false, false>), dim3(B), dim3(WITNESS_THREADS), 0, a);
         } else {
             if (C->witness_chains)
-                LAUNCH(C, "witness", (k_witness<true, true>), dim3(B), dim3(WITNESS_THREADS), 0, a);
+                LAUNCH(W.lane, "witness", (k_witness<true, true>), dim3(B), dim3(WITNESS_THREADS), 0, a);
             else
-                LAUNCH(C, "witness", (k_witness<true, false>), dim3(B), dim3(WITNESS_THREADS), 0, a);
+                LAUNCH(W.lane, "witness", (k_witness<true, false>), dim3(B), dim3(WITNESS_THREADS), 0, a);
         }
-        HIPCHECK(hipEventRecord(C->ev_witness, C->cur->stream));
+        HIPCHECK(hipEventRecord(C->ev_witness, W.lane.stream));
         C->witness_recorded = true;
     }
     if (!c.pi_slots.empty())
-        LAUNCH(C, "pi_hash", k_pi_hash, g1((size_t)B * 16, 64), dim3(64), 0, C->cur->d_values, c.num_slots, C->d_pi_slots, (u32)c.pi_slots.size(), B,
-               C->cur->d_pi_hash, d_proofs, C->pbytes, C->layout.body_bytes);  // a 16-lane group per proof
-    LAUNCH(C, "fill_wires", k_fill_wires, g1((size_t)R * n, 256, B), dim3(256), 0, C->d_wire_slot, C->cur->d_values, C->cur->d_wires, (size_t)R * n, c.num_slots, ws,
-           C->cur->d_status);
+        LAUNCH(W.lane, "pi_hash", k_pi_hash, g1((size_t)B * 16, 64), dim3(64), 0, W.d_values, c.num_slots, C->d_pi_slots, (u32)c.pi_slots.size(), B,
+               W.d_pi_hash, d_proofs, C->pbytes, C->layout.body_bytes);  // a 16-lane group per proof
+    LAUNCH(W.lane, "fill_wires", k_fill_wires, g1((size_t)R * n, 256, B), dim3(256), 0, C->d_wire_slot, W.d_values, W.wires.vals, (size_t)R * n, c.num_slots, ws,
+           W.d_status);
     if (act > R)
-        LAUNCH(C, "fill_advice", k_fill_advice, g1((size_t)55 * n, 256, B), dim3(256), 0, C->d_pos_index, C->cur->d_advice, C->cur->d_wires, (u32)n,
+        LAUNCH(W.lane, "fill_advice", k_fill_advice, g1((size_t)55 * n, 256, B), dim3(256), 0, C->d_pos_index, W.d_advice, W.wires.vals, (u32)n,
                (u32)c.poseidon_rows.size(), ws);
     if (c.cfg.zero_knowledge) {
         size_t cnt = (c.blind_rows.size() * 135 + 7) / 8 + (c.blind_zrows.size() * 80 + 7) / 8;  // PRF blocks of eight elements
-        LAUNCH(C, "fill_blind", k_fill_blind, g1(std::max<size_t>(cnt, 1), 256, B), dim3(256), 0, C->d_blind_rows, (u32)c.blind_rows.size(), C->d_blind_zrows,
-               (u32)c.blind_zrows.size(), C->cur->d_wires, ws, (u32)n, C->zk_key, proof_base);
+        LAUNCH(W.lane, "fill_blind", k_fill_blind, g1(std::max<size_t>(cnt, 1), 256, B), dim3(256), 0, C->d_blind_rows, (u32)c.blind_rows.size(), C->d_blind_zrows,
+               (u32)c.blind_zrows.size(), W.wires.vals, ws, (u32)n, C->zk_key, proof_base);
     }
     if (!c.luts.empty()) {
         LutRowsArgs a{};
@@ -818,42 +865,37 @@ static int prove_chunk(p2_circuit* C, u32 B, u32 n_inputs, const u64* d_values, 
         a.lut_offsets = C->d_lut_offsets;
         a.rows = C->d_lookup_rows;
         a.num_lookups = C->d_num_lookups;
-        a.mult = C->cur->d_mult;
+        a.mult = W.d_mult;
         a.total_lut_entries = C->total_lut_entries;
-        a.wires = C->cur->d_wires;
+        a.wires = W.wires.vals;
         a.wires_batch_stride = ws;
         a.n = (u32)n;
         a.num_luts = (u32)c.luts.size();
-        LAUNCH(C, "lut_rows", k_lut_rows, g1(std::max<size_t>(C->total_lut_entries, 256), 256, B), dim3(256), 0, a);
+        LAUNCH(W.lane, "lut_rows", k_lut_rows, g1(std::max<size_t>(C->total_lut_entries, 256), 256, B), dim3(256), 0, a);
     }
-    // 2. wires commitment
-    if (intt_cols(C, C->cur->d_wires, C->cur->d_wcoef, act, ws, B, C->cur->d_wlde, wls)) return P2_ERR_HIP;
-    if (lde_cols(C, C->cur->d_wcoef, ws, C->cur->d_wlde, wls, act, 0, B)) return P2_ERR_HIP;
-    if (salt) LAUNCH(C, "fill_salt", k_fill_salt, g1((size_t)salt * N / 8, 256, B), dim3(256), 0, C->cur->d_wlde + (size_t)act * N, wls, N, C->zk_key, proof_base, (u64)ZK_SALT + 1);
-    if (merkle_build(C, C->cur->d_wlde, c.cfg.num_wires + salt, act + salt, N, wls, C->cur->wtree, B)) return P2_ERR_HIP;
-    // 3. betas, gammas, deltas
-    if (challenger(C, 0, C->cur->wtree.dig + cap_off(C->cur->wtree, cap_h), C->cur->wtree.stride(), cap_words, nlp ? 1 : 0, 0, B)) return P2_ERR_HIP;
+    // 2. wires commitment; 3. betas, gammas, deltas
+    if (commit_oracle(C, W, W.wires, 0, nlp ? 1 : 0, proof_base, B)) return P2_ERR_HIP;
     // 4. partial products and Z
-    HIPCHECK(hipMemsetAsync(C->cur->d_zs, 0, (size_t)B * zs_s * 8, st));
-    LAUNCH(C, "perm_chunks", k_perm_chunks, g1(n, 256, B), dim3(256), 0, C->cur->d_wires, ws, C->d_sigmas, C->d_k_is, C->d_subgroup, C->cur->d_chal,
-           C->cur->d_permq, (size_t)NC * (npp + 1) * n, (u32)n, R, c.cfg.quotient_degree_factor, npp + 1, NC);
+    HIPCHECK(hipMemsetAsync(W.zs.vals, 0, (size_t)B * zs_s * 8, st));
+    LAUNCH(W.lane, "perm_chunks", k_perm_chunks, g1(n, 256, B), dim3(256), 0, W.wires.vals, ws, C->d_sigmas, C->d_k_is, C->d_subgroup, W.d_chal,
+           W.d_permq, (size_t)NC * (npp + 1) * n, (u32)n, R, c.cfg.quotient_degree_factor, npp + 1, NC);
     {
         // columns longer than 2^14 rows in segments of 2^14 (at most PERM_MAX_SEGS), a workgroup per segment
         const u32 segs = (u32)std::min<size_t>(std::max<size_t>(n >> 14, 1), PERM_MAX_SEGS);
         if (segs > 1)
-            LAUNCH(C, "perm_scan", k_perm_seg_products, dim3(NC, B, segs), dim3(1024), 0, C->cur->d_permq, (size_t)NC * (npp + 1) * n, C->cur->d_perm_seg, (u32)n, npp + 1);
-        LAUNCH(C, "perm_scan", k_perm_scan, dim3(NC, B, segs), dim3(1024), 0, C->cur->d_permq, (size_t)NC * (npp + 1) * n, C->cur->d_zs, zs_s, (u32)n, npp + 1, NC,
-               segs > 1 ? C->cur->d_perm_seg : nullptr);
+            LAUNCH(W.lane, "perm_scan", k_perm_seg_products, dim3(NC, B, segs), dim3(1024), 0, W.d_permq, (size_t)NC * (npp + 1) * n, W.d_perm_seg, (u32)n, npp + 1);
+        LAUNCH(W.lane, "perm_scan", k_perm_scan, dim3(NC, B, segs), dim3(1024), 0, W.d_permq, (size_t)NC * (npp + 1) * n, W.zs.vals, zs_s, (u32)n, npp + 1, NC,
+               segs > 1 ? W.d_perm_seg : nullptr);
     }
     // 5. lookup polynomials
     if (nlp) {
         LookupArgs a{};
-        a.wires = C->cur->d_wires;
+        a.wires = W.wires.vals;
         a.wires_batch_stride = ws;
-        a.chal = C->cur->d_chal;
-        a.zs = C->cur->d_zs;
+        a.chal = W.d_chal;
+        a.zs = W.zs.vals;
         a.zs_batch_stride = zs_s;
-        a.tmp = C->cur->d_lktmp;
+        a.tmp = W.d_lktmp;
         a.tmp_batch_stride = (size_t)NC * (nsldc + 1) * n;
         a.rows = C->d_lookup_rows;
         a.n = (u32)n;
@@ -863,32 +905,28 @@ static int prove_chunk(p2_circuit* C, u32 B, u32 n_inputs, const u64* d_values, 
         a.lu_deg = c.cfg.quotient_degree_factor - 1;
         a.num_challenges = NC;
         a.zs_lookup_col0 = c.num_zs_pp();
-        LAUNCH(C, "lookup_terms", k_lookup_terms, g1(n, 256, B, NC * (nsldc + 1)), dim3(256), 0, a);
-        LAUNCH(C, "lookup_scan", k_lookup_scan, dim3((u32)c.luts.size(), B, NC), dim3(1024), 0, a);
+        LAUNCH(W.lane, "lookup_terms", k_lookup_terms, g1(n, 256, B, NC * (nsldc + 1)), dim3(256), 0, a);
+        LAUNCH(W.lane, "lookup_scan", k_lookup_scan, dim3((u32)c.luts.size(), B, NC), dim3(1024), 0, a);
     }
     // 6. zs commitment, alphas
-    if (intt_cols(C, C->cur->d_zs, C->cur->d_zcoef, zc, zs_s, B, C->cur->d_zlde, zl_s)) return P2_ERR_HIP;
-    if (lde_cols(C, C->cur->d_zcoef, zs_s, C->cur->d_zlde, zl_s, zc, 0, B)) return P2_ERR_HIP;
-    if (salt) LAUNCH(C, "fill_salt", k_fill_salt, g1((size_t)salt * N / 8, 256, B), dim3(256), 0, C->cur->d_zlde + (size_t)zc * N, zl_s, N, C->zk_key, proof_base, (u64)ZK_SALT + 2);
-    if (merkle_build(C, C->cur->d_zlde, zc + salt, zc + salt, N, zl_s, C->cur->ztree, B)) return P2_ERR_HIP;
-    if (challenger(C, 1, C->cur->ztree.dig + cap_off(C->cur->ztree, cap_h), C->cur->ztree.stride(), cap_words, 0, 0, B)) return P2_ERR_HIP;
+    if (commit_oracle(C, W, W.zs, 1, 0, proof_base, B)) return P2_ERR_HIP;
     // 7. quotient
     {
         QuotientArgs a{};
-        a.pre_lde = C->d_pre_lde;
-        a.wires_lde = C->cur->d_wlde;
-        a.zs_lde = C->cur->d_zlde;
+        a.pre_lde = C->pre.lde;
+        a.wires_lde = W.wires.lde;
+        a.zs_lde = W.zs.lde;
         a.wires_batch_stride = wls;
         a.zs_batch_stride = zl_s;
-        a.chal = C->cur->d_chal;
+        a.chal = W.d_chal;
         a.xs = C->d_xs;
         a.l0 = C->d_l0;
         a.zh_inv = C->d_zh_inv;
         a.k_is = C->d_k_is;
-        a.out = C->cur->d_qvals;
+        a.out = W.d_qvals;
         a.out_batch_stride = (size_t)NC * N;
         a.n = (u32)n;
-        a.logn = C->logn;
+        a.logn = C->dom.logn;
         a.rate_bits = c.cfg.rate_bits;
         a.R = R;
         a.ncc = ncc;
@@ -905,138 +943,133 @@ static int prove_chunk(p2_circuit* C, u32 B, u32 n_inputs, const u64* d_values, 
         a.num_gate_constraints = c.num_gate_constraints;
         fill_gate_table(c, a);
         for (u32 l = 0; l < c.luts.size(); l++) a.lut_last_row[l] = c.lookup_rows[l].last_lut;
-        a.zs_values = C->cur->d_zs;
+        a.zs_values = W.zs.vals;
         a.zs_values_batch_stride = zs_s;
-        a.pi_hash = c.pi_slots.empty() ? nullptr : C->cur->d_pi_hash;
-        a.apow = C->cur->d_apow;
+        a.pi_hash = c.pi_slots.empty() ? nullptr : W.d_pi_hash;
+        a.apow = W.d_apow;
         {
             u32 nlk = nlp ? 4 + (u32)c.luts.size() + 2 * nsldc : 0;
             u32 nterms = NC + NC * (npp + 1) + NC * nlk + c.num_gate_constraints;
             if (nterms > APOW_STRIDE) return set_error("internal: too many vanishing terms for the alpha-power table"), P2_ERR_INVALID;
-            LAUNCH(C, "alpha_pows", k_alpha_pows, g1(2 * B, 64), dim3(64), 0, C->cur->d_chal, C->cur->d_apow, B, nterms);
+            LAUNCH(W.lane, "alpha_pows", k_alpha_pows, g1(2 * B, 64), dim3(64), 0, W.d_chal, W.d_apow, B, nterms);
         }
         if (c.poseidon_rows.empty())
-            LAUNCH(C, "quotient", (k_quotient<false, true>), g1(N, 256, B), dim3(256), 0, a);  // the wire columns read once
+            LAUNCH(W.lane, "quotient", (k_quotient<false, true>), g1(N, 256, B), dim3(256), 0, a);  // the wire columns read once
         else
-            LAUNCH(C, "quotient", k_quotient<true>, g1(N, 256, B), dim3(256), 0, a);
+            LAUNCH(W.lane, "quotient", k_quotient<true>, g1(N, 256, B), dim3(256), 0, a);
         // coset-wise inverse transform: residues r_j, then the 8-point cross-coset DFT
-        if (C->logn > LDS_NTT_MAX_BITS) {
+        if (C->dom.logn > LDS_NTT_MAX_BITS) {
             const size_t qs = (size_t)NC * N;
             u32 ident[8] = {0, 1, 2, 3, 4, 5, 6, 7};
-            LAUNCH(C, "bitrev_copy", k_bitrev_copy, g1(n, 256, B, NC * 8), dim3(256), 0, C->cur->d_qvals, N, qs, C->cur->d_qres, N, qs, (int)C->logn, 8u,
+            LAUNCH(W.lane, "bitrev_copy", k_bitrev_copy, g1(n, 256, B, NC * 8), dim3(256), 0, W.d_qvals, N, qs, W.d_qres, N, qs, (int)C->dom.logn, 8u,
                    (const u64*)nullptr, 0u);
-            if (ntt_big(C, "quotient_intt", C->cur->d_qres, C->cur->d_qvals, C->d_tw_inv_full, nullptr, C->logn, NC, 8, ident, 1, N, N, qs, qs, 1, B)) return P2_ERR_HIP;
-            LAUNCH(C, "bitrev_copy", k_bitrev_copy, g1(n, 256, B, NC * 8), dim3(256), 0, C->cur->d_qvals, N, qs, C->cur->d_qres, N, qs, (int)C->logn, 8u,
+            if (ntt_big(W.lane, C->dom, "quotient_intt", W.d_qres, W.d_qvals, C->dom.d_tw_inv_full, nullptr, C->dom.logn, NC, 8, ident, 1, N, N, qs, qs, 1, B)) return P2_ERR_HIP;
+            LAUNCH(W.lane, "bitrev_copy", k_bitrev_copy, g1(n, 256, B, NC * 8), dim3(256), 0, W.d_qvals, N, qs, W.d_qres, N, qs, (int)C->dom.logn, 8u,
                    (const u64*)C->d_shift_inv_pows, 1u);
         } else {
         NttArgs t{};
-        t.in = C->cur->d_qvals;
-        t.out = C->cur->d_qres;
-        t.tw = C->d_tw_inv;
+        t.in = W.d_qvals;
+        t.out = W.d_qres;
+        t.tw = C->dom.d_tw_inv;
         t.post = C->d_shift_inv_pows;
         t.post_scalar = 1;
         t.in_col_stride = t.out_col_stride = N;
         t.in_batch_stride = t.out_batch_stride = (size_t)NC * N;
-        t.logn = (int)C->logn;
+        t.logn = (int)C->dom.logn;
         t.cosets = 8;
         t.bitrev_in = 1;
         t.bitrev_out = 1;
         t.in_coset_blocks = 1;
         // input block rev3(j) holds coset j; residue r_j is written to the same block
         for (u32 j = 0; j < 8; j++) t.block_of_coset[j] = gl::bitrev(j, 3);
-        if (run_ntt(C, "quotient_intt", t, NC, B)) return P2_ERR_HIP;
+        if (run_ntt(W.lane, C->dom, "quotient_intt", t, NC, B)) return P2_ERR_HIP;
         }
-        LAUNCH(C, "quotient_chunks", k_quotient_chunks_rev, g1(n, 256, B, NC), dim3(256), 0, C->cur->d_qres, C->cur->d_qcoef, (u32)n, (size_t)NC * N, (size_t)qc * n,
+        LAUNCH(W.lane, "quotient_chunks", k_quotient_chunks_rev, g1(n, 256, B, NC), dim3(256), 0, W.d_qres, W.quot.coef, (u32)n, (size_t)NC * N, (size_t)qc * n,
                C->d_w8inv, C->d_qscale);
     }
-    if (lde_cols(C, C->cur->d_qcoef, (size_t)qc * n, C->cur->d_qlde, ql_s, qc, 0, B)) return P2_ERR_HIP;
-    if (salt) LAUNCH(C, "fill_salt", k_fill_salt, g1((size_t)salt * N / 8, 256, B), dim3(256), 0, C->cur->d_qlde + (size_t)qc * N, ql_s, N, C->zk_key, proof_base, (u64)ZK_SALT + 3);
-    if (merkle_build(C, C->cur->d_qlde, qc + salt, qc + salt, N, ql_s, C->cur->qtree, B)) return P2_ERR_HIP;
-    if (challenger(C, 2, C->cur->qtree.dig + cap_off(C->cur->qtree, cap_h), C->cur->qtree.stride(), cap_words, c.degree_bits, 0, B)) return P2_ERR_HIP;
+    if (commit_oracle(C, W, W.quot, 2, c.degree_bits, proof_base, B)) return P2_ERR_HIP;
     // 8. openings
-    LAUNCH(C, "zeta_pows", k_zeta_pows, g1(n, 256, B, 4), dim3(256), 0, C->cur->d_chal, C->cur->d_pows, (size_t)8 * n, (u32)n, gl::root_of_unity((int)C->logn));
-    HIPCHECK(hipMemsetAsync(C->cur->d_ev, 0, (size_t)B * 2 * C->ev_count * 8, st));
+    LAUNCH(W.lane, "zeta_pows", k_zeta_pows, g1(n, 256, B, 4), dim3(256), 0, W.d_chal, W.d_pows, (size_t)8 * n, (u32)n, gl::root_of_unity((int)C->dom.logn));
+    HIPCHECK(hipMemsetAsync(W.d_ev, 0, (size_t)B * 2 * C->ev_count * 8, st));
     {
         const size_t evs = 2 * (size_t)C->ev_count;
-        u64* ev = C->cur->d_ev;
-        LAUNCH(C, "eval_polys", k_eval_polys_refs, dim3(C->n_evalrefs, B), dim3(256), 0, C->cur->d_evalrefs, C->cur->d_pows, (size_t)8 * n, (u32)n, ev, evs);
-        LAUNCH(C, "gather_ext", k_gather_ext, g1(C->n_obs, 256, B), dim3(256), 0, C->cur->d_ev, evs, C->d_map_obs, C->n_obs, C->cur->d_obs, (size_t)2 * C->n_obs);
+        u64* ev = W.d_ev;
+        LAUNCH(W.lane, "eval_polys", k_eval_polys_refs, dim3(C->n_evalrefs, B), dim3(256), 0, W.d_evalrefs, W.d_pows, (size_t)8 * n, (u32)n, ev, evs);
+        LAUNCH(W.lane, "gather_ext", k_gather_ext, g1(C->n_obs, 256, B), dim3(256), 0, W.d_ev, evs, C->d_map_obs, C->n_obs, W.d_obs, (size_t)2 * C->n_obs);
     }
-    if (challenger(C, 3, C->cur->d_obs, (size_t)2 * C->n_obs, 2 * C->n_obs, 0, 0, B)) return P2_ERR_HIP;
+    if (challenger(C, W, 3, W.d_obs, (size_t)2 * C->n_obs, 2 * C->n_obs, 0, 0, B)) return P2_ERR_HIP;
     // 9. FRI: compose, divide, commit phase
-    LAUNCH(C, "fri_compose", k_fri_compose, g1(n, 256, B), dim3(256), 0, C->cur->d_polyrefs, C->n_b0, C->n_b1, C->cur->d_chal, (u32)n, C->cur->d_comp, (size_t)4 * n);
+    LAUNCH(W.lane, "fri_compose", k_fri_compose, g1(n, 256, B), dim3(256), 0, W.d_polyrefs, C->n_b0, C->n_b1, W.d_chal, (u32)n, W.d_comp, (size_t)4 * n);
     {
         const u32 segs = (u32)std::min<size_t>(std::max<size_t>(n >> 14, 1), FRI_MAX_SEGS);  // as in the permutation scan
         if (segs > 1)
-            LAUNCH(C, "fri_divide", k_fri_seg_sums, dim3(B, segs), dim3(1024), 0, C->cur->d_comp, (size_t)4 * n, C->cur->d_pows, (size_t)8 * n, (u32)n, C->cur->d_fri_seg);
-        LAUNCH(C, "fri_divide", k_fri_divide, dim3(B, segs), dim3(1024), 0, C->cur->d_comp, (size_t)4 * n, C->cur->d_pows, (size_t)8 * n, C->cur->d_chal, (u32)n, C->n_b1,
-               C->cur->d_fri_coef[0], (size_t)2 * n, segs > 1 ? C->cur->d_fri_seg : nullptr);
+            LAUNCH(W.lane, "fri_divide", k_fri_seg_sums, dim3(B, segs), dim3(1024), 0, W.d_comp, (size_t)4 * n, W.d_pows, (size_t)8 * n, (u32)n, W.d_fri_seg);
+        LAUNCH(W.lane, "fri_divide", k_fri_divide, dim3(B, segs), dim3(1024), 0, W.d_comp, (size_t)4 * n, W.d_pows, (size_t)8 * n, W.d_chal, (u32)n, C->n_b1,
+               W.d_fri_coef[0], (size_t)2 * n, segs > 1 ? W.d_fri_seg : nullptr);
     }
     {
-        u32 logn_r = C->logn;
-        for (u32 r = 0; r < C->arities.size(); r++) {
+        u32 logn_r = C->dom.logn;
+        for (u32 r = 0; r < C->dom.arities.size(); r++) {
             size_t n_r = (size_t)1 << logn_r, len = 8 * n_r;
-            u32 arity = 1u << C->arities[r];
-            if (lde_cols(C, C->cur->d_fri_coef[r], 2 * n_r, C->cur->d_fri_vals[r], 2 * len, 2, r, B)) return P2_ERR_HIP;
-            Tree& t = C->cur->fri_tree[r];
+            u32 arity = 1u << C->dom.arities[r];
+            if (lde_cols(W.lane, C->dom, W.d_fri_coef[r], 2 * n_r, W.d_fri_vals[r], 2 * len, 2, r, B)) return P2_ERR_HIP;
+            Tree& t = W.fri_tree[r];
             size_t leaves = len / arity;
-            if (c.cfg.hasher == HASHER_KECCAK)
-                LAUNCH(C, "hash_fri_leaves", k_kc_fri_leaves, g1(leaves, 256, B), dim3(256), 0, C->cur->d_fri_vals[r], len, 2 * len, (int)arity, t.dig, t.stride());
-            else
-                LAUNCH(C, "hash_fri_leaves", k_hash_fri_leaves, g1(leaves, 256, B), dim3(256), 0, C->cur->d_fri_vals[r], len, 2 * len, (int)arity, t.dig, t.stride());
-            if (merkle_levels(C, t, B)) return P2_ERR_HIP;
-            if (challenger(C, 4, t.dig + cap_off(t, cap_h), t.stride(), cap_words, r, 0, B)) return P2_ERR_HIP;
-            size_t n_next = n_r >> C->arities[r];
-            LAUNCH(C, "fri_fold", k_fri_fold, g1(n_next, 256, B), dim3(256), 0, C->cur->d_fri_coef[r], n_r, 2 * n_r, C->cur->d_fri_coef[r + 1], n_next, 2 * n_next, C->cur->d_chal, r,
+            LAUNCH(W.lane, "hash_fri_leaves", tree_kernels(C->dom.hasher).fri_leaves, g1(leaves, 256, B), dim3(256), 0, W.d_fri_vals[r], len, 2 * len, (int)arity, t.dig,
+                   t.stride());
+            if (merkle_levels(W.lane, C->dom, t, B)) return P2_ERR_HIP;
+            if (challenger(C, W, 4, t.dig + cap_off(t, cap_h), t.stride(), cap_words, r, 0, B)) return P2_ERR_HIP;
+            size_t n_next = n_r >> C->dom.arities[r];
+            LAUNCH(W.lane, "fri_fold", k_fri_fold, g1(n_next, 256, B), dim3(256), 0, W.d_fri_coef[r], n_r, 2 * n_r, W.d_fri_coef[r + 1], n_next, 2 * n_next, W.d_chal, r,
                    arity);
-            logn_r -= C->arities[r];
+            logn_r -= C->dom.arities[r];
         }
         // final polynomial (interleave components for observation)
         size_t fl = (size_t)1 << logn_r;
-        u32 R_ = (u32)C->arities.size();
-        LAUNCH(C, "interleave", k_interleave_ext, g1(fl, 256, B), dim3(256), 0, C->cur->d_fri_coef[R_], fl, 2 * fl, C->cur->d_obs, (size_t)2 * C->n_obs);
-        if (challenger(C, 5, C->cur->d_obs, (size_t)2 * C->n_obs, (u32)(2 * fl), 0, 0, B)) return P2_ERR_HIP;
+        u32 R_ = (u32)C->dom.arities.size();
+        LAUNCH(W.lane, "interleave", k_interleave_ext, g1(fl, 256, B), dim3(256), 0, W.d_fri_coef[R_], fl, 2 * fl, W.d_obs, (size_t)2 * C->n_obs);
+        if (challenger(C, W, 5, W.d_obs, (size_t)2 * C->n_obs, (u32)(2 * fl), 0, 0, B)) return P2_ERR_HIP;
         // proof of work
-        HIPCHECK(hipMemsetAsync(C->cur->d_pow_best, 0xFF, (size_t)B * 8, st));
+        HIPCHECK(hipMemsetAsync(W.d_pow_best, 0xFF, (size_t)B * 8, st));
         {
             u32 block0 = 0;
             for (int ph = 0; ph < 3; ph++) {
-                u32* list = ph ? C->cur->d_pow_list : nullptr;
-                if (ph) LAUNCH(C, "pow", k_pow_compact, dim3(1), dim3(256), 0, C->cur->d_pow_best, B, C->cur->d_pow_list, C->cur->d_pow_list + C->chunk);
+                u32* list = ph ? W.d_pow_list : nullptr;
+                if (ph) LAUNCH(W.lane, "pow", k_pow_compact, dim3(1), dim3(256), 0, W.d_pow_best, B, W.d_pow_list, W.d_pow_list + C->chunk);
                 const u32 slots = ph ? std::min<u32>(B, POW_PHASE_SLOTS[ph]) : B;
-                LAUNCH(C, "pow", k_pow, dim3(slots, POW_PHASE_BLOCKS[ph]), dim3(256), 0, C->cur->d_chal_state, C->cur->d_chal, (int)c.cfg.pow_bits, C->cur->d_pow_best,
+                LAUNCH(W.lane, "pow", k_pow, dim3(slots, POW_PHASE_BLOCKS[ph]), dim3(256), 0, W.d_chal_state, W.d_chal, (int)c.cfg.pow_bits, W.d_pow_best,
                        block0, (const u32*)list, (const u32*)(list ? list + C->chunk : nullptr));
                 block0 += POW_PHASE_BLOCKS[ph];
             }
         }
-        LAUNCH(C, "pow_finish", k_pow_finish, g1(B, 64), dim3(64), 0, C->cur->d_chal, C->cur->d_pow_best, B, C->cur->d_status);
-        if (challenger(C, 6, C->cur->d_obs, 0, 0, c.cfg.num_query_rounds, (u64)N, B)) return P2_ERR_HIP;
+        LAUNCH(W.lane, "pow_finish", k_pow_finish, g1(B, 64), dim3(64), 0, W.d_chal, W.d_pow_best, B, W.d_status);
+        if (challenger(C, W, 6, W.d_obs, 0, 0, c.cfg.num_query_rounds, (u64)N, B)) return P2_ERR_HIP;
         // 10. proof assembly
         const ProofLayout& L = C->layout;
         ProofSegs segs{};
         u32 nseg = 0;
         segs.proofs = d_proofs;
         segs.proof_bytes = L.bytes;
-        const Tree* caps[3] = {&C->cur->wtree, &C->cur->ztree, &C->cur->qtree};
-        for (int i = 0; i < 3; i++) segs.s[nseg++] = ProofSeg{caps[i]->dig + cap_off(*caps[i], cap_h), nullptr, caps[i]->stride(), 0, L.caps_off[i], cap_words, 0};
-        segs.s[nseg++] = ProofSeg{C->cur->d_ev, C->d_map_ser, 2 * (size_t)C->ev_count, 0, L.open[0].off, C->n_ser, 2};
+        const Oracle* oracles[4] = {&C->pre, &W.wires, &W.zs, &W.quot};
+        for (int o = 1; o < 4; o++) {
+            const Tree& t = oracles[o]->tree;
+            segs.s[nseg++] = ProofSeg{t.dig + cap_off(t, cap_h), nullptr, t.stride(), 0, L.caps_off[o - 1], cap_words, 0};
+        }
+        segs.s[nseg++] = ProofSeg{W.d_ev, C->d_map_ser, 2 * (size_t)C->ev_count, 0, L.open[0].off, C->n_ser, 2};
         if (R_ + 6 > 12) return set_error("internal: more FRI rounds than proof segments"), P2_ERR_INVALID;
         for (u32 r = 0; r < R_; r++) {
-            Tree& t = C->cur->fri_tree[r];
+            Tree& t = W.fri_tree[r];
             segs.s[nseg++] = ProofSeg{t.dig + cap_off(t, cap_h), nullptr, t.stride(), 0, L.fri_caps_off + r * L.cap_bytes, cap_words, 0};
         }
         QueryArgs q{};
-        const u64* ldes[4] = {C->d_pre_lde, C->cur->d_wlde, C->cur->d_zlde, C->cur->d_qlde};
-        const size_t lstr[4] = {0, wls, zl_s, ql_s};
-        const Tree* trees[4] = {&C->pre_tree, &C->cur->wtree, &C->cur->ztree, &C->cur->qtree};
-        const u32 actv[4] = {np, act + salt, zc + salt, qc + salt};
         for (int o = 0; o < 4; o++) {
-            q.oracles[o].lde = ldes[o];
-            q.oracles[o].lde_batch_stride = lstr[o];
-            q.oracles[o].digests = trees[o]->dig;
-            q.oracles[o].dig_batch_stride = o == 0 ? 0 : trees[o]->stride();
-            q.oracles[o].cols = L.init[o].width;  // blinded leaves end with the salt
-            q.oracles[o].active_cols = actv[o];
+            const Oracle& from = *oracles[o];
+            q.oracles[o].lde = from.lde;
+            q.oracles[o].lde_batch_stride = from.lde_stride;
+            q.oracles[o].digests = from.tree.dig;
+            q.oracles[o].dig_batch_stride = from.dig_stride();
+            q.oracles[o].cols = from.tree_cols + from.salt;  // blinded leaves end with the salt
+            q.oracles[o].active_cols = from.cols + from.salt;
         }
         q.lde_bits = C->lde_bits;
         q.cap_height = cap_h;
@@ -1044,45 +1077,26 @@ static int prove_chunk(p2_circuit* C, u32 B, u32 n_inputs, const u64* d_values, 
         q.num_rounds = R_;
         u32 lb = C->lde_bits;
         for (u32 r = 0; r < R_; r++) {
-            q.arity_bits[r] = C->arities[r];
-            q.fri_vals[r] = C->cur->d_fri_vals[r];
+            q.arity_bits[r] = C->dom.arities[r];
+            q.fri_vals[r] = W.d_fri_vals[r];
             q.fri_vals_batch_stride[r] = (size_t)2 << lb;
             q.fri_bits[r] = lb;
-            q.fri_digests[r] = C->cur->fri_tree[r].dig;
-            q.fri_dig_batch_stride[r] = C->cur->fri_tree[r].stride();
-            lb -= C->arities[r];
+            q.fri_digests[r] = W.fri_tree[r].dig;
+            q.fri_dig_batch_stride[r] = W.fri_tree[r].stride();
+            lb -= C->dom.arities[r];
         }
-        q.chal = C->cur->d_chal;
+        q.chal = W.d_chal;
         q.proofs = d_proofs;
         q.proof_bytes = L.bytes;
         q.queries_off = L.queries_off;
         q.query_bytes = L.query_bytes;
-        LAUNCH(C, "write_queries", k_write_queries, dim3(c.cfg.num_query_rounds, B), dim3(256), 0, q);
-        segs.s[nseg++] = ProofSeg{C->cur->d_fri_coef[R_], nullptr, 2 * fl, fl, L.final_off, (u32)fl, 1};
-        segs.s[nseg++] = ProofSeg{C->cur->d_chal + CH_POW, nullptr, (size_t)CH_WORDS, 0, L.pow_off, 1u, 0};  // the trailer: k_pi_hash
-        LAUNCH(C, "proof_segments", k_proof_segments, dim3(2, B, nseg), dim3(256), 0, segs);
+        LAUNCH(W.lane, "write_queries", k_write_queries, dim3(c.cfg.num_query_rounds, B), dim3(256), 0, q);
+        segs.s[nseg++] = ProofSeg{W.d_fri_coef[R_], nullptr, 2 * fl, fl, L.final_off, (u32)fl, 1};
+        segs.s[nseg++] = ProofSeg{W.d_chal + CH_POW, nullptr, (size_t)CH_WORDS, 0, L.pow_off, 1u, 0};  // the trailer: k_pi_hash
+        LAUNCH(W.lane, "proof_segments", k_proof_segments, dim3(2, B, nseg), dim3(256), 0, segs);
     }
-    LAUNCH(C, "finish", k_finish, g1(C->pbytes, 256, B), dim3(256), 0, C->cur->d_status, d_status_out, d_proofs, C->pbytes, B);
+    LAUNCH(W.lane, "finish", k_finish, g1(C->pbytes, 256, B), dim3(256), 0, W.d_status, d_status_out, d_proofs, C->pbytes, B);
     return 0;
-}
-
-static void collect_timing(p2_circuit* C) {
-    std::vector<std::pair<std::string, std::pair<hipEvent_t, hipEvent_t>>> all;
-    all.swap(C->setup_ws.pending);
-    for (Workspace* W : C->ws) {
-        all.insert(all.end(), W->pending.begin(), W->pending.end());
-        W->pending.clear();
-    }
-    for (auto& pe : all) {
-        float ms = 0;
-        (void)hipEventSynchronize(pe.second.second);
-        (void)hipEventElapsedTime(&ms, pe.second.first, pe.second.second);
-        auto& t = C->times[pe.first];
-        t.first += ms;
-        t.second++;
-        (void)hipEventDestroy(pe.second.first);
-        (void)hipEventDestroy(pe.second.second);
-    }
 }
 
 // Host-path staging: device buffers, pinned host mirrors and a stream, kept across p2_prove_batch calls (they only grow).
@@ -1210,10 +1224,10 @@ static int verify_setup(p2_circuit* C) {
     else if (c.cfg.cap_height != 4) why = "cap_height != 4";
     else if (c.k_is.size() != R) why = "k_is shape";
     else if (c.num_gate_constraints > VFY_MAX_GC || c.gates.size() > p2::MAX_GATE_TYPES || c.luts.size() > p2::MAX_LUTS) why = "gate / lookup table count";
-    else if (c.cfg.num_query_rounds > CH_WORDS - CH_QUERY || C->arities.size() > VFY_MAX_ROUNDS) why = "query rounds / FRI rounds";
+    else if (c.cfg.num_query_rounds > CH_WORDS - CH_QUERY || C->dom.arities.size() > VFY_MAX_ROUNDS) why = "query rounds / FRI rounds";
     else if (c.cfg.pow_bits == 0 || c.cfg.pow_bits > 32) why = "pow_bits";
     else if (C->pbytes >= (size_t)UINT32_MAX) why = "proof too large";
-    for (u32 ab : C->arities)
+    for (u32 ab : C->dom.arities)
         if (ab != VFY_ARITY_BITS) why = "FRI arity other than 16";
     if (!why.empty()) {
         C->vfy_error = "p2_verify_batch does not support this circuit: " + why;
@@ -1273,8 +1287,8 @@ static int verify_setup(p2_circuit* C) {
     a.n_b1 = L.set.n_b1;
     a.W = (u32)woff.size();
     a.n_cnt = (u32)coff.size();
-    if (upload(C, (u32**)&a.word_off, woff.data(), woff.size()) || upload(C, (u32**)&a.cnt_off, coff.data(), coff.size()) ||
-        upload(C, (uint8_t**)&a.cnt_exp, cexp.data(), cexp.size()) || upload(C, (u32**)&a.obs_map, obs.data(), obs.size()))
+    if (upload(C->allocs, (u32**)&a.word_off, woff.data(), woff.size()) || upload(C->allocs, (u32**)&a.cnt_off, coff.data(), coff.size()) ||
+        upload(C->allocs, (uint8_t**)&a.cnt_exp, cexp.data(), cexp.size()) || upload(C->allocs, (u32**)&a.obs_map, obs.data(), obs.size()))
         return P2_ERR_HIP;
     if (c.cfg.hasher == HASHER_KECCAK) {
         std::vector<u32> hidx;
@@ -1289,7 +1303,7 @@ static int verify_setup(p2_circuit* C) {
                 for (u32 l = 0; l < a.step_depth[k]; l++) hidx.push_back(base + a.step_sib_off[k] + 4 * l);
         }
         C->kc_hashes = (u32)hidx.size();
-        if (upload(C, &C->d_kc_hash_idx, hidx.data(), hidx.size())) return P2_ERR_HIP;
+        if (upload(C->allocs, &C->d_kc_hash_idx, hidx.data(), hidx.size())) return P2_ERR_HIP;
     }
     a.proof_bytes = C->pbytes;
     a.degree_bits = c.degree_bits;
@@ -1297,7 +1311,7 @@ static int verify_setup(p2_circuit* C) {
     a.cap_height = c.cfg.cap_height;
     a.pow_bits = c.cfg.pow_bits;
     a.num_queries = c.cfg.num_query_rounds;
-    a.num_rounds = (u32)C->arities.size();
+    a.num_rounds = (u32)C->dom.arities.size();
     a.has_lookup = nlp ? 1 : 0;
     a.R = R, a.num_wires = NW, a.NC = NC, a.npp = npp, a.qdf = qdf, a.nlp = nlp, a.nsldc = c.num_sldc_polys();
     a.lut_deg = nlp ? c.lut_degree() : 0;
@@ -1337,7 +1351,7 @@ static int cmp_setup(p2_circuit* C) {
             for (u32 e = 0; e < 4 * a.step_depth[r]; e++) wmap[base + a.step_sib_off[r] + e] = cmp_code(CW_SIB, q, 4 + r, e);
         }
     }
-    return upload(C, &C->d_cmp_wmap, wmap.data(), wmap.size());
+    return upload(C->allocs, &C->d_cmp_wmap, wmap.data(), wmap.size());
 }
 
 static VerifyWs* verify_lease(p2_circuit* C) {
@@ -1548,11 +1562,12 @@ p2_circuit* p2_circuit_load(const uint8_t* blob, size_t len, int device) {
             throw std::runtime_error("only CircuitConfig::standard_recursion_config() is supported");
         if (c.degree_bits > 22) throw std::runtime_error("degree_bits > 22 is not supported");
         C->device = device;
-        C->logn = c.degree_bits;
+        C->dom.logn = c.degree_bits;
+        C->dom.rate_bits = c.cfg.rate_bits, C->dom.cap_height = c.cfg.cap_height, C->dom.hasher = c.cfg.hasher;
         C->n = c.n();
         C->lde_bits = c.degree_bits + c.cfg.rate_bits;
         C->N = C->n << c.cfg.rate_bits;
-        C->arities = c.reduction_arity_bits();
+        C->dom.arities = c.reduction_arity_bits();
         // routed-only gates leave wires 80..134 identically zero (never materialised); PoseidonGate rows use all 135
         C->active_wires = (c.poseidon_rows.empty() && !c.cfg.zero_knowledge) ? c.cfg.num_routed_wires : c.cfg.num_wires;
         for (int i = 0; i < 4; i++) C->zk_key.k[i] = os_random_field();
@@ -1565,7 +1580,7 @@ p2_circuit* p2_circuit_load(const uint8_t* blob, size_t len, int device) {
         C->layout = make_proof_layout(c);
         C->pbytes = C->layout.bytes;
         if (hipSetDevice(device) != hipSuccess) throw std::runtime_error("hipSetDevice failed");
-        if (hipStreamCreate(&C->stream) != hipSuccess) throw std::runtime_error("hipStreamCreate failed");
+        if (hipStreamCreate(&C->setup.stream) != hipSuccess) throw std::runtime_error("hipStreamCreate failed");
         if (hipEventCreateWithFlags(&C->ev_witness, hipEventDisableTiming) != hipSuccess) throw std::runtime_error("hipEventCreate failed");
         if (raise_ntt_lds_limits() != hipSuccess) throw std::runtime_error("cannot raise the dynamic LDS limit for the NTT kernels");
         // opening maps: the evaluation slots in observed and in serialised order
@@ -1574,7 +1589,7 @@ p2_circuit* p2_circuit_load(const uint8_t* blob, size_t len, int device) {
         C->n_obs = (u32)obs.size();
         C->n_ser = (u32)ser.size();
         if (C->layout.final_len > C->n_obs) throw std::runtime_error("final polynomial larger than the observation buffer");
-        if (upload(C, &C->d_map_obs, obs.data(), obs.size()) || upload(C, &C->d_map_ser, ser.data(), ser.size())) throw std::runtime_error(g_last_error);
+        if (upload(C->allocs, &C->d_map_obs, obs.data(), obs.size()) || upload(C->allocs, &C->d_map_ser, ser.data(), ser.size())) throw std::runtime_error(g_last_error);
         if (circuit_setup(C)) throw std::runtime_error(g_last_error);
         if (verify_setup(C) || cmp_setup(C)) throw std::runtime_error(g_last_error);
         return C;
@@ -1598,8 +1613,7 @@ void p2_circuit_free(p2_circuit* C) {
         W->release();
         delete W;
     }
-    for (void* p : C->allocs) (void)hipFree(p);
-    if (C->stream) (void)hipStreamDestroy(C->stream);
+    if (C->setup.stream) (void)hipStreamDestroy(C->setup.stream);
     if (C->ev_witness) (void)hipEventDestroy(C->ev_witness);
     delete C;
 }
@@ -1639,40 +1653,6 @@ int p2_circuit_set_zk_seed(p2_circuit* C, uint64_t seed) {
     return p2_circuit_set_zk_key(C, key);
 }
 
-static int setup_polyrefs(p2_circuit* C) {
-    const Circuit& c = C->c;
-    const u32 np = c.num_preprocessed(), zc = c.num_zs_cols(), qc = c.num_quotient_cols();
-    const size_t n = C->n;
-    // the two FRI batches: the coefficient column behind every opening, in observed order
-    const OpeningSet& os = C->layout.set;
-    const PolyRef oracle[OS_SLOTS] = {{C->d_pre_coeffs, 0, 0, 0}, {C->cur->d_wcoef, (size_t)C->active_wires * n, 0, 0}, {C->cur->d_zcoef, (size_t)zc * n, 0, 0},
-                                      {C->cur->d_zcoef, (size_t)zc * n, 0, 0}, {C->cur->d_qcoef, (size_t)qc * n, 0, 0}};
-    std::vector<PolyRef> v;
-    for (OpenGroup k : OPEN_OBSERVED)
-        for (u32 i = os.g[k].lo; i < os.g[k].hi; i++) {
-            PolyRef r = oracle[os.g[k].slot];
-            r.col = i;
-            if (os.g[k].slot == OS_WIRES && i >= C->active_wires) r.base = nullptr;  // identically zero, never materialised
-            v.push_back(r);
-        }
-    C->n_b0 = os.n_b0;
-    C->n_b1 = os.n_b1;
-    // the opening set: every materialised column of every oracle at zeta, the Z columns at g zeta as well
-    std::vector<EvalRef> e;
-    const u32 cols[OS_SLOTS] = {np, C->active_wires, zc, zc, qc};
-    for (u32 b = 0; b < OS_SLOTS; b++)
-        for (u32 i = 0; i < cols[b]; i++) e.push_back({oracle[b].base, oracle[b].batch_stride, i, b == OS_Z_NEXT, os.slot_base[b] + i, 0});
-    C->n_evalrefs = (u32)e.size();
-    if (upload(C, &C->cur->d_evalrefs, e.data(), e.size())) return P2_ERR_HIP;
-    return upload(C, &C->cur->d_polyrefs, v.data(), v.size());
-}
-
-static int prove_batch_device_impl(p2_circuit* C, size_t batch, const p2_target* targets, size_t n_targets, const uint64_t* d_values, uint8_t* d_proofs, int* d_status,
-                                   void* stream);
-int p2_prove_batch_device(p2_circuit* C, size_t batch, const p2_target* targets, size_t n_targets, const uint64_t* d_values, uint8_t* d_proofs, int* d_status,
-                          void* stream) {
-    return guarded_rc([&] { return prove_batch_device_impl(C, batch, targets, n_targets, d_values, d_proofs, d_status, stream); });
-}
 static int prove_batch_device_impl(p2_circuit* C, size_t batch, const p2_target* targets, size_t n_targets, const uint64_t* d_values, uint8_t* d_proofs, int* d_status,
                                    void* stream) {
     std::lock_guard<std::mutex> lock(C->mu);
@@ -1731,7 +1711,7 @@ static int prove_batch_device_impl(p2_circuit* C, size_t batch, const p2_target*
     HIPCHECK(hipEventCreateWithFlags(&ev_guard.e, hipEventDisableTiming));
     hipEvent_t ev_in = ev_guard.e;
     HIPCHECK(hipEventRecord(ev_in, caller));
-    for (Workspace* W : C->ws) HIPCHECK(hipStreamWaitEvent(W->stream, ev_in, 0));
+    for (Workspace* W : C->ws) HIPCHECK(hipStreamWaitEvent(W->lane.stream, ev_in, 0));
     // the blinding counter advances before anything is enqueued: a batch that fails half-way must not leave its proof
     // indices to be used again under the same key
     const u64 proof_base0 = C->zk_counter;
@@ -1739,36 +1719,35 @@ static int prove_batch_device_impl(p2_circuit* C, size_t batch, const p2_target*
     size_t k = 0;
     for (size_t done = 0; done < batch; done += C->chunk, k++) {
         u32 B = (u32)std::min(C->chunk, batch - done);
-        C->cur = C->ws[k % C->ws.size()];
-        if (C->cur->h_input_slots != slots) {  // a new target list: wait for the workspace's earlier chunks, then upload
-            HIPCHECK(hipStreamSynchronize(C->cur->stream));
-            HIPCHECK(hipMemcpy(C->cur->d_input_slots, slots.data(), n_targets * 4, hipMemcpyHostToDevice));
-            C->cur->h_input_slots = slots;
+        Workspace& W = *C->ws[k % C->ws.size()];
+        if (W.h_input_slots != slots) {  // a new target list: wait for the workspace's earlier chunks, then upload
+            HIPCHECK(hipStreamSynchronize(W.lane.stream));
+            HIPCHECK(hipMemcpy(W.d_input_slots, slots.data(), n_targets * 4, hipMemcpyHostToDevice));
+            W.h_input_slots = slots;
         }
-        int rc = prove_chunk(C, B, (u32)n_targets, d_values + done * n_targets, d_proofs + done * C->pbytes, d_status + done, proof_base0 + done);
-        C->cur = nullptr;
+        int rc = prove_chunk(C, W, B, (u32)n_targets, d_values + done * n_targets, d_proofs + done * C->pbytes, d_status + done, proof_base0 + done);
         if (rc) return rc;
     }
     for (Workspace* W : C->ws) {
-        HIPCHECK(hipEventRecord(W->done, W->stream));
+        HIPCHECK(hipEventRecord(W->done, W->lane.stream));
         HIPCHECK(hipStreamWaitEvent(caller, W->done, 0));
     }
     return P2_OK;
+}
+int p2_prove_batch_device(p2_circuit* C, size_t batch, const p2_target* targets, size_t n_targets, const uint64_t* d_values, uint8_t* d_proofs, int* d_status,
+                          void* stream) {
+    return guarded_rc([&] { return prove_batch_device_impl(C, batch, targets, n_targets, d_values, d_proofs, d_status, stream); });
 }
 
 int p2_circuit_synchronize(p2_circuit* C) {
     std::lock_guard<std::mutex> lock(C->mu);
     HIPCHECK(hipSetDevice(C->device));
-    HIPCHECK(hipStreamSynchronize(C->stream));
-    for (Workspace* W : C->ws) HIPCHECK(hipStreamSynchronize(W->stream));
+    HIPCHECK(hipStreamSynchronize(C->setup.stream));
+    for (Workspace* W : C->ws) HIPCHECK(hipStreamSynchronize(W->lane.stream));
     if (C->timing_on) collect_timing(C);
     return P2_OK;
 }
 
-static int prove_batch_impl(p2_circuit* C, size_t batch, const p2_assignment* inputs, uint8_t* proofs, int* status);
-int p2_prove_batch(p2_circuit* C, size_t batch, const p2_assignment* inputs, uint8_t* proofs, int* status) {
-    return guarded_rc([&] { return prove_batch_impl(C, batch, inputs, proofs, status); });
-}
 static int prove_batch_impl(p2_circuit* C, size_t batch, const p2_assignment* inputs, uint8_t* proofs, int* status) {
     if (batch == 0) return P2_OK;
     HIPCHECK(hipSetDevice(C->device));
@@ -1835,14 +1814,13 @@ static int prove_batch_impl(p2_circuit* C, size_t batch, const p2_assignment* in
     if (dbg) fprintf(stderr, "[p2aes] pack %.3f enqueue %.3f wait %.3f unpack %.3f s\n", t_b - t_a, t_c - t_b, t_d - t_c, now() - t_d);
     return P2_OK;
 }
+int p2_prove_batch(p2_circuit* C, size_t batch, const p2_assignment* inputs, uint8_t* proofs, int* status) {
+    return guarded_rc([&] { return prove_batch_impl(C, batch, inputs, proofs, status); });
+}
 
 // In-process multi-device form of p2_prove_batch: contiguous balanced ranges of the batch, one host thread per handle.
 // zk circuits: every handle blinds with ITS OWN key (drawn from the OS at load) and its own proof counter; handles that were
 // given one fixed key by the test hook would blind different witnesses with the same (key, index) values.
-static int prove_batch_multi_impl(p2_circuit* const* handles, size_t n_handles, size_t batch, const p2_assignment* inputs, uint8_t* proofs, int* status);
-int p2_prove_batch_multi(p2_circuit* const* handles, size_t n_handles, size_t batch, const p2_assignment* inputs, uint8_t* proofs, int* status) {
-    return guarded_rc([&] { return prove_batch_multi_impl(handles, n_handles, batch, inputs, proofs, status); });
-}
 static int prove_batch_multi_impl(p2_circuit* const* handles, size_t n_handles, size_t batch, const p2_assignment* inputs, uint8_t* proofs, int* status) {
     if (n_handles == 0 || !handles) return set_error("p2_prove_batch_multi needs at least one handle"), P2_ERR_INVALID;
     for (size_t h = 0; h < n_handles; h++)
@@ -1868,6 +1846,9 @@ static int prove_batch_multi_impl(p2_circuit* const* handles, size_t n_handles, 
         if (rc[h] != P2_OK) return set_error("handle " + std::to_string(h) + " (device " + std::to_string(handles[h]->device) + "): " + err[h]), rc[h];
     return P2_OK;
 }
+int p2_prove_batch_multi(p2_circuit* const* handles, size_t n_handles, size_t batch, const p2_assignment* inputs, uint8_t* proofs, int* status) {
+    return guarded_rc([&] { return prove_batch_multi_impl(handles, n_handles, batch, inputs, proofs, status); });
+}
 
 int p2_circuit_set_option(p2_circuit* C, const char* name, long value) {
     std::lock_guard<std::mutex> lock(C->mu);
@@ -1892,7 +1873,8 @@ int p2_circuit_set_option(p2_circuit* C, const char* name, long value) {
 
 int p2_circuit_set_timing(p2_circuit* C, int enable) {
     std::lock_guard<std::mutex> lock(C->mu);
-    C->timing_on = enable != 0;
+    C->timing_on = C->setup.timing = enable != 0;
+    for (Workspace* W : C->ws) W->lane.timing = C->timing_on;
     C->times.clear();
     return P2_OK;
 }
@@ -1918,41 +1900,34 @@ int p2_circuit_debug_read(p2_circuit* C, const char* name_c, size_t index, uint6
     const Circuit& c = C->c;
     std::string name(name_c);
     // `index` addresses proof (index % chunk) of the workspace that handled chunk (index / chunk) of the last call
-    struct CurGuard {
-        p2_circuit* C;
-        ~CurGuard() { C->cur = nullptr; }
-    } guard{C};
-    if (!C->ws.empty()) {
-        C->cur = C->ws[(index / C->chunk) % C->ws.size()];
-        index %= C->chunk;
-    }
+    Workspace* W = C->ws.empty() ? nullptr : C->ws[(index / C->chunk) % C->ws.size()];
+    if (W) index %= C->chunk;
     const size_t n = C->n, N = C->N;
-    const u32 zc = c.num_zs_cols(), qc = c.num_quotient_cols(), act = C->active_wires, cap_words = 4u << c.cfg.cap_height;
     const u64* src = nullptr;
     size_t count = 0;
-    if (name == "pre_cap") { src = C->pre_tree.dig + cap_off(C->pre_tree, c.cfg.cap_height); count = cap_words; }
-    else if (name == "pre_coeffs") { src = C->d_pre_coeffs; count = (size_t)c.num_preprocessed() * n; }
-    else if (C->ws.empty()) return set_error("nothing has been proven yet"), P2_ERR_INVALID;
-    else if (name == "values") { src = C->cur->d_values + index * c.num_slots; count = c.num_slots; }
-    else if (name == "wires") { src = C->cur->d_wires + index * act * n; count = (size_t)act * n; }
-    else if (name == "wires_coeffs") { src = C->cur->d_wcoef + index * act * n; count = (size_t)act * n; }
-    else if (name == "wires_lde") { src = C->cur->d_wlde + index * (act + c.salt()) * N; count = (size_t)(act + c.salt()) * N; }
-    else if (name == "wires_cap") { src = C->cur->wtree.dig + index * C->cur->wtree.stride() + cap_off(C->cur->wtree, c.cfg.cap_height); count = cap_words; }
-    else if (name == "zs") { src = C->cur->d_zs + index * zc * n; count = (size_t)zc * n; }
-    else if (name == "zs_cap") { src = C->cur->ztree.dig + index * C->cur->ztree.stride() + cap_off(C->cur->ztree, c.cfg.cap_height); count = cap_words; }
-    else if (name == "quotient_values") { src = C->cur->d_qvals + index * 2 * N; count = 2 * N; }
-    else if (name == "quotient_coeffs") { src = C->cur->d_qcoef + index * qc * n; count = (size_t)qc * n; }
-    else if (name == "quotient_cap") { src = C->cur->qtree.dig + index * C->cur->qtree.stride() + cap_off(C->cur->qtree, c.cfg.cap_height); count = cap_words; }
+    // NAME (values), NAME_coeffs, NAME_lde and NAME_cap of every committed oracle
+    const std::pair<std::string, const Oracle*> oracles[] = {{"pre", &C->pre}, {"wires", W ? &W->wires : nullptr}, {"zs", W ? &W->zs : nullptr}, {"quotient", W ? &W->quot : nullptr}};
+    for (const auto& [prefix, o] : oracles) {
+        if (!o) continue;
+        if (name == prefix && o->vals) { src = o->vals + index * o->coef_stride; count = (size_t)o->cols * n; }
+        else if (name == prefix + "_coeffs") { src = o->coef + index * o->coef_stride; count = (size_t)o->cols * n; }
+        else if (name == prefix + "_lde") { src = o->lde + index * o->lde_stride; count = (size_t)(o->cols + o->salt) * N; }
+        else if (name == prefix + "_cap") { src = o->tree.dig + index * o->dig_stride() + cap_off(o->tree, c.cfg.cap_height); count = 4u << c.cfg.cap_height; }
+    }
+    if (src) {}  // one of the oracles' buffers
+    else if (!W) return set_error("nothing has been proven yet"), P2_ERR_INVALID;
+    else if (name == "values") { src = W->d_values + index * c.num_slots; count = c.num_slots; }
+    else if (name == "quotient_values") { src = W->d_qvals + index * 2 * N; count = 2 * N; }
     else if (name == "public_inputs_hash" && c.pi_slots.empty()) {
         if (cap < 4) return set_error("debug buffer too small"), P2_ERR_INVALID;
         for (int i = 0; i < 4; i++) out[i] = 0;  // hash_no_pad of zero public inputs
         *n_written = 4;
         return P2_OK;
     }
-    else if (name == "public_inputs_hash") { src = C->cur->d_pi_hash + index * 4; count = 4; }
-    else if (name == "challenges") { src = C->cur->d_chal + index * CH_WORDS; count = CH_WORDS; }
-    else if (name == "openings") { src = C->cur->d_ev + index * 2 * C->ev_count; count = 2 * (size_t)C->ev_count; }
-    else if (name == "fri_final_poly_in") { src = C->cur->d_fri_coef[0] + index * 2 * n; count = 2 * n; }
+    else if (name == "public_inputs_hash") { src = W->d_pi_hash + index * 4; count = 4; }
+    else if (name == "challenges") { src = W->d_chal + index * CH_WORDS; count = CH_WORDS; }
+    else if (name == "openings") { src = W->d_ev + index * 2 * C->ev_count; count = 2 * (size_t)C->ev_count; }
+    else if (name == "fri_final_poly_in") { src = W->d_fri_coef[0] + index * 2 * n; count = 2 * n; }
     else return set_error("unknown debug buffer"), P2_ERR_INVALID;
     if (count > cap) return set_error("debug buffer too small"), P2_ERR_INVALID;
     HIPCHECK(hipMemcpy(out, src, count * 8, hipMemcpyDeviceToHost));
@@ -2067,26 +2042,24 @@ __global__ __launch_bounds__(64) void k_selftest_coop(unsigned long long* bad, u
 
 int p2_selftest_device(uint64_t seed, size_t threads, int device) {
     if (hipSetDevice(device) != hipSuccess) return set_error("no such HIP device"), -P2_ERR_HIP;
+    Allocs mem;
     unsigned long long* d = nullptr;
-    if (hipMalloc((void**)&d, 8) != hipSuccess || hipMemset(d, 0, 8) != hipSuccess) return set_error("hipMalloc failed"), -P2_ERR_HIP;
+    if (dalloc(mem, &d, 1) || hipMemset(d, 0, 8) != hipSuccess) return set_error("hipMalloc failed"), -P2_ERR_HIP;
     hipLaunchKernelGGL(p2k::k_selftest, dim3((u32)((threads + 255) / 256)), dim3(256), 0, 0, d, (u64)seed, threads);
     hipLaunchKernelGGL(p2k::k_selftest_coop, dim3((u32)std::min<size_t>(std::max<size_t>(threads / 64, 1), 4096)), dim3(64), 0, 0, d, (u64)seed);
     unsigned long long h = 0;
-    hipError_t e = hipMemcpy(&h, d, 8, hipMemcpyDeviceToHost);
-    (void)hipFree(d);
-    if (e != hipSuccess) return set_error(hipGetErrorString(e)), -P2_ERR_HIP;
+    if (hipError_t e = hipMemcpy(&h, d, 8, hipMemcpyDeviceToHost)) return set_error(hipGetErrorString(e)), -P2_ERR_HIP;
     return (int)std::min<unsigned long long>(h, 0x7FFFFFFF);
 }
 
 int p2_gpu_poseidon(uint64_t* states, size_t n_perm, int device) {
     if (int rc = pick_device(device)) return rc;
+    Allocs mem;
     u64* d;
-    HIPCHECK(hipMalloc((void**)&d, n_perm * 96));
-    HIPCHECK(hipMemcpy(d, states, n_perm * 96, hipMemcpyHostToDevice));
+    if (upload(mem, &d, (const u64*)states, n_perm * 12)) return P2_ERR_HIP;
     hipLaunchKernelGGL(k_poseidon_states, g1(n_perm, 256), dim3(256), 0, 0, d, n_perm);
     HIPCHECK(hipGetLastError());
     HIPCHECK(hipMemcpy(states, d, n_perm * 96, hipMemcpyDeviceToHost));
-    (void)hipFree(d);
     return P2_OK;
 }
 // The three tree kernels on their own (tests): host arrays in, host arrays out, one launch each.
@@ -2095,16 +2068,14 @@ int p2_gpu_hash_leaves(const uint64_t* data, size_t cols, size_t active_cols, si
     if (cols == 0 || cols > (1u << 20) || num_leaves == 0 || batch == 0 || batch > 65535) return set_error("shape out of range"), P2_ERR_INVALID;
     if (int rc = pick_device(device)) return rc;
     const size_t stored = std::min(active_cols, cols), in_words = std::max<size_t>(stored, 1) * num_leaves;
+    Allocs mem;
     u64 *d_in, *d_out;
-    HIPCHECK(hipMalloc((void**)&d_in, batch * in_words * 8));
-    HIPCHECK(hipMalloc((void**)&d_out, batch * num_leaves * 32));
+    if (dalloc(mem, &d_in, batch * in_words) || dalloc(mem, &d_out, batch * num_leaves * 4)) return P2_ERR_HIP;
     HIPCHECK(hipMemcpy(d_in, data, batch * stored * num_leaves * 8, hipMemcpyHostToDevice));
     hipLaunchKernelGGL(k_hash_leaves, g1(num_leaves, 256, (u32)batch), dim3(256), 0, 0, d_in, (int)cols, (int)active_cols, num_leaves, stored * num_leaves, num_leaves,
                        d_out, num_leaves * 4);
     HIPCHECK(hipGetLastError());
     HIPCHECK(hipMemcpy(digests, d_out, batch * num_leaves * 32, hipMemcpyDeviceToHost));
-    (void)hipFree(d_in);
-    (void)hipFree(d_out);
     return P2_OK;
 }
 //   child [batch][2 * num_parents][4] -> parent [batch][num_parents][4]
@@ -2112,15 +2083,12 @@ int p2_gpu_merkle_level(const uint64_t* child, size_t num_parents, size_t batch,
     if (num_parents == 0 || batch == 0 || batch > 65535) return set_error("shape out of range"), P2_ERR_INVALID;
     if (int rc = pick_device(device)) return rc;
     const size_t stride = 8 * num_parents;  // the kernel strides children and parents alike (levels of one digest buffer)
+    Allocs mem;
     u64 *d_in, *d_out;
-    HIPCHECK(hipMalloc((void**)&d_in, batch * stride * 8));
-    HIPCHECK(hipMalloc((void**)&d_out, batch * stride * 8));
-    HIPCHECK(hipMemcpy(d_in, child, batch * stride * 8, hipMemcpyHostToDevice));
+    if (upload(mem, &d_in, (const u64*)child, batch * stride) || dalloc(mem, &d_out, batch * stride)) return P2_ERR_HIP;
     hipLaunchKernelGGL(k_merkle_level, g1(num_parents, 256, (u32)batch), dim3(256), 0, 0, d_in, d_out, num_parents, stride);
     HIPCHECK(hipGetLastError());
     for (size_t b = 0; b < batch; b++) HIPCHECK(hipMemcpy(parent + b * 4 * num_parents, d_out + b * stride, num_parents * 32, hipMemcpyDeviceToHost));
-    (void)hipFree(d_in);
-    (void)hipFree(d_out);
     return P2_OK;
 }
 //   vals [batch][2][len] (the two components of len extension values) -> digests [batch][len / arity][4]
@@ -2128,31 +2096,25 @@ int p2_gpu_hash_fri_leaves(const uint64_t* vals, size_t len, int arity, size_t b
     if (arity < 1 || arity > 64 || len == 0 || len % (size_t)arity || batch == 0 || batch > 65535) return set_error("shape out of range"), P2_ERR_INVALID;
     if (int rc = pick_device(device)) return rc;
     const size_t leaves = len / (size_t)arity;
+    Allocs mem;
     u64 *d_in, *d_out;
-    HIPCHECK(hipMalloc((void**)&d_in, batch * 2 * len * 8));
-    HIPCHECK(hipMalloc((void**)&d_out, batch * leaves * 32));
-    HIPCHECK(hipMemcpy(d_in, vals, batch * 2 * len * 8, hipMemcpyHostToDevice));
+    if (upload(mem, &d_in, (const u64*)vals, batch * 2 * len) || dalloc(mem, &d_out, batch * leaves * 4)) return P2_ERR_HIP;
     hipLaunchKernelGGL(k_hash_fri_leaves, g1(leaves, 256, (u32)batch), dim3(256), 0, 0, d_in, len, 2 * len, arity, d_out, leaves * 4);
     HIPCHECK(hipGetLastError());
     HIPCHECK(hipMemcpy(digests, d_out, batch * leaves * 32, hipMemcpyDeviceToHost));
-    (void)hipFree(d_in);
-    (void)hipFree(d_out);
     return P2_OK;
 }
-// A throw-away circuit-less context for the NTT / Merkle primitives
+// What the NTT / Merkle primitives need of a handle: a lane, the transform tables of one size and the allocations behind them.
 struct PrimCtx {
-    p2_circuit C;
+    Lane lane;
+    Domain dom;
+    Allocs mem;
     int init(int device, int degree_bits) {
         if (int rc = pick_device(device)) return rc;
-        C.device = device;
-        C.logn = (u32)degree_bits;
-        C.n = (size_t)1 << degree_bits;
-        C.c.degree_bits = (u32)degree_bits;
-        C.lde_bits = C.logn + 3;
-        C.N = C.n << 3;
-        HIPCHECK(hipStreamCreate(&C.stream));
+        dom.logn = (u32)degree_bits;
+        HIPCHECK(hipStreamCreate(&lane.stream));
         HIPCHECK(raise_ntt_lds_limits());
-        size_t n = C.n;
+        const size_t n = dom.n();
         std::vector<u64> twf(n), twi(n);
         u64 w = gl::root_of_unity(degree_bits), wi = gl::inv(w), x = 1, xi = 1;
         for (size_t i = 0; i < n; i++) {
@@ -2161,36 +2123,34 @@ struct PrimCtx {
             x = gl::mul(x, w);
             xi = gl::mul(xi, wi);
         }
-        if (upload(&C, &C.d_tw_fwd_full, twf.data(), n) || upload(&C, &C.d_tw_inv_full, twi.data(), n)) return P2_ERR_HIP;
-        C.d_tw_fwd = C.d_tw_fwd_full;
-        C.d_tw_inv = C.d_tw_inv_full;
-        if (ensure_pass1_table(&C, C.d_tw_fwd_full, (u32)degree_bits) || ensure_pass1_table(&C, C.d_tw_inv_full, (u32)degree_bits)) return P2_ERR_HIP;
+        if (upload(mem, &dom.d_tw_fwd_full, twf.data(), n) || upload(mem, &dom.d_tw_inv_full, twi.data(), n)) return P2_ERR_HIP;
+        dom.d_tw_fwd = dom.d_tw_fwd_full;
+        dom.d_tw_inv = dom.d_tw_inv_full;
+        if (ensure_pass1_table(lane, dom, mem, dom.d_tw_fwd_full, dom.logn) || ensure_pass1_table(lane, dom, mem, dom.d_tw_inv_full, dom.logn)) return P2_ERR_HIP;
         std::vector<u64> bases(8);
         u64 wl = gl::root_of_unity(degree_bits + 3);
         for (u32 j = 0; j < 8; j++) bases[j] = gl::mul(gl::MULT_GEN, gl::pow(wl, j));
         u64* d_b;
-        if (upload(&C, &d_b, bases.data(), 8)) return P2_ERR_HIP;
-        if (dalloc(&C, &C.d_shift_pows[0], 8 * n)) return P2_ERR_HIP;
-        hipLaunchKernelGGL(k_pow_table, g1(n, 256, 8), dim3(256), 0, C.stream, C.d_shift_pows[0], d_b, (u32)n, (u64)1);
+        if (upload(mem, &d_b, bases.data(), 8)) return P2_ERR_HIP;
+        if (dalloc(mem, &dom.d_shift_pows[0], 8 * n)) return P2_ERR_HIP;
+        hipLaunchKernelGGL(k_pow_table, g1(n, 256, 8), dim3(256), 0, lane.stream, dom.d_shift_pows[0], d_b, (u32)n, (u64)1);
         HIPCHECK(hipGetLastError());
         return 0;
     }
-    ~PrimCtx() {
-        if (C.stream) (void)hipStreamSynchronize(C.stream);
-        for (void* p : C.allocs) (void)hipFree(p);
-        if (C.stream) (void)hipStreamDestroy(C.stream);
+    ~PrimCtx() {  // (`mem` goes after this body: nothing is still running on what it frees)
+        if (lane.stream) (void)hipStreamSynchronize(lane.stream);
+        if (lane.stream) (void)hipStreamDestroy(lane.stream);
     }
 };
 int p2_gpu_intt(const uint64_t* values, size_t cols, int degree_bits, uint64_t* coeffs, int device) {
     if (degree_bits < 1 || degree_bits > 22) return set_error("degree_bits must be in 1..22"), P2_ERR_INVALID;
     PrimCtx ctx;
     if (int rc = ctx.init(device, degree_bits)) return rc;
-    p2_circuit* C = &ctx.C;
-    size_t n = C->n;
+    const size_t n = ctx.dom.n();
     u64 *d_in, *d_out, *d_scratch;
-    if (upload(C, &d_in, values, cols * n) || dalloc(C, &d_out, cols * n) || dalloc(C, &d_scratch, cols * n)) return P2_ERR_HIP;
-    if (intt_cols(C, d_in, d_out, (u32)cols, 0, 1, d_scratch, 0)) return P2_ERR_HIP;
-    HIPCHECK(hipStreamSynchronize(C->stream));
+    if (upload(ctx.mem, &d_in, (const u64*)values, cols * n) || dalloc(ctx.mem, &d_out, cols * n) || dalloc(ctx.mem, &d_scratch, cols * n)) return P2_ERR_HIP;
+    if (intt_cols(ctx.lane, ctx.dom, d_in, d_out, (u32)cols, 0, 1, d_scratch, 0)) return P2_ERR_HIP;
+    HIPCHECK(hipStreamSynchronize(ctx.lane.stream));
     HIPCHECK(hipMemcpy(coeffs, d_out, cols * n * 8, hipMemcpyDeviceToHost));
     return P2_OK;
 }
@@ -2198,13 +2158,11 @@ int p2_gpu_lde(const uint64_t* coeffs, size_t cols, int degree_bits, int rate_bi
     if (degree_bits < 1 || degree_bits > 22 || rate_bits != 3) return set_error("degree_bits must be in 1..22 and rate_bits 3"), P2_ERR_INVALID;
     PrimCtx ctx;
     if (int rc = ctx.init(device, degree_bits)) return rc;
-    p2_circuit* C = &ctx.C;
-    C->c.cfg.rate_bits = 3;
-    size_t n = C->n;
+    const size_t n = ctx.dom.n();
     u64 *d_in, *d_out;
-    if (upload(C, &d_in, coeffs, cols * n) || dalloc(C, &d_out, cols * 8 * n)) return P2_ERR_HIP;
-    if (lde_cols(C, d_in, 0, d_out, 0, (u32)cols, 0, 1)) return P2_ERR_HIP;
-    HIPCHECK(hipStreamSynchronize(C->stream));
+    if (upload(ctx.mem, &d_in, (const u64*)coeffs, cols * n) || dalloc(ctx.mem, &d_out, cols * 8 * n)) return P2_ERR_HIP;
+    if (lde_cols(ctx.lane, ctx.dom, d_in, 0, d_out, 0, (u32)cols, 0, 1)) return P2_ERR_HIP;
+    HIPCHECK(hipStreamSynchronize(ctx.lane.stream));
     HIPCHECK(hipMemcpy(lde, d_out, cols * 8 * n * 8, hipMemcpyDeviceToHost));
     return P2_OK;
 }
@@ -2219,15 +2177,14 @@ int p2_gpu_merkle_cap_hasher(const uint64_t* cols_major, size_t cols, size_t num
     if (((size_t)1 << bits) != num_leaves || (int)bits < cap_height) return set_error("num_leaves must be a power of two >= 2^cap_height"), P2_ERR_INVALID;
     PrimCtx ctx;
     if (int rc = ctx.init(device, 4)) return rc;
-    p2_circuit* C = &ctx.C;
-    C->c.cfg.cap_height = (u32)cap_height;
-    C->c.cfg.hasher = (u32)hasher;
+    ctx.dom.cap_height = (u32)cap_height;
+    ctx.dom.hasher = (u32)hasher;
     u64* d_in;
     Tree t;
     t.bits = bits;
-    if (upload(C, &d_in, cols_major, cols * num_leaves) || dalloc(C, &t.dig, t.stride())) return P2_ERR_HIP;
-    if (merkle_build(C, d_in, (u32)cols, (u32)cols, num_leaves, 0, t, 1)) return P2_ERR_HIP;
-    HIPCHECK(hipStreamSynchronize(C->stream));
+    if (upload(ctx.mem, &d_in, (const u64*)cols_major, cols * num_leaves) || dalloc(ctx.mem, &t.dig, t.stride())) return P2_ERR_HIP;
+    if (merkle_build(ctx.lane, ctx.dom, d_in, (u32)cols, (u32)cols, num_leaves, 0, t, 1)) return P2_ERR_HIP;
+    HIPCHECK(hipStreamSynchronize(ctx.lane.stream));
     HIPCHECK(hipMemcpy(cap, t.dig + cap_off(t, (u32)cap_height), ((size_t)4 << cap_height) * 8, hipMemcpyDeviceToHost));
     return P2_OK;
 }

@@ -575,6 +575,50 @@ def test_failed_workspace_allocation_is_rolled_back(gpu, monkeypatch):
     assert ref.prove_batch(pws)[0] == proofs
 
 
+def test_kernel_timing_counts_launches(gpu):
+    """Per-kernel timing (p2_circuit_set_timing / p2_circuit_get_timing, read by the tools/gpu_* scripts): every launch of the
+    pipeline is counted once under its stage name, also across a regrowth of the workspaces, and timing changes no proof byte.
+    A first prove(pw) sizes one workspace for one proof; the batch of five that follows WITHOUT a synchronize in between
+    regrows to two workspaces of two proofs, and the events still pending in the old workspace must be collected before it
+    is released.  Chunks: 1 + ceil(5 / 2) = 4."""
+    import math
+    pairs = [((11 * i + 3) & 0xFF, (5 * i + 1) & 0xFF) for i in range(7)]
+    data, pws = circuits.gf_2_8_add(gpu, pairs)
+    lib, h = gpu.lib(), data.gpu()
+    data.set_option("chunk", 2)
+    data.set_option("streams", 2)
+    assert lib.p2_circuit_set_timing(h, 1) == 0
+    first = data.prove(pws[0])
+    rest, status = data.prove_batch(pws[1:6])
+    assert status == [0] * 5
+    data.synchronize()
+    arr = (gpu.api._KernelTime * 128)()
+    k = lib.p2_circuit_get_timing(h, arr, 128)
+    assert 0 < k <= 128
+    count = {arr[i].name.decode(): arr[i].count for i in range(k)}
+    ms = {arr[i].name.decode(): arr[i].ms for i in range(k)}
+    chunks = 4
+    for name in ("witness", "fill_wires", "quotient", "write_queries", "proof_segments", "pow_finish", "finish"):
+        assert count.get(name) == chunks, (name, count)
+    assert count.get("pow") == 5 * chunks, count        # three search launches and two compactions per chunk
+    rounds, rem = divmod(count.get("hash_fri_leaves", 0), chunks)
+    assert rounds >= 1 and rem == 0, count
+    assert rounds == data.info["num_fri_rounds"]
+    assert count.get("fri_fold") == count["hash_fri_leaves"], count
+    assert count.get("challenger") == chunks * (6 + rounds), count
+    for name, t in ms.items():
+        assert math.isfinite(t) and t > 0, (name, t)
+    # timing changes scheduling only: the same proofs from a handle that never had it on
+    plain, _ = circuits.gf_2_8_add(gpu, pairs)
+    want, status = plain.prove_batch(pws)
+    assert status == [0] * 7 and [first] + rest == want[:6]
+    assert lib.p2_circuit_set_timing(h, 0) == 0
+    assert lib.p2_circuit_get_timing(h, arr, 128) == 0
+    assert data.prove(pws[6]) == want[6]                # nothing is recorded once timing is off
+    data.synchronize()
+    assert lib.p2_circuit_get_timing(h, arr, 128) == 0
+
+
 def test_same_blob_on_every_visible_device(gpu):
     """Multi-GPU path by construction: the compiled circuit is replicated per device, proofs are independent.
     Load the blob on every visible device: equal verifier data, byte-equal proofs.  (One device on this pool.)"""
