@@ -133,6 +133,27 @@ pub mod iop {
                 Ok(())
             }
         }
+        /// What `CircuitData::generate_partial_witness` returns: the value the witness run gave every virtual target of the
+        /// circuit (upstream's `PartitionWitness`, read with `get_target`).  Routed wires are read with
+        /// `CircuitData::generate_witness_targets`.
+        pub struct Witness<F> {
+            pub(crate) values: Vec<u64>,   // by virtual target index; u64::MAX = the run did not determine it
+            pub(crate) _f: PhantomData<F>,
+        }
+        impl<F: Field> Witness<F> {
+            /// `None` for a routed wire, a target of another circuit, or a target the run did not determine.
+            pub fn try_get_target(&self, target: Target) -> Option<F> {
+                match self.values.get(usize::try_from(target.0).ok()?) {
+                    Some(&v) if v != crate::ffi::P2_VALUE_UNSET => Some(F::from_canonical_u64(v)),
+                    _ => None,
+                }
+            }
+            /// `Witness::get_target`; panics where upstream does (the target has no value).
+            pub fn get_target(&self, target: Target) -> F {
+                self.try_get_target(target).unwrap_or_else(|| panic!("target {:?} has no value in this witness", target))
+            }
+            pub fn get_targets(&self, targets: &[Target]) -> Vec<F> { targets.iter().map(|t| self.get_target(*t)).collect() }
+        }
         impl<F: Field> WitnessWrite<F> for PartialWitness<F> {
             /// Setting a target twice is fine when the values agree and an error otherwise, as in plonky2.
             fn set_target(&mut self, target: Target, value: F) -> anyhow::Result<()> {
@@ -163,7 +184,8 @@ pub mod plonk {
     }
     pub mod circuit_data {
         use crate::field::types::Field;
-        use crate::iop::witness::PartialWitness;
+        use crate::iop::target::Target;
+        use crate::iop::witness::{PartialWitness, Witness};
         use crate::{ffi, last_error};
         use core::marker::PhantomData;
 
@@ -254,6 +276,40 @@ pub mod plonk {
                     3 => Err(anyhow::anyhow!("Opening point is in the subgroup.")),
                     s => Err(anyhow::anyhow!("prove failed with status {s}")),
                 }).collect())
+            }
+            /// Witness generation on the GPU without proving (upstream `generate_partial_witness`): set the inputs, read what the
+            /// circuit computed with `Witness::get_target`.  `Err` carries the explained fault (`p2_witness_explain`): which
+            /// target, which entry of `pw`, what was computed and what was found.
+            pub fn generate_partial_witness(&self, pw: PartialWitness<F>) -> anyhow::Result<Witness<F>> {
+                let mut info = ffi::P2CircuitInfo::default();
+                let rc = unsafe { ffi::p2_blob_info(self.blob.as_ptr(), self.blob.len(), &mut info) };
+                if rc != ffi::P2_OK { return Err(last_error()); }
+                let all: Vec<Target> = (0..info.num_virtual_targets as u64).map(Target).collect();
+                let values = self.generate_witness_raw(&pw, &all)?;
+                Ok(Witness { values, _f: PhantomData })
+            }
+            /// The same for a chosen list of targets, routed wires included; one value per target, in order.
+            pub fn generate_witness_targets(&self, pw: PartialWitness<F>, targets: &[Target]) -> anyhow::Result<Vec<F>> {
+                let values = self.generate_witness_raw(&pw, targets)?;
+                values.iter().zip(targets).map(|(&v, t)| {
+                    anyhow::ensure!(v != ffi::P2_VALUE_UNSET, "target {:?} has no value in this witness", t);
+                    Ok(F::from_canonical_u64(v))
+                }).collect()
+            }
+            fn generate_witness_raw(&self, pw: &PartialWitness<F>, targets: &[Target]) -> anyhow::Result<Vec<u64>> {
+                let asg = ffi::P2Assignment { targets: pw.targets.as_ptr(), values: pw.values.as_ptr(), count: pw.targets.len() };
+                let outs: Vec<u64> = targets.iter().map(|t| t.0).collect();
+                let mut values = vec![0u64; outs.len()];
+                let mut status: std::os::raw::c_int = 0;
+                let rc = unsafe { ffi::p2_witness_batch(self.handle, 1, &asg, outs.as_ptr(), outs.len(), values.as_mut_ptr(), &mut status) };
+                if rc != ffi::P2_OK { return Err(last_error()); }
+                if status == 0 { return Ok(values); }
+                let mut fault = ffi::P2WitnessFault::default();
+                let rc = unsafe { ffi::p2_witness_explain(self.handle, &asg, &mut status, &mut fault as *mut ffi::P2WitnessFault as *mut std::os::raw::c_void) };
+                if rc != ffi::P2_OK { return Err(last_error()); }
+                let kind = ffi::P2_FAULT_KINDS.get(fault.kind as usize).copied().unwrap_or("UNKNOWN");
+                Err(anyhow::anyhow!("witness generation failed ({kind}): target {:#x}, entry {} of the witness, gate row {}, computed {}, found {}",
+                                    fault.target, fault.input_index, fault.gate_row as i32, fault.computed, fault.found))
             }
             /// The public-input trailer of a proof of this circuit: u64 k || k values, the last 8 (k + 1) bytes (none for k = 0).
             /// Reads those bytes only, so it costs O(k) per proof of a batch.

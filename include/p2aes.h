@@ -326,6 +326,72 @@ int p2_prove_batch_multi(p2_circuit* const* handles, size_t n_handles, size_t ba
 int p2_prove_batch_device(p2_circuit*, size_t batch, const p2_target* targets, size_t n_targets, const uint64_t* d_values,
                           uint8_t* d_proofs, int* d_status, void* stream);
 int p2_circuit_synchronize(p2_circuit*);
+
+/* ------------------------------------------------------------------ witness outputs, dry runs, fault diagnosis */
+/* What the circuit computed (upstream: generate_partial_witness, then witness.get_target).  `connect` merges targets into
+ * slots and a slot takes its first producer, so a computed target that the assignment leaves out is simply computed: set the
+ * inputs, name the targets to read.  (Trap: an AesGcmTarget built with TAG = false still has its 16 range-checked tag targets,
+ * which nothing computes: set them, to zero, or the witness is P2_PROOF_MISSING_INPUT.)
+ * On input P2_VALUE_UNSET means "this witness does not assign the target" (device forms); on output it means "the witness run
+ * did not determine this target" (its generator never ran, or lost a lookup).
+ * Out-target lists follow the rules of input target lists: shared by the batch, host pointers, virtual targets and routed
+ * wires in the encoding p2_prove_batch_device accepts, duplicates allowed, n_out == 0 legal; a target without a slot in this
+ * circuit is P2_ERR_INVALID ("output target is not a target of this circuit"), checked before anything is enqueued. */
+#define P2_VALUE_UNSET UINT64_MAX
+/* p2_prove_batch(_device) with read-back: d_out / out_values [batch][n_out] come from the witness run the proof is made from
+ * and are written for every proof whatever its status; proofs and statuses are exactly those of p2_prove_batch(_device), which
+ * are these calls with n_out = 0.  Host form: a witness rejected on the host (a value >= p, one target assigned two values)
+ * never runs as given, and all its outputs are P2_VALUE_UNSET. */
+int p2_prove_batch_outputs_device(p2_circuit*, size_t batch, const p2_target* targets, size_t n_targets, const uint64_t* d_values,
+                                  const p2_target* out_targets, size_t n_out, uint64_t* d_out, uint8_t* d_proofs, int* d_status, void* stream);
+int p2_prove_batch_outputs(p2_circuit*, size_t batch, const p2_assignment* inputs, const p2_target* out_targets, size_t n_out,
+                           uint64_t* out_values, uint8_t* proofs, int* status);
+/* Witness generation only: no proof is made and the zk proof counter does not advance.  status[i] is 0, 1 or 2 and equals
+ * what p2_prove_batch reports for that witness whenever that is 0, 1 or 2.  A failed witness still gets its outputs: a value
+ * >= p or a conflicting entry of the assignment is skipped and the run goes on (after two conflicting entries of one slot the
+ * slot holds one of the two values).  Device form: the kernels run on `stream` (NULL = the default stream) behind the work
+ * already enqueued there, so p2_witness_batch_device -> (copy d_out into the prover's d_values) -> p2_prove_batch_device on one
+ * stream needs no host synchronisation; asynchronous, synchronise `stream` before reading.  Thread safety as p2_verify_batch:
+ * own workspaces (option "witness_chunk" witnesses each), never waits for the proving streams. */
+int p2_witness_batch_device(p2_circuit*, size_t batch, const p2_target* targets, size_t n_targets, const uint64_t* d_values,
+                            const p2_target* out_targets, size_t n_out, uint64_t* d_out, int* d_status, void* stream);
+int p2_witness_batch(p2_circuit*, size_t batch, const p2_assignment* inputs, const p2_target* out_targets, size_t n_out,
+                     uint64_t* out_values, int* status);
+/* Why one witness failed.  The run is followed by a data-parallel check of the final slot values (csrc/witness_check.h; exact
+ * after the fact because a slot never changes once set).  One fault is reported, the first of:
+ *   INPUT_NOT_CANONICAL  an entry whose value is >= p: the lowest index; found = the value
+ *   INPUT_CONFLICT       two entries of one slot with different values: the lowest index of a later entry; found = its value,
+ *                        computed = the earlier entry's
+ *   LOOKUP_MISS / GENERATOR_CONFLICT   the generator with the lowest index in the blob's op order: its operands are set and
+ *                        its input is not in its table (found = the input), or its recomputed output (computed) differs from what
+ *                        the slot holds (found); input_index = the entry that set that slot, if one did
+ *   NOT_SET              a slot no generator produces, that a generator or a routed wire needs, and that is unset: the lowest target
+ * kind == P2_FAULT_NONE iff *status == 0, kinds 1-4 iff *status == 1, kind 5 iff *status == 2. */
+typedef struct {
+    int32_t kind;        /* P2_FAULT_* */
+    int32_t op_kind;     /* generator kind (csrc/circuit.h OP_*) at fault, -1 if none */
+    int64_t input_index; /* entry of the assignment involved, -1 if none */
+    p2_target target;    /* a target of the slot at fault: its lowest virtual target, else its lowest routed wire; UINT64_MAX if none */
+    uint32_t gate_row;   /* a row holding a routed wire of that slot (the PoseidonGate row for OP_POSEIDON), UINT32_MAX if none */
+    uint64_t computed, found;
+} p2_witness_fault;
+enum {
+    P2_FAULT_NONE = 0,
+    P2_FAULT_INPUT_NOT_CANONICAL = 1,
+    P2_FAULT_INPUT_CONFLICT = 2,
+    P2_FAULT_LOOKUP_MISS = 3,
+    P2_FAULT_GENERATOR_CONFLICT = 4,
+    P2_FAULT_NOT_SET = 5
+};
+/* out: a p2_witness_fault*, passed as void* like the streams -- the foreign-function declarations generated from this header
+ * (tools/gen_rust_ffi.py) carry scalar and handle types only. */
+int p2_witness_explain(p2_circuit*, const p2_assignment* input, int* status, void* out);
+/* The host twin of the three calls above for one witness, from the blob (no device; like p2_host_hash_leaves it exists for the
+ * CPU test suite and the prover never calls it): a sequential interpreter of the scheduled op program and the check function the
+ * device kernels use.  fault: a p2_witness_fault* as above, or NULL. */
+int p2_host_witness(const uint8_t* blob, size_t len, const p2_assignment* input, const p2_target* out_targets, size_t n_out,
+                    uint64_t* out_values, int* status, void* fault);
+
 /* Batched verification on the GPU: the verdict of verify_proof for each proof, as a P2_VERIFY_* code.
  * proofs: batch * p2_circuit_proof_bytes() bytes (the fixed layout of DESIGN.md section 8; every Merkle path has the depth the
  * circuit implies, so a sibling-count byte that differs is P2_VERIFY_SHAPE -- also where the host reader, misled by two count
@@ -366,9 +432,10 @@ int p2_decompress_batch_device(p2_circuit*, size_t batch, const uint8_t* d_cproo
 int p2_verify_compressed_batch_device(p2_circuit*, size_t batch, const uint8_t* d_cproofs, const uint32_t* d_lengths,
                                       const uint64_t* verifier_data, size_t vd_len, int* d_status, void* stream);
 /* Tuning knobs of a handle: "chunk" (proofs per workspace, default 128), "streams" (proving streams, default 2),
- * "debug_timing" (host-path phase times on stderr), "verify_chunk" (proofs per p2_verify_batch chunk).  The environment
- * variables P2AES_CHUNK / P2AES_STREAMS / P2AES_DEBUG_TIMING / P2AES_VERIFY_CHUNK set the defaults and are read once, in
- * p2_circuit_load. */
+ * "debug_timing" (host-path phase times on stderr), "verify_chunk" (proofs per p2_verify_batch chunk), "witness_chunk"
+ * (witnesses per chunk of the witness-only calls, default 256: one workgroup per compute unit; capped so that a workspace fits
+ * in 80 % of the free HBM).  The environment variables P2AES_CHUNK / P2AES_STREAMS / P2AES_DEBUG_TIMING / P2AES_VERIFY_CHUNK /
+ * P2AES_WITNESS_CHUNK set the defaults and are read once, in p2_circuit_load. */
 int p2_circuit_set_option(p2_circuit*, const char* name, long value);
 /* Per-kernel timing of the most recent batch (HIP events on the proving stream). */
 typedef struct {

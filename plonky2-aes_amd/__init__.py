@@ -8,7 +8,9 @@ from .api import (  # noqa: F401
     CircuitBuilder,
     CircuitData,
     ECGFP5SecretKey,
+    FAULT_KINDS,
     HASHERS,
+    OP_KINDS,
     P2Error,
     PartialWitness,
     PoseidonEncryptTarget,
@@ -24,7 +26,10 @@ from .api import (  # noqa: F401
     VERIFY_SHAPE,
     VERIFY_VANISHING,
     VERIFY_ZETA_IN_SUBGROUP,
+    VALUE_UNSET,
+    WitnessFault,
     ecgfp5,
+    host_witness,
     keccak_native,
     lib,
     lib_path,

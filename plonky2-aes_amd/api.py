@@ -59,6 +59,12 @@ VERIFY_REASONS = {
     "query indices differ from the transcript": VERIFY_SHAPE,
 }
 
+# p2_witness_explain / p2_host_witness fault kinds (include/p2aes.h P2_FAULT_*), by code
+FAULT_KINDS = ("NONE", "INPUT_NOT_CANONICAL", "INPUT_CONFLICT", "LOOKUP_MISS", "GENERATOR_CONFLICT", "NOT_SET")
+# witness generator kinds (csrc/circuit.h OP_*), by code
+OP_KINDS = ("ARITH", "CONST", "LOOKUP", "EQ", "EQINV", "POSEIDON")
+VALUE_UNSET = 0xFFFFFFFFFFFFFFFF   # P2_VALUE_UNSET: "not assigned" on input, "the run did not determine it" on output
+
 u32p = C.POINTER(C.c_uint32)
 
 
@@ -85,6 +91,67 @@ HASHERS = {"poseidon": 0, "keccak": 1}
 
 class _Assignment(C.Structure):
     _fields_ = [("targets", u64p), ("values", u64p), ("count", sz)]
+
+
+class _Fault(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("op_kind", C.c_int32), ("input_index", C.c_int64), ("target", C.c_uint64), ("gate_row", C.c_uint32),
+                ("computed", C.c_uint64), ("found", C.c_uint64)]
+
+
+class WitnessFault:
+    """p2_witness_fault as a record: kind (a FAULT_KINDS name), op_kind (an OP_KINDS name or None), input_index, target and
+    gate_row (None where the C struct says "none"), computed, found."""
+
+    def __init__(self, f, status):
+        self.status = status
+        self.kind = FAULT_KINDS[f.kind]
+        self.op_kind = OP_KINDS[f.op_kind] if f.op_kind >= 0 else None
+        self.input_index = f.input_index if f.input_index >= 0 else None
+        self.target = f.target if f.target != VALUE_UNSET else None
+        self.gate_row = f.gate_row if f.gate_row != 0xFFFFFFFF else None
+        self.computed, self.found = f.computed, f.found
+
+    def _key(self):
+        return (self.status, self.kind, self.op_kind, self.input_index, self.target, self.gate_row, self.computed, self.found)
+
+    def __eq__(self, other): return isinstance(other, WitnessFault) and self._key() == other._key()
+    def __hash__(self): return hash(self._key())
+
+    def __repr__(self):
+        return "WitnessFault(status=%d, kind=%s, op_kind=%s, input_index=%s, target=%s, gate_row=%s, computed=%d, found=%d)" % self._key()
+
+    def __str__(self):
+        if self.kind == "NONE":
+            return "no fault"
+        where = "target %s" % ("none" if self.target is None else "%#x" % self.target)
+        if self.input_index is not None:
+            where += " (entry %d of the assignment)" % self.input_index
+        return {"INPUT_NOT_CANONICAL": "value %d of %s is not a canonical field element" % (self.found, where),
+                "INPUT_CONFLICT": "%s is set to %d but an earlier entry of its slot sets %d" % (where, self.found, self.computed),
+                "LOOKUP_MISS": "lookup input %d at %s is not in its table" % (self.found, where),
+                "GENERATOR_CONFLICT": "%s generator computes %d for %s, which holds %d" % (self.op_kind, self.computed, where, self.found),
+                "NOT_SET": "%s is needed and was never set" % where}[self.kind]
+
+
+def _assignment(pw_or_map):
+    """(struct, keep-alive) of one PartialWitness or target -> value mapping; values are passed as they are."""
+    m = pw_or_map.map if hasattr(pw_or_map, "map") else pw_or_map
+    ts, vs = _arr(list(m.keys())), _arr(list(m.values()))
+    a = _Assignment()
+    a.targets, a.values, a.count = C.cast(ts, u64p), C.cast(vs, u64p), len(m)
+    return a, (ts, vs)
+
+
+def host_witness(blob, pw, outputs=(), explain=True):
+    """p2_host_witness: the host twin of generate_witness / explain for one witness, from the blob alone (no device).
+    Returns (values of `outputs`, status, WitnessFault or None)."""
+    a, keep = _assignment(pw)
+    outs = list(outputs)
+    vals = (u64 * max(len(outs), 1))()
+    st, f = C.c_int(), _Fault()
+    if lib().p2_host_witness(blob, len(blob), C.byref(a), _arr(outs) if outs else None, len(outs), vals, C.byref(st), C.byref(f) if explain else None):
+        raise P2Error("p2_host_witness failed: " + _err())
+    return list(vals[: len(outs)]), st.value, (WitnessFault(f, st.value) if explain else None)
 
 
 class _KernelTime(C.Structure):
@@ -183,6 +250,12 @@ def lib():
         "p2_prove_batch": (C.c_int, [vp, sz, C.POINTER(_Assignment), C.c_char_p, C.POINTER(C.c_int)]),
         "p2_prove_batch_device": (C.c_int, [vp, sz, u64p, sz, vp, vp, vp, vp]),
         "p2_circuit_synchronize": (C.c_int, [vp]),
+        "p2_prove_batch_outputs": (C.c_int, [vp, sz, C.POINTER(_Assignment), u64p, sz, u64p, C.c_char_p, C.POINTER(C.c_int)]),
+        "p2_prove_batch_outputs_device": (C.c_int, [vp, sz, u64p, sz, vp, u64p, sz, vp, vp, vp, vp]),
+        "p2_witness_batch": (C.c_int, [vp, sz, C.POINTER(_Assignment), u64p, sz, u64p, C.POINTER(C.c_int)]),
+        "p2_witness_batch_device": (C.c_int, [vp, sz, u64p, sz, vp, u64p, sz, vp, vp, vp]),
+        "p2_witness_explain": (C.c_int, [vp, C.POINTER(_Assignment), C.POINTER(C.c_int), vp]),
+        "p2_host_witness": (C.c_int, [C.c_char_p, sz, C.POINTER(_Assignment), u64p, sz, u64p, C.POINTER(C.c_int), vp]),
         "p2_verify_batch": (C.c_int, [vp, sz, C.c_char_p, u64p, sz, C.POINTER(C.c_int)]),
         "p2_verify_batch_device": (C.c_int, [vp, sz, vp, u64p, sz, vp, vp]),
         "p2_compress_batch": (C.c_int, [vp, sz, C.c_char_p, u64p, sz, C.c_char_p, u32p, C.POINTER(C.c_int)]),
@@ -502,25 +575,78 @@ class CircuitData:
         return list(self._vd)
 
     def set_option(self, name, value):
-        """Tuning knobs of the GPU handle: "chunk", "streams", "debug_timing", "verify_chunk" (include/p2aes.h)."""
+        """Tuning knobs of the GPU handle: "chunk", "streams", "debug_timing", "verify_chunk", "witness_chunk" (include/p2aes.h)."""
         if lib().p2_circuit_set_option(self.gpu(), name.encode(), int(value)):
             raise P2Error(_err())
 
-    def prove_batch(self, pws):
-        """Returns (proofs: list[bytes|None], status: list[int])."""
+    @staticmethod
+    def _assignments(pws):
         B = len(pws)
-        asg = (_Assignment * B)()
+        asg = (_Assignment * max(B, 1))()
         keep = []
         for i, pw in enumerate(pws):
-            ts, vs = _arr(list(pw.map.keys())), _arr(list(pw.map.values()))
+            m = pw.map if hasattr(pw, "map") else pw
+            ts, vs = _arr(list(m.keys())), _arr(list(m.values()))
             keep.append((ts, vs))
-            asg[i].targets, asg[i].values, asg[i].count = C.cast(ts, u64p), C.cast(vs, u64p), len(pw.map)
-        buf = C.create_string_buffer(B * self.proof_bytes)
-        status = (C.c_int * B)()
-        if lib().p2_prove_batch(self.gpu(), B, asg, buf, status):
-            raise P2Error("p2_prove_batch failed: " + _err())
+            asg[i].targets, asg[i].values, asg[i].count = C.cast(ts, u64p), C.cast(vs, u64p), len(m)
+        return asg, keep
+
+    def prove_batch(self, pws, outputs=None):
+        """Returns (proofs: list[bytes|None], status: list[int]); with `outputs` (a list of targets to read back from the
+        witness run each proof is made from: p2_prove_batch_outputs) also their values, one list per witness, VALUE_UNSET
+        where the run did not determine one."""
+        B = len(pws)
+        asg, keep = self._assignments(pws)
+        buf = C.create_string_buffer(max(B * self.proof_bytes, 1))
+        status = (C.c_int * max(B, 1))()
+        if outputs is None:
+            if lib().p2_prove_batch(self.gpu(), B, asg, buf, status):
+                raise P2Error("p2_prove_batch failed: " + _err())
+        else:
+            outs = list(outputs)
+            vals = (u64 * max(B * len(outs), 1))()
+            if lib().p2_prove_batch_outputs(self.gpu(), B, asg, _arr(outs) if outs else None, len(outs), vals, buf, status):
+                raise P2Error("p2_prove_batch_outputs failed: " + _err())
         pb, base = self.proof_bytes, C.addressof(buf)   # (buf.raw would copy the whole buffer once per proof)
-        return [C.string_at(base + i * pb, pb) if status[i] == 0 else None for i in range(B)], list(status)
+        res = [C.string_at(base + i * pb, pb) if status[i] == 0 else None for i in range(B)], list(status[:B])
+        if outputs is None:
+            return res
+        return res + ([list(vals[i * len(outs):(i + 1) * len(outs)]) for i in range(B)],)
+
+    def generate_witness(self, pws, outputs):
+        """Witness generation only (p2_witness_batch; upstream: generate_partial_witness, then get_target): set the inputs,
+        name the targets to read.  Returns (values: one list per witness, VALUE_UNSET where the run did not determine a target;
+        statuses: 0, 1 or 2 as prove_batch reports them).  No proof is made."""
+        B, outs = len(pws), list(outputs)
+        asg, keep = self._assignments(pws)
+        vals = (u64 * max(B * len(outs), 1))()
+        status = (C.c_int * max(B, 1))()
+        if lib().p2_witness_batch(self.gpu(), B, asg, _arr(outs) if outs else None, len(outs), vals, status):
+            raise P2Error("p2_witness_batch failed: " + _err())
+        return [list(vals[i * len(outs):(i + 1) * len(outs)]) for i in range(B)], list(status[:B])
+
+    def explain(self, pw):
+        """Why a witness fails (p2_witness_explain): a WitnessFault; kind "NONE" for a witness that generates."""
+        a, keep = _assignment(pw)
+        st, f = C.c_int(), _Fault()
+        if lib().p2_witness_explain(self.gpu(), C.byref(a), C.byref(st), C.byref(f)):
+            raise P2Error("p2_witness_explain failed: " + _err())
+        return WitnessFault(f, st.value)
+
+    def witness_batch_device(self, targets, d_values, outputs, d_out, d_status, batch, stream=None):
+        """Device-resident witness generation: `d_values` [batch][len(targets)] u64 in, `d_out` [batch][len(outputs)] u64 and
+        `d_status` int32[batch] out (raw device pointers); runs on `stream` (a raw hipStream_t or None), asynchronously."""
+        outs = list(outputs)
+        if lib().p2_witness_batch_device(self.gpu(), batch, _arr(list(targets)), len(targets), d_values, _arr(outs) if outs else None, len(outs), d_out, d_status,
+                                         stream):
+            raise P2Error("p2_witness_batch_device failed: " + _err())
+
+    def prove_batch_outputs_device(self, targets, d_values, outputs, d_out, d_proofs, d_status, batch, stream=None):
+        """prove_batch_device that also leaves the values of `outputs` in `d_out` [batch][len(outputs)]."""
+        outs = list(outputs)
+        if lib().p2_prove_batch_outputs_device(self.gpu(), batch, _arr(list(targets)), len(targets), d_values, _arr(outs) if outs else None, len(outs), d_out,
+                                               d_proofs, d_status, stream):
+            raise P2Error("p2_prove_batch_outputs_device failed: " + _err())
 
     @staticmethod
     def prove_batch_multi(datas, pws):

@@ -10,6 +10,7 @@
 #include "poseidon_cipher.h"
 #include "poseidon_fast.h"
 #include "verifier.h"
+#include "witness_check.h"
 #include "witness_schedule.h"
 
 using namespace p2;
@@ -680,6 +681,119 @@ int p2_witness_schedule_check(const uint8_t* blob, size_t len, uint32_t fuse, ui
         out[1] = (u32)s.chains.size();
         out[2] = s.max_chain;
         out[3] = (u32)s.fused_ops;
+        return P2_OK;
+    } catch (std::exception& e) {
+        return set_error(e.what()), P2_ERR_INVALID;
+    }
+}
+// The host twin of the device's witness run (k_witness, k_witness_wired_unset, k_gather_slots, k_witness_check/_report): the
+// scheduled op program interpreted one op after the other, with the kernel's rules -- an op with an unset operand does not run
+// (2), a conflict or a lookup miss (1) outranks it, nothing stops the run -- and then the shared check of witness_check.h.
+int p2_host_witness(const uint8_t* blob, size_t len, const p2_assignment* input, const p2_target* out_targets, size_t n_out, uint64_t* out_values, int* status,
+                    void* fault_out) {
+    p2_witness_fault* fault = (p2_witness_fault*)fault_out;
+    try {
+        if (!blob || !input || !status || (n_out && (!out_targets || !out_values)) || (input->count && (!input->targets || !input->values)))
+            return set_error("p2_host_witness: null argument"), P2_ERR_INVALID;
+        const Circuit c = deserialize(blob, len);
+        std::vector<u32> in_slots(input->count), out_slots(n_out);
+        for (size_t i = 0; i < input->count; i++) {
+            const int32_t s = target_slot(c, input->targets[i]);
+            if (s < 0) return set_error("input target is not a target of this circuit"), P2_ERR_INVALID;
+            in_slots[i] = (u32)s;
+        }
+        for (size_t i = 0; i < n_out; i++) {
+            const int32_t s = target_slot(c, out_targets[i]);
+            if (s < 0) return set_error("output target is not a target of this circuit"), P2_ERR_INVALID;
+            out_slots[i] = (u32)s;
+        }
+        const WitnessTables T = witness_tables(c);
+        const WitnessSchedule sched = schedule_witness(c, 1);
+        const size_t n = c.n();
+        std::vector<u64> val(c.num_slots, W_UNSET);
+        int worst = 0;  // 0 ok, 2 missing input, 3 conflict: the encoding of k_witness's s_status
+        auto put = [&](u32 slot, u64 v) {
+            if (val[slot] == W_UNSET) val[slot] = v;
+            else if (val[slot] != v) worst = 3;
+        };
+        for (size_t i = 0; i < input->count; i++) {
+            if (input->values[i] >= gl::P) worst = 3;  // an assignment has no "absent" marker: 2^64-1 is a non-canonical value like any other
+            else put(in_slots[i], input->values[i]);
+        }
+        for (const Op& o : sched.ops) {
+            if (o.kind == OP_POSEIDON) {
+                u64 w[135];
+                bool ready = true;
+                for (u32 col = 0; col < 12; col++) ready &= (w[col] = val[c.wire_slot[(size_t)col * n + o.a]]) != W_UNSET;
+                ready &= (w[PG_SWAP] = val[c.wire_slot[(size_t)PG_SWAP * n + o.a]]) != W_UNSET;
+                if (!ready) {
+                    worst = std::max(worst, 2);
+                    continue;
+                }
+                poseidon_gate_witness(w);
+                for (u32 col = PG_OUT; col < c.cfg.num_routed_wires; col++)
+                    if (col != PG_SWAP) put((u32)c.wire_slot[(size_t)col * n + o.a], w[col]);
+                continue;
+            }
+            u64 x = 0, y = 0, z = 0, r = 0;
+            if (o.kind != OP_CONST) x = val[o.a];
+            if (o.kind == OP_ARITH || o.kind == OP_EQ || o.kind == OP_EQINV) y = val[o.b];
+            if (o.kind == OP_ARITH) z = val[o.c];
+            if (x == W_UNSET || y == W_UNSET || z == W_UNSET) {
+                worst = std::max(worst, 2);
+                continue;
+            }
+            if (o.kind == OP_ARITH) {
+                r = gl::add(gl::mul(gl::mul(x, y), o.k0), gl::mul(z, o.k1));
+            } else if (o.kind == OP_CONST) {
+                r = o.k0;
+            } else if (o.kind == OP_LOOKUP) {
+                const u64 ent = x < 65536 ? T.lut_ent[(size_t)o.aux * 65536 + x] : ~0ull;
+                if (ent == ~0ull) {
+                    worst = 3;
+                    continue;
+                }
+                r = ent & 0xFFFF;
+            } else if (o.kind == OP_EQ) {
+                r = x == y ? 1 : 0;
+            } else {
+                r = x == y ? 0 : gl::inv(gl::sub(x, y));
+            }
+            put(o.out, r);
+        }
+        int st = worst == 3 ? 1 : worst;
+        if (st == 0)  // k_fill_wires' rule, as k_witness_wired_unset keeps it
+            for (u32 s : T.wired_slots)
+                if (val[s] == W_UNSET) {
+                    st = 2;
+                    break;
+                }
+        *status = st;
+        for (size_t i = 0; i < n_out; i++) out_values[i] = val[out_slots[i]];
+        if (!fault) return P2_OK;
+        const std::vector<u32> prev = input_prev_links(in_slots, c.num_slots);
+        WCheckCtx x{};
+        x.ops = c.ops.data(), x.num_ops = (u32)c.ops.size(), x.num_slots = c.num_slots, x.n = (u32)n;
+        x.val = val.data(), x.lut_ent = T.lut_ent.data(), x.wire_slot = c.wire_slot.data();
+        x.free_slots = T.free_slots.data(), x.num_free = (u32)T.free_slots.size(), x.slot_target = T.slot_target.data(), x.slot_row = T.slot_row.data();
+        x.input_slots = in_slots.data(), x.input_values = input->values, x.n_inputs = (u32)input->count, x.absent_marker = 0;
+        u32 bad_input = W_NO_INDEX, conflict_input = W_NO_INDEX, bad_op = W_NO_INDEX, unset_free = W_NO_INDEX, slot = W_NO_INDEX;
+        for (u32 i = x.n_inputs; i-- > 0;) {
+            u64 earlier;
+            const int k = wcheck_input(x, prev.data(), i, &earlier);
+            if (k == P2_FAULT_INPUT_NOT_CANONICAL) bad_input = i;
+            if (k == P2_FAULT_INPUT_CONFLICT) conflict_input = i;
+        }
+        for (u32 i = 0; i < x.num_ops && bad_op == W_NO_INDEX; i++)
+            if (wcheck_op(x, i).kind) bad_op = i;
+        for (u32 j = 0; j < x.num_free && unset_free == W_NO_INDEX; j++)
+            if (val[T.free_slots[j]] == W_UNSET) unset_free = j;
+        wfault_report(x, prev.data(), st, bad_input, conflict_input, bad_op, unset_free, fault, &slot);
+        for (u32 i = 0; slot != W_NO_INDEX && i < x.n_inputs; i++)
+            if (in_slots[i] == slot && winput_sets(x, i)) {
+                fault->input_index = i;
+                break;
+            }
         return P2_OK;
     } catch (std::exception& e) {
         return set_error(e.what()), P2_ERR_INVALID;

@@ -18,6 +18,7 @@
 #include "kernels2.h"
 #include "kernels_compress.h"
 #include "kernels_keccak.h"
+#include "kernels_witness_io.h"
 #include "verifier.h"
 
 using namespace p2;
@@ -121,6 +122,9 @@ struct Workspace {
     int* d_status = nullptr;
     u64* d_advice = nullptr;
     u64* d_pi_hash = nullptr;          // [chunk][4] public-input hash per proof (k_pi_hash; circuits with public inputs)
+    u32* d_out_slots = nullptr;        // slot of every out-target (p2_prove_batch_outputs*), as last uploaded; grown on demand
+    std::vector<u32> h_out_slots;
+    size_t cap_out_slots = 0;
     Oracle wires, zs, quot;
     u64 *d_permq = nullptr, *d_perm_seg = nullptr, *d_fri_seg = nullptr, *d_lktmp = nullptr;
     u64 *d_qvals = nullptr, *d_qres = nullptr;
@@ -201,6 +205,14 @@ struct p2_circuit {
     // Keccak circuits: the word index of every hash of the unpacked proof, the caps first (k_kcv_range)
     u32* d_kc_hash_idx = nullptr;
     u32 kc_cap_hashes = 0, kc_hashes = 0;
+    // witness-only calls and witness outputs (kernels_witness_io.h): the distinct wired slots (built at load), workspaces
+    // leased per call like the verification ones, and the tables of the fault check, uploaded by the first p2_witness_explain
+    u32* d_wired_slots = nullptr;
+    u32 n_wired = 0;
+    size_t wit_chunk = 256;  // option "witness_chunk"
+    std::vector<struct WitnessWs*> wit_free;
+    std::mutex wit_mu;
+    struct ExplainTables* explain = nullptr;
     long fail_alloc_after = -1;            // test hook, see dalloc_ws
     // timing
     bool timing_on = false;
@@ -452,6 +464,11 @@ static int circuit_setup(p2_circuit* C) {
         if (upload(C->allocs, &C->d_wchains, ws.chains.data(), ws.chains.size())) return P2_ERR_HIP;
     }
     if (upload(C->allocs, &C->d_wire_slot, c.wire_slot.data(), c.wire_slot.size())) return P2_ERR_HIP;
+    {
+        const std::vector<u32> wired = wired_slot_list(c);
+        C->n_wired = (u32)wired.size();
+        if (upload(C->allocs, &C->d_wired_slots, wired.data(), wired.size())) return P2_ERR_HIP;
+    }
     if (!c.pi_slots.empty() && upload(C->allocs, &C->d_pi_slots, c.pi_slots.data(), c.pi_slots.size())) return P2_ERR_HIP;
     {
         // witness generation resolves a lookup with ONE load: input value -> (flat entry index << 16) | output
@@ -641,6 +658,7 @@ static void release_workspaces(p2_circuit* C) {
         }
         if (W->lane.stream) (void)hipStreamDestroy(W->lane.stream);
         if (W->done) (void)hipEventDestroy(W->done);
+        if (W->d_out_slots) (void)hipFree(W->d_out_slots);
         delete W;
     }
     C->ws.clear();
@@ -795,7 +813,9 @@ static int commit_oracle(p2_circuit* C, Workspace& W, Oracle& o, u32 stage, u32 
     return challenger(C, W, stage, o.tree.dig + cap_off(o.tree, cap_h), o.tree.stride(), 4u << cap_h, aux, 0, B);
 }
 // the target slots are already in the workspace (d_input_slots); d_values: [batch][n_inputs] device; proofs/status: device.
-static int prove_chunk(p2_circuit* C, Workspace& W, u32 B, u32 n_inputs, const u64* d_values, uint8_t* d_proofs, int* d_status_out, u64 proof_base) {
+// n_out > 0: the values of W.d_out_slots are read back into d_out [B][n_out] right behind the witness.
+static int prove_chunk(p2_circuit* C, Workspace& W, u32 B, u32 n_inputs, const u64* d_values, u32 n_out, u64* d_out, uint8_t* d_proofs, int* d_status_out,
+                       u64 proof_base) {
     const Circuit& c = C->c;
     const size_t n = C->n, N = C->N;
     const u32 R = c.cfg.num_routed_wires, NC = c.cfg.num_challenges, npp = c.num_partial_products(), nlp = c.num_lookup_polys();
@@ -849,6 +869,7 @@ static int prove_chunk(p2_circuit* C, Workspace& W, u32 B, u32 n_inputs, const u
     if (!c.pi_slots.empty())
         LAUNCH(W.lane, "pi_hash", k_pi_hash, g1((size_t)B * 16, 64), dim3(64), 0, W.d_values, c.num_slots, C->d_pi_slots, (u32)c.pi_slots.size(), B,
                W.d_pi_hash, d_proofs, C->pbytes, C->layout.body_bytes);  // a 16-lane group per proof
+    if (n_out) LAUNCH(W.lane, "gather_slots", k_gather_slots, g1(n_out, 256, B), dim3(256), 0, W.d_values, c.num_slots, W.d_out_slots, n_out, d_out);
     LAUNCH(W.lane, "fill_wires", k_fill_wires, g1((size_t)R * n, 256, B), dim3(256), 0, C->d_wire_slot, W.d_values, W.wires.vals, (size_t)R * n, c.num_slots, ws,
            W.d_status);
     if (act > R)
@@ -1106,11 +1127,14 @@ struct Staging {
     u64 *d_vals = nullptr, *h_vals = nullptr;
     uint8_t *d_proofs = nullptr, *h_proofs = nullptr;
     int *d_stat = nullptr, *h_stat = nullptr;
-    size_t cap_vals = 0, cap_proofs = 0, cap_stat = 0;
+    u64 *d_out = nullptr, *h_out = nullptr;  // witness outputs (p2_prove_batch_outputs); never allocated by p2_prove_batch
+    size_t cap_vals = 0, cap_proofs = 0, cap_stat = 0, cap_out = 0;
     void release() {
         if (d_vals) (void)hipFree(d_vals);
         if (d_proofs) (void)hipFree(d_proofs);
         if (d_stat) (void)hipFree(d_stat);
+        if (d_out) (void)hipFree(d_out);
+        if (h_out) (void)hipHostFree(h_out);
         if (h_vals) (void)hipHostFree(h_vals);
         if (h_proofs) (void)hipHostFree(h_proofs);
         if (h_stat) (void)hipHostFree(h_stat);
@@ -1133,7 +1157,7 @@ struct StagingLease {
     p2_circuit* C;
     Staging* S = nullptr;
     explicit StagingLease(p2_circuit* c) : C(c) {}
-    Staging* get(size_t vals_bytes, size_t proofs_bytes, size_t batch) {
+    Staging* get(size_t vals_bytes, size_t proofs_bytes, size_t batch, size_t out_bytes) {
         {
             std::lock_guard<std::mutex> lock(C->staging_mu);
             if (!C->staging_free.empty()) {
@@ -1144,7 +1168,7 @@ struct StagingLease {
         if (!S) S = new Staging();
         if ((!S->stream && hipStreamCreateWithFlags(&S->stream, hipStreamNonBlocking) != hipSuccess) ||
             !Staging::grow(&S->d_vals, &S->h_vals, &S->cap_vals, vals_bytes) || !Staging::grow(&S->d_proofs, &S->h_proofs, &S->cap_proofs, proofs_bytes) ||
-            !Staging::grow(&S->d_stat, &S->h_stat, &S->cap_stat, batch * sizeof(int))) {
+            !Staging::grow(&S->d_stat, &S->h_stat, &S->cap_stat, batch * sizeof(int)) || !Staging::grow(&S->d_out, &S->h_out, &S->cap_out, out_bytes)) {
             set_error("staging buffers for p2_prove_batch could not be allocated");
             S->release();
             delete S;
@@ -1534,6 +1558,364 @@ static int proof_batch_impl(p2_circuit* C, ProofOp op, size_t batch, const uint8
     return rc;
 }
 
+// ---------------------------------------------------------------------------------- witness-only runs, fault diagnosis
+// (kernels_witness_io.h)  A lean workspace, leased per call like the verification ones: per witness the slot values, the
+// multiplicity counters and the PoseidonGate advice block that k_witness writes -- megabytes where a proving workspace holds
+// the oracles of DESIGN.md section 4.  The witness-only path launches the k_witness instantiations the prover launches and
+// does not join the prover's ev_witness chain.
+struct WitnessWs {
+    hipStream_t stream = nullptr;  // the host forms' stream
+    hipEvent_t done = nullptr;     // behind the last kernel that used the workspace
+    size_t chunk = 0, asked = 0;   // witnesses it holds; the "witness_chunk" option it was made under (chunk is that, capped by free HBM)
+    u64 *d_values = nullptr, *d_advice = nullptr;
+    u32* d_mult = nullptr;
+    // the target lists as last uploaded (re-uploaded only when a call brings other ones), grown on demand
+    u32 *d_input_slots = nullptr, *d_out_slots = nullptr;
+    std::vector<u32> h_input_slots, h_out_slots;
+    size_t cap_input_slots = 0, cap_out_slots = 0;
+    // host forms: staging of inputs, outputs and statuses (device + pinned host), grown on demand
+    u64 *d_in = nullptr, *h_in = nullptr, *d_out = nullptr, *h_out = nullptr;
+    int *d_status = nullptr, *h_status = nullptr;
+    size_t cap_in = 0, cap_out = 0, cap_status = 0;  // bytes
+    // p2_witness_explain
+    u64* d_ex_in = nullptr;
+    u32* d_prev = nullptr;
+    size_t cap_ex_in = 0, cap_prev = 0;
+    unsigned long long* d_keys = nullptr;  // the two reduction keys, then the run's status word
+    p2_witness_fault *d_fault = nullptr, *h_fault = nullptr;
+    void release() {
+        for (void* p : {(void*)d_values, (void*)d_advice, (void*)d_mult, (void*)d_input_slots, (void*)d_out_slots, (void*)d_in, (void*)d_out, (void*)d_status,
+                        (void*)d_ex_in, (void*)d_prev, (void*)d_keys, (void*)d_fault})
+            if (p) (void)hipFree(p);
+        for (void* p : {(void*)h_in, (void*)h_out, (void*)h_status, (void*)h_fault})
+            if (p) (void)hipHostFree(p);
+        if (stream) (void)hipStreamDestroy(stream);
+        if (done) (void)hipEventDestroy(done);
+        *this = WitnessWs();
+    }
+};
+// the tables of the fault check on the device (witness_check.h), uploaded by the first p2_witness_explain of a handle: the
+// ops in blob order are as large as the scheduled copy, so a handle that never explains does not carry them
+struct ExplainTables {
+    Allocs mem;
+    Op* d_ops = nullptr;
+    u32 *d_free_slots = nullptr, *d_slot_row = nullptr;
+    u64* d_slot_target = nullptr;
+    u32 n_free = 0;
+};
+static void witness_release_all(p2_circuit* C) {
+    for (WitnessWs* W : C->wit_free) {
+        W->release();
+        delete W;
+    }
+    C->wit_free.clear();
+    delete C->explain;
+    C->explain = nullptr;
+}
+// device bytes one witness takes in a WitnessWs
+static size_t witness_ws_bytes(const p2_circuit* C) {
+    return 8 * (size_t)C->c.num_slots + 4 * std::max<size_t>(C->total_lut_entries, 1) + 8 * 55 * std::max<size_t>(C->c.poseidon_rows.size(), 1);
+}
+template <class T>
+static bool grow_dev(T** d, size_t* cap, size_t count) {
+    if (*cap >= count) return true;
+    if (*d) (void)hipFree(*d);
+    *d = nullptr, *cap = 0;
+    const size_t want = count + count / 4;
+    if (hipMalloc((void**)d, want * sizeof(T)) != hipSuccess) return false;
+    *cap = want;
+    return true;
+}
+static WitnessWs* witness_lease(p2_circuit* C) {
+    WitnessWs* W = nullptr;
+    std::vector<WitnessWs*> stale;  // made before the "witness_chunk" option changed
+    size_t chunk;
+    {
+        std::lock_guard<std::mutex> lock(C->wit_mu);
+        chunk = C->wit_chunk;
+        while (!C->wit_free.empty() && !W) {
+            W = C->wit_free.back();
+            C->wit_free.pop_back();
+            if (W->asked != chunk) {
+                stale.push_back(W);
+                W = nullptr;
+            }
+        }
+    }
+    for (WitnessWs* S : stale) {
+        (void)hipEventSynchronize(S->done);
+        S->release();
+        delete S;
+    }
+    if (W) return W;
+    // the same cap as the prover's: a workspace takes at most 80 % of the HBM that is free
+    const size_t per = witness_ws_bytes(C);
+    size_t free_b = 0, total_b = 0;
+    W = new WitnessWs();
+    W->asked = chunk;
+    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) chunk = std::max<size_t>(1, std::min(chunk, (size_t)(0.8 * (double)free_b) / per));
+    W->chunk = chunk;
+    const bool ok = hipStreamCreateWithFlags(&W->stream, hipStreamNonBlocking) == hipSuccess && hipEventCreateWithFlags(&W->done, hipEventDisableTiming) == hipSuccess &&
+                    hipMalloc((void**)&W->d_values, chunk * 8 * (size_t)C->c.num_slots) == hipSuccess &&
+                    hipMalloc((void**)&W->d_mult, chunk * 4 * std::max<size_t>(C->total_lut_entries, 1)) == hipSuccess &&
+                    hipMalloc((void**)&W->d_advice, chunk * 8 * 55 * std::max<size_t>(C->c.poseidon_rows.size(), 1)) == hipSuccess;
+    if (!ok) {
+        set_error("witness workspace could not be allocated");
+        W->release();
+        delete W;
+        return nullptr;
+    }
+    return W;
+}
+static void witness_return(p2_circuit* C, WitnessWs* W) {
+    std::lock_guard<std::mutex> lock(C->wit_mu);
+    C->wit_free.push_back(W);
+}
+// targets -> slots; `what` names the list in the error ("input" / "output")
+static int target_slots(const p2_circuit* C, const p2_target* targets, size_t n, const char* what, std::vector<u32>& slots) {
+    slots.resize(n);
+    for (size_t i = 0; i < n; i++) {
+        const int32_t slot = target_slot(C->c, targets[i]);
+        if (slot < 0) return set_error(std::string(what) + " target is not a target of this circuit"), P2_ERR_INVALID;
+        slots[i] = (u32)slot;
+    }
+    return P2_OK;
+}
+// A slot list of a workspace: uploaded only when it differs from the one the workspace holds, and then behind everything that
+// still reads the old one.
+static int witness_put_slots(WitnessWs* W, u32** d, size_t* cap, std::vector<u32>& held, const std::vector<u32>& slots) {
+    if (held == slots && *d) return P2_OK;
+    HIPCHECK(hipEventSynchronize(W->done));
+    if (!grow_dev(d, cap, std::max<size_t>(slots.size(), 1))) return set_error("witness workspace could not be allocated"), P2_ERR_HIP;
+    if (!slots.empty()) HIPCHECK(hipMemcpy(*d, slots.data(), slots.size() * 4, hipMemcpyHostToDevice));
+    held = slots;
+    return P2_OK;
+}
+static int launch_witness(p2_circuit* C, hipStream_t st, u32 B, const WitnessArgs& a) {
+    const bool pos = !C->c.poseidon_rows.empty();
+    if (!pos && C->witness_chains) LAUNCH_ON(st, (k_witness<false, true>), dim3(B), dim3(512), a);
+    if (!pos && !C->witness_chains) LAUNCH_ON(st, (k_witness<false, false>), dim3(B), dim3(512), a);
+    if (pos && C->witness_chains) LAUNCH_ON(st, (k_witness<true, true>), dim3(B), dim3(512), a);
+    if (pos && !C->witness_chains) LAUNCH_ON(st, (k_witness<true, false>), dim3(B), dim3(512), a);
+    return P2_OK;
+}
+// Enqueues witness generation of `batch` witnesses on `st`, a chunk of the workspace at a time: k_witness, the wired-slot
+// rule, the gather.  Every pointer is device memory; the slot lists are in the workspace.
+static int witness_run(p2_circuit* C, WitnessWs* W, size_t batch, u32 n_inputs, const u64* d_values, u32 n_out, u64* d_out, int* d_status, hipStream_t st) {
+    const Circuit& c = C->c;
+    HIPCHECK(hipStreamWaitEvent(st, W->done, 0));  // the workspace's previous user
+    for (size_t done = 0; done < batch; done += W->chunk) {
+        const u32 B = (u32)std::min(W->chunk, batch - done);
+        HIPCHECK(hipMemsetAsync(W->d_mult, 0, (size_t)B * std::max<size_t>(C->total_lut_entries, 1) * 4, st));
+        WitnessArgs a{};
+        a.ops = C->d_ops, a.levels = C->d_wlevels, a.chains = C->d_wchains;
+        a.num_levels = C->witness_levels, a.num_slots = c.num_slots, a.n_inputs = n_inputs;
+        a.input_slots = W->d_input_slots, a.input_values = d_values + done * n_inputs;
+        a.values = W->d_values, a.lut_ent = C->d_lut_ent, a.mult = W->d_mult, a.total_lut_entries = C->total_lut_entries;
+        a.status = d_status + done, a.wire_slot = C->d_wire_slot, a.advice = W->d_advice;
+        a.n = (u32)C->n, a.num_poseidon_rows = (u32)c.poseidon_rows.size();
+        if (int rc = launch_witness(C, st, B, a)) return rc;
+        if (C->n_wired)
+            LAUNCH_ON(st, k_witness_wired_unset, dim3((u32)std::min<size_t>((C->n_wired + 255) / 256, 64), B), dim3(256), W->d_values, c.num_slots, C->d_wired_slots,
+                      C->n_wired, d_status + done);
+        if (n_out) LAUNCH_ON(st, k_gather_slots, g1(n_out, 256, B), dim3(256), W->d_values, c.num_slots, W->d_out_slots, n_out, d_out + done * n_out);
+    }
+    HIPCHECK(hipEventRecord(W->done, st));
+    return P2_OK;
+}
+// RAII lease: the workspace goes back on every way out; after a failure whatever was enqueued is drained first
+struct WitnessLease {
+    p2_circuit* C;
+    WitnessWs* W;
+    hipStream_t drain = nullptr;  // the caller's stream of a device form (NULL = the default stream)
+    bool failed = true;
+    explicit WitnessLease(p2_circuit* c) : C(c), W(witness_lease(c)) {}
+    ~WitnessLease() {
+        if (!W) return;
+        if (failed) {
+            (void)hipStreamSynchronize(drain);
+            (void)hipStreamSynchronize(W->stream);
+        }
+        witness_return(C, W);
+    }
+};
+static int witness_null_handle(const char* name) {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return set_error("no HIP device available: witness generation on a handle has no CPU fallback"), P2_ERR_NO_DEVICE;
+    return set_error(std::string(name) + ": null circuit handle"), P2_ERR_INVALID;
+}
+static int witness_batch_device_impl(p2_circuit* C, size_t batch, const p2_target* targets, size_t n_targets, const uint64_t* d_values, const p2_target* out_targets,
+                                     size_t n_out, uint64_t* d_out, int* d_status, void* stream) {
+    if (!C) return witness_null_handle("p2_witness_batch_device");
+    if ((n_targets && !targets) || (n_out && (!out_targets || !d_out)) || (batch && (!d_status || (n_targets && !d_values))))
+        return set_error("p2_witness_batch_device: null buffer"), P2_ERR_INVALID;
+    std::vector<u32> in_slots, out_slots;
+    if (int rc = target_slots(C, targets, n_targets, "input", in_slots)) return rc;
+    if (int rc = target_slots(C, out_targets, n_out, "output", out_slots)) return rc;
+    if (batch == 0) return P2_OK;
+    HIPCHECK(hipSetDevice(C->device));
+    WitnessLease lease(C);
+    WitnessWs* W = lease.W;
+    if (!W) return P2_ERR_HIP;
+    lease.drain = (hipStream_t)stream;
+    if (int rc = witness_put_slots(W, &W->d_input_slots, &W->cap_input_slots, W->h_input_slots, in_slots)) return rc;
+    if (int rc = witness_put_slots(W, &W->d_out_slots, &W->cap_out_slots, W->h_out_slots, out_slots)) return rc;
+    if (int rc = witness_run(C, W, batch, (u32)n_targets, d_values, (u32)n_out, d_out, d_status, (hipStream_t)stream)) return rc;
+    lease.failed = false;
+    return P2_OK;
+}
+
+// One layout of a batch of assignments for the device: [batch][nt] values on a shared target list.  Fast path: every
+// PartialWitness assigns the same target list in the same order.  Otherwise the batch is put on the union of the targets, a
+// witness that does not assign a target gets the "absent" marker (2^64-1, not a field element), and a witness that assigns
+// one target two different values fails on the host like set_target does.  Either way a value that is not a canonical field
+// element fails that witness here, on the host (host_status).  zero_rejected: such a value goes to the device as 0 (the
+// prover: the witness is rejected whatever runs); otherwise it goes as it is and k_witness skips it.
+struct PackedInputs {
+    size_t nt = 0;
+    const p2_target* targets = nullptr;
+    std::vector<u64> union_targets;
+    std::map<u64, size_t> col;
+    bool same = true;
+    std::vector<int> host_status;
+    size_t nvals(size_t batch) const { return batch * std::max<size_t>(nt, 1); }
+    void plan(size_t batch, const p2_assignment* inputs) {
+        nt = inputs[0].count;
+        for (size_t i = 1; i < batch && same; i++) same = inputs[i].count == nt && memcmp(inputs[i].targets, inputs[0].targets, nt * 8) == 0;
+        host_status.assign(batch, 0);
+        targets = inputs[0].targets;
+        if (!same) {
+            for (size_t i = 0; i < batch; i++)
+                for (size_t k = 0; k < inputs[i].count; k++)
+                    if (col.emplace(inputs[i].targets[k], union_targets.size()).second) union_targets.push_back(inputs[i].targets[k]);
+            nt = union_targets.size();
+            targets = union_targets.data();
+        }
+    }
+    void fill(size_t batch, const p2_assignment* inputs, u64* hv, bool zero_rejected) {
+        if (same) {
+            for (size_t i = 0; i < batch; i++)
+                for (size_t k = 0; k < nt; k++) {
+                    u64 v = inputs[i].values[k];
+                    if (v >= gl::P) {
+                        host_status[i] = P2_PROOF_WITNESS_CONFLICT;
+                        if (zero_rejected) v = 0;
+                    }
+                    hv[i * nt + k] = v;
+                }
+        } else {
+            std::fill(hv, hv + nvals(batch), ~0ull);
+            for (size_t i = 0; i < batch; i++)
+                for (size_t k = 0; k < inputs[i].count; k++) {
+                    u64& cell = hv[i * nt + col[inputs[i].targets[k]]];
+                    u64 v = inputs[i].values[k];
+                    const bool rejected = v >= gl::P || (cell != ~0ull && cell != v);
+                    if (rejected) host_status[i] = P2_PROOF_WITNESS_CONFLICT;
+                    if (rejected && zero_rejected) v = 0;
+                    if (zero_rejected || cell == ~0ull) cell = v;  // (witness-only: the first value of a target stays, as in the slot)
+                }
+        }
+    }
+};
+
+static int witness_batch_impl(p2_circuit* C, size_t batch, const p2_assignment* inputs, const p2_target* out_targets, size_t n_out, uint64_t* out_values, int* status) {
+    if (!C) return witness_null_handle("p2_witness_batch");
+    if (n_out && (!out_targets || (batch && !out_values))) return set_error("p2_witness_batch: null output buffer"), P2_ERR_INVALID;
+    std::vector<u32> in_slots, out_slots;
+    if (int rc = target_slots(C, out_targets, n_out, "output", out_slots)) return rc;
+    if (batch == 0) return P2_OK;
+    if (!inputs || !status) return set_error("p2_witness_batch: null inputs or status"), P2_ERR_INVALID;
+    for (size_t i = 0; i < batch; i++)
+        if (inputs[i].count && (!inputs[i].targets || !inputs[i].values)) return set_error("p2_witness_batch: null assignment"), P2_ERR_INVALID;
+    PackedInputs pk;
+    pk.plan(batch, inputs);
+    if (int rc = target_slots(C, pk.targets, pk.nt, "input", in_slots)) return rc;
+    HIPCHECK(hipSetDevice(C->device));
+    WitnessLease lease(C);
+    WitnessWs* W = lease.W;
+    if (!W) return P2_ERR_HIP;
+    const size_t nvals = pk.nvals(batch), nouts = batch * std::max<size_t>(n_out, 1);
+    HIPCHECK(hipEventSynchronize(W->done));  // the staging buffers may be replaced below
+    if (!Staging::grow(&W->d_in, &W->h_in, &W->cap_in, nvals * 8) || !Staging::grow(&W->d_out, &W->h_out, &W->cap_out, nouts * 8) ||
+        !Staging::grow(&W->d_status, &W->h_status, &W->cap_status, batch * sizeof(int)))
+        return set_error("staging buffers for p2_witness_batch could not be allocated"), P2_ERR_HIP;
+    pk.fill(batch, inputs, W->h_in, false);
+    if (int rc = witness_put_slots(W, &W->d_input_slots, &W->cap_input_slots, W->h_input_slots, in_slots)) return rc;
+    if (int rc = witness_put_slots(W, &W->d_out_slots, &W->cap_out_slots, W->h_out_slots, out_slots)) return rc;
+    HIPCHECK(hipMemcpyAsync(W->d_in, W->h_in, nvals * 8, hipMemcpyHostToDevice, W->stream));
+    if (int rc = witness_run(C, W, batch, (u32)pk.nt, W->d_in, (u32)n_out, W->d_out, W->d_status, W->stream)) return rc;
+    if (n_out) HIPCHECK(hipMemcpyAsync(W->h_out, W->d_out, batch * n_out * 8, hipMemcpyDeviceToHost, W->stream));
+    HIPCHECK(hipMemcpyAsync(W->h_status, W->d_status, batch * sizeof(int), hipMemcpyDeviceToHost, W->stream));
+    HIPCHECK(hipStreamSynchronize(W->stream));
+    if (n_out) memcpy(out_values, W->h_out, batch * n_out * 8);
+    for (size_t i = 0; i < batch; i++) status[i] = pk.host_status[i] ? pk.host_status[i] : W->h_status[i];
+    lease.failed = false;
+    return P2_OK;
+}
+
+static int explain_tables(p2_circuit* C) {
+    std::lock_guard<std::mutex> lock(C->wit_mu);
+    if (C->explain) return P2_OK;
+    const WitnessTables T = witness_tables(C->c, false);
+    ExplainTables* E = new ExplainTables();
+    E->n_free = (u32)T.free_slots.size();
+    if (upload(E->mem, &E->d_ops, C->c.ops.data(), C->c.ops.size()) || upload(E->mem, &E->d_free_slots, T.free_slots.data(), T.free_slots.size()) ||
+        upload(E->mem, &E->d_slot_row, T.slot_row.data(), T.slot_row.size()) || upload(E->mem, &E->d_slot_target, T.slot_target.data(), T.slot_target.size())) {
+        delete E;
+        return P2_ERR_HIP;
+    }
+    C->explain = E;
+    return P2_OK;
+}
+static int witness_explain_impl(p2_circuit* C, const p2_assignment* input, int* status, p2_witness_fault* out) {
+    if (!C) return witness_null_handle("p2_witness_explain");
+    if (!input || !status || !out || (input->count && (!input->targets || !input->values))) return set_error("p2_witness_explain: null argument"), P2_ERR_INVALID;
+    std::vector<u32> in_slots;
+    if (int rc = target_slots(C, input->targets, input->count, "input", in_slots)) return rc;
+    HIPCHECK(hipSetDevice(C->device));
+    if (int rc = explain_tables(C)) return rc;
+    const ExplainTables& E = *C->explain;
+    WitnessLease lease(C);
+    WitnessWs* W = lease.W;
+    if (!W) return P2_ERR_HIP;
+    const u32 ni = (u32)input->count;
+    const std::vector<u32> prev = input_prev_links(in_slots, C->c.num_slots);
+    int force_status = 0;  // an assignment has no "absent" marker: any value >= p is non-canonical, also the one k_witness takes for the marker
+    for (u32 i = 0; i < ni; i++)
+        if (input->values[i] >= gl::P) force_status = 1;
+    HIPCHECK(hipEventSynchronize(W->done));
+    if (!grow_dev(&W->d_ex_in, &W->cap_ex_in, std::max<size_t>(ni, 1))) return set_error("witness workspace could not be allocated"), P2_ERR_HIP;
+    if (!grow_dev(&W->d_prev, &W->cap_prev, std::max<size_t>(ni, 1))) return set_error("witness workspace could not be allocated"), P2_ERR_HIP;
+    if (!W->d_keys && (hipMalloc((void**)&W->d_keys, 24) != hipSuccess || hipMalloc((void**)&W->d_fault, sizeof(p2_witness_fault)) != hipSuccess ||
+                       hipHostMalloc((void**)&W->h_fault, sizeof(p2_witness_fault) + sizeof(int), hipHostMallocDefault) != hipSuccess))
+        return set_error("witness workspace could not be allocated"), P2_ERR_HIP;
+    int* d_status = (int*)(W->d_keys + 2);
+    if (int rc = witness_put_slots(W, &W->d_input_slots, &W->cap_input_slots, W->h_input_slots, in_slots)) return rc;
+    hipStream_t st = W->stream;
+    if (ni) {
+        HIPCHECK(hipMemcpy(W->d_ex_in, input->values, (size_t)ni * 8, hipMemcpyHostToDevice));
+        HIPCHECK(hipMemcpy(W->d_prev, prev.data(), (size_t)ni * 4, hipMemcpyHostToDevice));
+    }
+    HIPCHECK(hipMemsetAsync(W->d_keys, 0xFF, 16, st));
+    if (int rc = witness_run(C, W, 1, ni, W->d_ex_in, 0, nullptr, d_status, st)) return rc;
+    WCheckCtx x{};
+    x.ops = E.d_ops, x.num_ops = (u32)C->c.ops.size(), x.num_slots = C->c.num_slots, x.n = (u32)C->n;
+    x.val = W->d_values, x.lut_ent = C->d_lut_ent, x.wire_slot = C->d_wire_slot;
+    x.free_slots = E.d_free_slots, x.num_free = E.n_free, x.slot_target = E.d_slot_target, x.slot_row = E.d_slot_row;
+    x.input_slots = W->d_input_slots, x.input_values = W->d_ex_in, x.n_inputs = ni, x.absent_marker = 0;
+    LAUNCH_ON(st, k_witness_check, g1(std::max<size_t>((size_t)x.num_ops + x.num_free, 1), 256), dim3(256), x, W->d_keys);
+    LAUNCH_ON(st, k_witness_report, dim3(1), dim3(256), x, (const u32*)W->d_prev, d_status, force_status, (const unsigned long long*)W->d_keys, W->d_fault);
+    HIPCHECK(hipEventRecord(W->done, st));
+    int* h_status = (int*)(W->h_fault + 1);
+    HIPCHECK(hipMemcpyAsync(W->h_fault, W->d_fault, sizeof(p2_witness_fault), hipMemcpyDeviceToHost, st));
+    HIPCHECK(hipMemcpyAsync(h_status, d_status, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPCHECK(hipStreamSynchronize(st));
+    *out = *W->h_fault;
+    *status = *h_status;
+    lease.failed = false;
+    return P2_OK;
+}
+
 extern "C" {
 
 int p2_gpu_device_count(void) {
@@ -1576,6 +1958,7 @@ p2_circuit* p2_circuit_load(const uint8_t* blob, size_t len, int device) {
         if (const char* e = getenv("P2AES_STREAMS")) C->opt_streams = (size_t)std::min(8, std::max(1, atoi(e)));
         if (const char* e = getenv("P2AES_WITNESS_FUSE")) C->opt_witness_fuse = (u32)std::min(1024, std::max(1, atoi(e)));
         C->opt_debug_timing = getenv("P2AES_DEBUG_TIMING") != nullptr;
+        if (const char* e = getenv("P2AES_WITNESS_CHUNK")) C->wit_chunk = (size_t)std::min(4096, std::max(1, atoi(e)));
         if (const char* e = getenv("P2AES_TEST_FAIL_ALLOC_AFTER")) C->fail_alloc_after = atol(e);
         C->layout = make_proof_layout(c);
         C->pbytes = C->layout.bytes;
@@ -1613,6 +1996,7 @@ void p2_circuit_free(p2_circuit* C) {
         W->release();
         delete W;
     }
+    witness_release_all(C);
     if (C->setup.stream) (void)hipStreamDestroy(C->setup.stream);
     if (C->ev_witness) (void)hipEventDestroy(C->ev_witness);
     delete C;
@@ -1653,24 +2037,17 @@ int p2_circuit_set_zk_seed(p2_circuit* C, uint64_t seed) {
     return p2_circuit_set_zk_key(C, key);
 }
 
-static int prove_batch_device_impl(p2_circuit* C, size_t batch, const p2_target* targets, size_t n_targets, const uint64_t* d_values, uint8_t* d_proofs, int* d_status,
-                                   void* stream) {
+// out_targets / n_out / d_out: the targets read back from every witness ([batch][n_out]); n_out = 0 is p2_prove_batch_device
+static int prove_batch_device_impl(p2_circuit* C, size_t batch, const p2_target* targets, size_t n_targets, const uint64_t* d_values, const p2_target* out_targets,
+                                   size_t n_out, uint64_t* d_out, uint8_t* d_proofs, int* d_status, void* stream) {
+    if (!C) return witness_null_handle("p2_prove_batch_outputs_device");
+    if (n_out && (!out_targets || !d_out)) return set_error("p2_prove_batch_outputs_device: null output buffer"), P2_ERR_INVALID;
     std::lock_guard<std::mutex> lock(C->mu);
     hipStream_t caller = (hipStream_t)stream;
     HIPCHECK(hipSetDevice(C->device));
-    std::vector<u32> slots(n_targets);
-    for (size_t i = 0; i < n_targets; i++) {
-        u64 t = targets[i];
-        int32_t slot = -1;
-        if (t >> 63) {  // Target::Wire(row, column)
-            u64 row = (t & ~(1ull << 63)) >> 8, col = t & 0xFF;
-            if (row < C->n && col < C->c.cfg.num_routed_wires) slot = C->c.wire_slot[col * C->n + row];
-        } else if (t < C->c.vt_slot.size()) {
-            slot = C->c.vt_slot[t];
-        }
-        if (slot < 0) return set_error("input target is not a target of this circuit"), P2_ERR_INVALID;
-        slots[i] = (u32)slot;
-    }
+    std::vector<u32> slots, out_slots;
+    if (int rc = target_slots(C, targets, n_targets, "input", slots)) return rc;
+    if (int rc = target_slots(C, out_targets, n_out, "output", out_slots)) return rc;
     // Chunk size / stream count: options "chunk" (default 128 proofs per chunk) and "streams" (default 2).  A batch smaller
     // than chunk x streams is split evenly over the streams, so that the serial stages of one chunk (witness levels,
     // the Fiat-Shamir chain, proof-of-work) overlap the wide kernels of the other.  A later, larger batch regrows the
@@ -1725,7 +2102,14 @@ static int prove_batch_device_impl(p2_circuit* C, size_t batch, const p2_target*
             HIPCHECK(hipMemcpy(W.d_input_slots, slots.data(), n_targets * 4, hipMemcpyHostToDevice));
             W.h_input_slots = slots;
         }
-        int rc = prove_chunk(C, W, B, (u32)n_targets, d_values + done * n_targets, d_proofs + done * C->pbytes, d_status + done, proof_base0 + done);
+        if (n_out && (W.h_out_slots != out_slots || !W.d_out_slots)) {  // likewise the out-target list
+            HIPCHECK(hipStreamSynchronize(W.lane.stream));
+            if (!grow_dev(&W.d_out_slots, &W.cap_out_slots, n_out)) return set_error("out-target list could not be allocated"), P2_ERR_HIP;
+            HIPCHECK(hipMemcpy(W.d_out_slots, out_slots.data(), n_out * 4, hipMemcpyHostToDevice));
+            W.h_out_slots = out_slots;
+        }
+        int rc = prove_chunk(C, W, B, (u32)n_targets, d_values + done * n_targets, (u32)n_out, n_out ? d_out + done * n_out : nullptr, d_proofs + done * C->pbytes,
+                             d_status + done, proof_base0 + done);
         if (rc) return rc;
     }
     for (Workspace* W : C->ws) {
@@ -1736,7 +2120,21 @@ static int prove_batch_device_impl(p2_circuit* C, size_t batch, const p2_target*
 }
 int p2_prove_batch_device(p2_circuit* C, size_t batch, const p2_target* targets, size_t n_targets, const uint64_t* d_values, uint8_t* d_proofs, int* d_status,
                           void* stream) {
-    return guarded_rc([&] { return prove_batch_device_impl(C, batch, targets, n_targets, d_values, d_proofs, d_status, stream); });
+    return guarded_rc([&] { return prove_batch_device_impl(C, batch, targets, n_targets, d_values, nullptr, 0, nullptr, d_proofs, d_status, stream); });
+}
+int p2_prove_batch_outputs_device(p2_circuit* C, size_t batch, const p2_target* targets, size_t n_targets, const uint64_t* d_values, const p2_target* out_targets,
+                                  size_t n_out, uint64_t* d_out, uint8_t* d_proofs, int* d_status, void* stream) {
+    return guarded_rc([&] { return prove_batch_device_impl(C, batch, targets, n_targets, d_values, out_targets, n_out, d_out, d_proofs, d_status, stream); });
+}
+int p2_witness_batch_device(p2_circuit* C, size_t batch, const p2_target* targets, size_t n_targets, const uint64_t* d_values, const p2_target* out_targets, size_t n_out,
+                            uint64_t* d_out, int* d_status, void* stream) {
+    return guarded_rc([&] { return witness_batch_device_impl(C, batch, targets, n_targets, d_values, out_targets, n_out, d_out, d_status, stream); });
+}
+int p2_witness_batch(p2_circuit* C, size_t batch, const p2_assignment* inputs, const p2_target* out_targets, size_t n_out, uint64_t* out_values, int* status) {
+    return guarded_rc([&] { return witness_batch_impl(C, batch, inputs, out_targets, n_out, out_values, status); });
+}
+int p2_witness_explain(p2_circuit* C, const p2_assignment* input, int* status, void* out) {
+    return guarded_rc([&] { return witness_explain_impl(C, input, status, (p2_witness_fault*)out); });
 }
 
 int p2_circuit_synchronize(p2_circuit* C) {
@@ -1748,74 +2146,55 @@ int p2_circuit_synchronize(p2_circuit* C) {
     return P2_OK;
 }
 
-static int prove_batch_impl(p2_circuit* C, size_t batch, const p2_assignment* inputs, uint8_t* proofs, int* status) {
+static int prove_batch_impl(p2_circuit* C, size_t batch, const p2_assignment* inputs, const p2_target* out_targets, size_t n_out, uint64_t* out_values,
+                            uint8_t* proofs, int* status) {
+    if (!C) return witness_null_handle("p2_prove_batch_outputs");
+    if (n_out && (!out_targets || (batch && !out_values))) return set_error("p2_prove_batch_outputs: null output buffer"), P2_ERR_INVALID;
+    if (n_out) {  // an out-target outside the circuit is an error of the call, whatever the batch
+        std::vector<u32> out_slots;
+        if (int rc = target_slots(C, out_targets, n_out, "output", out_slots)) return rc;
+    }
     if (batch == 0) return P2_OK;
     HIPCHECK(hipSetDevice(C->device));
-    // Fast path: every PartialWitness assigns the same target list in the same order.  Otherwise the batch is put on
-    // the union of the targets, a witness that does not assign a target gets the "absent" marker (2^64-1, not a field
-    // element), and a witness that assigns one target two different values fails on the host like set_target does.
-    // Either way a value that is not a canonical field element fails that witness here, on the host.
-    size_t nt = inputs[0].count;
-    bool same = true;
-    for (size_t i = 1; i < batch && same; i++) same = inputs[i].count == nt && memcmp(inputs[i].targets, inputs[0].targets, nt * 8) == 0;
-    std::vector<u64> union_targets;
-    std::map<u64, size_t> col;
-    std::vector<int> host_status(batch, 0);
-    const p2_target* targets = inputs[0].targets;
-    if (!same) {
-        for (size_t i = 0; i < batch; i++)
-            for (size_t k = 0; k < inputs[i].count; k++)
-                if (col.emplace(inputs[i].targets[k], union_targets.size()).second) union_targets.push_back(inputs[i].targets[k]);
-        nt = union_targets.size();
-        targets = union_targets.data();
-    }
-    const size_t nvals = batch * std::max<size_t>(nt, 1);
+    PackedInputs pk;  // the layout of the batch on one target list, and the witnesses the host rejects
+    pk.plan(batch, inputs);
+    const size_t nt = pk.nt, nvals = pk.nvals(batch);
     StagingLease lease(C);
-    Staging* S = lease.get(nvals * 8, batch * C->pbytes, batch);
+    Staging* S = lease.get(nvals * 8, batch * C->pbytes, batch, batch * n_out * 8);
     if (!S) return P2_ERR_HIP;
     const auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     const bool dbg = C->opt_debug_timing;
     double t_a = now();
-    u64* hv = S->h_vals;  // pinned: the values are laid out straight into the buffer the DMA engine reads
-    if (same) {
-        for (size_t i = 0; i < batch; i++)
-            for (size_t k = 0; k < nt; k++) {
-                u64 v = inputs[i].values[k];
-                if (v >= gl::P) host_status[i] = P2_PROOF_WITNESS_CONFLICT, v = 0;
-                hv[i * nt + k] = v;
-            }
-    } else {
-        std::fill(hv, hv + nvals, ~0ull);
-        for (size_t i = 0; i < batch; i++)
-            for (size_t k = 0; k < inputs[i].count; k++) {
-                u64& cell = hv[i * nt + col[inputs[i].targets[k]]];
-                u64 v = inputs[i].values[k];
-                if (v >= gl::P || (cell != ~0ull && cell != v)) host_status[i] = P2_PROOF_WITNESS_CONFLICT, v = 0;
-                cell = v;
-            }
-    }
+    pk.fill(batch, inputs, S->h_vals, true);  // pinned: the values are laid out straight into the buffer the DMA engine reads
     double t_b = now();
     // one stream carries upload -> prove -> download; p2_prove_batch_device orders the proving streams with it
-    HIPCHECK(hipMemcpyAsync(S->d_vals, hv, nvals * 8, hipMemcpyHostToDevice, S->stream));
-    int rc = p2_prove_batch_device(C, batch, targets, nt, S->d_vals, S->d_proofs, S->d_stat, (void*)S->stream);
+    HIPCHECK(hipMemcpyAsync(S->d_vals, S->h_vals, nvals * 8, hipMemcpyHostToDevice, S->stream));
+    int rc = p2_prove_batch_outputs_device(C, batch, pk.targets, nt, S->d_vals, out_targets, n_out, S->d_out, S->d_proofs, S->d_stat, (void*)S->stream);
     if (rc != P2_OK) return rc;  // (the lease drains S->stream on every way out)
     HIPCHECK(hipMemcpyAsync(S->h_proofs, S->d_proofs, batch * C->pbytes, hipMemcpyDeviceToHost, S->stream));
     HIPCHECK(hipMemcpyAsync(S->h_stat, S->d_stat, batch * sizeof(int), hipMemcpyDeviceToHost, S->stream));
+    if (n_out) HIPCHECK(hipMemcpyAsync(S->h_out, S->d_out, batch * n_out * 8, hipMemcpyDeviceToHost, S->stream));
     double t_c = now();
     HIPCHECK(hipStreamSynchronize(S->stream));
     double t_d = now();
     memcpy(proofs, S->h_proofs, batch * C->pbytes);
     memcpy(status, S->h_stat, batch * sizeof(int));
+    if (n_out) memcpy(out_values, S->h_out, batch * n_out * 8);
     for (size_t i = 0; i < batch; i++)
-        if (host_status[i]) {
-            status[i] = host_status[i];
+        if (pk.host_status[i]) {
+            status[i] = pk.host_status[i];
             memset(proofs + i * C->pbytes, 0, C->pbytes);
+            std::fill(out_values + i * n_out, out_values + (i + 1) * n_out, P2_VALUE_UNSET);  // what ran was not this witness
         }
     if (dbg) fprintf(stderr, "[p2aes] pack %.3f enqueue %.3f wait %.3f unpack %.3f s\n", t_b - t_a, t_c - t_b, t_d - t_c, now() - t_d);
     return P2_OK;
 }
+int p2_prove_batch_outputs(p2_circuit* C, size_t batch, const p2_assignment* inputs, const p2_target* out_targets, size_t n_out, uint64_t* out_values, uint8_t* proofs,
+                           int* status) {
+    return guarded_rc([&] { return prove_batch_impl(C, batch, inputs, out_targets, n_out, out_values, proofs, status); });
+}
 int p2_prove_batch(p2_circuit* C, size_t batch, const p2_assignment* inputs, uint8_t* proofs, int* status) {
-    return guarded_rc([&] { return prove_batch_impl(C, batch, inputs, proofs, status); });
+    return guarded_rc([&] { return prove_batch_impl(C, batch, inputs, nullptr, 0, nullptr, proofs, status); });
 }
 
 // In-process multi-device form of p2_prove_batch: contiguous balanced ranges of the batch, one host thread per handle.
@@ -1865,8 +2244,12 @@ int p2_circuit_set_option(p2_circuit* C, const char* name, long value) {
         if (value < 1 || value > 4096) return set_error("option verify_chunk: 1..4096 proofs"), P2_ERR_INVALID;
         std::lock_guard<std::mutex> vlock(C->vfy_mu);
         C->vfy_chunk = (size_t)value;
+    } else if (k == "witness_chunk") {
+        if (value < 1 || value > 4096) return set_error("option witness_chunk: 1..4096 witnesses"), P2_ERR_INVALID;
+        std::lock_guard<std::mutex> wlock(C->wit_mu);
+        C->wit_chunk = (size_t)value;
     } else {
-        return set_error("unknown option (known: chunk, streams, debug_timing, verify_chunk)"), P2_ERR_INVALID;
+        return set_error("unknown option (known: chunk, streams, debug_timing, verify_chunk, witness_chunk)"), P2_ERR_INVALID;
     }
     return P2_OK;
 }
