@@ -210,6 +210,10 @@ int p2_selftest_device(uint64_t seed, size_t threads, int device);
  * as 0 (the words declared zero are not read); rows bit r = output word r is kept (canonical), the others are unspecified;
  * parts 0 = the round loops as the kernels run them, 1 = first round, middle and last round as separate functions. */
 int p2_host_poseidon_known(uint64_t* states, size_t n_perm, int kind, uint32_t rows, int parts);
+/* The partial-round section of that permutation alone, in place on count x 12 words that may be ANY u64: from "the state carries
+ * round 4's constants" to "the state carries round 26's" (some representative of each word, not canonical).  After four full
+ * rounds a test cannot steer what reaches the folds of the section; through this entry point, and p2_gpu_partial_rounds, it can. */
+int p2_host_partial_rounds(uint64_t* states, size_t count);
 /* k_hash_leaves' sponge on the host: data [min(active_cols, cols)][num_leaves] -> digests [num_leaves][4] */
 int p2_host_hash_leaves(const uint64_t* data, size_t cols, size_t active_cols, size_t num_leaves, uint64_t* digests);
 
@@ -461,6 +465,8 @@ int p2_gpu_merkle_cap_hasher(const uint64_t* cols_major, size_t cols, size_t num
 /* the tree kernels on their own, one launch each (tests/test_gpu_sponge.py):
  * data [batch][min(active_cols, cols)][num_leaves], columns >= active_cols are zero and not stored -> digests [batch][num_leaves][4] */
 int p2_gpu_hash_leaves(const uint64_t* data, size_t cols, size_t active_cols, size_t num_leaves, size_t batch, uint64_t* digests, int device);
+/* p2_host_partial_rounds on the device: one thread per state, at the hash kernels' occupancy (tests/test_gpu_partial_rounds.py) */
+int p2_gpu_partial_rounds(uint64_t* states, size_t count, int device);
 /* child [batch][2 * num_parents][4] -> parent [batch][num_parents][4] */
 int p2_gpu_merkle_level(const uint64_t* child, size_t num_parents, size_t batch, uint64_t* parent, int device);
 /* vals [batch][2][len] -> digests [batch][len / arity][4] */

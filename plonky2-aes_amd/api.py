@@ -268,6 +268,8 @@ def lib():
         "p2_circuit_get_timing": (sz, [vp, C.POINTER(_KernelTime), sz]),
         "p2_gpu_device_count": (C.c_int, []),
         "p2_gpu_poseidon": (C.c_int, [u64p, sz, C.c_int]),
+        "p2_host_partial_rounds": (C.c_int, [u64p, sz]),
+        "p2_gpu_partial_rounds": (C.c_int, [u64p, sz, C.c_int]),
         "p2_gpu_lde": (C.c_int, [u64p, sz, C.c_int, C.c_int, u64p, C.c_int]),
         "p2_gpu_intt": (C.c_int, [u64p, sz, C.c_int, u64p, C.c_int]),
         "p2_gpu_merkle_cap": (C.c_int, [u64p, sz, sz, C.c_int, u64p, C.c_int]),

@@ -526,6 +526,11 @@ int p2_host_poseidon_known(uint64_t* states, size_t n_perm, int kind, uint32_t r
     }
     return P2_OK;
 }
+// The 22 partial rounds alone (glf::partial_block), on arbitrary u64 words: what reaches its folds is the caller's choice.
+int p2_host_partial_rounds(uint64_t* states, size_t count) {
+    for (size_t i = 0; i < count; i++) glf::partial_block(states + 12 * i);
+    return P2_OK;
+}
 // k_hash_leaves on the host, with the same sponge steps (glf::sponge_permute): data [active][num_leaves] column-major, columns
 // >= active_cols are zero and not stored; digests [num_leaves][4].
 int p2_host_hash_leaves(const uint64_t* data, size_t cols, size_t active_cols, size_t num_leaves, uint64_t* digests) {

@@ -175,6 +175,16 @@ __global__ void k_poseidon_states(u64* states, size_t n) {
     for (int k = 0; k < 12; k++) states[12 * i + k] = st[k];
 }
 
+// the partial-round section alone, one thread per state, built like the hash kernels (test entry point)
+__global__ __launch_bounds__(256) P2_HASH_WAVES void k_partial_rounds(u64* states, size_t n) {
+    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    u64 st[12];
+    for (int k = 0; k < 12; k++) st[k] = states[12 * i + k];
+    glf::partial_block(st);
+    for (int k = 0; k < 12; k++) states[12 * i + k] = st[k];
+}
+
 // ------------------------------------------------------------------------------------------- NTT
 // One workgroup transforms one column (n = 2^logn <= 2^14 points, 8 B each => up to 128 KiB of the CU's
 // 160 KiB LDS), decimation in frequency: natural order in, bit-reversed order out, log n LDS stages.

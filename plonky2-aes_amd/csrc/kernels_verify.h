@@ -406,6 +406,7 @@ __global__ __launch_bounds__(256) void k_vfy_vanishing(VerifyArgs a) {
 // ------------------------------------------------------------------------------------------- 4. queries
 // The tree hasher of the circuit's configuration, as the path walks of the verifier (vfy_merkle) and of the compressor
 // (cmp_merkle, kernels_compress.h) use it: a policy type per hasher, KeccakTree (kernels_keccak.h) with the same members.
+// (glf::poseidon_sparse: the permutation with the sparse partial rounds -- k_vfy_queries' register count is held to that form.)
 struct PoseidonTree {
     // the digest of a leaf: the leaf itself if it fits in a digest, else the overwrite-mode sponge
     static __device__ __forceinline__ void hash_or_noop(const u64* in, u32 len, u64* out) {
@@ -422,7 +423,7 @@ struct PoseidonTree {
 #pragma unroll
             for (u32 i = 0; i < 8; i++)
                 if (i < k) st[i] = in[off + i];  // overwrite mode: a short last chunk keeps the state's other rate words
-            glf::poseidon(st);
+            glf::poseidon_sparse(st);
         }
 #pragma unroll
         for (int i = 0; i < 4; i++) out[i] = st[i];
@@ -436,7 +437,7 @@ struct PoseidonTree {
             st[4 + i] = right ? cur[i] : sib[i];
             st[8 + i] = 0;
         }
-        glf::poseidon(st);
+        glf::poseidon_sparse(st);
 #pragma unroll
         for (int i = 0; i < 4; i++) cur[i] = st[i];
     }

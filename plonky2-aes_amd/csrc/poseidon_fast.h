@@ -1,20 +1,24 @@
-// Poseidon-12 for the hashing kernels: same permutation as gl::poseidon (gl.h), restructured for VALU issue slots
-// (15.5 k VALU instructions per permutation, PMC-counted: profiles/r02_valu.json, r03_valu.json; the plain 30-round form
-// compiles to 41 k, round 1's restructuring to 28 k):
+// Poseidon-12 for the hashing kernels: same permutation as gl::poseidon (gl.h), restructured for VALU issue slots (the plain
+// 30-round form compiles to 41 k VALU instructions per permutation, round 1's restructuring to 28 k, the sparse partial rounds
+// that this file used until the block form to 15.5 k, PMC-counted: profiles/r02_valu.json, r03_valu.json):
 //   * lazy reduction -- state words are arbitrary u64 representatives (not < p) inside the permutation; every product is
 //     reduced once from 128 bits without canonicalisation; outputs are canonicalised;
 //   * multiply-reduce built from v_mad_u64_u32 (gl::mulr_add_dev): the mad is a 64-bit adder with a free multiplier and a
 //     carry-out, and costs what ONE 32-bit add-with-carry costs (tools/microbench/valu_rates.hip);
 //   * round constants are never added on their own: every linear layer starts its accumulators from the constants of the
 //     layer that follows;
-//   * the 22 partial rounds use the sparse-matrix form derived by tools/gen_poseidon_fast.py: 23 multiply-accumulates per
-//     round instead of a 144-term MDS, the 12-term dot product in a carry-counting accumulator reduced once, and the dense
-//     11x11 layer that opens them merged into the fourth full round's linear step (PF_E);
+//   * the 22 partial rounds run in blocks of three (tools/gen_poseidon_fast.py, "block form"): the linear maps between the
+//     S-boxes of a block are composed into small-integer matrices (entries below 2^21), so that every term is one
+//     v_mad_u64_u32 per 32-bit half, as in a full round's MDS, with no carry counts and one fold per output word; inside a
+//     block only row 0, the next S-box's input, is evaluated, and all twelve rows once at its end.  The sparse-matrix form
+//     (fewest multiplications, but every constant a 64-bit field element: 8 slots a term, 12 with its reduction) remains
+//     for poseidon_coop, where a lane holds one word, and as poseidon_sparse for the verifier's Merkle path walks;
 //   * the tree kernels never run the whole of it: permute_known / sponge_permute leave out the S-boxes and MDS terms of words
 //     that enter as 0 (the capacity in front of a first chunk, a chunk of known-zero columns) and the last round's MDS rows
 //     of outputs the sponge overwrites or never reads;
 //   * poseidon_coop: one state over 12 lanes of a 16-lane group, for the sequential Fiat-Shamir chain.
-// The host build of the same functions (plain 128-bit arithmetic) is what p2_selftest_host and the CPU tests exercise.
+// The host build of the same functions (plain 64-bit arithmetic on the same tables) is what p2_selftest_host and the CPU tests
+// exercise.
 #pragma once
 #include "gl.h"
 
@@ -214,12 +218,13 @@ GL_HD u64 add_wrap(u64 a, u64 c) {
     return ((u64)r1 << 32) | r0;
 }
 
-// value = al + 2^32 * ah with al, ah < 2^43 (sums of at most 13 products of a 32-bit half with a coefficient < 2^6, plus
-// a 32-bit half of a round constant)  ->  some u64 congruent to it.
-//   ah' = ah + (al >> 32);  value = x0 + 2^32 x1 + 2^64 x2  with x0 = lo32(al), (x1, x2) = halves of ah', x2 < 2^12
+// value = al + 2^32 * ah with al, ah < 2^57  ->  some u64 congruent to it.  A full round's MDS gives al, ah < 2^43 (at most 13
+// products of a 32-bit half with a coefficient < 2^6, plus a 32-bit half of a round constant), the end of a block of three
+// partial rounds al, ah < 2^56 (coefficients summing to less than 2^24; the generator proves the bounds used here row by row).
+//   ah' = ah + (al >> 32) < 2^58;  value = x0 + 2^32 x1 + 2^64 x2  with x0 = lo32(al), (x1, x2) = halves of ah', x2 < 2^26
 //   = {x1:x0} + x2 * (2^32 - 1): ONE v_mad_u64_u32 (the 64-bit add rides on the multiply; a 32-bit add-with-carry costs
-//   the same issue time as the whole mad, valu_rates.hip), and its carry-out -- possible only when x1 >= 2^32 - 2^12 --
-//   is folded back by a second mad, which cannot wrap (the wrapped sum is < 2^44).
+//   the same issue time as the whole mad, valu_rates.hip), and its carry-out -- possible only when x1 >= 2^32 - x2 --
+//   is folded back by a second mad, which cannot wrap (the wrapped sum is < x2 * 2^32 < 2^58).
 GL_HD u64 fold_al_ah(u64 al, u64 ah) {
 #if defined(__HIP_DEVICE_COMPILE__)
     const u64 ah2 = gl::add_u32(ah, (u32)(al >> 32));  // through the multiplier: no zero-extension of al's high half
@@ -229,7 +234,8 @@ GL_HD u64 fold_al_ah(u64 al, u64 ah) {
     const u32 x2 = (u32)(ah2 >> 32);
     const u64 base = (ah2 << 32) | (u32)al;
 #if defined(__HIP_DEVICE_COMPILE__)
-    // the carry needs x1 >= 2^32 - 2^12: once in 2^20 on random data, so its fold sits behind a wave-uniform branch
+    // the carry needs x1 >= 2^32 - x2: once in 2^20 on random data after a full round and about one lane in 250 at the end of a
+    // block of partial rounds (a wave in four), so its fold sits behind a wave-uniform branch
     gl::sg sc, dead;
     u64 r = gl::mad_eps_co(x2, base, sc);
     if (__builtin_expect(sc != 0, 0)) r = gl::mad_eps_co(gl::one_where(sc), r, dead);
@@ -258,7 +264,7 @@ GL_HD void mds_full(u64* s, const unsigned long long* rc, const u32 rows = 0xFFF
     }
     // One asm block per output word: 24 (26) mads on two accumulators.  As separate statements each mad is followed by the
     // compiler's boundary pad (it defines an SGPR pair, the unused carry-out, and the compiler cannot see that nobody reads
-    // it): 2 500 s_nop per permutation.  29 operands -- the limit is 30.
+    // it): 2 500 s_nop per permutation.  29 operands -- the limit is 30.  (The macros serve mds_row0 as well.)
 #define P2_MDS_T(n, K) "v_mad_u64_u32 %[al], %[d], %[l" #n "], " #K ", %[al]\n\tv_mad_u64_u32 %[ah], %[d], %[h" #n "], " #K ", %[ah]\n\t"
 #define P2_MDS_TAIL P2_MDS_T(1, 15) P2_MDS_T(2, 41) P2_MDS_T(3, 16) P2_MDS_T(4, 2) P2_MDS_T(5, 28) P2_MDS_T(6, 13) P2_MDS_T(7, 13) \
                     P2_MDS_T(8, 39) P2_MDS_T(9, 18) P2_MDS_T(10, 34) P2_MDS_T(11, 20)
@@ -298,9 +304,6 @@ GL_HD void mds_full(u64* s, const unsigned long long* rc, const u32 rows = 0xFFF
         }
         res[r] = fold_al_ah(al, ah);
     }
-#undef P2_MDS_T
-#undef P2_MDS_TAIL
-#undef P2_MDS_IN
 #pragma unroll
     for (int i = 0; i < 12; i++) s[i] = res[i];
     return;
@@ -337,13 +340,19 @@ GL_HD void mds_full(u64* s, const unsigned long long* rc, const u32 rows = 0xFFF
 GL_HD u64 mds_row0(const u64* s, u64 rc) {
 #if defined(__HIP_DEVICE_COMPILE__)
     {
-        u64 al = gl::madk_s<17>((u32)s[0], (u64)(u32)rc), ah = gl::madk_s<17>((u32)(s[0] >> 32), rc >> 32);
-#define P2_MDS_TERM(i, K)                       \
-    al = gl::madk<K>((u32)s[i], al);            \
-    ah = gl::madk<K>((u32)(s[i] >> 32), ah);
-        P2_MDS_TERM(1, 15) P2_MDS_TERM(2, 41) P2_MDS_TERM(3, 16) P2_MDS_TERM(4, 2) P2_MDS_TERM(5, 28) P2_MDS_TERM(6, 13)
-        P2_MDS_TERM(7, 13) P2_MDS_TERM(8, 39) P2_MDS_TERM(9, 18) P2_MDS_TERM(10, 34) P2_MDS_TERM(11, 20) P2_MDS_TERM(0, 8)
-#undef P2_MDS_TERM
+        u32 l[12], h[12];
+#pragma unroll
+        for (int i = 0; i < 12; i++) {
+            l[i] = (u32)s[i];
+            h[i] = (u32)(s[i] >> 32);
+        }
+        const u64 rl = (u64)(u32)rc, rh = rc >> 32;
+        u64 al, ah;
+        gl::sg dead;
+        asm("v_mad_u64_u32 %[al], %[d], %[l0], 17, %[rl]\n\tv_mad_u64_u32 %[ah], %[d], %[h0], 17, %[rh]\n\t" P2_MDS_TAIL
+            "v_mad_u64_u32 %[al], %[d], %[l0], 8, %[al]\n\tv_mad_u64_u32 %[ah], %[d], %[h0], 8, %[ah]"
+            : [al] "=&v"(al), [ah] "=&v"(ah), [d] "=&s"(dead)
+            : [rl] "s"(rl), [rh] "s"(rh), P2_MDS_IN(0));
         return fold_al_ah(al, ah);
     }
 #endif
@@ -358,6 +367,11 @@ GL_HD u64 mds_row0(const u64* s, u64 rc) {
     ah += (s[0] >> 32) * 8;
     return fold_al_ah(al, ah);
 }
+#if defined(__HIP_DEVICE_COMPILE__)
+#undef P2_MDS_T
+#undef P2_MDS_TAIL
+#undef P2_MDS_IN
+#endif
 
 // One full round on a state that already carries this round's constants: S-box, then MDS + next constants.
 GL_HD void full_round(u64* s, const unsigned long long* rc_next) {
@@ -390,7 +404,7 @@ GL_HD u64 mulr_add_k(u64 k, u64 b, u64 c) {
 // only the words that the next chunk does not overwrite (or the digest words 0..3) are read.
 //   first_round    + constants, S-box, MDS, with the words known to be 0 left out: such a word leaves the S-box as the constant
 //                  RC[k]^7, and its MDS terms are part of the row's addend (RC1_ZCAP / RC1_ZRATE, tools/gen_poseidon_fast.py);
-//   middle         full rounds 1..3 (the dense layer merged into the last of them), the 22 partial rounds, full rounds 26..28;
+//   middle         full rounds 1..3, the 22 partial rounds, full rounds 26..28;
 //   last_round     S-box, then only the MDS rows somebody reads, canonicalised.
 // `kind` and `rows` are compile-time constants (first_round<KIND>, last_round<ROWS>) or WAVE-UNIFORM run-time values (the leaf
 // kernels, whose chunks differ): then every group of terms sits behind a scalar branch and there is still one copy of each.
@@ -534,43 +548,114 @@ GL_HD void first_round(u64* s) {
     first_round_any(s, KIND);
 }
 
-// The partial-round block: the fourth full round with the dense layer merged in, the 22 partial rounds, round 26's constants.
+// ---- The 22 partial rounds, in blocks of three (and one round left over), on a state that carries round 4's constants; out:
+// the state carries round 26's.  With y = (s_0^7, s_1, .., s_11), the state in front of a block's linear maps, and t_1, t_2 the
+// outputs of its second and third S-box (tools/gen_poseidon_fast.py has the derivation and proves the accumulator bounds):
+//   input of the second S-box   M[0] . y + K1                                       mds_row0: inline coefficients
+//   input of the third          PB_ROW0_D2 . y + 25 t_1 + K2                        block_row0_d2
+//   the block's end, row r      PB_END[r][1..] . y + PB_END[r][0] t_1 + M[r][0] t_2 + K[r]     block_end
+// Every term is one v_mad_u64_u32 per half: the half in a VGPR, the coefficient in an SGPR (scalar loads) or, where it is an
+// MDS entry, an inline constant.  A VOP3 instruction reads one SGPR operand, so a row cannot start from its K in the mad of a
+// term whose coefficient is in an SGPR: the term with the inline coefficient opens the row and carries K as its addend.
+// The block of one round (the last: 22 = 7 * 3 + 1) is the same end stage on the table of M itself with t_1 = t_2 = 0.
+#if defined(__HIP_DEVICE_COMPILE__)
+#define P2_PB_T(n) "v_mad_u64_u32 %[al], %[d], %[l" #n "], %[k" #n "], %[al]\n\tv_mad_u64_u32 %[ah], %[d], %[h" #n "], %[k" #n "], %[ah]\n\t"
+#define P2_PB_LAST(n) "v_mad_u64_u32 %[al], %[d], %[l" #n "], %[k" #n "], %[al]\n\tv_mad_u64_u32 %[ah], %[d], %[h" #n "], %[k" #n "], %[ah]"
+#define P2_PB_IN(n) [l##n] "v"(l[n]), [h##n] "v"(h[n]), [k##n] "s"(c[n])
+// Asm statements take 30 operands, a row of fourteen terms needs 45: two statements a row (29 + 21 operands, 25 + 21).
+GL_D u64 block_row0_d2(const u32* l, const u32* h, const u64 t1, const unsigned int* c, const u64 k) {
+    const u64 rl = (u64)(u32)k, rh = k >> 32;
+    u64 al, ah;
+    gl::sg dead;
+    asm("v_mad_u64_u32 %[al], %[d], %[lt], 25, %[rl]\n\tv_mad_u64_u32 %[ah], %[d], %[ht], 25, %[rh]\n\t"  //
+        P2_PB_T(0) P2_PB_T(1) P2_PB_T(2) P2_PB_T(3) P2_PB_T(4) P2_PB_LAST(5)
+        : [al] "=&v"(al), [ah] "=&v"(ah), [d] "=&s"(dead)
+        : [rl] "s"(rl), [rh] "s"(rh), [lt] "v"((u32)t1), [ht] "v"((u32)(t1 >> 32)), P2_PB_IN(0), P2_PB_IN(1), P2_PB_IN(2), P2_PB_IN(3),
+          P2_PB_IN(4), P2_PB_IN(5));
+    asm(P2_PB_T(6) P2_PB_T(7) P2_PB_T(8) P2_PB_T(9) P2_PB_T(10) P2_PB_LAST(11)
+        : [al] "+v"(al), [ah] "+v"(ah), [d] "=&s"(dead)
+        : P2_PB_IN(6), P2_PB_IN(7), P2_PB_IN(8), P2_PB_IN(9), P2_PB_IN(10), P2_PB_IN(11));
+    return fold_al_ah(al, ah);
+}
+template <int R>
+GL_D u64 block_end_row(const u32* l, const u32* h, const u64 t1, const u64 t2, const unsigned int* e, const u64 k) {
+    const u64 rl = (u64)(u32)k, rh = k >> 32;
+    const unsigned int* c = e + 1;
+    u64 al, ah;
+    gl::sg dead;
+    asm("v_mad_u64_u32 %[al], %[d], %[lu], %[ku], %[rl]\n\tv_mad_u64_u32 %[ah], %[d], %[hu], %[ku], %[rh]\n\t"  //
+        P2_PB_T(t) P2_PB_T(0) P2_PB_T(1) P2_PB_T(2) P2_PB_T(3) P2_PB_T(4) P2_PB_LAST(5)
+        : [al] "=&v"(al), [ah] "=&v"(ah), [d] "=&s"(dead)
+        : [rl] "s"(rl), [rh] "s"(rh), [lu] "v"((u32)t2), [hu] "v"((u32)(t2 >> 32)), [ku] "n"(mds_coef(R, 0)), [lt] "v"((u32)t1),
+          [ht] "v"((u32)(t1 >> 32)), [kt] "s"(e[0]), P2_PB_IN(0), P2_PB_IN(1), P2_PB_IN(2), P2_PB_IN(3), P2_PB_IN(4), P2_PB_IN(5));
+    asm(P2_PB_T(6) P2_PB_T(7) P2_PB_T(8) P2_PB_T(9) P2_PB_T(10) P2_PB_LAST(11)
+        : [al] "+v"(al), [ah] "+v"(ah), [d] "=&s"(dead)
+        : P2_PB_IN(6), P2_PB_IN(7), P2_PB_IN(8), P2_PB_IN(9), P2_PB_IN(10), P2_PB_IN(11));
+    return fold_al_ah(al, ah);
+}
+#undef P2_PB_T
+#undef P2_PB_LAST
+#undef P2_PB_IN
+#else
+// one row on the host: k + c . y (+ ct1 t_1 + ct2 t_2) on halves, in 64-bit accumulators, as the device forms it
+GL_HD u64 block_row(const u64* y, const unsigned int* c, const u64 t1, const u32 ct1, const u64 t2, const u32 ct2, const u64 k) {
+    u64 al = (u64)(u32)k + (t1 & gl::EPS) * ct1 + (t2 & gl::EPS) * ct2, ah = (k >> 32) + (t1 >> 32) * ct1 + (t2 >> 32) * ct2;
+    for (int j = 0; j < 12; j++) {
+        al += (y[j] & gl::EPS) * c[j];
+        ah += (y[j] >> 32) * c[j];
+    }
+    return fold_al_ah(al, ah);
+}
+#endif
+// s = the twelve rows of a block's end; e: the block's table (PB_END or its second half), k: its twelve constants
+GL_HD void block_end(u64* s, const u64 t1, const u64 t2, const unsigned int* e, const unsigned long long* k) {
+    u64 res[12];
+#if defined(__HIP_DEVICE_COMPILE__)
+    u32 l[12], h[12];
+#pragma unroll
+    for (int i = 0; i < 12; i++) {
+        l[i] = (u32)s[i];
+        h[i] = (u32)(s[i] >> 32);
+    }
+#define P2_PB_ROW(r) res[r] = block_end_row<r>(l, h, t1, t2, e + 13 * r, k[r]);
+    P2_PB_ROW(0) P2_PB_ROW(1) P2_PB_ROW(2) P2_PB_ROW(3) P2_PB_ROW(4) P2_PB_ROW(5) P2_PB_ROW(6) P2_PB_ROW(7) P2_PB_ROW(8) P2_PB_ROW(9)
+    P2_PB_ROW(10) P2_PB_ROW(11)
+#undef P2_PB_ROW
+#else
+    for (int r = 0; r < 12; r++) res[r] = block_row(s, e + 13 * r + 1, t1, e[13 * r], t2, mds_coef(r, 0), k[r]);
+#endif
+#pragma unroll
+    for (int i = 0; i < 12; i++) s[i] = res[i];
+}
+// ONE copy of the block body per kernel: a rolled loop whose last trip skips the two inner S-boxes and reads M's own table.
 GL_HD void partial_block(u64* s) {
-    {
-        // 4th full round with the dense 11x11 layer of the partial-round block merged into its linear step: lane 0 is the
-        // MDS row (+ a_0, the first partial S-box's constant), lanes 1.. are rows of E = D0 . MDS[1.., :] (gen_poseidon_fast.py)
-        u64 z[12];
-#pragma unroll
-        for (int i = 0; i < 12; i++) z[i] = sbox7(s[i]);
 #pragma nounroll
-        for (int r = 0; r < 11; r++) {
-            Acc a;
-            a.init();
+    for (int b = 0; b < 8; b++) {
+        const unsigned long long* K = PB_K + 14 * b;
+        const bool three = b < 7;
+        s[0] = sbox7(s[0]);
+        u64 t1 = 0, t2 = 0;
+        if (three) {
+            t1 = sbox7(mds_row0(s, K[0]));
+#if defined(__HIP_DEVICE_COMPILE__)
+            u32 l[12], h[12];
 #pragma unroll
-            for (int c = 0; c < 12; c++) a.fma_k(PF_E[r * 12 + c], z[c]);
-            s[1 + r] = a.reduce();  // straight into the (dead) state: a separate result array costs 34 VGPRs and a wave of occupancy
+            for (int i = 0; i < 12; i++) {
+                l[i] = (u32)s[i];
+                h[i] = (u32)(s[i] >> 32);
+            }
+            t2 = sbox7(block_row0_d2(l, h, t1, PB_ROW0_D2, K[1]));
+#else
+            t2 = sbox7(block_row(s, PB_ROW0_D2, t1, mds_coef(0, 0), 0, 0, K[1]));
+#endif
         }
-        s[0] = mds_row0(z, PF_A[0]);
+        block_end(s, t1, t2, PB_END + (three ? 0 : 12 * 13), K + 2);
     }
-    for (int i = 0; i < 22; i++) {
-        u64 s0 = sbox7(s[0]);
-        Acc a;
-        a.init();
-        a.e01 = i < 21 ? PF_A[i + 1] : PF_RC26[0];  // the next S-box's / next full round's constant for lane 0
-        a.fma_small(25, s0);
-#pragma unroll
-        for (int j = 0; j < 11; j++) a.fma_k(PF_WHAT[i * 11 + j], s[1 + j]);
-#pragma unroll
-        for (int j = 0; j < 11; j++) s[1 + j] = mulr_add_k(PF_V[i * 11 + j], s0, s[1 + j]);
-        s[0] = a.reduce();
-    }
-#pragma unroll
-    for (int j = 1; j < 12; j++) s[j] = add_wrap(s[j], PF_RC26[j]);
 }
 // Everything between the first and the last full round; the same for every use of the permutation.
 GL_HD void middle(u64* s) {
     const unsigned long long* RC = poseidon_rc();
-    for (int r = 1; r < 3; r++) full_round(s, RC + 12 * (r + 1));
+    for (int r = 1; r < 4; r++) full_round(s, RC + 12 * (r + 1));
     partial_block(s);
     for (int r = 26; r < 29; r++) full_round(s, RC + 12 * (r + 1));
 }
@@ -591,13 +676,13 @@ GL_HD void last_round(u64* s) {
 }
 
 // first_round(kind), middle, last_round(rows) as the kernels run them: the first round is the first trip of the loop over
-// rounds 0..2 and the last round the last trip of the loop over rounds 26..29, so a kernel holds ONE copy of each loop body
+// rounds 0..3 and the last round the last trip of the loop over rounds 26..29, so a kernel holds ONE copy of each loop body
 // whatever it knows about its inputs (the hash kernels are larger than the instruction cache as it is).
 GL_HD void permute_known_any(u64* s, const u32 kind, const u32 rows) {
     const unsigned long long* RC = poseidon_rc();
     const unsigned long long* add0 = kind == FR_ZERO_CAP ? RC1_ZCAP : kind == FR_ZERO_RATE ? RC1_ZRATE : RC + 12;
 #pragma nounroll
-    for (int r = 0; r < 3; r++) full_round_known(s, r == 0 ? kind : (u32)FR_GENERAL, r == 0 ? RC : nullptr, r == 0 ? add0 : RC + 12 * (r + 1));
+    for (int r = 0; r < 4; r++) full_round_known(s, r == 0 ? kind : (u32)FR_GENERAL, r == 0 ? RC : nullptr, r == 0 ? add0 : RC + 12 * (r + 1));
     partial_block(s);
 #pragma nounroll
     for (int r = 26; r < 30; r++) {
@@ -622,8 +707,74 @@ GL_HD void poseidon(u64* s) {
     const unsigned long long* RC = poseidon_rc();
 #pragma unroll
     for (int i = 0; i < 12; i++) s[i] = add_wrap(s[i], RC[i]);
-    for (int r = 0; r < 3; r++) full_round(s, RC + 12 * (r + 1));
+    for (int r = 0; r < 4; r++) full_round(s, RC + 12 * (r + 1));
     partial_block(s);
+    for (int r = 26; r < 29; r++) full_round(s, RC + 12 * (r + 1));
+    full_round(s, nullptr);
+#pragma unroll
+    for (int i = 0; i < 12; i++) s[i] = canon(s[i]);
+}
+
+// ---- The sparse-matrix form of the same rounds (tools/gen_poseidon_fast.py, form 1), as these kernels ran them until the block
+// form: the fourth full round with the dense 11x11 layer merged into its linear step (PF_E), then 23 multiply-accumulates per
+// round on 64-bit constants.  One user is left: PoseidonTree (kernels_verify.h), the Merkle path walks of the verifier and the
+// compressor.  tests/test_public_inputs_host.py holds k_vfy_queries to the register count it has with this form, so those two
+// kernels keep it; they hash a few hundred nodes per proof and are not where the time goes.
+GL_HD u64 mds_row0_terms(const u64* s, u64 rc) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    {
+        u64 al = gl::madk_s<17>((u32)s[0], (u64)(u32)rc), ah = gl::madk_s<17>((u32)(s[0] >> 32), rc >> 32);
+#define P2_MDS_TERM(i, K)                       \
+    al = gl::madk<K>((u32)s[i], al);            \
+    ah = gl::madk<K>((u32)(s[i] >> 32), ah);
+        P2_MDS_TERM(1, 15) P2_MDS_TERM(2, 41) P2_MDS_TERM(3, 16) P2_MDS_TERM(4, 2) P2_MDS_TERM(5, 28) P2_MDS_TERM(6, 13)
+        P2_MDS_TERM(7, 13) P2_MDS_TERM(8, 39) P2_MDS_TERM(9, 18) P2_MDS_TERM(10, 34) P2_MDS_TERM(11, 20) P2_MDS_TERM(0, 8)
+#undef P2_MDS_TERM
+        return fold_al_ah(al, ah);
+    }
+#endif
+    return mds_row0(s, rc);
+}
+// In: the state in front of the fourth full round's S-boxes; out: the state carries round 26's constants.
+GL_HD void partial_block_sparse(u64* s) {
+    {
+        // 4th full round with the dense 11x11 layer of the partial-round block merged into its linear step: lane 0 is the
+        // MDS row (+ a_0, the first partial S-box's constant), lanes 1.. are rows of E = D0 . MDS[1.., :] (gen_poseidon_fast.py)
+        u64 z[12];
+#pragma unroll
+        for (int i = 0; i < 12; i++) z[i] = sbox7(s[i]);
+#pragma nounroll
+        for (int r = 0; r < 11; r++) {
+            Acc a;
+            a.init();
+#pragma unroll
+            for (int c = 0; c < 12; c++) a.fma_k(PF_E[r * 12 + c], z[c]);
+            s[1 + r] = a.reduce();  // straight into the (dead) state: a separate result array costs 34 VGPRs and a wave of occupancy
+        }
+        s[0] = mds_row0_terms(z, PF_A[0]);
+    }
+    for (int i = 0; i < 22; i++) {
+        u64 s0 = sbox7(s[0]);
+        Acc a;
+        a.init();
+        a.e01 = i < 21 ? PF_A[i + 1] : PF_RC26[0];  // the next S-box's / next full round's constant for lane 0
+        a.fma_small(25, s0);
+#pragma unroll
+        for (int j = 0; j < 11; j++) a.fma_k(PF_WHAT[i * 11 + j], s[1 + j]);
+#pragma unroll
+        for (int j = 0; j < 11; j++) s[1 + j] = mulr_add_k(PF_V[i * 11 + j], s0, s[1 + j]);
+        s[0] = a.reduce();
+    }
+#pragma unroll
+    for (int j = 1; j < 12; j++) s[j] = add_wrap(s[j], PF_RC26[j]);
+}
+// glf::poseidon with the sparse partial rounds.  In: canonical or not; out: canonical.
+GL_HD void poseidon_sparse(u64* s) {
+    const unsigned long long* RC = poseidon_rc();
+#pragma unroll
+    for (int i = 0; i < 12; i++) s[i] = add_wrap(s[i], RC[i]);
+    for (int r = 0; r < 3; r++) full_round(s, RC + 12 * (r + 1));
+    partial_block_sparse(s);
     for (int r = 26; r < 29; r++) full_round(s, RC + 12 * (r + 1));
     full_round(s, nullptr);
 #pragma unroll
