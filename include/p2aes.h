@@ -214,6 +214,10 @@ int p2_host_poseidon_known(uint64_t* states, size_t n_perm, int kind, uint32_t r
  * round 4's constants" to "the state carries round 26's" (some representative of each word, not canonical).  After four full
  * rounds a test cannot steer what reaches the folds of the section; through this entry point, and p2_gpu_partial_rounds, it can. */
 int p2_host_partial_rounds(uint64_t* states, size_t count);
+/* The section the hash kernels run in its place (glf::merged_middle): round 3's MDS and the 22 partial rounds as one chain, in
+ * place on count x 12 words that may be ANY u64: from "round 3's twelve S-box outputs" to "the state carries round 26's constants"
+ * (some representative of each word, not canonical).  p2_gpu_merged_middle is the same on the device. */
+int p2_host_merged_middle(uint64_t* states, size_t count);
 /* k_hash_leaves' sponge on the host: data [min(active_cols, cols)][num_leaves] -> digests [num_leaves][4] */
 int p2_host_hash_leaves(const uint64_t* data, size_t cols, size_t active_cols, size_t num_leaves, uint64_t* digests);
 
@@ -467,6 +471,8 @@ int p2_gpu_merkle_cap_hasher(const uint64_t* cols_major, size_t cols, size_t num
 int p2_gpu_hash_leaves(const uint64_t* data, size_t cols, size_t active_cols, size_t num_leaves, size_t batch, uint64_t* digests, int device);
 /* p2_host_partial_rounds on the device: one thread per state, at the hash kernels' occupancy (tests/test_gpu_partial_rounds.py) */
 int p2_gpu_partial_rounds(uint64_t* states, size_t count, int device);
+/* p2_host_merged_middle on the device, the same way (tests/test_gpu_merged_middle.py) */
+int p2_gpu_merged_middle(uint64_t* states, size_t count, int device);
 /* child [batch][2 * num_parents][4] -> parent [batch][num_parents][4] */
 int p2_gpu_merkle_level(const uint64_t* child, size_t num_parents, size_t batch, uint64_t* parent, int device);
 /* vals [batch][2][len] -> digests [batch][len / arity][4] */

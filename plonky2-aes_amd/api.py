@@ -270,6 +270,8 @@ def lib():
         "p2_gpu_poseidon": (C.c_int, [u64p, sz, C.c_int]),
         "p2_host_partial_rounds": (C.c_int, [u64p, sz]),
         "p2_gpu_partial_rounds": (C.c_int, [u64p, sz, C.c_int]),
+        "p2_host_merged_middle": (C.c_int, [u64p, sz]),
+        "p2_gpu_merged_middle": (C.c_int, [u64p, sz, C.c_int]),
         "p2_gpu_lde": (C.c_int, [u64p, sz, C.c_int, C.c_int, u64p, C.c_int]),
         "p2_gpu_intt": (C.c_int, [u64p, sz, C.c_int, u64p, C.c_int]),
         "p2_gpu_merkle_cap": (C.c_int, [u64p, sz, sz, C.c_int, u64p, C.c_int]),

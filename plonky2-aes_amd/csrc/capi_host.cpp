@@ -531,6 +531,11 @@ int p2_host_partial_rounds(uint64_t* states, size_t count) {
     for (size_t i = 0; i < count; i++) glf::partial_block(states + 12 * i);
     return P2_OK;
 }
+// Round 3's MDS and the partial rounds as one chain (glf::merged_middle), on arbitrary u64 words: round 3's S-box outputs in.
+int p2_host_merged_middle(uint64_t* states, size_t count) {
+    for (size_t i = 0; i < count; i++) glf::merged_middle(states + 12 * i);
+    return P2_OK;
+}
 // k_hash_leaves on the host, with the same sponge steps (glf::sponge_permute): data [active][num_leaves] column-major, columns
 // >= active_cols are zero and not stored; digests [num_leaves][4].
 int p2_host_hash_leaves(const uint64_t* data, size_t cols, size_t active_cols, size_t num_leaves, uint64_t* digests) {

@@ -185,6 +185,16 @@ __global__ __launch_bounds__(256) P2_HASH_WAVES void k_partial_rounds(u64* state
     for (int k = 0; k < 12; k++) states[12 * i + k] = st[k];
 }
 
+// round 3's MDS and the partial rounds as one chain (glf::merged_middle), the same way (test entry point)
+__global__ __launch_bounds__(256) P2_HASH_WAVES void k_merged_middle(u64* states, size_t n) {
+    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    u64 st[12];
+    for (int k = 0; k < 12; k++) st[k] = states[12 * i + k];
+    glf::merged_middle(st);
+    for (int k = 0; k < 12; k++) states[12 * i + k] = st[k];
+}
+
 // ------------------------------------------------------------------------------------------- NTT
 // One workgroup transforms one column (n = 2^logn <= 2^14 points, 8 B each => up to 128 KiB of the CU's
 // 160 KiB LDS), decimation in frequency: natural order in, bit-reversed order out, log n LDS stages.
@@ -1380,7 +1390,7 @@ __global__ __launch_bounds__(256) void k_pow(const ChalState* st, u64* chal, int
         u64 r[12];
 #pragma unroll
         for (int i = 0; i < 12; i++) r[i] = ((u32)i == pos) ? cand : sh[i];
-        glf::poseidon(r);
+        glf::poseidon<false>(r);  // the blocks of three: see glf::poseidon
         if ((r[7] >> (64 - pow_bits)) == 0) atomicMin(&best[p], (unsigned long long)cand);
     }
 }

@@ -225,6 +225,11 @@ GL_HD u64 add_wrap(u64 a, u64 c) {
 //   = {x1:x0} + x2 * (2^32 - 1): ONE v_mad_u64_u32 (the 64-bit add rides on the multiply; a 32-bit add-with-carry costs
 //   the same issue time as the whole mad, valu_rates.hip), and its carry-out -- possible only when x1 >= 2^32 - x2 --
 //   is folded back by a second mad, which cannot wrap (the wrapped sum is < x2 * 2^32 < 2^58).
+// ALWAYS: for al, ah up to 2^64 - 1 with ah + (al >> 32) < 2^64 still (the end rows of a block of four layers, merged_middle: the
+// generator proves it per row).  x2 is then any 32-bit value and the first mad wraps on every second lane, so the second step
+// runs branch-free on all of them: a 0/1 select on the carry mask and the mad, two wait states behind the mad that wrote the mask
+// (as gl::one_where pays them).  It cannot wrap either: the wrapped sum is < x2 (2^32 - 1) <= 2^64 - 2^33 + 1.
+template <bool ALWAYS = false>
 GL_HD u64 fold_al_ah(u64 al, u64 ah) {
 #if defined(__HIP_DEVICE_COMPILE__)
     const u64 ah2 = gl::add_u32(ah, (u32)(al >> 32));  // through the multiplier: no zero-extension of al's high half
@@ -237,6 +242,16 @@ GL_HD u64 fold_al_ah(u64 al, u64 ah) {
     // the carry needs x1 >= 2^32 - x2: once in 2^20 on random data after a full round and about one lane in 250 at the end of a
     // block of partial rounds (a wave in four), so its fold sits behind a wave-uniform branch
     gl::sg sc, dead;
+    if (ALWAYS) {
+        u64 r = base;   // in place: the 0/1 select lands in x2's register, which the first mad has consumed
+        u32 c01 = x2;
+        asm("v_mad_u64_u32 %[r], %[sc], %[c], -1, %[r]\n\t"
+            "s_nop 1\n\t"
+            "v_cndmask_b32_e64 %[c], 0, 1, %[sc]\n\t"
+            "v_mad_u64_u32 %[r], %[d], %[c], -1, %[r]"
+            : [r] "+v"(r), [c] "+v"(c01), [sc] "=&s"(sc), [d] "=&s"(dead));
+        return r;
+    }
     u64 r = gl::mad_eps_co(x2, base, sc);
     if (__builtin_expect(sc != 0, 0)) r = gl::mad_eps_co(gl::one_where(sc), r, dead);
     return r;
@@ -473,24 +488,17 @@ GL_D u64 zero_rate_row(const u32* l, const u32* h, const u64 add) {
 }
 #endif
 
-// One full round with the words that `kind` (FR_*) declares zero left out; they are not read.  pre: the constants the S-box
-// inputs still lack (the first round) or nullptr (the state carries them); add: the addend of every MDS row.
-GL_HD void full_round_known(u64* s, const u32 kind, const unsigned long long* pre, const unsigned long long* add) {
+// One full round with the words that `kind` (FR_*) declares zero left out; they are not read.  In two stages, because round 3
+// runs the first alone (its MDS is the first layer of merged_middle):
+//   sbox_layer_known    pre: the constants the S-box inputs still lack (the first round) or nullptr (the state carries them);
+//   linear_layer_known  add: the addend of every MDS row.
+GL_HD void sbox_layer_known(u64* s, const u32 kind, const unsigned long long* pre) {
 #if defined(__HIP_DEVICE_COMPILE__)
-    // A zero rate is a region of its own (four S-boxes, twelve rows of eight terms) and not a third arm of every row below:
-    // with three arms per row the register allocator needed 22 more VGPRs in k_hash_leaves and spilled.
-    u32 l[12], h[12];
+    // A zero rate is a region of its own in both stages (four S-boxes, twelve rows of eight terms) and not a third arm of every
+    // row below: with three arms per row the register allocator needed 22 more VGPRs in k_hash_leaves and spilled.
     if (kind == FR_ZERO_RATE) {
 #pragma unroll
-        for (int i = 8; i < 12; i++) {
-            const u64 z = sbox7(pre ? add_wrap(s[i], pre[i]) : s[i]);
-            l[i] = (u32)z;
-            h[i] = (u32)(z >> 32);
-        }
-#define P2_FR_ROW(r) s[r] = zero_rate_row<r>(l, h, add[r]);
-        P2_FR_ROW(0) P2_FR_ROW(1) P2_FR_ROW(2) P2_FR_ROW(3) P2_FR_ROW(4) P2_FR_ROW(5) P2_FR_ROW(6) P2_FR_ROW(7) P2_FR_ROW(8) P2_FR_ROW(9)
-        P2_FR_ROW(10) P2_FR_ROW(11)
-#undef P2_FR_ROW
+        for (int i = 8; i < 12; i++) s[i] = sbox7(pre ? add_wrap(s[i], pre[i]) : s[i]);
         return;
     }
     if (pre) {
@@ -507,10 +515,25 @@ GL_HD void full_round_known(u64* s, const u32 kind, const unsigned long long* pr
 #pragma unroll
         for (int i = 8; i < 12; i++) s[i] = sbox7(s[i]);
     }
+#else
+    const int j0 = kind == FR_ZERO_RATE ? 8 : 0, j1 = kind == FR_ZERO_CAP ? 8 : 12;
+    for (int j = j0; j < j1; j++) s[j] = sbox7(pre ? add_wrap(s[j], pre[j]) : s[j]);
+#endif
+}
+GL_HD void linear_layer_known(u64* s, const u32 kind, const unsigned long long* add) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    u32 l[12], h[12];
 #pragma unroll
     for (int i = 0; i < 12; i++) {
         l[i] = (u32)s[i];
         h[i] = (u32)(s[i] >> 32);
+    }
+    if (kind == FR_ZERO_RATE) {
+#define P2_FR_ROW(r) s[r] = zero_rate_row<r>(l, h, add[r]);
+        P2_FR_ROW(0) P2_FR_ROW(1) P2_FR_ROW(2) P2_FR_ROW(3) P2_FR_ROW(4) P2_FR_ROW(5) P2_FR_ROW(6) P2_FR_ROW(7) P2_FR_ROW(8) P2_FR_ROW(9)
+        P2_FR_ROW(10) P2_FR_ROW(11)
+#undef P2_FR_ROW
+        return;
     }
 #define P2_FR_ROW(r) s[r] = first_round_row<r>(kind, l, h, add[r]);
     P2_FR_ROW(0) P2_FR_ROW(1) P2_FR_ROW(2) P2_FR_ROW(3) P2_FR_ROW(4) P2_FR_ROW(5) P2_FR_ROW(6) P2_FR_ROW(7) P2_FR_ROW(8) P2_FR_ROW(9)
@@ -519,7 +542,6 @@ GL_HD void full_round_known(u64* s, const u32 kind, const unsigned long long* pr
 #else
     const int j0 = kind == FR_ZERO_RATE ? 8 : 0, j1 = kind == FR_ZERO_CAP ? 8 : 12;
     u64 out[12];
-    for (int j = j0; j < j1; j++) s[j] = sbox7(pre ? add_wrap(s[j], pre[j]) : s[j]);
     for (int r = 0; r < 12; r++) {
         u64 al = (u32)add[r], ah = add[r] >> 32;
         for (int j = j0; j < j1; j++) {
@@ -530,6 +552,10 @@ GL_HD void full_round_known(u64* s, const u32 kind, const unsigned long long* pr
     }
     for (int i = 0; i < 12; i++) s[i] = out[i];
 #endif
+}
+GL_HD void full_round_known(u64* s, const u32 kind, const unsigned long long* pre, const unsigned long long* add) {
+    sbox_layer_known(s, kind, pre);
+    linear_layer_known(s, kind, add);
 }
 GL_HD const unsigned long long* poseidon_rc() {
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -593,6 +619,42 @@ GL_D u64 block_end_row(const u32* l, const u32* h, const u64 t1, const u64 t2, c
         : P2_PB_IN(6), P2_PB_IN(7), P2_PB_IN(8), P2_PB_IN(9), P2_PB_IN(10), P2_PB_IN(11));
     return fold_al_ah(al, ah);
 }
+// The rows merged_middle adds (below): row 0 at depth 3 (fourteen terms: 29 + 21 operands) and an end row of up to four layers
+// (fifteen terms: 29 + 24).  e: the row's table entries, the coefficients of the earlier t first.
+static_assert((PM_ALWAYS_ROW0 & 3) == 0, "mds_row0 and block_row0_d2 fold with the rare-carry branch");
+GL_D u64 merged_row0_d3(const u32* l, const u32* h, const u64 t1, const u64 t2, const unsigned int* e, const u64 k) {
+    const u64 rl = (u64)(u32)k, rh = k >> 32;
+    const unsigned int* c = e + 1;
+    u64 al, ah;
+    gl::sg dead;
+    asm("v_mad_u64_u32 %[al], %[d], %[lu], 25, %[rl]\n\tv_mad_u64_u32 %[ah], %[d], %[hu], 25, %[rh]\n\t"  //
+        P2_PB_T(t) P2_PB_T(0) P2_PB_T(1) P2_PB_T(2) P2_PB_T(3) P2_PB_T(4) P2_PB_LAST(5)
+        : [al] "=&v"(al), [ah] "=&v"(ah), [d] "=&s"(dead)
+        : [rl] "s"(rl), [rh] "s"(rh), [lu] "v"((u32)t2), [hu] "v"((u32)(t2 >> 32)), [lt] "v"((u32)t1), [ht] "v"((u32)(t1 >> 32)),
+          [kt] "s"(e[0]), P2_PB_IN(0), P2_PB_IN(1), P2_PB_IN(2), P2_PB_IN(3), P2_PB_IN(4), P2_PB_IN(5));
+    asm(P2_PB_T(6) P2_PB_T(7) P2_PB_T(8) P2_PB_T(9) P2_PB_T(10) P2_PB_LAST(11)
+        : [al] "+v"(al), [ah] "+v"(ah), [d] "=&s"(dead)
+        : P2_PB_IN(6), P2_PB_IN(7), P2_PB_IN(8), P2_PB_IN(9), P2_PB_IN(10), P2_PB_IN(11));
+    return fold_al_ah<((PM_ALWAYS_ROW0 >> 2) & 1) != 0>(al, ah);
+}
+template <int R>
+GL_D u64 merged_end_row(const u32* l, const u32* h, const u64 t1, const u64 t2, const u64 t3, const unsigned int* e, const u64 k) {
+    const u64 rl = (u64)(u32)k, rh = k >> 32;
+    const unsigned int* c = e + 2;
+    u64 al, ah;
+    gl::sg dead;
+    asm("v_mad_u64_u32 %[al], %[d], %[lu], %[ku], %[rl]\n\tv_mad_u64_u32 %[ah], %[d], %[hu], %[ku], %[rh]\n\t"  //
+        P2_PB_T(t) P2_PB_T(v) P2_PB_T(0) P2_PB_T(1) P2_PB_T(2) P2_PB_T(3) P2_PB_LAST(4)
+        : [al] "=&v"(al), [ah] "=&v"(ah), [d] "=&s"(dead)
+        : [rl] "s"(rl), [rh] "s"(rh), [lu] "v"((u32)t3), [hu] "v"((u32)(t3 >> 32)), [ku] "n"(mds_coef(R, 0)), [lt] "v"((u32)t1),
+          [ht] "v"((u32)(t1 >> 32)), [kt] "s"(e[0]), [lv] "v"((u32)t2), [hv] "v"((u32)(t2 >> 32)), [kv] "s"(e[1]), P2_PB_IN(0), P2_PB_IN(1),
+          P2_PB_IN(2), P2_PB_IN(3), P2_PB_IN(4));
+    asm(P2_PB_T(5) P2_PB_T(6) P2_PB_T(7) P2_PB_T(8) P2_PB_T(9) P2_PB_T(10) P2_PB_LAST(11)
+        : [al] "+v"(al), [ah] "+v"(ah), [d] "=&s"(dead)
+        : P2_PB_IN(5), P2_PB_IN(6), P2_PB_IN(7), P2_PB_IN(8), P2_PB_IN(9), P2_PB_IN(10), P2_PB_IN(11));
+    // one copy of the row serves both depths: the second step runs always if either table's row needs it
+    return fold_al_ah<(((PM_ALWAYS_END4 | PM_ALWAYS_END3) >> R) & 1) != 0>(al, ah);
+}
 #undef P2_PB_T
 #undef P2_PB_LAST
 #undef P2_PB_IN
@@ -605,6 +667,17 @@ GL_HD u64 block_row(const u64* y, const unsigned int* c, const u64 t1, const u32
         ah += (y[j] >> 32) * c[j];
     }
     return fold_al_ah(al, ah);
+}
+// the same with a third t: the rows of merged_middle
+GL_HD u64 merged_row(const u64* y, const unsigned int* c, const u64 t1, const u32 ct1, const u64 t2, const u32 ct2, const u64 t3, const u32 ct3,
+                     const u64 k) {
+    u64 al = (u64)(u32)k + (t1 & gl::EPS) * ct1 + (t2 & gl::EPS) * ct2 + (t3 & gl::EPS) * ct3;
+    u64 ah = (k >> 32) + (t1 >> 32) * ct1 + (t2 >> 32) * ct2 + (t3 >> 32) * ct3;
+    for (int j = 0; j < 12; j++) {
+        al += (y[j] & gl::EPS) * c[j];
+        ah += (y[j] >> 32) * c[j];
+    }
+    return fold_al_ah<true>(al, ah);   // on the host both forms of the fold are the same compare
 }
 #endif
 // s = the twelve rows of a block's end; e: the block's table (PB_END or its second half), k: its twelve constants
@@ -652,11 +725,68 @@ GL_HD void partial_block(u64* s) {
         block_end(s, t1, t2, PB_END + (three ? 0 : 12 * 13), K + 2);
     }
 }
+
+// ---- The merged middle: round 3's MDS and the 22 partial rounds as ONE chain of 23 linear layers, M after round 3's S-boxes and
+// then [S-box on word 0, M] x 22, in five blocks of four layers and one of three (PM_DEPTH).  Round 3's MDS on its own was twelve
+// rows that fed one S-box and more linear maps; as the first layer of the first block it costs that block one more column of
+// coefficients.  In: round 3's twelve S-box outputs (any u64); out: the state carries round 26's constants.  A block of four:
+//   t_1 = S(M[0] . y + K1)   t_2 = S(PB_ROW0_D2 . y + 25 t_1 + K2)   t_3 = S(PM_ROW0_D3[1..] . y + PM_ROW0_D3[0] t_1 + 25 t_2 + K3)
+//   end, row r               PM_END[r][2..] . y + PM_END[r][0] t_1 + PM_END[r][1] t_2 + M[r][0] t_3 + K[r]
+// with y = (s_0^7, s_1, .., s_11), and y = s in the first block: round 3's S-box layer has run.  The coefficients at depth four
+// reach 2^28.3 and a row's sum 2^31.8, so the half-accumulators come close to 2^64 and the end rows fold with the always-on
+// second step (fold_al_ah<true>; tools/gen_poseidon_fast.py proves the bounds per row and emits PM_ALWAYS_*).
+// ONE rolled copy of the body: the trip of depth three skips the third stage (t_3 = 0) and reads the second end table, in which
+// the slot of t_2, its last real t, holds M[r][0].
+GL_HD void merged_end(u64* s, const u64 t1, const u64 t2, const u64 t3, const unsigned int* e, const unsigned long long* k) {
+    u64 res[12];
+#if defined(__HIP_DEVICE_COMPILE__)
+    u32 l[12], h[12];
+#pragma unroll
+    for (int i = 0; i < 12; i++) {
+        l[i] = (u32)s[i];
+        h[i] = (u32)(s[i] >> 32);
+    }
+#define P2_PM_ROW(r) res[r] = merged_end_row<r>(l, h, t1, t2, t3, e + 14 * r, k[r]);
+    P2_PM_ROW(0) P2_PM_ROW(1) P2_PM_ROW(2) P2_PM_ROW(3) P2_PM_ROW(4) P2_PM_ROW(5) P2_PM_ROW(6) P2_PM_ROW(7) P2_PM_ROW(8) P2_PM_ROW(9)
+    P2_PM_ROW(10) P2_PM_ROW(11)
+#undef P2_PM_ROW
+#else
+    for (int r = 0; r < 12; r++) res[r] = merged_row(s, e + 14 * r + 2, t1, e[14 * r], t2, e[14 * r + 1], t3, mds_coef(r, 0), k[r]);
+#endif
+#pragma unroll
+    for (int i = 0; i < 12; i++) s[i] = res[i];
+}
+GL_HD void merged_middle(u64* s) {
+#pragma nounroll
+    for (int b = 0; b < 6; b++) {
+        const unsigned long long* K = PM_K + 15 * b;
+        const bool four = PM_DEPTH[b] == 4;
+        if (b) s[0] = sbox7(s[0]);
+        const u64 t1 = sbox7(mds_row0(s, K[0]));
+        u64 t3 = 0;
+#if defined(__HIP_DEVICE_COMPILE__)
+        u32 l[12], h[12];
+#pragma unroll
+        for (int i = 0; i < 12; i++) {
+            l[i] = (u32)s[i];
+            h[i] = (u32)(s[i] >> 32);
+        }
+        const u64 t2 = sbox7(block_row0_d2(l, h, t1, PB_ROW0_D2, K[1]));
+        if (four) t3 = sbox7(merged_row0_d3(l, h, t1, t2, PM_ROW0_D3, K[2]));
+#else
+        const u64 t2 = sbox7(block_row(s, PB_ROW0_D2, t1, mds_coef(0, 0), 0, 0, K[1]));
+        if (four) t3 = sbox7(merged_row(s, PM_ROW0_D3 + 1, t1, PM_ROW0_D3[0], t2, mds_coef(0, 0), 0, 0, K[2]));
+#endif
+        merged_end(s, t1, t2, t3, PM_END + (four ? 0 : 12 * 14), K + 3);
+    }
+}
 // Everything between the first and the last full round; the same for every use of the permutation.
 GL_HD void middle(u64* s) {
     const unsigned long long* RC = poseidon_rc();
-    for (int r = 1; r < 4; r++) full_round(s, RC + 12 * (r + 1));
-    partial_block(s);
+    for (int r = 1; r < 3; r++) full_round(s, RC + 12 * (r + 1));
+#pragma unroll
+    for (int i = 0; i < 12; i++) s[i] = sbox7(s[i]);
+    merged_middle(s);
     for (int r = 26; r < 29; r++) full_round(s, RC + 12 * (r + 1));
 }
 
@@ -678,12 +808,30 @@ GL_HD void last_round(u64* s) {
 // first_round(kind), middle, last_round(rows) as the kernels run them: the first round is the first trip of the loop over
 // rounds 0..3 and the last round the last trip of the loop over rounds 26..29, so a kernel holds ONE copy of each loop body
 // whatever it knows about its inputs (the hash kernels are larger than the instruction cache as it is).
+// Round 3 is an S-box layer only: its MDS opens merged_middle.  Two ways to leave it out, chosen per kernel by what the register
+// allocator makes of them (the state is one 12-word register tuple to it, and every join of two paths costs a copy of the tuple):
+//   !OWN_SBOX3  one loop body serves rounds 0..3: a trip is the MDS of round r - 1 (skipped, wave-uniformly, on the first) and
+//               the S-boxes of round r.  The tree kernels' form (k_merkle_level 82 VGPRs, k_merkle_top 84, no spill).
+//   OWN_SBOX3   rounds 0..2 as whole rounds and round 3's twelve S-boxes as a copy of their own, 11 KB more code: the sponge
+//               kernels' form.  With the skip inside the loop k_hash_leaves needs 98 VGPRs where five waves leave 96, and
+//               with the loop left between the two stages of round 3 it spills the state once per MDS row.
+template <bool OWN_SBOX3 = false>
 GL_HD void permute_known_any(u64* s, const u32 kind, const u32 rows) {
     const unsigned long long* RC = poseidon_rc();
     const unsigned long long* add0 = kind == FR_ZERO_CAP ? RC1_ZCAP : kind == FR_ZERO_RATE ? RC1_ZRATE : RC + 12;
+    if (OWN_SBOX3) {
 #pragma nounroll
-    for (int r = 0; r < 4; r++) full_round_known(s, r == 0 ? kind : (u32)FR_GENERAL, r == 0 ? RC : nullptr, r == 0 ? add0 : RC + 12 * (r + 1));
-    partial_block(s);
+        for (int r = 0; r < 3; r++) full_round_known(s, r == 0 ? kind : (u32)FR_GENERAL, r == 0 ? RC : nullptr, r == 0 ? add0 : RC + 12 * (r + 1));
+#pragma unroll
+        for (int i = 0; i < 12; i++) s[i] = sbox7(s[i]);
+    } else {
+#pragma nounroll
+        for (int r = 0; r < 4; r++) {
+            if (r) linear_layer_known(s, r == 1 ? kind : (u32)FR_GENERAL, r == 1 ? add0 : RC + 12 * r);
+            sbox_layer_known(s, r == 0 ? kind : (u32)FR_GENERAL, r == 0 ? RC : nullptr);
+        }
+    }
+    merged_middle(s);
 #pragma nounroll
     for (int r = 26; r < 30; r++) {
 #pragma unroll
@@ -703,12 +851,22 @@ GL_HD void permute_known(u64* s) {
 // The whole permutation on twelve unknown words.  In: canonical or not; out: canonical.
 // Round constants are never added on their own (except the very first ones): each layer's linear step starts its
 // accumulators from the constants of the layer that follows.
+template <bool MERGED = true>
 GL_HD void poseidon(u64* s) {
     const unsigned long long* RC = poseidon_rc();
 #pragma unroll
     for (int i = 0; i < 12; i++) s[i] = add_wrap(s[i], RC[i]);
-    for (int r = 0; r < 4; r++) full_round(s, RC + 12 * (r + 1));
-    partial_block(s);
+    if (MERGED) {
+        for (int r = 0; r < 4; r++) {
+#pragma unroll
+            for (int i = 0; i < 12; i++) s[i] = sbox7(s[i]);
+            if (r < 3) mds_full(s, RC + 12 * (r + 1));   // round 3's MDS opens merged_middle
+        }
+        merged_middle(s);
+    } else {   // k_pow: the merged form costs it nine spilled SGPRs and a wave of occupancy (66 VGPRs), so it keeps the blocks of three
+        for (int r = 0; r < 4; r++) full_round(s, RC + 12 * (r + 1));
+        partial_block(s);
+    }
     for (int r = 26; r < 29; r++) full_round(s, RC + 12 * (r + 1));
     full_round(s, nullptr);
 #pragma unroll
@@ -789,7 +947,7 @@ GL_HD u32 sponge_first_kind(int c0, int width, int live) {
     return c0 == 0 ? (u32)FR_ZERO_CAP : (c0 >= live && c0 + 8 <= width) ? (u32)FR_ZERO_RATE : (u32)FR_GENERAL;
 }
 GL_HD void sponge_permute(u64* s, int c0, int width, int live) {
-    permute_known_any(s, sponge_first_kind(c0, width, live), rows_before_chunk(width - (c0 + 8)));
+    permute_known_any<true>(s, sponge_first_kind(c0, width, live), rows_before_chunk(width - (c0 + 8)));
 }
 // two_to_one(a, b): words 0..7 = a || b, zero capacity, digest out
 GL_HD void two_to_one_permute(u64* s) {

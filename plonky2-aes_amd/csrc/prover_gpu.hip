@@ -2472,6 +2472,17 @@ int p2_gpu_partial_rounds(uint64_t* states, size_t count, int device) {
     HIPCHECK(hipMemcpy(states, d, count * 96, hipMemcpyDeviceToHost));
     return P2_OK;
 }
+int p2_gpu_merged_middle(uint64_t* states, size_t count, int device) {
+    if (count == 0 || count > (1u << 24)) return set_error("count out of range"), P2_ERR_INVALID;
+    if (int rc = pick_device(device)) return rc;
+    Allocs mem;
+    u64* d;
+    if (upload(mem, &d, (const u64*)states, count * 12)) return P2_ERR_HIP;
+    hipLaunchKernelGGL(k_merged_middle, g1(count, 256), dim3(256), 0, 0, d, count);
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipMemcpy(states, d, count * 96, hipMemcpyDeviceToHost));
+    return P2_OK;
+}
 //   child [batch][2 * num_parents][4] -> parent [batch][num_parents][4]
 int p2_gpu_merkle_level(const uint64_t* child, size_t num_parents, size_t batch, uint64_t* parent, int device) {
     if (num_parents == 0 || batch == 0 || batch > 65535) return set_error("shape out of range"), P2_ERR_INVALID;

@@ -25,6 +25,15 @@ and is merged into the previous round's matrix, recursively, from the last round
    block's end.  The matrices are the same for every block, only the K_i differ, and the last block's K carries round 26's
    constants.  Every coefficient is a small non-negative integer: a row's two half-accumulators stay far below 2^64 for
    arbitrary u64 state words (block_bounds proves it, and the bound of the fold that follows, for every row emitted).
+
+3. The merged middle (MERGED, merged_tables): the block form again, over 23 linear layers instead of 22.  The MDS of the last
+   full round in front of the partial rounds (round 3) is one more M in front of the chain [S-box on word 0, M] x 22, with
+   y = round 3's twelve S-box outputs and round 4's constants as its K_1, so it opens the first block instead of running on its
+   own.  The blocks are up to four layers deep:
+       x(4) = MZMZMZM y + (MZMZM e0) t_1 + (MZM e0) t_2 + (M e0) t_3 + K_4
+   whose coefficients stay below 2^29 and whose rows sum to less than 2^32: a half-accumulator still fits 64 bits (depth 5
+   does not: its coefficients need 37 bits), but the fold's x2 is no longer small, so its second step runs on every lane
+   instead of behind a rare branch (row_fold decides that per emitted row, and proves the bounds either way).
 """
 import os
 import random
@@ -160,6 +169,20 @@ def block_rows(size):
     return rows
 
 
+def row_fold(coef, tcols, key=None):
+    """The three 64-bit bounds of one row on arbitrary 32-bit halves, and which fold it gets: 'rare' (x2 < 2^26: the carry of
+    the fold's first step is rare, its second step sits behind a wave-uniform branch, fold_al_ah) or 'always' (the second
+    step runs branch-free on every lane).  -> (worst accumulator, fold)."""
+    acc = (sum(coef) + sum(tcols)) * MASK32 + MASK32
+    assert all(0 <= c <= MASK32 for c in list(coef) + list(tcols)), key
+    assert acc < 1 << 64, key
+    ah2 = acc + (acc >> 32)
+    assert ah2 < 1 << 64, key
+    x2 = ah2 >> 32
+    assert x2 * MASK32 + MASK32 < 1 << 64, key
+    return acc, ("rare" if x2 < 1 << 26 else "always")
+
+
 def block_bounds(size):
     """Worst case of a row's half-accumulators on arbitrary 32-bit halves, with a 32-bit half of K on top, and of the fold
     that follows (poseidon_fast.h, fold_al_ah): ah' = ah + (al >> 32) must fit 64 bits, and with x2 = ah' >> 32 the sum
@@ -176,11 +199,12 @@ def block_bounds(size):
     return worst
 
 
-def block_constants(rc, sizes):
-    """Per block: [K of row 0 at depth 1, .., size - 1] and the twelve K of the block's end, canonical."""
-    assert sum(sizes) == 22
+def block_constants(rc, sizes, first=4):
+    """Per block: [K of row 0 at depth 1, .., size - 1] and the twelve K of the block's end, canonical.  first = 4: the 22
+    layers of the partial rounds; first = 3: the 23 layers that begin with round 3's own MDS."""
+    assert sum(sizes) == 26 - first
     M = mds_int()
-    out, r = [], 4
+    out, r = [], first
     for size in sizes:
         K, row0 = [0] * W, []
         for i in range(1, size + 1):
@@ -206,9 +230,10 @@ def fold_halves(al, ah):
     return t
 
 
-def partial_rounds_blocks(x, rc, sizes):
+def partial_rounds_blocks(x, rc, sizes, first=4):
     """The 22 partial rounds in block form on halves, as poseidon_fast.h evaluates them.  x: twelve arbitrary u64 carrying
-    round 4's constants; out: twelve u64 carrying round 26's."""
+    round 4's constants; out: twelve u64 carrying round 26's.  first = 3: the merged middle -- x is round 3's S-box layer
+    (arbitrary u64), and the first block has no S-box of its own in front."""
     def sbox(v):
         return pow(v % P, 7, P)
 
@@ -220,9 +245,9 @@ def partial_rounds_blocks(x, rc, sizes):
         return fold_halves(al, ah)
 
     x = list(x)
-    for size, (k_row0, k_end) in zip(sizes, block_constants(rc, sizes)):
+    for b, (size, (k_row0, k_end)) in enumerate(zip(sizes, block_constants(rc, sizes, first))):
         rows = block_rows(size)
-        y, t = [sbox(x[0])] + x[1:], []
+        y, t = [x[0] if first == 3 and b == 0 else sbox(x[0])] + x[1:], []
         for d in range(1, size):
             t.append(sbox(row(*rows[("row0", d)], y, t, k_row0[d - 1])))
         x = [row(*rows[("end", r)], y, t, k_end[r]) for r in range(W)]
@@ -282,6 +307,81 @@ def block_tables(rc):
     return r3[("row0", 2)][0], end, K
 
 
+# ---- merged middle
+MERGED = [4, 4, 4, 4, 4, 3]        # what poseidon_fast.h evaluates: one loop body of depth four, whose last trip skips a stage
+MERGED_FALLBACK = [3] * 7 + [2]    # the same 23 layers within the bounds of the blocks of three
+
+
+def merged_naive(z, rc):
+    """z: round 3's twelve S-box outputs.  M z + round 4's constants, then rounds 4..25; out: carries round 26's constants."""
+    M = mds_int()
+    z = [v % P for v in z]
+    return partial_rounds_naive([(sum(M[a][c] * z[c] for c in range(W)) + rc[48 + a]) % P for a in range(W)], rc)
+
+
+def check_merged(rc, rnd):
+    assert sum(MERGED) == 23 and max(MERGED) <= 4
+    folds = {}
+    for size in sorted(set(MERGED)):
+        for key, (coef, tcols) in block_rows(size).items():
+            folds[(size,) + key] = row_fold(coef, tcols, (size, key))
+    assert all(f == "always" for (size, kind, _), (_, f) in folds.items() if size == 4 and kind == "end")
+    assert all(f == "rare" for (size, kind, _), (_, f) in folds.items() if size < 4 or kind == "row0")
+    try:   # depth 5 does not fit: some row's accumulator passes 2^64
+        for coef, tcols in block_rows(5).values():
+            row_fold(coef, tcols)
+        raise SystemExit("a block of five fits after all?")
+    except AssertionError:
+        pass
+    for sizes in (MERGED, MERGED_FALLBACK, [4] * 5 + [2, 1], [1] * 23):
+        for t in range(12):
+            st = [[0] * 12, [P - 1] * 12, [(1 << 64) - 1] * 12][t] if t < 3 else \
+                [rnd.randrange(1 << 64) if (t + k) % 3 else rnd.randrange(P) for k in range(12)]
+            got = partial_rounds_blocks(st, rc, sizes, first=3)
+            assert [v % P for v in got] == merged_naive(st, rc), (sizes, t)
+    for t in range(4):   # and inside the whole permutation
+        st = [rnd.randrange(P) for _ in range(12)]
+        s = st
+        for r in range(4):
+            s = [pow((s[i] + rc[12 * r + i]) % P, 7, P) for i in range(W)]
+            if r < 3:
+                s = [(sum(s[(i + k) % W] * MDS_CIRC[i] for i in range(W)) + s[k] * MDS_DIAG[k]) % P for k in range(W)]
+        s = [v % P for v in partial_rounds_blocks(s, rc, MERGED, first=3)]
+        for r in range(26, 30):
+            s = [pow(v, 7, P) for v in s]
+            s = [(sum(s[(i + k) % W] * MDS_CIRC[i] for i in range(W)) + s[k] * MDS_DIAG[k] + (rc[12 * (r + 1) + k] if r < 29 else 0)) % P
+                 for k in range(W)]
+        assert s == permute(st, rc)
+    return max(acc for acc, _ in folds.values())
+
+
+def merged_tables(rc):
+    """The tables poseidon_fast.h reads for MERGED (one loop body of depth four; the trip of depth three skips its third stage).
+      PM_DEPTH[6]        the partition
+      PM_ROW0_D3[13]     row 0 at depth 3: the t_1 coefficient, then the twelve y-coefficients (t_2's is M[0][0], inline; depths
+                         1 and 2 are mds_row0 and PB_ROW0_D2, as in the blocks of three)
+      PM_END[2][12][14]  per depth (4, then 3) and output row: the coefficients of t_1 and t_2, then the twelve of y.  At depth 4
+                         t_3 keeps M[r][0], an inline constant; at depth 3 the loop body runs with t_3 = 0 and the slot of t_2,
+                         the last real t, holds M[r][0].
+      PM_K[6][15]        per block: K of row 0 at depths 1, 2, 3 (0 where the block is shallower), then the twelve K of its end.
+      PM_ALWAYS_*        bit per row: the fold's second step runs always (row_fold); ROW0: bit d - 1 for depth d."""
+    assert MERGED == [4] * 5 + [3]
+    r4, r3 = block_rows(4), block_rows(3)
+    M = mds_int()
+    assert r4[("row0", 1)] == (M[0], []) and r4[("row0", 2)] == (r3[("row0", 2)][0], [M[0][0]]) and r4[("row0", 3)][1][1] == M[0][0]
+    assert all(r4[("end", r)][1][2] == M[r][0] and r3[("end", r)][1][1] == M[r][0] for r in range(W))
+    row0_d3 = [r4[("row0", 3)][1][0]] + r4[("row0", 3)][0]
+    end = [r4[("end", r)][1][:2] + r4[("end", r)][0] for r in range(W)] + [r3[("end", r)][1] + r3[("end", r)][0] for r in range(W)]
+    K = [(k0 + [0, 0, 0])[:3] + kend for k0, kend in block_constants(rc, MERGED, first=3)]
+    assert K[0][0] == rc[48]   # the first block's K_1 is round 4's constants
+    always = {
+        "ROW0": sum((row_fold(*r4[("row0", d)])[1] == "always") << (d - 1) for d in (1, 2, 3)),
+        "END4": sum((row_fold(*r4[("end", r)])[1] == "always") << r for r in range(W)),
+        "END3": sum((row_fold(*r3[("end", r)])[1] == "always") << r for r in range(W)),
+    }
+    return row0_d3, end, K, always
+
+
 if __name__ == "__main__":
     rc, a, what, v, D0, L, E = derive()
     rnd = random.Random(1)
@@ -303,6 +403,10 @@ if __name__ == "__main__":
     check_blocks(rc, rnd)
     print("block form of the partial rounds == naive rounds, accumulator and fold bounds hold for blocks of 1, 2, 3 rounds")
     row0_d2, end, K = block_tables(rc)
+    worst = check_merged(rc, rnd)
+    print("merged middle (23 layers as %s) == round 3's MDS + naive rounds; accumulators below 2^%.2f, fold bounds hold per row"
+          % (MERGED, __import__("math").log2(worst)))
+    m_row0_d3, m_end, m_K, m_always = merged_tables(rc)
     if len(sys.argv) > 1:
         with open(sys.argv[1], "w") as f:
             f.write("// Generated by tools/gen_poseidon_fast.py; equivalence with the naive permutation checked at generation time.\n")
@@ -328,4 +432,10 @@ if __name__ == "__main__":
             arr32("PB_ROW0_D2", row0_d2, "[12]", 12)
             arr32("PB_END", [x for row in end for x in row], "[2 * 12 * 13]", 13)
             arr("PB_K", [x for row in K for x in row], "[8 * 14]")
+            arr32("PM_DEPTH", MERGED, "[6]", 6)
+            arr32("PM_ROW0_D3", m_row0_d3, "[13]", 13)
+            arr32("PM_END", [x for row in m_end for x in row], "[2 * 12 * 14]", 14)
+            arr("PM_K", [x for row in m_K for x in row], "[6 * 15]")
+            for name in ("ROW0", "END4", "END3"):
+                f.write("static constexpr unsigned int PM_ALWAYS_%s = 0x%03xu;\n" % (name, m_always[name]))
         print("wrote", sys.argv[1])
