@@ -206,6 +206,11 @@ int p2_selftest_host(uint64_t seed, size_t n_reductions, size_t n_permutations);
  * textbook forms as the reference): guards against code-generation regressions such as the add-with-carry fold described
  * in DESIGN.md.  Returns the number of mismatches, or a negative P2_ERR_* code. */
 int p2_selftest_device(uint64_t seed, size_t threads, int device);
+/* The lazy compositions of the polynomial-side kernels (permutation term and product step, the table-slot and looking-slot steps
+ * of the one-walk quotient, exact dot products, the table-power multiply) and the operand contracts of gl.h against the textbook canonical forms, on operands drawn from the extremes
+ * (0, 1, 2^32 - 1, 2^32, p - 1, p, p + 1, 2^64 - 1, zero limbs, random) and NOT reduced where a contract allows any u64; with one
+ * planted violation per contract that must show.  Returns the number of mismatches, or a negative P2_ERR_* code. */
+int p2_selftest_lazy_device(uint64_t seed, size_t threads, int device);
 /* The host build of the hash kernels' permutation: kind 0 = twelve unknown words, 1 = words 8..11 enter as 0, 2 = words 0..7 enter
  * as 0 (the words declared zero are not read); rows bit r = output word r is kept (canonical), the others are unspecified;
  * parts 0 = the round loops as the kernels run them, 1 = first round, middle and last round as separate functions. */
@@ -477,6 +482,9 @@ int p2_gpu_merged_middle(uint64_t* states, size_t count, int device);
 int p2_gpu_merkle_level(const uint64_t* child, size_t num_parents, size_t batch, uint64_t* parent, int device);
 /* vals [batch][2][len] -> digests [batch][len / arity][4] */
 int p2_gpu_hash_fri_leaves(const uint64_t* vals, size_t len, int arity, size_t batch, uint64_t* digests, int device);
+/* the opening-point power tables on their own (tests/test_gpu_side_kernels.py): z = (c0, c1) canonical, n a power of two up to 2^22
+ * -> pows [4][2][n]: point k = 0: z, 1: g z, 2: 1 / z, 3: 1 / (g z), g the primitive n-th root of unity; row [k][0] holds c0 */
+int p2_gpu_zeta_pows(const uint64_t* z, size_t n, uint64_t* pows, int device);
 /* debug: copy a named intermediate buffer of proof `index` of the last batch to the host
  * ("wires", "wires_cap", "zs", "zs_cap", "quotient_coeffs", "quotient_cap", "challenges", "openings",
  * "public_inputs_hash", ...) */

@@ -351,6 +351,29 @@ GL_HD u64 mul_nc(u64 a, u64 b) {
     return mul(a, b);
 #endif
 }
+// k * b + c as some u64 with `k` a UNIFORM value (a table entry read with scalar loads): its halves stay in SGPRs (mad_co_k)
+GL_HD u64 mul_add_nc_k(u64 k, u64 b, u64 c) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return mulr_add_dev<true, true>(k, b, c);
+#else
+    return add(mul(k, b), c);
+#endif
+}
+GL_HD u64 mul_nc_k(u64 k, u64 b) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return mulr_add_dev<false, true>(k, b, 0);
+#else
+    return mul(k, b);
+#endif
+}
+// Operand contracts of the lazy forms (p2_selftest_lazy_device checks each of them, with a planted violation per line):
+//   - the factors and the addend of mul / mul_add / mul*_nc / mulr_add_dev and the operands of glf::Acc::fma* may be ANY u64;
+//     mul and mul_add return the canonical representative, the _nc forms and Acc::reduce some representative
+//   - sub(a, b): b must be canonical; a may be any u64, and the result is then some representative (canonical if a is)
+//   - add(a, b): one operand must be canonical, the other may be any u64; the result is canonical if both are, else some
+//     representative (a wrapped sum gets + (2^32 - 1), which can land in [p, 2^64))
+// (sub with b >= p can end 2^64 away from the difference, add of two values >= p can wrap twice: neither folds a second time.)
+// Every value STORED to memory is canonical: a kernel canonicalises (canon_dev, or a final mul / add) what it writes.
 
 GL_HD u64 pow(u64 b, u64 e) {
     u64 r = 1;

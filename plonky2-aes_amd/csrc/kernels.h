@@ -1434,6 +1434,11 @@ __device__ __forceinline__ u64 block_scan_inclusive(u64 v, u64* lds) {
 // together (Montgomery's trick: one Fermat inversion and 3 multiplications per value instead of 20 inversions -- the
 // inversions were 3/4 of this kernel's multiplies).
 static const u32 PERM_MAX_CHUNKS = 12;
+// One factor of a chunk's numerator or denominator, w + beta f + gamma with t = w + gamma formed once per challenge, as a fused
+// multiply-add; and one step of a running product.  Both return SOME representative: their next use is a product.  Any u64 for
+// every operand.
+__device__ __forceinline__ u64 perm_term(u64 beta, u64 f, u64 t) { return gl::mul_add_nc(beta, f, t); }
+__device__ __forceinline__ u64 perm_step(u64 prod, u64 term) { return gl::mul_nc(prod, term); }
 __global__ __launch_bounds__(256) void k_perm_chunks(const u64* __restrict__ wires, size_t wires_batch_stride, const u64* __restrict__ sigmas,
                                                      const u64* __restrict__ k_is, const u64* __restrict__ subgroup, const u64* __restrict__ chal,
                                                      u64* __restrict__ q, size_t q_batch_stride, u32 n, u32 num_routed, u32 chunk_size, u32 num_chunks,
@@ -1446,19 +1451,40 @@ __global__ __launch_bounds__(256) void k_perm_chunks(const u64* __restrict__ wir
     const bool two = num_challenges > 1;
     const u64 b0 = cw[CH_BETAS], g0 = cw[CH_GAMMAS], b1 = two ? cw[CH_BETAS + 1] : 0, g1 = two ? cw[CH_GAMMAS + 1] : 0;
     const u64 x = subgroup[row], bx0 = gl::mul(b0, x), bx1 = gl::mul(b1, x);
+    // Only stored values are canonical: the terms and the running products are representatives (gl.h, operand contracts),
+    // every product starts from its first factor, and the padded entries (c >= num_chunks, the second challenge of a
+    // one-challenge configuration) take no part in the inversion.
     u64 num[2 * PERM_MAX_CHUNKS], den[2 * PERM_MAX_CHUNKS], pre[2 * PERM_MAX_CHUNKS];
+    auto factors = [&](u32 j, u64& tn0, u64& td0, u64& tn1, u64& td1) {
+        const u64 wv = w[(size_t)j * n], s = sg[(size_t)j * n], kj = k_is[j];
+        const u64 t0 = gl::add(wv, g0);
+        tn0 = perm_term(bx0, kj, t0);
+        td0 = perm_term(b0, s, t0);
+        if (two) {
+            const u64 t1 = gl::add(wv, g1);
+            tn1 = perm_term(bx1, kj, t1);
+            td1 = perm_term(b1, s, t1);
+        }
+    };
 #pragma unroll
     for (u32 c = 0; c < PERM_MAX_CHUNKS; c++) {
         u64 n0 = 1, d0 = 1, n1 = 1, d1 = 1;
         if (c < num_chunks) {
-            const u32 j1 = min(num_routed, (c + 1) * chunk_size);
-            for (u32 j = c * chunk_size; j < j1; j++) {
-                const u64 wv = w[(size_t)j * n], s = sg[(size_t)j * n], kj = k_is[j];
-                n0 = gl::mul(n0, gl::add(gl::add(wv, gl::mul(bx0, kj)), g0));
-                d0 = gl::mul(d0, gl::add(gl::add(wv, gl::mul(b0, s)), g0));
-                if (two) {
-                    n1 = gl::mul(n1, gl::add(gl::add(wv, gl::mul(bx1, kj)), g1));
-                    d1 = gl::mul(d1, gl::add(gl::add(wv, gl::mul(b1, s)), g1));
+            const u32 j0 = c * chunk_size, j1 = min(num_routed, (c + 1) * chunk_size);
+            for (u32 j = j0; j < j1; j++) {
+                u64 tn0, td0, tn1 = 1, td1 = 1;
+                factors(j, tn0, td0, tn1, td1);
+                // a uniform branch, not a second copy of the body in front of the loop: that one grows the twelve-fold unrolled
+                // chunk loop past the unroller's budget, and num / den / pre land in scratch
+                if (j == j0) {
+                    n0 = tn0, d0 = td0, n1 = tn1, d1 = td1;
+                } else {
+                    n0 = perm_step(n0, tn0);
+                    d0 = perm_step(d0, td0);
+                    if (two) {
+                        n1 = perm_step(n1, tn1);
+                        d1 = perm_step(d1, td1);
+                    }
                 }
             }
         }
@@ -1471,18 +1497,22 @@ __global__ __launch_bounds__(256) void k_perm_chunks(const u64* __restrict__ wir
 #pragma unroll
     for (u32 k = 0; k < 2 * PERM_MAX_CHUNKS; k++) {
         pre[k] = run;
-        run = gl::mul(run, den[k]);
+        if (k == 0)
+            run = den[0];  // num_chunks >= 1
+        else if (k % PERM_MAX_CHUNKS < num_chunks && k / PERM_MAX_CHUNKS < num_challenges)
+            run = perm_step(run, den[k]);
     }
     // A zero denominator (probability ~2^-45 per proof; upstream's quotient computation fails on it) zeroes the whole
     // row here, where value-by-value inversion would zero one chunk: no valid proof exists either way.
     u64 inv = gl::inv(run);
 #pragma unroll
     for (u32 kk = 2 * PERM_MAX_CHUNKS; kk-- > 0;) {
-        const u64 dinv = gl::mul(inv, pre[kk]);
-        inv = gl::mul(inv, den[kk]);
         const u32 ch = kk / PERM_MAX_CHUNKS, c = kk % PERM_MAX_CHUNKS;
-        if (c < num_chunks && ch < num_challenges)
+        if (c < num_chunks && ch < num_challenges) {
+            const u64 dinv = kk == 0 ? inv : perm_step(inv, pre[kk]);
+            if (kk) inv = perm_step(inv, den[kk]);
             q[(size_t)blockIdx.y * q_batch_stride + ((size_t)ch * num_chunks + c) * n + row] = gl::mul(num[kk], dinv);
+        }
     }
 }
 

@@ -58,6 +58,38 @@ struct AlphaAcc {
     }
 };
 
+// The per-slot steps of the lookup argument for one challenge.  LAZY (the one-walk quotient): a value whose next use is a factor
+// or an addend stays SOME representative (gl.h, operand contracts).  LAZY = false is the two-walk kernel's code as it was.  What
+// a subtraction takes away is canonical in both forms.
+//   table slot (inp, out, mult): RE Horner cur' = cur dD + (dB out + inp); f = dAl - (dA out + inp); sum' = sum f + mult prod;
+//   prod' = prod f
+template <bool LAZY>
+__device__ __forceinline__ void lut_step(u64& cur, u64& tsum, u64& tprod, u64 dA, u64 dB, u64 dAl, u64 dD, u64 win, u64 wout, u64 wm) {
+    const u64 re = gl::mul_add_nc(dB, wout, win), f = gl::sub(dAl, gl::mul_add(dA, wout, win));
+    if (LAZY) {
+        cur = gl::mul_add_nc(cur, dD, re);
+        tsum = gl::mul_add_nc(tsum, f, gl::mul_nc(wm, tprod));
+        tprod = gl::mul_nc(tprod, f);
+    } else {
+        cur = gl::mul_add(cur, dD, re);
+        tsum = gl::mul_add(tsum, f, gl::mul_nc(wm, tprod));  // sum' = sum*f + mult*prod
+        tprod = gl::mul(tprod, f);
+    }
+}
+//   looking slot (inp, out): f as above; sum' = sum f + prod; prod' = prod f.  Canonical in both kernels: with lazy products here
+//   the compiler's size estimate of the one-walk kernel's eight-column loop passes the unroller's budget, and the loop stays rolled
+//   with dynamic column indices.
+__device__ __forceinline__ void lu_step(u64& lsum, u64& lprod, u64 dA, u64 dAl, u64 win, u64 wout) {
+    const u64 f = gl::sub(dAl, gl::mul_add(dA, wout, win));
+    lsum = gl::mul_add(lsum, f, lprod);
+    lprod = gl::mul(lprod, f);
+}
+// the closing terms of a partial polynomial, before the selector: prod diff - sum, prod diff + sum
+template <bool LAZY>
+__device__ __forceinline__ u64 lut_close(u64 tprod, u64 tsum, u64 diff) {
+    return LAZY ? gl::sub(gl::mul_nc(tprod, diff), glf::canon(tsum)) : gl::sub(gl::mul(tprod, diff), tsum);
+}
+__device__ __forceinline__ u64 lu_close(u64 lprod, u64 lsum, u64 diff) { return gl::add(gl::mul(lprod, diff), lsum); }
 // One thread per point of the LDE coset (bit-reversed position p); evaluates every constraint of
 // eval_vanishing_poly_base (term k is weighted by alpha^k, k in plonky2's order [Z(1) | partial products | lookups |
 // gates]) for both challenges at once and divides by Z_H.  The 80 wire columns are walked TWICE: once for the permutation
@@ -142,18 +174,15 @@ __global__ __launch_bounds__(256, 4) void k_quotient(QuotientArgs a) {
     }
     // LookupTableGate view (slots (inp, out, mult): RE Horner and the Sum transition of each partial poly) and LookupGate view
     // (slots (inp, out): the LDC transition of each partial poly)
-    auto lut_slot = [&](u32 s_, u64 win, u64 wout, u64 wm) {
-        for (u32 i = 0; i < 2; i++) {
-            cur[i] = gl::mul_add(cur[i], dD[i], gl::mul_add_nc(dB[i], wout, win));
-            const u64 f = gl::sub(dAl[i], gl::mul_add(dA[i], wout, win));
-            tsum[i] = gl::mul_add(tsum[i], f, gl::mul_nc(wm, tprod[i]));  // sum' = sum*f + mult*prod
-            tprod[i] = gl::mul(tprod[i], f);
-        }
+    // a term on its way into the AlphaAcc needs no canonical form: fma_k is exact on any u64
+    auto term_mul = [](u64 x, u64 y) __attribute__((always_inline)) { return ONE_WALK ? gl::mul_nc(x, y) : gl::mul(x, y); };
+    auto lut_slot = [&](u32 s_, u64 win, u64 wout, u64 wm) __attribute__((always_inline)) {
+        for (u32 i = 0; i < 2; i++) lut_step<ONE_WALK>(cur[i], tsum[i], tprod[i], dA[i], dB[i], dAl[i], dD[i], win, wout, wm);
         if (++tin == a.lut_deg || s_ + 1 == p2::LUT_SLOTS) {
             for (u32 i = 0; i < 2; i++) {
                 u64 prev = tpoly == 0 ? lzn[i][(size_t)a.nsldc * N] : lz[i][(size_t)tpoly * N];
                 u64 diff = gl::sub(lz[i][(size_t)(1 + tpoly) * N], prev);
-                A.add(idx_lk + i * nlk + 4 + a.num_luts + 2 * tpoly, gl::mul(s_sre, gl::sub(gl::mul(tprod[i], diff), tsum[i])));
+                A.add(idx_lk + i * nlk + 4 + a.num_luts + 2 * tpoly, term_mul(s_sre, lut_close<ONE_WALK>(tprod[i], tsum[i], diff)));
                 tprod[i] = 1;
                 tsum[i] = 0;
             }
@@ -161,17 +190,13 @@ __global__ __launch_bounds__(256, 4) void k_quotient(QuotientArgs a) {
             tin = 0;
         }
     };
-    auto lu_slot = [&](u32 s_, u64 win, u64 wout) {
-        for (u32 i = 0; i < 2; i++) {
-            const u64 f = gl::sub(dAl[i], gl::mul_add(dA[i], wout, win));
-            lsum[i] = gl::mul_add(lsum[i], f, lprod[i]);
-            lprod[i] = gl::mul(lprod[i], f);
-        }
+    auto lu_slot = [&](u32 s_, u64 win, u64 wout) __attribute__((always_inline)) {
+        for (u32 i = 0; i < 2; i++) lu_step(lsum[i], lprod[i], dA[i], dAl[i], win, wout);
         if (++lin == lu_deg || s_ + 1 == p2::LU_SLOTS) {
             for (u32 i = 0; i < 2; i++) {
                 u64 prev = lpoly == 0 ? lzn[i][(size_t)a.nsldc * N] : lz[i][(size_t)lpoly * N];
                 u64 diff = gl::sub(lz[i][(size_t)(1 + lpoly) * N], prev);
-                A.add(idx_lk + i * nlk + 4 + a.num_luts + 2 * lpoly + 1, gl::mul(s_ldc, gl::add(gl::mul(lprod[i], diff), lsum[i])));
+                A.add(idx_lk + i * nlk + 4 + a.num_luts + 2 * lpoly + 1, term_mul(s_ldc, lu_close(lprod[i], lsum[i], diff)));
                 lprod[i] = 1;
                 lsum[i] = 0;
             }
@@ -199,15 +224,19 @@ __global__ __launch_bounds__(256, 4) void k_quotient(QuotientArgs a) {
                     // w + gamma once per challenge, the beta term as a fused multiply-add whose (non-canonical) result goes
                     // straight into the running product: 2 adds + 4 fused ops + 4 products instead of 8 adds + 8 products
                     // (one challenge after the other: with both sums live the kernel spills at its 128-register budget)
+                    // The running products are representatives (their next use is a product), and column 0 of the chunk starts
+                    // them: k is a compile-time constant in this unrolled loop.
                     {
                         const u64 t = gl::add(wv, g0);
-                        num0 = gl::mul(num0, gl::mul_add_nc(bx0, kj, t));
-                        den0 = gl::mul(den0, gl::mul_add_nc(b0, sg, t));
+                        const u64 tn = perm_term(bx0, kj, t), td = perm_term(b0, sg, t);
+                        num0 = k == 0 ? tn : perm_step(num0, tn);
+                        den0 = k == 0 ? td : perm_step(den0, td);
                     }
                     {
                         const u64 t = gl::add(wv, g1);
-                        num1 = gl::mul(num1, gl::mul_add_nc(bx1, kj, t));
-                        den1 = gl::mul(den1, gl::mul_add_nc(b1, sg, t));
+                        const u64 tn = perm_term(bx1, kj, t), td = perm_term(b1, sg, t);
+                        num1 = k == 0 ? tn : perm_step(num1, tn);
+                        den1 = k == 0 ? td : perm_step(den1, td);
                     }
                 }
             } else {
@@ -224,13 +253,13 @@ __global__ __launch_bounds__(256, 4) void k_quotient(QuotientArgs a) {
                 // ArithmeticGate ops 2*chunk and 2*chunk + 1 occupy exactly these 8 wires: out - (c0 m0 m1 + c1 addend)
                 for (u32 h = 0; h < 2; h++) {
                     const u64 m0 = w8[4 * h], m1 = w8[4 * h + 1], ad = w8[4 * h + 2], o = w8[4 * h + 3];
-                    A.add(idx_gate + 2 * chunk + h, gl::mul(f_arith, gl::sub(o, gl::mul_add(gl::mul_nc(m0, m1), c0, gl::mul_nc(ad, c1)))));
+                    A.add(idx_gate + 2 * chunk + h, term_mul(f_arith, gl::sub(o, gl::mul_add(gl::mul_nc(m0, m1), c0, gl::mul_nc(ad, c1)))));
                 }
             }
             for (u32 i = 0; i < 2; i++) {
                 u64 prev = chunk == 0 ? Zs[(size_t)i * N] : Zs[(size_t)(a.NC + i * a.npp + chunk - 1) * N];
                 u64 next = chunk == a.npp ? Zn[(size_t)i * N] : Zs[(size_t)(a.NC + i * a.npp + chunk) * N];
-                A.add(idx_pp + i * (a.npp + 1) + chunk, gl::sub(gl::mul(prev, i ? num1 : num0), gl::mul(next, i ? den1 : den0)));
+                A.add(idx_pp + i * (a.npp + 1) + chunk, gl::sub(term_mul(prev, i ? num1 : num0), gl::mul(next, i ? den1 : den0)));
             }
             if (ONE_WALK && a.nlp) {
                 // the slots that end in this chunk: column c = 8 chunk + k closes table slot c / 3 when c % 3 == 2 (c < 78) and
@@ -264,7 +293,7 @@ __global__ __launch_bounds__(256, 4) void k_quotient(QuotientArgs a) {
             }
             lu_slot(39, W[(size_t)78 * N], W[(size_t)79 * N]);
         }
-        for (u32 i = 0; i < 2; i++) A.add(idx_lk + i * nlk + 3 + a.num_luts, gl::mul(s_sre, gl::sub(lz[i][0], cur[i])));
+        for (u32 i = 0; i < 2; i++) A.add(idx_lk + i * nlk + 3 + a.num_luts, term_mul(s_sre, gl::sub(lz[i][0], ONE_WALK ? glf::canon(cur[i]) : cur[i])));
     }
     // gate constraints: constraint slot k collects every gate's k-th constraint times the gate's filter
     {
@@ -301,15 +330,49 @@ __global__ __launch_bounds__(256, 4) void k_quotient(QuotientArgs a) {
 
 // ------------------------------------------------------------------------------------------- openings
 // pows[k][i] = z_k^i (extension), k = 0: zeta, 1: g*zeta, 2: 1/zeta, 3: 1/(g*zeta).  layout [k][2][n] (c0 | c1)
-__global__ void k_zeta_pows(const u64* chal, u64* pows, size_t pows_batch_stride, u32 n, u64 g) {
-    u32 i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
+// Two levels: z^i = z^(i mod 256) * (z^256)^(i div 256).  k_zeta_tabs writes, per (proof, point), the 256 low powers as
+// (c0, c1) pairs and the max(n / 256, 1) high powers as (c0, c1, 7 c1) triples -- the only exponentiations -- and k_zeta_pows
+// forms every element with one extension multiply whose high factor is uniform per workgroup (256 threads = one high entry).
+static const u32 ZT_LO = 256;
+__host__ __device__ inline u32 zeta_tab_hi(u32 n) { return n > ZT_LO ? n / ZT_LO : 1; }
+__host__ __device__ inline size_t zeta_tab_words(u32 n) { return 2 * (size_t)ZT_LO + 3 * (size_t)zeta_tab_hi(n); }  // per (proof, point)
+__global__ __launch_bounds__(256) void k_zeta_tabs(const u64* chal, u64* tabs, u32 n, u64 g) {
+    const u32 t = blockIdx.x * blockDim.x + threadIdx.x, nhi = zeta_tab_hi(n);
+    if (t >= ZT_LO + nhi) return;
     const u64* cw = chal + (size_t)blockIdx.y * CH_WORDS;
     E2 z = gl::e2(cw[CH_ZETA], cw[CH_ZETA + 1]);
-    u32 k = blockIdx.z;
+    const u32 k = blockIdx.z;
     if (k & 1) z = gl::mul(z, g);
     if (k & 2) z = gl::inv(z);
-    E2 r = gl::pow(z, i);
+    u64* o = tabs + ((size_t)blockIdx.y * 4 + k) * zeta_tab_words(n);
+    if (t < ZT_LO) {
+        const E2 r = gl::pow(z, t);
+        o[2 * t] = r.a;
+        o[2 * t + 1] = r.b;
+    } else {
+        const u32 q = t - ZT_LO;
+        const E2 r = gl::pow(gl::exp_pow2(z, 8), q);
+        u64* h = o + 2 * ZT_LO + 3 * (size_t)q;
+        h[0] = r.a;
+        h[1] = r.b;
+        h[2] = gl::mul(r.b, gl::W_EXT);
+    }
+}
+// (l0 + l1 x)(h0 + h1 x) = l0 h0 + l1 (7 h1) + (l0 h1 + l1 h0) x with the high factor uniform (its words read from SGPRs) and
+// 7 h1 from the table: four fused products whose addends ride on the mads, canonical result.  Any u64 for every operand.
+__device__ __forceinline__ E2 tabpow_mul(E2 lo, u64 h0, u64 h1, u64 h1w) {
+    const u64 c0 = gl::mul_add_nc_k(h0, lo.a, gl::mul_nc_k(h1w, lo.b));
+    const u64 c1 = gl::mul_add_nc_k(h1, lo.a, gl::mul_nc_k(h0, lo.b));
+    return gl::e2(glf::canon(c0), glf::canon(c1));
+}
+__global__ __launch_bounds__(256) void k_zeta_pows(const u64* __restrict__ tabs, u64* __restrict__ pows, size_t pows_batch_stride, u32 n) {
+    static_assert(ZT_LO == 256, "one workgroup of 256 threads shares one high-table entry");
+    const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const u32 k = blockIdx.z;
+    const u64* tb = tabs + ((size_t)blockIdx.y * 4 + k) * zeta_tab_words(n);
+    const u64* h = tb + 2 * ZT_LO + 3 * (size_t)blockIdx.x;  // blockIdx.x = i / 256 < max(n / 256, 1): uniform
+    const E2 r = tabpow_mul(gl::e2(tb[2 * threadIdx.x], tb[2 * threadIdx.x + 1]), h[0], h[1], h[2]);
     u64* o = pows + (size_t)blockIdx.y * pows_batch_stride + (size_t)k * 2 * n;
     o[i] = r.a;
     o[n + i] = r.b;
@@ -318,6 +381,13 @@ __global__ void k_zeta_pows(const u64* chal, u64* pows, size_t pows_batch_stride
 // workgroup per (entry, proof) (round 2 launched a kernel per oracle and point: preprocessed, wires, Z at zeta, Z at g zeta,
 // quotient): entry e = column `col` of the coefficient matrix `base`, evaluated with power table pw_k (0: zeta, 1: g zeta),
 // result to extension slot `out`.
+// One base-field value times a uniform extension value (ka + kb x, read from SGPRs), into the two component sums; and the
+// canonical value of such a sum.  Any u64 for every operand (the Acc takes exact integer sums).
+__device__ __forceinline__ void acc_dot2_k(glf::Acc& sa, glf::Acc& sb, u64 v, u64 ka, u64 kb) {
+    sa.fma_k(ka, v);
+    sb.fma_k(kb, v);
+}
+__device__ __forceinline__ u64 acc_value(const glf::Acc& a) { return glf::canon(a.reduce()); }
 struct EvalRef {
     const u64* base;      // coefficient matrix of the oracle (proof 0)
     size_t batch_stride;  // 0 for the shared preprocessed oracle
@@ -331,7 +401,9 @@ __global__ __launch_bounds__(256) void k_eval_polys_refs(const EvalRef* __restri
     const u64* pa = pows + (size_t)blockIdx.y * pw_batch_stride + (size_t)r.pw_k * 2 * n;
     u64 sa = 0, sb = 0;
     u32 i = threadIdx.x;
-    // four rows per trip, their twelve loads issued before the first product (loads_issued, kernels.h)
+    // four rows per trip, their twelve loads issued before the first product (loads_issued, kernels.h).  (Exact glf::Acc sums
+    // instead of a canonical multiply and add per coefficient: 0.930 -> 0.925 ms per 128-proof chunk, nothing -- the kernel waits
+    // on its reads.)
     for (; i + 3 * blockDim.x < n; i += 4 * blockDim.x) {
         u64 v[4], wa[4], wb[4];
 #pragma unroll
@@ -377,25 +449,53 @@ struct PolyRef {
     u32 col;
     u32 pad;
 };
+// alpha^j (extension) for j < count, per proof: fpow[proof][j] = (c0, c1).  One thread per entry (j < 2^16: at most 32 products).
+__global__ void k_fri_alpha_pows(const u64* chal, u64* fpow, u32 count) {
+    const u32 j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= count) return;
+    const u64* cw = chal + (size_t)blockIdx.y * CH_WORDS;
+    const E2 r = gl::pow(gl::e2(cw[CH_FRI_ALPHA], cw[CH_FRI_ALPHA + 1]), j);
+    u64* o = fpow + ((size_t)blockIdx.y * count + j) * 2;
+    o[0] = r.a;
+    o[1] = r.b;
+}
 // comp[b][k] = sum_j alpha^j f_{b,j}[k]   for the two FRI batches (b = 0: zeta, b = 1: g*zeta); output [b][2][n]
-__global__ __launch_bounds__(256) void k_fri_compose(const PolyRef* __restrict__ polys, u32 n0, u32 n1, const u64* chal, u32 n, u64* comp, size_t comp_batch_stride) {
+// f is a base-field value, so the two components are the exact sums sum_j alpha^j.c0 f_j and sum_j alpha^j.c1 f_j: two fma_k per
+// polynomial with the power (uniform: per proof and j) read from SGPRs, one reduction per component at the end.  (Horner in
+// GF(p^2) spent an extension multiply and a canonical add per polynomial.)
+__global__ __launch_bounds__(256) void k_fri_compose(const PolyRef* __restrict__ polys, u32 n0, u32 n1, const u64* __restrict__ fpow, u32 fpow_count, u32 n,
+                                                      u64* __restrict__ comp, size_t comp_batch_stride) {
     u32 k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= n) return;
-    const u64* cw = chal + (size_t)blockIdx.y * CH_WORDS;
-    const E2 alpha = gl::e2(cw[CH_FRI_ALPHA], cw[CH_FRI_ALPHA + 1]);
+    const u64* pw = fpow + (size_t)blockIdx.y * fpow_count * 2;
     u64* o = comp + (size_t)blockIdx.y * comp_batch_stride;
     u32 off = 0;
     for (u32 b = 0; b < 2; b++) {
         u32 cnt = b == 0 ? n0 : n1;
-        E2 acc = gl::e2(0, 0);
-        for (u32 j = cnt; j-- > 0;) {  // Horner: acc = acc*alpha + f_j[k]
-            const PolyRef pr = polys[off + j];
-            u64 v = pr.base ? pr.base[(size_t)blockIdx.y * pr.batch_stride + (size_t)pr.col * n + k] : 0;
-            acc = gl::mul(acc, alpha);
-            acc.a = gl::add(acc.a, v);
+        glf::Acc c0, c1;
+        c0.init();
+        c1.init();
+        // a null base contributes 0 (uniform).  Four polynomials per trip, their loads issued before the first product
+        // (loads_issued, kernels.h): with 16 instructions per value the kernel waits on its reads, not on issue slots
+        // (the column pointer comes out of memory, so the compiler cannot tell its address space and would use flat loads, whose
+        // counter the scalar loads of the next PolyRef share: each value would be waited for before the next is asked for)
+        typedef const u64 __attribute__((address_space(1))) * gptr;
+        auto value = [&](const PolyRef& pr) -> u64 { return pr.base ? ((gptr)pr.base)[(size_t)blockIdx.y * pr.batch_stride + (size_t)pr.col * n + k] : 0; };
+        u32 j = 0;
+        for (; j + 4 <= cnt; j += 4) {
+            PolyRef pr[4];
+            u64 v[4];
+#pragma unroll
+            for (int i = 0; i < 4; i++) pr[i] = polys[off + j + i];
+#pragma unroll
+            for (int i = 0; i < 4; i++) v[i] = value(pr[i]);
+            loads_issued();
+#pragma unroll
+            for (int i = 0; i < 4; i++) acc_dot2_k(c0, c1, v[i], pw[2 * (j + i)], pw[2 * (j + i) + 1]);
         }
-        o[(size_t)(2 * b) * n + k] = acc.a;
-        o[(size_t)(2 * b + 1) * n + k] = acc.b;
+        for (; j < cnt; j++) acc_dot2_k(c0, c1, value(polys[off + j]), pw[2 * j], pw[2 * j + 1]);
+        o[(size_t)(2 * b) * n + k] = acc_value(c0);
+        o[(size_t)(2 * b + 1) * n + k] = acc_value(c1);
         off += cnt;
     }
 }

@@ -131,6 +131,7 @@ struct Workspace {
     ChalState* d_chal_state = nullptr;
     u64* d_chal = nullptr;
     u64 *d_pows = nullptr, *d_ev = nullptr, *d_obs = nullptr, *d_comp = nullptr, *d_apow = nullptr;
+    u64 *d_ztab = nullptr, *d_fripow = nullptr;  // per proof: the two-level tables of k_zeta_tabs, the FRI alpha powers
     u64* d_fri_coef[9] = {nullptr};  // [2][n_r]
     u64* d_fri_vals[9] = {nullptr};  // [2][8 n_r]
     Tree fri_tree[9];
@@ -705,6 +706,9 @@ static int dalloc_ws(p2_circuit* C, size_t& counter, void** p, size_t bytes) {
     *p = q;
     return 0;
 }
+// entries of the per-proof table of FRI alpha powers: the longer of the two batches.  From the layout, which the handle has from
+// load on -- C->n_b0 / n_b1 are set by setup_polyrefs, at the END of the first build_workspace.
+static u32 fri_pow_count(const p2_circuit* C) { return std::max<u32>(std::max(C->layout.set.n_b0, C->layout.set.n_b1), 1); }
 static int build_workspace(p2_circuit* C, Workspace* W, size_t chunk, u32 ws_inputs, size_t& counter) {
     const Circuit& c = C->c;
     const size_t n = C->n, N = C->N;
@@ -747,6 +751,8 @@ static int build_workspace(p2_circuit* C, Workspace* W, size_t chunk, u32 ws_inp
     WS_ALLOC(W->d_obs, chunk * 2 * C->n_obs);
     WS_ALLOC(W->d_comp, chunk * 4 * n);
     WS_ALLOC(W->d_apow, chunk * 2 * APOW_STRIDE);
+    WS_ALLOC(W->d_ztab, chunk * 4 * zeta_tab_words((u32)n));
+    WS_ALLOC(W->d_fripow, chunk * 2 * fri_pow_count(C));
     u32 logn_r = C->dom.logn;
     for (u32 r = 0; r <= C->dom.arities.size(); r++) {
         size_t n_r = (size_t)1 << logn_r;
@@ -1010,7 +1016,9 @@ static int prove_chunk(p2_circuit* C, Workspace& W, u32 B, u32 n_inputs, const u
     }
     if (commit_oracle(C, W, W.quot, 2, c.degree_bits, proof_base, B)) return P2_ERR_HIP;
     // 8. openings
-    LAUNCH(W.lane, "zeta_pows", k_zeta_pows, g1(n, 256, B, 4), dim3(256), 0, W.d_chal, W.d_pows, (size_t)8 * n, (u32)n, gl::root_of_unity((int)C->dom.logn));
+    // (the table launch goes under the same name: the stage's time is the sum of the two)
+    LAUNCH(W.lane, "zeta_pows", k_zeta_tabs, g1(ZT_LO + zeta_tab_hi((u32)n), 256, B, 4), dim3(256), 0, W.d_chal, W.d_ztab, (u32)n, gl::root_of_unity((int)C->dom.logn));
+    LAUNCH(W.lane, "zeta_pows", k_zeta_pows, g1(n, 256, B, 4), dim3(256), 0, W.d_ztab, W.d_pows, (size_t)8 * n, (u32)n);
     HIPCHECK(hipMemsetAsync(W.d_ev, 0, (size_t)B * 2 * C->ev_count * 8, st));
     {
         const size_t evs = 2 * (size_t)C->ev_count;
@@ -1020,7 +1028,11 @@ static int prove_chunk(p2_circuit* C, Workspace& W, u32 B, u32 n_inputs, const u
     }
     if (challenger(C, W, 3, W.d_obs, (size_t)2 * C->n_obs, 2 * C->n_obs, 0, 0, B)) return P2_ERR_HIP;
     // 9. FRI: compose, divide, commit phase
-    LAUNCH(W.lane, "fri_compose", k_fri_compose, g1(n, 256, B), dim3(256), 0, W.d_polyrefs, C->n_b0, C->n_b1, W.d_chal, (u32)n, W.d_comp, (size_t)4 * n);
+    {
+        const u32 npow = fri_pow_count(C);
+        LAUNCH(W.lane, "fri_compose", k_fri_alpha_pows, g1(npow, 64, B), dim3(64), 0, W.d_chal, W.d_fripow, npow);
+        LAUNCH(W.lane, "fri_compose", k_fri_compose, g1(n, 256, B), dim3(256), 0, W.d_polyrefs, C->n_b0, C->n_b1, W.d_fripow, npow, (u32)n, W.d_comp, (size_t)4 * n);
+    }
     {
         const u32 segs = (u32)std::min<size_t>(std::max<size_t>(n >> 14, 1), FRI_MAX_SEGS);  // as in the permutation scan
         if (segs > 1)
@@ -2433,6 +2445,163 @@ int p2_selftest_device(uint64_t seed, size_t threads, int device) {
     unsigned long long h = 0;
     if (hipError_t e = hipMemcpy(&h, d, 8, hipMemcpyDeviceToHost)) return set_error(hipGetErrorString(e)), -P2_ERR_HIP;
     return (int)std::min<unsigned long long>(h, 0x7FFFFFFF);
+}
+
+// ---- self-test of the lazy compositions of the polynomial-side kernels (gl.h, operand contracts)
+namespace p2k {
+// What a non-canonical intermediate does to these compositions shows only for values in [p, 2^64), which random data reaches with
+// probability 2^-32: the operands are therefore drawn from the extremes, and wherever a contract says "any u64" they are not
+// reduced first.  `r` is the random word the draw may use, `sel` chooses.
+__device__ __forceinline__ u64 lazy_draw(u64 r, u32 sel) {
+    switch (sel % 12) {
+        case 0: return 0;
+        case 1: return 1;
+        case 2: return gl::EPS;
+        case 3: return 1ull << 32;
+        case 4: return gl::P - 1;
+        case 5: return gl::P;
+        case 6: return gl::P + 1;
+        case 7: return ~0ull;
+        case 8: return ((r & 0xFFFF) | 1) << 48;  // zero low limbs: the reduction's borrow case
+        case 9: return (r & gl::EPS) << 32;
+        default: return r;
+    }
+}
+__global__ void k_selftest_lazy(unsigned long long* bad, u64 seed, size_t threads) {
+    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= threads) return;
+    u64 x = (seed | 1) + 0x9E3779B97F4A7C15ull * (t + 1), xu = (seed | 1) ^ 0xD1B54A32D192ED03ull;  // xu: the same in every thread
+    auto step = [](u64& v) {
+        v ^= v << 13;
+        v ^= v >> 7;
+        v ^= v << 17;
+        return v;
+    };
+    auto rnd = [&]() {
+        const u64 r = step(x);
+        return lazy_draw(r, (u32)(r >> 40));
+    };
+    auto rnd_uniform = [&]() {  // for the operands that the kernels read from SGPRs: a lane-dependent value may not go there
+        const u64 r = step(xu);
+        return lazy_draw(r, (u32)(r >> 40));
+    };
+    auto M = [](u64 a, u64 b) { return gl::mul_ref(a % gl::P, b % gl::P); };
+    unsigned long long b = 0;
+    for (int i = 0; i < 16; i++) {
+        // permutation term and product step: w and gamma canonical as loaded, everything else any u64; two terms multiplied
+        // without a canonical value in between, then the running product continued
+        const u64 w = rnd() % gl::P, g = rnd() % gl::P, beta = rnd(), f0 = rnd(), f1 = rnd(), prod = rnd();
+        const u64 tt = gl::add(w, g);
+        if (tt != gl::add_ref(w, g)) b++;
+        const u64 t0 = perm_term(beta, f0, tt), t1 = perm_term(beta, f1, tt);
+        const u64 r0 = gl::add_ref(M(beta, f0), tt), r1 = gl::add_ref(M(beta, f1), tt);
+        if (glf::canon(t0) != r0 || glf::canon(t1) != r1) b++;
+        if (glf::canon(perm_step(perm_step(prod, t0), t1)) != M(M(prod, r0), r1)) b++;
+        if (gl::mul(perm_step(t0, t1), prod) != M(M(r0, r1), prod)) b++;  // what is stored: canonical
+        const u64 any = rnd();
+        if (glf::canon(perm_term(beta, f0, any)) != gl::add_ref(M(beta, f0), any % gl::P)) b++;  // the addend may be any u64 too
+        // Acc dot product: five terms, any u64, the extension factor uniform
+        {
+            glf::Acc ka, kb;
+            ka.init(), kb.init();
+            u64 wka = 0, wkb = 0;
+            for (int j = 0; j < 5; j++) {
+                const u64 v = rnd(), ua = rnd_uniform(), ub = rnd_uniform();
+                acc_dot2_k(ka, kb, v, ua, ub);
+                wka = gl::add_ref(wka, M(v, ua));
+                wkb = gl::add_ref(wkb, M(v, ub));
+            }
+            if (acc_value(ka) != wka || acc_value(kb) != wkb) b++;
+        }
+        // table-power multiply: the high factor (and its 7-fold second word, an operand of its own here) uniform
+        {
+            const u64 l0 = rnd(), l1 = rnd(), h0 = rnd_uniform(), h1 = rnd_uniform(), h1w = rnd_uniform();
+            const E2 got = tabpow_mul(gl::e2(l0, l1), h0, h1, h1w);
+            if (got.a != gl::add_ref(M(l0, h0), M(l1, h1w)) || got.b != gl::add_ref(M(l0, h1), M(l1, h0))) b++;
+            const u64 c = rnd_uniform() % gl::P, d = rnd_uniform() % gl::P;  // and as the table holds it: h1w = 7 h1, canonical
+            const E2 lo = gl::e2(l0 % gl::P, l1 % gl::P), want = gl::mul(lo, gl::e2(c, d)), have = tabpow_mul(lo, c, d, gl::mul(d, gl::W_EXT));
+            if (have.a != want.a || have.b != want.b) b++;
+        }
+        // table-slot and looking-slot steps of the one-walk quotient: challenges and wire values canonical as loaded, the
+        // running values any u64; three steps, each on what the one before left (never canonicalised in between), then the
+        // closing terms; and the plain forms on canonical values
+        {
+            const u64 dA = rnd_uniform() % gl::P, dB = rnd_uniform() % gl::P, dAl = rnd_uniform() % gl::P, dD = rnd_uniform() % gl::P;
+            u64 cur = rnd(), tsum = rnd(), tprod = rnd(), lsum = rnd(), lprod = rnd();
+            u64 rcur = cur % gl::P, rtsum = tsum % gl::P, rtprod = tprod % gl::P, rlsum = lsum % gl::P, rlprod = lprod % gl::P;
+            for (int st = 0; st < 3; st++) {
+                const u64 win = rnd() % gl::P, wout = rnd() % gl::P, wm = rnd() % gl::P;
+                const u64 f = gl::sub_ref(dAl, gl::add_ref(gl::mul_ref(dA, wout), win));
+                const u64 ncur = gl::add_ref(gl::mul_ref(rcur, dD), gl::add_ref(gl::mul_ref(dB, wout), win));
+                const u64 nts = gl::add_ref(gl::mul_ref(rtsum, f), gl::mul_ref(wm, rtprod)), ntp = gl::mul_ref(rtprod, f);
+                const u64 nls = gl::add_ref(gl::mul_ref(rlsum, f), rlprod), nlp = gl::mul_ref(rlprod, f);
+                {  // the plain forms from the same canonical state: canonical results
+                    u64 c2 = rcur, s2 = rtsum, p2_ = rtprod;
+                    lut_step<false>(c2, s2, p2_, dA, dB, dAl, dD, win, wout, wm);
+                    if (c2 != ncur || s2 != nts || p2_ != ntp) b++;
+                }
+                lut_step<true>(cur, tsum, tprod, dA, dB, dAl, dD, win, wout, wm);
+                lu_step(lsum, lprod, dA, dAl, win, wout);  // canonical from the second step on, whatever it started from
+                rcur = ncur, rtsum = nts, rtprod = ntp, rlsum = nls, rlprod = nlp;
+                if (glf::canon(cur) != rcur || glf::canon(tsum) != rtsum || glf::canon(tprod) != rtprod) b++;
+                if (lsum != rlsum || lprod != rlprod) b++;
+            }
+            const u64 diff = rnd() % gl::P;
+            if (glf::canon(lut_close<true>(tprod, tsum, diff)) != gl::sub_ref(gl::mul_ref(rtprod, diff), rtsum)) b++;
+            if (glf::canon(lu_close(lprod, lsum, diff)) != gl::add_ref(gl::mul_ref(rlprod, diff), rlsum)) b++;
+            if (gl::sub(dAl, glf::canon(cur)) != gl::sub_ref(dAl, rcur)) b++;  // the RE term's subtrahend, canonicalised once
+        }
+        // sub: canonical subtrahend, any minuend; add: one canonical operand
+        {
+            const u64 a = rnd(), c = rnd() % gl::P;
+            if (glf::canon(gl::sub(a, c)) != gl::sub_ref(a % gl::P, c)) b++;
+            if (glf::canon(gl::add(a, c)) != gl::add_ref(a % gl::P, c) || glf::canon(gl::add(c, a)) != gl::add_ref(a % gl::P, c)) b++;
+            if (glf::canon(gl::mul_nc(gl::sub(a, c), f0)) != M(gl::sub_ref(a % gl::P, c), f0)) b++;
+        }
+    }
+    // Planted violations, one per contract that can be broken: the comparison above must SEE them.  A non-canonical subtrahend
+    // (p + 1 for 1) and two non-canonical summands must give something other than the field result; if they do not, the checks
+    // above prove nothing, and that counts as a mismatch.
+    {
+        const u64 one_nc = gl::P + 1 + (x & 0), top = ~0ull - (x & 0);
+        if (glf::canon(gl::sub(0, one_nc)) == gl::sub_ref(0, one_nc % gl::P)) b++;
+        if (glf::canon(gl::add(top, top)) == gl::add_ref(top % gl::P, top % gl::P)) b++;
+    }
+    if (b) atomicAdd(bad, b);
+}
+}  // namespace p2k
+
+int p2_selftest_lazy_device(uint64_t seed, size_t threads, int device) {
+    if (hipSetDevice(device) != hipSuccess) return set_error("no such HIP device"), -P2_ERR_HIP;
+    if (threads == 0 || threads > ((size_t)1 << 30)) return set_error("thread count out of range"), -P2_ERR_INVALID;
+    Allocs mem;
+    unsigned long long* d = nullptr;
+    if (dalloc(mem, &d, 1) || hipMemset(d, 0, 8) != hipSuccess) return set_error("hipMalloc failed"), -P2_ERR_HIP;
+    hipLaunchKernelGGL(p2k::k_selftest_lazy, dim3((u32)((threads + 255) / 256)), dim3(256), 0, 0, d, (u64)seed, threads);
+    unsigned long long h = 0;
+    if (hipError_t e = hipMemcpy(&h, d, 8, hipMemcpyDeviceToHost)) return set_error(hipGetErrorString(e)), -P2_ERR_HIP;
+    return (int)std::min<unsigned long long>(h, 0x7FFFFFFF);
+}
+// k_zeta_tabs and k_zeta_pows on their own: z = (z[0], z[1]) -> pows [4][2][n], the powers of z, g z, 1/z and 1/(g z) with g the
+// primitive n-th root of unity (n a power of two up to 2^22)
+int p2_gpu_zeta_pows(const uint64_t* z, size_t n, uint64_t* pows, int device) {
+    if (n == 0 || n > ((size_t)1 << 22) || (n & (n - 1))) return set_error("n must be a power of two up to 2^22"), P2_ERR_INVALID;
+    if (z[0] >= gl::P || z[1] >= gl::P) return set_error("z is not canonical"), P2_ERR_INVALID;
+    if (int rc = pick_device(device)) return rc;
+    int logn = 0;
+    while (((size_t)1 << logn) < n) logn++;
+    std::vector<u64> chal(CH_WORDS, 0);
+    chal[CH_ZETA] = z[0];
+    chal[CH_ZETA + 1] = z[1];
+    Allocs mem;
+    u64 *d_chal, *d_tab, *d_pows;
+    if (upload(mem, &d_chal, chal.data(), chal.size()) || dalloc(mem, &d_tab, 4 * zeta_tab_words((u32)n)) || dalloc(mem, &d_pows, 8 * n)) return P2_ERR_HIP;
+    hipLaunchKernelGGL(k_zeta_tabs, g1(ZT_LO + zeta_tab_hi((u32)n), 256, 1, 4), dim3(256), 0, 0, d_chal, d_tab, (u32)n, gl::root_of_unity(logn));
+    HIPCHECK(hipGetLastError());
+    hipLaunchKernelGGL(k_zeta_pows, g1(n, 256, 1, 4), dim3(256), 0, 0, d_tab, d_pows, (size_t)8 * n, (u32)n);
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipMemcpy(pows, d_pows, 8 * n * 8, hipMemcpyDeviceToHost));
+    return P2_OK;
 }
 
 int p2_gpu_poseidon(uint64_t* states, size_t n_perm, int device) {
