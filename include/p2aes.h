@@ -211,6 +211,12 @@ int p2_selftest_device(uint64_t seed, size_t threads, int device);
  * (0, 1, 2^32 - 1, 2^32, p - 1, p, p + 1, 2^64 - 1, zero limbs, random) and NOT reduced where a contract allows any u64; with one
  * planted violation per contract that must show.  Returns the number of mismatches, or a negative P2_ERR_* code. */
 int p2_selftest_lazy_device(uint64_t seed, size_t threads, int device);
+/* The transform arithmetic: gl::mul_nb -- the NTT kernels' multiply, whose two-sided correction no other code uses -- on unreduced
+ * extremes, on the operand pairs (2^j, m 2^(96 - j)), j = 33, 36, .., 63, that take the reduction's borrow-only path (even lanes; odd
+ * lanes draw at random), the butterfly, and the four register stages of a radix-16 step in both forms, against the textbook
+ * operations; with one planted violation that must show.  threads x 16 rounds.  Returns the number of mismatches, or a negative
+ * P2_ERR_* code. */
+int p2_selftest_ntt_device(uint64_t seed, size_t threads, int device);
 /* The host build of the hash kernels' permutation: kind 0 = twelve unknown words, 1 = words 8..11 enter as 0, 2 = words 0..7 enter
  * as 0 (the words declared zero are not read); rows bit r = output word r is kept (canonical), the others are unspecified;
  * parts 0 = the round loops as the kernels run them, 1 = first round, middle and last round as separate functions. */
@@ -467,6 +473,16 @@ int p2_gpu_poseidon(uint64_t* states, size_t n_perm, int device);
 int p2_gpu_lde(const uint64_t* coeffs, size_t cols, int degree_bits, int rate_bits, uint64_t* lde, int device);
 /* values [cols][n] -> coefficients [cols][n]; degree_bits 1..22 (above 14: two-pass transform) */
 int p2_gpu_intt(const uint64_t* values, size_t cols, int degree_bits, uint64_t* coeffs, int device);
+/* The LDE of FRI round `round` as the prover's commit phase runs it, on the tables of a circuit of 2^degree_bits rows whose FRI
+ * schedule is arities[0..n_rounds): n_r = n >> (arities[0] + .. + arities[round - 1]) coefficients per column, coset shift
+ * g^(2^(arities[0] + ..)).  coeffs: batch x in_batch_stride words, [cols][n_r] at the start of each; out: batch x out_batch_stride
+ * words, [cols][8 n_r] in bit-reversed order written at the start of each, the words between left as they came in.  round = 0 (any
+ * n_rounds) is the main LDE; otherwise round < n_rounds. */
+int p2_gpu_lde_round(const uint64_t* coeffs, size_t cols, int degree_bits, const uint32_t* arities, size_t n_rounds, size_t round, size_t batch,
+                     size_t in_batch_stride, uint64_t* out, size_t out_batch_stride, int device);
+/* The prover's quotient inverse: qvals [batch][chunks][8 n], the values of `chunks` polynomials of degree < 8 n on the LDE coset in
+ * bit-reversed order -> out [batch][chunks * 8][n], their coefficients, n per row.  degree_bits 2..22. */
+int p2_gpu_quotient_chunks(const uint64_t* qvals, size_t chunks, int degree_bits, size_t batch, uint64_t* out, int device);
 /* column-major leaves [cols][num_leaves] -> cap digests (2^cap_height * 4 u64) */
 int p2_gpu_merkle_cap(const uint64_t* cols_major, size_t cols, size_t num_leaves, int cap_height, uint64_t* cap, int device);
 /* the same with the tree hasher chosen (P2_HASHER_*); Keccak needs cols >= 4 (every leaf is hashed, there is no no-op case) */

@@ -229,6 +229,7 @@ def lib():
         "p2_builder_hashed_elgamal_encrypt": (C.c_int, [vp, u64p, u64p, u64p, u64p, u64p]),
         "p2_selftest_host": (C.c_int, [u64, sz, sz]), "p2_selftest_device": (C.c_int, [u64, sz, C.c_int]),
         "p2_selftest_lazy_device": (C.c_int, [u64, sz, C.c_int]),
+        "p2_selftest_ntt_device": (C.c_int, [u64, sz, C.c_int]),
         "p2_native_gf_2_8_mul": (C.c_uint8, [C.c_uint8, C.c_uint8]),
         "p2_native_aes_key_expansion": (None, [C.c_char_p, C.c_int, C.c_int, C.c_char_p]),
         "p2_native_aes_encrypt_block": (None, [C.c_char_p, C.c_int, C.c_int, C.c_char_p, C.c_char_p]),
@@ -275,6 +276,8 @@ def lib():
         "p2_gpu_merged_middle": (C.c_int, [u64p, sz, C.c_int]),
         "p2_gpu_lde": (C.c_int, [u64p, sz, C.c_int, C.c_int, u64p, C.c_int]),
         "p2_gpu_intt": (C.c_int, [u64p, sz, C.c_int, u64p, C.c_int]),
+        "p2_gpu_lde_round": (C.c_int, [u64p, sz, C.c_int, u32p, sz, sz, sz, sz, u64p, sz, C.c_int]),
+        "p2_gpu_quotient_chunks": (C.c_int, [u64p, sz, C.c_int, sz, u64p, C.c_int]),
         "p2_gpu_merkle_cap": (C.c_int, [u64p, sz, sz, C.c_int, u64p, C.c_int]),
         "p2_gpu_zeta_pows": (C.c_int, [u64p, sz, u64p, C.c_int]),
         "p2_circuit_debug_read": (C.c_int, [vp, C.c_char_p, sz, u64p, sz, C.POINTER(sz)]),

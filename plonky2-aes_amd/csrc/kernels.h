@@ -308,7 +308,8 @@ struct NttLdsWalk {
 // under the barrier (rocprofv3: the kernel's waves were parked 55 % of the time; a wave's loads retire in order, so the
 // only place to hide them is ahead of work the same wave does anyway).
 __device__ __forceinline__ void ntt_r16_load_tw(u64* w, const u64* __restrict__ tw, u32 tp, int m, int tw_log, int nstages) {
-    // 32-bit byte offsets from the uniform table base (the table is at most 2^14 * 8 B)
+    // 32-bit byte offsets from the uniform table base: a strided table (a FRI round's transform on the order-n table, or pass 2
+    // of the two-pass transform) reaches 2^22 entries, 2^25 B, and the offset still fits
 #pragma unroll
     for (int A = 0; A < 4; A++) {
         if (A >= nstages) break;

@@ -328,6 +328,73 @@ static int ntt_big(Lane& L, const Domain& D, const char* name, const u64* in, u6
     LAUNCH(L, name, k_ntt_r16<false>, dim3((u32)rows, batch), dim3(1u << (log_n2 - 4)), r16_lds_bytes((int)log_n2), b);
     return 0;
 }
+// The transform tables of a domain: D.logn, D.rate_bits and D.arities in; the twiddles of both directions, the order-n_r tables
+// of the FRI rounds that still take two passes, every pass-1 output table, the coset shift powers of every round, the folded
+// table of the half-column kernel and (where `shift_inv_pows` is given) the quotient inverse's [8][n] (g w^j)^-i / n out.  The
+// loader and the primitives' PrimCtx both call it: one copy, so that a hook runs on the tables the prover runs on.
+static int build_transform_tables(Lane& L, Domain& D, Allocs& mem, u64** shift_inv_pows) {
+    const size_t n = D.n();
+    {
+        std::vector<u64> sub(n), twi(n);
+        u64 w = gl::root_of_unity((int)D.logn), wi = gl::inv(w), x = 1, xi = 1;
+        for (size_t i = 0; i < n; i++) {
+            sub[i] = x;
+            twi[i] = xi;
+            x = gl::mul(x, w);
+            xi = gl::mul(xi, wi);
+        }
+        if (upload(mem, &D.d_tw_fwd_full, sub.data(), n)) return P2_ERR_HIP;  // w^k, k < n
+        if (upload(mem, &D.d_tw_inv_full, twi.data(), n)) return P2_ERR_HIP;
+        D.d_tw_fwd = D.d_tw_fwd_full;    // the single-pass kernel only indexes k < n/2
+        D.d_tw_inv = D.d_tw_inv_full;
+        if (ensure_pass1_table(L, D, mem, D.d_tw_fwd_full, D.logn) || ensure_pass1_table(L, D, mem, D.d_tw_inv_full, D.logn)) return P2_ERR_HIP;
+        // FRI rounds whose polynomial is still > 2^14 need their own order-n_r table
+        u32 logn_r = D.logn;
+        for (u32 r = 0; r < D.arities.size(); r++) {
+            logn_r -= D.arities[r];
+            if (logn_r > LDS_NTT_MAX_BITS) {
+                size_t n_r = (size_t)1 << logn_r;
+                std::vector<u64> t(n_r);
+                for (size_t i = 0; i < n_r; i++) t[i] = sub[i << (D.logn - logn_r)];
+                if (upload(mem, &D.d_tw_fwd_round[r + 1], t.data(), n_r)) return P2_ERR_HIP;
+                if (ensure_pass1_table(L, D, mem, D.d_tw_fwd_round[r + 1], logn_r)) return P2_ERR_HIP;
+            }
+        }
+    }
+    {
+        // LDE shift tables for round r: bases s_{r,j} = g^(16^r) * w_{8 n_r}^j
+        u32 logn_r = D.logn;
+        u64 shift = gl::MULT_GEN;
+        for (u32 r = 0; r <= D.arities.size(); r++) {
+            size_t n_r = (size_t)1 << logn_r;
+            std::vector<u64> bases(8);
+            u64 wl = gl::root_of_unity((int)(logn_r + D.rate_bits));
+            for (u32 j = 0; j < 8; j++) bases[j] = gl::mul(shift, gl::pow(wl, j));
+            u64* d_b;
+            if (upload(mem, &d_b, bases.data(), 8)) return P2_ERR_HIP;
+            if (dalloc(mem, &D.d_shift_pows[r], 8 * n_r)) return P2_ERR_HIP;
+            hipLaunchKernelGGL(k_pow_table, g1(n_r, 256, 8), dim3(256), 0, L.stream, D.d_shift_pows[r], d_b, (u32)n_r, (u64)1);
+            if (r == 0 && D.logn >= 13 && D.logn <= LDS_NTT_MAX_BITS) {
+                if (dalloc(mem, &D.d_shift_tw, 8 * (n_r / 2))) return P2_ERR_HIP;
+                hipLaunchKernelGGL(k_mul_tables, g1(n_r / 2, 256, 8), dim3(256), 0, L.stream, D.d_shift_tw, D.d_shift_pows[0], n_r, D.d_tw_fwd, 0, (u32)(n_r / 2));
+            }
+            if (r == 0 && shift_inv_pows) {
+                std::vector<u64> ib(8);
+                for (u32 j = 0; j < 8; j++) ib[j] = gl::inv(bases[j]);
+                u64* d_ib;
+                if (upload(mem, &d_ib, ib.data(), 8)) return P2_ERR_HIP;
+                if (dalloc(mem, shift_inv_pows, 8 * n_r)) return P2_ERR_HIP;
+                hipLaunchKernelGGL(k_pow_table, g1(n_r, 256, 8), dim3(256), 0, L.stream, *shift_inv_pows, d_ib, (u32)n_r, gl::inv((u64)n % gl::P));
+            }
+            if (r < D.arities.size()) {
+                shift = gl::pow(shift, (u64)1 << D.arities[r]);
+                logn_r -= D.arities[r];
+            }
+        }
+        HIPCHECK(hipGetLastError());
+    }
+    return 0;
+}
 // values [cols][n] -> coeffs [cols][n].  `scratch` ([cols][n] per proof, same batch stride) is needed when n > 2^14.
 static int intt_cols(Lane& L, const Domain& D, const u64* vals, u64* coeffs, u32 cols, size_t batch_stride, u32 batch, u64* scratch = nullptr,
                      size_t scratch_batch_stride = 0) {
@@ -381,6 +448,46 @@ static int lde_cols(Lane& L, const Domain& D, const u64* coeffs, size_t in_batch
     a.cosets = 1 << D.rate_bits;
     for (u32 j = 0; j < 8; j++) a.block_of_coset[j] = blocks[j];
     return run_ntt(L, D, "lde", a, cols, batch);
+}
+// Quotient values on the LDE coset -> coefficient chunks.  qvals: [B][chunks][8 n] in the LDE's bit-reversed order (block
+// rev3(j) = coset j), overwritten; qres: scratch of the same shape; coef: [B] x coef_batch_stride, [chunks * 8][n].
+// Coset-wise inverse transform (residues r_j, scaled by (g w^j)^-i / n), then the 8-point cross-coset DFT.
+static int quotient_chunks(Lane& L, const Domain& D, u64* qvals, u64* qres, u64* coef, u32 chunks, size_t coef_batch_stride, u32 B, const u64* shift_inv_pows,
+                           const u64* w8inv, const u64* qscale) {
+    const size_t n = D.n(), N = n << D.rate_bits, qs = (size_t)chunks * N;
+    if (D.logn > LDS_NTT_MAX_BITS) {
+        u32 ident[8] = {0, 1, 2, 3, 4, 5, 6, 7};
+        LAUNCH(L, "bitrev_copy", k_bitrev_copy, g1(n, 256, B, chunks * 8), dim3(256), 0, qvals, N, qs, qres, N, qs, (int)D.logn, 8u, (const u64*)nullptr, 0u);
+        if (ntt_big(L, D, "quotient_intt", qres, qvals, D.d_tw_inv_full, nullptr, D.logn, chunks, 8, ident, 1, N, N, qs, qs, 1, B)) return P2_ERR_HIP;
+        LAUNCH(L, "bitrev_copy", k_bitrev_copy, g1(n, 256, B, chunks * 8), dim3(256), 0, qvals, N, qs, qres, N, qs, (int)D.logn, 8u, shift_inv_pows, 1u);
+    } else {
+        NttArgs t{};
+        t.in = qvals;
+        t.out = qres;
+        t.tw = D.d_tw_inv;
+        t.post = shift_inv_pows;
+        t.post_scalar = 1;
+        t.in_col_stride = t.out_col_stride = N;
+        t.in_batch_stride = t.out_batch_stride = qs;
+        t.logn = (int)D.logn;
+        t.cosets = 8;
+        t.bitrev_in = 1;
+        t.bitrev_out = 1;
+        t.in_coset_blocks = 1;
+        // input block rev3(j) holds coset j; residue r_j is written to the same block
+        for (u32 j = 0; j < 8; j++) t.block_of_coset[j] = gl::bitrev(j, 3);
+        if (run_ntt(L, D, "quotient_intt", t, chunks, B)) return P2_ERR_HIP;
+    }
+    LAUNCH(L, "quotient_chunks", k_quotient_chunks_rev, g1(n, 256, B, chunks), dim3(256), 0, qres, coef, (u32)n, qs, coef_batch_stride, w8inv, qscale);
+    return 0;
+}
+// The two 8-entry tables of k_quotient_chunks_rev: w8^-j, and s^-c / 8 with s = g^n.
+static void quotient_chunk_scales(u32 logn, u64* w8inv, u64* qscale) {
+    const u64 gn = gl::pow(gl::MULT_GEN, (u64)1 << logn), w8 = gl::root_of_unity(3);
+    for (u32 j = 0; j < 8; j++) {
+        w8inv[j] = gl::inv(gl::pow(w8, j));
+        qscale[j] = gl::mul(gl::inv(gl::pow(gn, j)), gl::inv(8));
+    }
 }
 // The three tree kernels of a hasher (one parameter list each for both hashers), and whether the top of a tree may be fused.
 struct TreeKernels {
@@ -500,66 +607,8 @@ static int circuit_setup(p2_circuit* C) {
     if (upload(C->allocs, &C->d_sigmas, c.sigmas.data(), c.sigmas.size())) return P2_ERR_HIP;
     if (upload(C->allocs, &C->d_k_is, c.k_is.data(), c.k_is.size())) return P2_ERR_HIP;
     // twiddles, subgroup, coset tables (host-computed once; O(n) field ops)
-    {
-        std::vector<u64> sub(n), twi(n);
-        u64 w = gl::root_of_unity((int)D.logn), wi = gl::inv(w), x = 1, xi = 1;
-        for (size_t i = 0; i < n; i++) {
-            sub[i] = x;
-            twi[i] = xi;
-            x = gl::mul(x, w);
-            xi = gl::mul(xi, wi);
-        }
-        if (upload(C->allocs, &C->d_subgroup, sub.data(), n)) return P2_ERR_HIP;
-        if (upload(C->allocs, &D.d_tw_inv_full, twi.data(), n)) return P2_ERR_HIP;
-        D.d_tw_fwd_full = C->d_subgroup;  // w^k, k < n
-        D.d_tw_fwd = D.d_tw_fwd_full;    // the single-pass kernel only indexes k < n/2
-        D.d_tw_inv = D.d_tw_inv_full;
-        if (ensure_pass1_table(C->setup, D, C->allocs, D.d_tw_fwd_full, D.logn) || ensure_pass1_table(C->setup, D, C->allocs, D.d_tw_inv_full, D.logn)) return P2_ERR_HIP;
-        // FRI rounds whose polynomial is still > 2^14 need their own order-n_r table
-        u32 logn_r = D.logn;
-        for (u32 r = 0; r < D.arities.size(); r++) {
-            logn_r -= D.arities[r];
-            if (logn_r > LDS_NTT_MAX_BITS) {
-                size_t n_r = (size_t)1 << logn_r;
-                std::vector<u64> t(n_r);
-                for (size_t i = 0; i < n_r; i++) t[i] = sub[i << (D.logn - logn_r)];
-                if (upload(C->allocs, &D.d_tw_fwd_round[r + 1], t.data(), n_r)) return P2_ERR_HIP;
-                if (ensure_pass1_table(C->setup, D, C->allocs, D.d_tw_fwd_round[r + 1], logn_r)) return P2_ERR_HIP;
-            }
-        }
-    }
-    {
-        // LDE shift tables for round r: bases s_{r,j} = g^(16^r) * w_{8 n_r}^j
-        u32 logn_r = D.logn;
-        u64 shift = gl::MULT_GEN;
-        for (u32 r = 0; r <= D.arities.size(); r++) {
-            size_t n_r = (size_t)1 << logn_r;
-            std::vector<u64> bases(8);
-            u64 wl = gl::root_of_unity((int)(logn_r + c.cfg.rate_bits));
-            for (u32 j = 0; j < 8; j++) bases[j] = gl::mul(shift, gl::pow(wl, j));
-            u64* d_b;
-            if (upload(C->allocs, &d_b, bases.data(), 8)) return P2_ERR_HIP;
-            if (dalloc(C->allocs, &D.d_shift_pows[r], 8 * n_r)) return P2_ERR_HIP;
-            hipLaunchKernelGGL(k_pow_table, g1(n_r, 256, 8), dim3(256), 0, C->setup.stream, D.d_shift_pows[r], d_b, (u32)n_r, (u64)1);
-            if (r == 0 && D.logn >= 13 && D.logn <= LDS_NTT_MAX_BITS) {
-                if (dalloc(C->allocs, &D.d_shift_tw, 8 * (n_r / 2))) return P2_ERR_HIP;
-                hipLaunchKernelGGL(k_mul_tables, g1(n_r / 2, 256, 8), dim3(256), 0, C->setup.stream, D.d_shift_tw, D.d_shift_pows[0], n_r, D.d_tw_fwd, 0, (u32)(n_r / 2));
-            }
-            if (r == 0) {
-                std::vector<u64> ib(8);
-                for (u32 j = 0; j < 8; j++) ib[j] = gl::inv(bases[j]);
-                u64* d_ib;
-                if (upload(C->allocs, &d_ib, ib.data(), 8)) return P2_ERR_HIP;
-                if (dalloc(C->allocs, &C->d_shift_inv_pows, 8 * n_r)) return P2_ERR_HIP;
-                hipLaunchKernelGGL(k_pow_table, g1(n_r, 256, 8), dim3(256), 0, C->setup.stream, C->d_shift_inv_pows, d_ib, (u32)n_r, gl::inv((u64)n % gl::P));
-            }
-            if (r < D.arities.size()) {
-                shift = gl::pow(shift, (u64)1 << D.arities[r]);
-                logn_r -= D.arities[r];
-            }
-        }
-        HIPCHECK(hipGetLastError());
-    }
+    if (int rc = build_transform_tables(C->setup, D, C->allocs, &C->d_shift_inv_pows)) return rc;
+    C->d_subgroup = D.d_tw_fwd_full;  // w^k, k < n
     {
         // per-point tables on the LDE coset (position p <-> natural index rev(p))
         std::vector<u64> xs(N), l0(N), zh_inv(8), w8inv(8), qscale(8);
@@ -575,9 +624,8 @@ static int circuit_setup(p2_circuit* C) {
         for (u32 j = 0; j < 8; j++) {
             zh[j] = gl::sub(gl::mul(gn, gl::pow(w8, j)), 1);
             zh_inv[j] = gl::inv(zh[j]);
-            w8inv[j] = gl::inv(gl::pow(w8, j));
-            qscale[j] = gl::mul(gl::inv(gl::pow(gn, j)), gl::inv(8));
         }
+        quotient_chunk_scales(D.logn, w8inv.data(), qscale.data());
         // batch inversion of n*(x-1)
         std::vector<u64> den(N), pref(N);
         u64 acc = 1;
@@ -984,35 +1032,7 @@ static int prove_chunk(p2_circuit* C, Workspace& W, u32 B, u32 n_inputs, const u
             LAUNCH(W.lane, "quotient", (k_quotient<false, true>), g1(N, 256, B), dim3(256), 0, a);  // the wire columns read once
         else
             LAUNCH(W.lane, "quotient", k_quotient<true>, g1(N, 256, B), dim3(256), 0, a);
-        // coset-wise inverse transform: residues r_j, then the 8-point cross-coset DFT
-        if (C->dom.logn > LDS_NTT_MAX_BITS) {
-            const size_t qs = (size_t)NC * N;
-            u32 ident[8] = {0, 1, 2, 3, 4, 5, 6, 7};
-            LAUNCH(W.lane, "bitrev_copy", k_bitrev_copy, g1(n, 256, B, NC * 8), dim3(256), 0, W.d_qvals, N, qs, W.d_qres, N, qs, (int)C->dom.logn, 8u,
-                   (const u64*)nullptr, 0u);
-            if (ntt_big(W.lane, C->dom, "quotient_intt", W.d_qres, W.d_qvals, C->dom.d_tw_inv_full, nullptr, C->dom.logn, NC, 8, ident, 1, N, N, qs, qs, 1, B)) return P2_ERR_HIP;
-            LAUNCH(W.lane, "bitrev_copy", k_bitrev_copy, g1(n, 256, B, NC * 8), dim3(256), 0, W.d_qvals, N, qs, W.d_qres, N, qs, (int)C->dom.logn, 8u,
-                   (const u64*)C->d_shift_inv_pows, 1u);
-        } else {
-        NttArgs t{};
-        t.in = W.d_qvals;
-        t.out = W.d_qres;
-        t.tw = C->dom.d_tw_inv;
-        t.post = C->d_shift_inv_pows;
-        t.post_scalar = 1;
-        t.in_col_stride = t.out_col_stride = N;
-        t.in_batch_stride = t.out_batch_stride = (size_t)NC * N;
-        t.logn = (int)C->dom.logn;
-        t.cosets = 8;
-        t.bitrev_in = 1;
-        t.bitrev_out = 1;
-        t.in_coset_blocks = 1;
-        // input block rev3(j) holds coset j; residue r_j is written to the same block
-        for (u32 j = 0; j < 8; j++) t.block_of_coset[j] = gl::bitrev(j, 3);
-        if (run_ntt(W.lane, C->dom, "quotient_intt", t, NC, B)) return P2_ERR_HIP;
-        }
-        LAUNCH(W.lane, "quotient_chunks", k_quotient_chunks_rev, g1(n, 256, B, NC), dim3(256), 0, W.d_qres, W.quot.coef, (u32)n, (size_t)NC * N, (size_t)qc * n,
-               C->d_w8inv, C->d_qscale);
+        if (quotient_chunks(W.lane, C->dom, W.d_qvals, W.d_qres, W.quot.coef, NC, (size_t)qc * n, B, C->d_shift_inv_pows, C->d_w8inv, C->d_qscale)) return P2_ERR_HIP;
     }
     if (commit_oracle(C, W, W.quot, 2, c.degree_bits, proof_base, B)) return P2_ERR_HIP;
     // 8. openings
@@ -2582,6 +2602,138 @@ int p2_selftest_lazy_device(uint64_t seed, size_t threads, int device) {
     if (hipError_t e = hipMemcpy(&h, d, 8, hipMemcpyDeviceToHost)) return set_error(hipGetErrorString(e)), -P2_ERR_HIP;
     return (int)std::min<unsigned long long>(h, 0x7FFFFFFF);
 }
+// ---- self-test of the transform arithmetic: gl::mul_nb (the branch-free two-sided correction, which only the NTT kernels use) and
+// the register butterflies of kernels.h built on it
+namespace p2k {
+// 2^j for j = 33, 36, .., 63 -- the forward twiddles w_64^k = 8^k, k = 11..21 -- and m 2^(96 - j) with 1 <= m < 2^(j - 32): the
+// product m 2^96 has zero low limbs and no carry, so the reduction borrows and does nothing else
+__device__ __forceinline__ void borrow_pair(u64 r, u64& pw, u64& q) {
+    const int j = 33 + 3 * (int)((r >> 56) % 11);
+    const u64 m = 1 + (r & 0xFFFFFFFFFFFFull) % (((u64)1 << (j - 32)) - 1);
+    pw = (u64)1 << j;
+    q = m << (96 - j);
+}
+// stage A of ntt_r16_stage, written out with the textbook operations
+__device__ void ref_r16_stage(u64* x, const u64* w, int A) {
+    const int half = 8 >> A, base = 16 - 2 * half;
+    for (int r = 0; r < 16; r++) {
+        if (r & half) continue;
+        const u64 u = x[r], v = x[r + half];
+        x[r] = gl::add_ref(u, v);
+        x[r + half] = gl::mul_ref(gl::sub_ref(u, v), w[base + r % half]);
+    }
+}
+__global__ void k_selftest_ntt(unsigned long long* bad, u64 seed, size_t threads) {
+    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= threads) return;
+    u64 x = (seed | 1) + 0x9E3779B97F4A7C15ull * (t + 1);
+    auto step = [&]() {
+        x ^= x << 13;
+        x ^= x >> 7;
+        x ^= x << 17;
+        return x;
+    };
+    auto rnd = [&]() {  // lazy_draw's extremes, unreduced
+        const u64 r = step();
+        return lazy_draw(r, (u32)(r >> 40));
+    };
+    auto C = [](u64 v) { return v >= gl::P ? v - gl::P : v; };  // v mod p
+    auto rndc = [&]() { return C(rnd()); };
+    auto M = [&](u64 a, u64 b) { return gl::mul_ref(C(a), C(b)); };
+    const bool odd = t & 1;
+    unsigned long long b = 0;
+    for (int i = 0; i < 16; i++) {
+        // any u64 in, canonical out
+        {
+            const u64 a = rnd(), c = rnd();
+            if (gl::mul_nb(a, c) != M(a, c)) b++;
+        }
+        // the borrow-only correction, in both operand orders: even lanes borrow, odd lanes draw at random, so that one wave holds
+        // borrowing, carrying and plain lanes (the correction is built from two lane masks)
+        u64 pw, q;
+        borrow_pair(step(), pw, q);
+        {
+            const u64 ea = odd ? step() : pw, eb = odd ? step() : q, want = M(ea, eb);
+            if (gl::mul_nb(ea, eb) != want || gl::mul_nb(eb, ea) != want) b++;
+        }
+        // the butterfly on canonical values, and with u - v a borrow operand against a power-of-two twiddle
+        {
+            const u64 u = rndc(), v = rndc(), w = rndc();
+            if (gl::add(u, v) != gl::add_ref(u, v)) b++;
+            if (gl::mul_nb(gl::sub(u, v), w) != gl::mul_ref(gl::sub_ref(u, v), w)) b++;
+            const u64 ub = gl::add_ref(v, q), wb = odd ? w : pw;
+            if (gl::add(ub, v) != gl::add_ref(ub, v)) b++;
+            if (gl::mul_nb(gl::sub(ub, v), wb) != gl::mul_ref(q, wb)) b++;
+        }
+        // a 16-point register block through the four stages of a step: extremes, and in even lanes a borrow operand at one pair
+        // of the first stage
+        u64 xs[16], tw[15], got[16], want[16];
+        for (int k = 0; k < 16; k++) xs[k] = rndc();
+        for (int k = 0; k < 15; k++) tw[k] = rndc();
+        if (!odd) {
+            const int r = i & 7;
+            tw[r] = pw;
+            xs[r] = gl::add_ref(xs[r + 8], q);
+        }
+        for (int k = 0; k < 16; k++) got[k] = want[k] = xs[k];
+        ntt_r16_stage<0>(got, tw);
+        ntt_r16_stage<1>(got, tw);
+        ntt_r16_stage<2>(got, tw);
+        ntt_r16_stage<3>(got, tw);
+        for (int A = 0; A < 4; A++) ref_r16_stage(want, tw, A);
+        for (int k = 0; k < 16; k++) b += got[k] != want[k];
+        // the last step's form skips the products by the first twiddle of every stage: equal to the plain form where those are 1
+        tw[0] = tw[8] = tw[12] = tw[14] = 1;
+        for (int k = 0; k < 16; k++) got[k] = want[k] = xs[k];
+        ntt_r16_stage_m0<0>(got, tw);
+        ntt_r16_stage_m0<1>(got, tw);
+        ntt_r16_stage_m0<2>(got, tw);
+        ntt_r16_stage_m0<3>(got, tw);
+        for (int A = 0; A < 4; A++) ref_r16_stage(want, tw, A);
+        for (int k = 0; k < 16; k++) b += got[k] != want[k];
+        for (int k = 0; k < 16; k++) got[k] = xs[k];
+        ntt_r16_stage<0>(got, tw);
+        ntt_r16_stage<1>(got, tw);
+        ntt_r16_stage<2>(got, tw);
+        ntt_r16_stage<3>(got, tw);
+        for (int k = 0; k < 16; k++) b += got[k] != want[k];
+        // a later stage on its own, with the borrow operand at one of ITS pairs (stage A pairs r and r + (8 >> A))
+        {
+            const int A = 1 + i % 3, half = 8 >> A, base = 16 - 2 * half, r = ((i >> 2) & 1) * 2 * half + (i % half);
+            for (int k = 0; k < 16; k++) got[k] = want[k];  // canonical values: what the stages above left
+            if (!odd) {
+                tw[base + r % half] = pw;
+                got[r] = gl::add_ref(got[r + half], q);
+            }
+            for (int k = 0; k < 16; k++) want[k] = got[k];
+            if (A == 1) ntt_r16_stage<1>(got, tw);
+            if (A == 2) ntt_r16_stage<2>(got, tw);
+            if (A == 3) ntt_r16_stage<3>(got, tw);
+            ref_r16_stage(want, tw, A);
+            for (int k = 0; k < 16; k++) b += got[k] != want[k];
+        }
+    }
+    // The planted violation: a non-canonical subtrahend (p + 1 for 1) in the butterfly must give something other than the field
+    // result; if it does not, the comparisons above prove nothing, and that counts as a mismatch.
+    {
+        const u64 one_nc = gl::P + 1 + (x & 0), w = (u64)1 << 33;
+        if (gl::mul_nb(gl::sub(0, one_nc), w) == gl::mul_ref(gl::sub_ref(0, C(one_nc)), w)) b++;
+    }
+    if (b) atomicAdd(bad, b);
+}
+}  // namespace p2k
+
+int p2_selftest_ntt_device(uint64_t seed, size_t threads, int device) {
+    if (hipSetDevice(device) != hipSuccess) return set_error("no such HIP device"), -P2_ERR_HIP;
+    if (threads == 0 || threads > ((size_t)1 << 30)) return set_error("thread count out of range"), -P2_ERR_INVALID;
+    Allocs mem;
+    unsigned long long* d = nullptr;
+    if (dalloc(mem, &d, 1) || hipMemset(d, 0, 8) != hipSuccess) return set_error("hipMalloc failed"), -P2_ERR_HIP;
+    hipLaunchKernelGGL(p2k::k_selftest_ntt, dim3((u32)((threads + 255) / 256)), dim3(256), 0, 0, d, (u64)seed, threads);
+    unsigned long long h = 0;
+    if (hipError_t e = hipMemcpy(&h, d, 8, hipMemcpyDeviceToHost)) return set_error(hipGetErrorString(e)), -P2_ERR_HIP;
+    return (int)std::min<unsigned long long>(h, 0x7FFFFFFF);
+}
 // k_zeta_tabs and k_zeta_pows on their own: z = (z[0], z[1]) -> pows [4][2][n], the powers of z, g z, 1/z and 1/(g z) with g the
 // primitive n-th root of unity (n a power of two up to 2^22)
 int p2_gpu_zeta_pows(const uint64_t* z, size_t n, uint64_t* pows, int device) {
@@ -2683,33 +2835,15 @@ struct PrimCtx {
     Lane lane;
     Domain dom;
     Allocs mem;
-    int init(int device, int degree_bits) {
+    u64* d_shift_inv_pows = nullptr;  // with_quotient: [8][n] (g w^j)^-i / n
+    // the tables come from the loader's own builder (build_transform_tables); `arities` as the circuit's FRI schedule
+    int init(int device, int degree_bits, const std::vector<u32>& arities = {}, bool with_quotient = false) {
         if (int rc = pick_device(device)) return rc;
         dom.logn = (u32)degree_bits;
+        dom.arities = arities;
         HIPCHECK(hipStreamCreate(&lane.stream));
         HIPCHECK(raise_ntt_lds_limits());
-        const size_t n = dom.n();
-        std::vector<u64> twf(n), twi(n);
-        u64 w = gl::root_of_unity(degree_bits), wi = gl::inv(w), x = 1, xi = 1;
-        for (size_t i = 0; i < n; i++) {
-            twf[i] = x;
-            twi[i] = xi;
-            x = gl::mul(x, w);
-            xi = gl::mul(xi, wi);
-        }
-        if (upload(mem, &dom.d_tw_fwd_full, twf.data(), n) || upload(mem, &dom.d_tw_inv_full, twi.data(), n)) return P2_ERR_HIP;
-        dom.d_tw_fwd = dom.d_tw_fwd_full;
-        dom.d_tw_inv = dom.d_tw_inv_full;
-        if (ensure_pass1_table(lane, dom, mem, dom.d_tw_fwd_full, dom.logn) || ensure_pass1_table(lane, dom, mem, dom.d_tw_inv_full, dom.logn)) return P2_ERR_HIP;
-        std::vector<u64> bases(8);
-        u64 wl = gl::root_of_unity(degree_bits + 3);
-        for (u32 j = 0; j < 8; j++) bases[j] = gl::mul(gl::MULT_GEN, gl::pow(wl, j));
-        u64* d_b;
-        if (upload(mem, &d_b, bases.data(), 8)) return P2_ERR_HIP;
-        if (dalloc(mem, &dom.d_shift_pows[0], 8 * n)) return P2_ERR_HIP;
-        hipLaunchKernelGGL(k_pow_table, g1(n, 256, 8), dim3(256), 0, lane.stream, dom.d_shift_pows[0], d_b, (u32)n, (u64)1);
-        HIPCHECK(hipGetLastError());
-        return 0;
+        return build_transform_tables(lane, dom, mem, with_quotient ? &d_shift_inv_pows : nullptr);
     }
     ~PrimCtx() {  // (`mem` goes after this body: nothing is still running on what it frees)
         if (lane.stream) (void)hipStreamSynchronize(lane.stream);
@@ -2738,6 +2872,49 @@ int p2_gpu_lde(const uint64_t* coeffs, size_t cols, int degree_bits, int rate_bi
     if (lde_cols(ctx.lane, ctx.dom, d_in, 0, d_out, 0, (u32)cols, 0, 1)) return P2_ERR_HIP;
     HIPCHECK(hipStreamSynchronize(ctx.lane.stream));
     HIPCHECK(hipMemcpy(lde, d_out, cols * 8 * n * 8, hipMemcpyDeviceToHost));
+    return P2_OK;
+}
+// lde_cols as step 9 of the prover calls it: the polynomials of FRI round `round` (n_r = n >> sum of arities[0..round)), `batch`
+// proofs with their own strides.  coeffs: [batch] x in_batch_stride words holding [cols][n_r]; out: [batch] x out_batch_stride
+// words, [cols][8 n_r] in bit-reversed order written (words between the proofs are left as they came in).
+int p2_gpu_lde_round(const uint64_t* coeffs, size_t cols, int degree_bits, const uint32_t* arities, size_t n_rounds, size_t round, size_t batch,
+                     size_t in_batch_stride, uint64_t* out, size_t out_batch_stride, int device) {
+    if (degree_bits < 1 || degree_bits > 22 || cols == 0 || cols > 4096 || batch == 0 || batch > 65535 || n_rounds > 8 || (round && round >= n_rounds))
+        return set_error("shape out of range"), P2_ERR_INVALID;
+    u32 logn_r = (u32)degree_bits, left = (u32)degree_bits;
+    std::vector<u32> ar(arities, arities + n_rounds);
+    for (size_t r = 0; r < n_rounds; r++) {
+        if (ar[r] == 0 || ar[r] >= left) return set_error("arities reduce the degree to nothing"), P2_ERR_INVALID;
+        left -= ar[r];
+        if (r < round) logn_r = left;
+    }
+    const size_t n_r = (size_t)1 << logn_r;
+    if (in_batch_stride < cols * n_r || out_batch_stride < 8 * cols * n_r) return set_error("batch stride smaller than a proof's columns"), P2_ERR_INVALID;
+    PrimCtx ctx;
+    if (int rc = ctx.init(device, degree_bits, ar)) return rc;
+    u64 *d_in, *d_out;
+    if (upload(ctx.mem, &d_in, (const u64*)coeffs, batch * in_batch_stride) || upload(ctx.mem, &d_out, (const u64*)out, batch * out_batch_stride)) return P2_ERR_HIP;
+    if (lde_cols(ctx.lane, ctx.dom, d_in, in_batch_stride, d_out, out_batch_stride, (u32)cols, (u32)round, (u32)batch)) return P2_ERR_HIP;
+    HIPCHECK(hipStreamSynchronize(ctx.lane.stream));
+    HIPCHECK(hipMemcpy(out, d_out, batch * out_batch_stride * 8, hipMemcpyDeviceToHost));
+    return P2_OK;
+}
+// The prover's quotient inverse on its own (quotient_chunks): qvals [batch][chunks][8 n], the values of `chunks` polynomials of
+// degree < 8 n on the LDE coset in bit-reversed order -> out [batch][chunks * 8][n], their coefficients n at a time.
+int p2_gpu_quotient_chunks(const uint64_t* qvals, size_t chunks, int degree_bits, size_t batch, uint64_t* out, int device) {
+    if (degree_bits < 2 || degree_bits > 22 || chunks == 0 || chunks > 64 || batch == 0 || batch > 65535) return set_error("shape out of range"), P2_ERR_INVALID;
+    PrimCtx ctx;
+    if (int rc = ctx.init(device, degree_bits, {}, true)) return rc;
+    const size_t words = batch * chunks * (ctx.dom.n() << ctx.dom.rate_bits);
+    u64 w8inv[8], qscale[8];
+    quotient_chunk_scales(ctx.dom.logn, w8inv, qscale);
+    u64 *d_q, *d_res, *d_coef, *d_w8inv, *d_qscale;
+    if (upload(ctx.mem, &d_q, (const u64*)qvals, words) || dalloc(ctx.mem, &d_res, words) || dalloc(ctx.mem, &d_coef, words) ||
+        upload(ctx.mem, &d_w8inv, w8inv, 8) || upload(ctx.mem, &d_qscale, qscale, 8))
+        return P2_ERR_HIP;
+    if (quotient_chunks(ctx.lane, ctx.dom, d_q, d_res, d_coef, (u32)chunks, words / batch, (u32)batch, ctx.d_shift_inv_pows, d_w8inv, d_qscale)) return P2_ERR_HIP;
+    HIPCHECK(hipStreamSynchronize(ctx.lane.stream));
+    HIPCHECK(hipMemcpy(out, d_coef, words * 8, hipMemcpyDeviceToHost));
     return P2_OK;
 }
 int p2_gpu_merkle_cap(const uint64_t* cols_major, size_t cols, size_t num_leaves, int cap_height, uint64_t* cap, int device) {
