@@ -420,6 +420,32 @@ pub mod plonk {
                 assert!(rc == ffi::P2_OK, "{}", last_error());
                 out.into_iter().map(Target).collect()
             }
+            /// `assert_bool`: t * t - t = 0.
+            pub fn assert_bool(&mut self, b: BoolTarget) {
+                let rc = unsafe { ffi::p2_builder_assert_bool(self.h, b.target.0) };
+                assert!(rc == ffi::P2_OK, "{}", last_error());
+            }
+            /// `le_sum` of 1 to 64 little-endian bits.  Unlike upstream's, with exactly 64 bits it also refuses the spelling
+            /// of value + p: the result always denotes the integer the bits spell.
+            pub fn le_sum(&mut self, bits: impl Iterator<Item = impl std::borrow::Borrow<BoolTarget>>) -> Target {
+                let inp: Vec<u64> = bits.map(|b| b.borrow().target.0).collect();
+                let mut out = 0u64;
+                let rc = unsafe { ffi::p2_builder_le_sum(self.h, inp.as_ptr(), inp.len(), &mut out) };
+                assert!(rc == ffi::P2_OK, "{}", last_error());
+                Target(out)
+            }
+            /// `split_le`: the num_bits (1 to 64) little-endian bits of x; no witness exists if x >= 2^num_bits.
+            pub fn split_le(&mut self, x: Target, num_bits: usize) -> Vec<BoolTarget> {
+                let mut out = vec![0u64; num_bits.clamp(1, 64)];
+                let rc = unsafe { ffi::p2_builder_split_le(self.h, x.0, num_bits, out.as_mut_ptr()) };
+                assert!(rc == ffi::P2_OK, "{}", last_error());
+                out.into_iter().map(|t| BoolTarget::new_unsafe(Target(t))).collect()
+            }
+            /// `range_check`: x < 2^n_log, n_log 1 to 63.
+            pub fn range_check(&mut self, x: Target, n_log: usize) {
+                let rc = unsafe { ffi::p2_builder_range_check(self.h, x.0, n_log) };
+                assert!(rc == ffi::P2_OK, "{}", last_error());
+            }
             pub fn num_gates(&self) -> usize { unsafe { ffi::p2_builder_num_gates(self.h) } }
             /// `build::<PoseidonGoldilocksConfig>()` (19 sites) or `build::<KeccakGoldilocksConfig>()`: compile on the host, then upload the circuit
             /// to HIP device P2AES_DEVICE (default 0) and commit constants | sigmas there.

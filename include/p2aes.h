@@ -97,6 +97,25 @@ p2_target p2_builder_mul(p2_builder*, p2_target x, p2_target y);
 p2_target p2_builder_select(p2_builder*, p2_target b, p2_target x, p2_target y); /* if b {x} else {y} */
 p2_target p2_builder_is_equal(p2_builder*, p2_target x, p2_target y);
 void p2_builder_connect(p2_builder*, p2_target x, p2_target y);
+/* Bits and bytes of a field element (CircuitBuilder::assert_bool, le_sum, split_le, range_check; byte forms for the AES
+ * gadgets).  Built from ArithmeticGate ops, the byte lookup and one hint per limb; no BaseSumGate, so gate counts differ
+ * from upstream's.  All little-endian.  P2_ERR_INVALID with a message if a width is out of range.
+ *   assert_bool      t * t - t = 0
+ *   le_sum           1..64 boolean targets -> sum of bits[i] * 2^i.  Unlike upstream's, with exactly 64 bits it also refuses
+ *                    the spelling of value + p: the result always denotes the integer the bits spell
+ *   split_le         x -> num_bits (1..64) boolean targets, with le_sum(bits) == x enforced; no witness if x >= 2^num_bits
+ *   range_check      x < 2^num_bits, num_bits 1..63
+ *   le_bytes_sum     1..8 range-checked byte targets -> sum of bytes[i] * 256^i; canonical with 8 bytes, as le_sum
+ *   split_bytes_le   x -> num_bytes (1..8) byte targets, each looked up in byte table u8_table_idx (p2_aes_sbox_lut) as
+ *                    p2_aes_add_virtual_byte_target does
+ *   is_less_than     *out = (x < y) for x, y < 2^num_bits, num_bits 1..62; both operands are range-checked */
+int p2_builder_assert_bool(p2_builder*, p2_target t);
+int p2_builder_le_sum(p2_builder*, const p2_target* bits, size_t n, p2_target* out);
+int p2_builder_split_le(p2_builder*, p2_target x, size_t num_bits, p2_target* bits);
+int p2_builder_range_check(p2_builder*, p2_target x, size_t num_bits);
+int p2_builder_le_bytes_sum(p2_builder*, const p2_target* bytes, size_t n, p2_target* out);
+int p2_builder_split_bytes_le(p2_builder*, p2_target x, size_t num_bytes, size_t u8_table_idx, p2_target* bytes);
+int p2_builder_is_less_than(p2_builder*, p2_target x, p2_target y, size_t num_bits, p2_target* out);
 /* CircuitBuilder::register_public_input: the target's value becomes public input number (calls so far); duplicates allowed.
  * build() hashes the public inputs in the circuit (hash_n_to_hash_no_pad) into the PublicInputGate, and every proof of the
  * circuit ends with the trailer u64 k || k x u64 value.  A circuit with none is built exactly as before.  P2_ERR_INVALID
@@ -388,7 +407,8 @@ int p2_witness_batch(p2_circuit*, size_t batch, const p2_assignment* inputs, con
  * kind == P2_FAULT_NONE iff *status == 0, kinds 1-4 iff *status == 1, kind 5 iff *status == 2. */
 typedef struct {
     int32_t kind;        /* P2_FAULT_* */
-    int32_t op_kind;     /* generator kind (csrc/circuit.h OP_*) at fault, -1 if none */
+    int32_t op_kind;     /* generator kind (csrc/circuit.h OP_*: 0 ARITH .. 5 POSEIDON, 6 LIMB = a bit or byte hint of split_le /
+                          * split_bytes_le) at fault, -1 if none */
     int64_t input_index; /* entry of the assignment involved, -1 if none */
     p2_target target;    /* a target of the slot at fault: its lowest virtual target, else its lowest routed wire; UINT64_MAX if none */
     uint32_t gate_row;   /* a row holding a routed wire of that slot (the PoseidonGate row for OP_POSEIDON), UINT32_MAX if none */

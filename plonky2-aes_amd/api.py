@@ -62,7 +62,7 @@ VERIFY_REASONS = {
 # p2_witness_explain / p2_host_witness fault kinds (include/p2aes.h P2_FAULT_*), by code
 FAULT_KINDS = ("NONE", "INPUT_NOT_CANONICAL", "INPUT_CONFLICT", "LOOKUP_MISS", "GENERATOR_CONFLICT", "NOT_SET")
 # witness generator kinds (csrc/circuit.h OP_*), by code
-OP_KINDS = ("ARITH", "CONST", "LOOKUP", "EQ", "EQINV", "POSEIDON")
+OP_KINDS = ("ARITH", "CONST", "LOOKUP", "EQ", "EQINV", "POSEIDON", "LIMB")
 VALUE_UNSET = 0xFFFFFFFFFFFFFFFF   # P2_VALUE_UNSET: "not assigned" on input, "the run did not determine it" on output
 
 u32p = C.POINTER(C.c_uint32)
@@ -186,6 +186,10 @@ def lib():
         "p2_builder_add": (u64, [vp, u64, u64]), "p2_builder_sub": (u64, [vp, u64, u64]), "p2_builder_mul": (u64, [vp, u64, u64]),
         "p2_builder_select": (u64, [vp, u64, u64, u64]), "p2_builder_is_equal": (u64, [vp, u64, u64]),
         "p2_builder_connect": (None, [vp, u64, u64]),
+        "p2_builder_assert_bool": (C.c_int, [vp, u64]), "p2_builder_range_check": (C.c_int, [vp, u64, sz]),
+        "p2_builder_le_sum": (C.c_int, [vp, u64p, sz, u64p]), "p2_builder_le_bytes_sum": (C.c_int, [vp, u64p, sz, u64p]),
+        "p2_builder_split_le": (C.c_int, [vp, u64, sz, u64p]), "p2_builder_split_bytes_le": (C.c_int, [vp, u64, sz, sz, u64p]),
+        "p2_builder_is_less_than": (C.c_int, [vp, u64, u64, sz, u64p]),
         "p2_builder_register_public_input": (C.c_int, [vp, u64]),
         "p2_proof_public_inputs": (C.c_int, [C.c_char_p, sz, C.c_char_p, sz, u64p, sz, C.POINTER(sz)]),
         "p2_builder_add_lookup_table_from_pairs": (sz, [vp, u16p, sz]),
@@ -336,6 +340,42 @@ class CircuitBuilder:
     def select(self, b, x, y): return lib().p2_builder_select(self._h, b, x, y)
     def is_equal(self, x, y): return lib().p2_builder_is_equal(self._h, x, y)
     def connect(self, x, y): lib().p2_builder_connect(self._h, x, y)
+
+    # ---- bits and bytes of a field element (little-endian; include/p2aes.h has the rules)
+    def assert_bool(self, t):
+        if lib().p2_builder_assert_bool(self._h, t):
+            raise P2Error(_err())
+
+    def _sum(self, fn, limbs):
+        out = (u64 * 1)()
+        if fn(self._h, _arr(limbs), len(limbs), out):
+            raise P2Error(_err())
+        return out[0]
+
+    def le_sum(self, bits): return self._sum(lib().p2_builder_le_sum, bits)
+    def le_bytes_sum(self, byte_targets): return self._sum(lib().p2_builder_le_bytes_sum, byte_targets)
+
+    def split_le(self, x, num_bits):
+        out = (u64 * max(min(int(num_bits), 64), 1))()
+        if lib().p2_builder_split_le(self._h, x, num_bits, out):
+            raise P2Error(_err())
+        return list(out)
+
+    def range_check(self, x, num_bits):
+        if lib().p2_builder_range_check(self._h, x, num_bits):
+            raise P2Error(_err())
+
+    def split_bytes_le(self, x, num_bytes, u8_table_idx):
+        out = (u64 * max(min(int(num_bytes), 8), 1))()
+        if lib().p2_builder_split_bytes_le(self._h, x, num_bytes, u8_table_idx, out):
+            raise P2Error(_err())
+        return list(out)
+
+    def is_less_than(self, a, b, num_bits):
+        out = (u64 * 1)()
+        if lib().p2_builder_is_less_than(self._h, a, b, num_bits, out):
+            raise P2Error(_err())
+        return out[0]
 
     def register_public_input(self, t):
         """CircuitBuilder::register_public_input: every proof carries the target's value (in registration order)."""

@@ -147,6 +147,68 @@ class CircuitBuilder {
         return inv;
     }
 
+    // ---- bits and bytes of a field element (plonky2 gadgets/split_base.rs, split_join.rs, range_check.rs) ----------
+    // Same names and meaning as upstream; the gates differ by construction (no BaseSumGate: booleanity is an ArithmeticGate
+    // op, the sum a Horner chain, the limbs come from OP_LIMB hints), as they already do for the ecgfp5 circuits.
+    // Arithmetic ops: assert_bool 1; le_sum n - 1 (64 bits: 68); split_le 2n (64 bits: 2n + 5); le_bytes_sum n - 1 (8 bytes:
+    // 12); split_bytes_le n (8 bytes: 13) and one lookup per byte; is_less_than 6n + 5.
+    void assert_bool(Target t) { connect(mul_sub(t, t, t), zero()); }
+
+    // sum of bits[i] * 2^i.  The bits must be boolean already (assert_bool, or the result of a gadget).  With exactly 64 bits
+    // the sum could pass p and wrap, so two spellings would denote the same field element; here the non-canonical one is
+    // refused -- the result always denotes the integer the bits spell.  Upstream's le_sum does NOT do this: there the caller
+    // has to know that 64 bits of a Goldilocks element are ambiguous.
+    Target le_sum(const std::vector<BoolTarget>& bits) {
+        if (bits.empty() || bits.size() > 64) throw std::runtime_error("le_sum: 1 to 64 bits");
+        std::vector<Target> limbs;
+        for (BoolTarget b : bits) limbs.push_back(b.target);
+        return le_limbs_sum(limbs, 1);
+    }
+    // The little-endian bits of x, as upstream's split_le -- but sound for 64 bits too (see le_sum).  x must be below
+    // 2^num_bits, or no witness exists.
+    std::vector<BoolTarget> split_le(Target x, size_t num_bits) {
+        if (num_bits < 1 || num_bits > 64) throw std::runtime_error("split_le: num_bits must be 1 to 64");
+        std::vector<BoolTarget> bits(num_bits);
+        for (size_t i = 0; i < num_bits; i++) {
+            bits[i] = add_virtual_bool_target_unsafe();
+            gens_.push_back(Gen{OP_LIMB, bits[i].target, x, 0, 0, 0, (u64)i, 1});
+            assert_bool(bits[i].target);
+        }
+        assert_equal_to_input(le_sum(bits), x);
+        return bits;
+    }
+    void range_check(Target x, size_t num_bits) {
+        if (num_bits < 1 || num_bits > 63) throw std::runtime_error("range_check: num_bits must be 1 to 63");
+        (void)split_le(x, num_bits);
+    }
+    // sum of bytes[i] * 256^i of range-checked bytes (ByteTargets); with exactly 8 bytes canonical, as le_sum with 64 bits
+    Target le_bytes_sum(const std::vector<Target>& bytes) {
+        if (bytes.empty() || bytes.size() > 8) throw std::runtime_error("le_bytes_sum: 1 to 8 bytes");
+        return le_limbs_sum(bytes, 8);
+    }
+    // The little-endian bytes of x, each range-checked by a lookup into the byte table `u8_table_idx` the way
+    // aes::add_virtual_byte_target does it, so they are ByteTargets of the AES gadgets.
+    std::vector<Target> split_bytes_le(Target x, size_t num_bytes, size_t u8_table_idx) {
+        if (num_bytes < 1 || num_bytes > 8) throw std::runtime_error("split_bytes_le: num_bytes must be 1 to 8");
+        if (u8_table_idx >= luts_.size()) throw std::runtime_error("lut index not in luts");
+        std::vector<Target> bytes(num_bytes);
+        for (size_t i = 0; i < num_bytes; i++) {
+            bytes[i] = add_virtual_target();
+            gens_.push_back(Gen{OP_LIMB, bytes[i], x, 0, 0, 0, (u64)(8 * i), 8});
+            add_lookup_from_index(bytes[i], u8_table_idx);  // aes::assert_byte
+        }
+        assert_equal_to_input(le_bytes_sum(bytes), x);
+        return bytes;
+    }
+    // a < b for a, b below 2^num_bits (both are range-checked here): the top bit of a - b + 2^num_bits is clear
+    BoolTarget is_less_than(Target a, Target b, size_t num_bits) {
+        if (num_bits < 1 || num_bits > 62) throw std::runtime_error("is_less_than: num_bits must be 1 to 62");
+        range_check(a, num_bits);
+        range_check(b, num_bits);
+        Target d = add(sub(a, b), constant(1ull << num_bits));
+        return not_(split_le(d, num_bits + 1)[num_bits]);
+    }
+
     // ---- lookups (plonky2 gadgets/lookup.rs) ------------------------------------------------------
     size_t add_lookup_table_from_pairs(const std::vector<std::pair<u16, u16>>& table) {
         for (size_t i = 0; i < luts_.size(); i++)
@@ -258,6 +320,26 @@ class CircuitBuilder {
         }
         return false;
     }
+
+    // Horner chain over limbs [lo, hi) of `width` bits each, most significant first: hi - lo - 1 ops on one ArithmeticGate shape
+    Target horner(const std::vector<Target>& limbs, size_t lo, size_t hi, u32 width) {
+        Target acc = limbs[hi - 1];
+        for (size_t i = hi - 1; i-- > lo;) acc = mul_const_add(1ull << width, acc, limbs[i]);
+        return acc;
+    }
+    // le_sum / le_bytes_sum.  64 bits in all: the integer must be below p = 2^64 - 2^32 + 1, that is, NOT (high half all
+    // ones and low half non-zero): is_equal(hi, 2^32 - 1) * lo = 0.
+    Target le_limbs_sum(const std::vector<Target>& limbs, u32 width) {
+        const size_t n = limbs.size();
+        if (n * width < 64) return horner(limbs, 0, n, width);
+        Target lo = horner(limbs, 0, n / 2, width), hi = horner(limbs, n / 2, n, width);
+        BoolTarget top = is_equal(hi, constant(0xFFFFFFFFull));
+        connect(mul(top.target, lo), zero());
+        return mul_const_add(1ull << 32, hi, lo);
+    }
+    // sum == x for the x a split started from.  Not connect(sum, x): that would make the sum's generator a producer of x's
+    // slot, which the limb hints read -- a witness program that waits on itself whenever x is a plain input.
+    void assert_equal_to_input(Target sum, Target x) { connect(sub(sum, x), zero()); }
 
     u32 add_gate(u32 kind, u64 c0 = 0, u64 c1 = 0) {
         u32 row = (u32)gate_instances_.size();
@@ -557,7 +639,7 @@ inline Circuit CircuitBuilder::build() {
             o.a = slot(g.a);
             o.b = slot(g.b);
             o.c = slot(g.c);
-        } else if (g.kind == OP_LOOKUP) {
+        } else if (g.kind == OP_LOOKUP || g.kind == OP_LIMB) {
             o.a = slot(g.a);
         } else if (g.kind == OP_EQ || g.kind == OP_EQINV) {
             o.a = slot(g.a);
@@ -590,7 +672,7 @@ inline Circuit CircuitBuilder::build() {
         auto wslot = [&](u32 row, u32 col) -> u32 { return (u32)slot_of[find((u32)(V + (u64)row * R + col))]; };
         auto inputs = [&](const Op& o, u32* in) -> int {
             if (o.kind == OP_ARITH) { in[0] = o.a; in[1] = o.b; in[2] = o.c; return 3; }
-            if (o.kind == OP_LOOKUP) { in[0] = o.a; return 1; }
+            if (o.kind == OP_LOOKUP || o.kind == OP_LIMB) { in[0] = o.a; return 1; }
             if (o.kind == OP_EQ || o.kind == OP_EQINV) { in[0] = o.a; in[1] = o.b; return 2; }
             if (o.kind == OP_POSEIDON) {
                 for (u32 k = 0; k < 12; k++) in[k] = wslot(o.a, PG_IN + k);

@@ -132,6 +132,33 @@ p2_target p2_builder_add_lookup_from_index(p2_builder* b, p2_target in, size_t l
         return UINT64_MAX;
     }
 }
+int p2_builder_assert_bool(p2_builder* b, p2_target t) { return guarded([&] { b->b.assert_bool(t); }); }
+int p2_builder_le_sum(p2_builder* b, const p2_target* bits, size_t n, p2_target* out) {
+    return guarded([&] {
+        std::vector<BoolTarget> v(n);
+        for (size_t i = 0; i < n; i++) v[i] = BoolTarget{bits[i]};
+        *out = b->b.le_sum(v);
+    });
+}
+int p2_builder_split_le(p2_builder* b, p2_target x, size_t num_bits, p2_target* bits) {
+    return guarded([&] {
+        auto v = b->b.split_le(x, num_bits);
+        for (size_t i = 0; i < v.size(); i++) bits[i] = v[i].target;
+    });
+}
+int p2_builder_range_check(p2_builder* b, p2_target x, size_t num_bits) { return guarded([&] { b->b.range_check(x, num_bits); }); }
+int p2_builder_le_bytes_sum(p2_builder* b, const p2_target* bytes, size_t n, p2_target* out) {
+    return guarded([&] { *out = b->b.le_bytes_sum(std::vector<Target>(bytes, bytes + n)); });
+}
+int p2_builder_split_bytes_le(p2_builder* b, p2_target x, size_t num_bytes, size_t u8_table_idx, p2_target* bytes) {
+    return guarded([&] {
+        auto v = b->b.split_bytes_le(x, num_bytes, u8_table_idx);
+        std::copy(v.begin(), v.end(), bytes);
+    });
+}
+int p2_builder_is_less_than(p2_builder* b, p2_target x, p2_target y, size_t num_bits, p2_target* out) {
+    return guarded([&] { *out = b->b.is_less_than(x, y, num_bits).target; });
+}
 size_t p2_builder_num_gates(const p2_builder* b) { return guarded_sz([&]() -> size_t { return b->b.num_gates(); }); }
 int p2_builder_build(p2_builder* b, uint8_t** blob, size_t* len) {
     try {
@@ -612,7 +639,7 @@ int p2_witness_schedule_check(const uint8_t* blob, size_t len, uint32_t fuse, ui
         auto slots_of = [&](const Op& o, u32* d, int& first_out) {
             int nd = 0;
             if (o.kind == OP_ARITH) d[nd++] = o.a, d[nd++] = o.b, d[nd++] = o.c;
-            else if (o.kind == OP_LOOKUP) d[nd++] = o.a;
+            else if (o.kind == OP_LOOKUP || o.kind == OP_LIMB) d[nd++] = o.a;
             else if (o.kind == OP_EQ || o.kind == OP_EQINV) d[nd++] = o.a, d[nd++] = o.b;
             else if (o.kind == OP_POSEIDON) {
                 for (u32 k = 0; k < 12; k++) d[nd++] = (u32)c.wire_slot[(size_t)(PG_IN + k) * n + o.a];
@@ -766,6 +793,8 @@ int p2_host_witness(const uint8_t* blob, size_t len, const p2_assignment* input,
                 r = ent & 0xFFFF;
             } else if (o.kind == OP_EQ) {
                 r = x == y ? 1 : 0;
+            } else if (o.kind == OP_LIMB) {
+                r = limb_of(x, o.k0, o.k1);
             } else {
                 r = x == y ? 0 : gl::inv(gl::sub(x, y));
             }

@@ -89,6 +89,7 @@ enum OpKind : u32 {
     OP_EQINV = 4,   // out = a==b ? 0 : 1/(a-b)       (EqualityGenerator.inv)
     OP_POSEIDON = 5,  // PoseidonGenerator of gate row `a`: reads wires 0..11 and 24 of the row, writes every other wire of
                       // the row (routed ones through their slots, wires >= 80 into advice block `aux`)
+    OP_LIMB = 6,    // out = (a >> k0) & (2^k1 - 1) of the canonical value in slot a   (one limb of upstream's SplitGenerator)
 };
 struct Op {
     u32 kind, out, a, b, c, aux;
@@ -331,7 +332,8 @@ static inline Circuit deserialize(const void* data, size_t len) {
         if (o.kind == OP_LOOKUP && (o.a >= c.num_slots || o.aux >= c.luts.size())) throw std::runtime_error("lookup op");
         if ((o.kind == OP_EQ || o.kind == OP_EQINV) && (o.a >= c.num_slots || o.b >= c.num_slots)) throw std::runtime_error("eq op");
         if (o.kind == OP_POSEIDON && (o.a >= n || o.aux >= c.poseidon_rows.size() || c.poseidon_rows[o.aux] != o.a)) throw std::runtime_error("poseidon op");
-        if (o.kind > OP_POSEIDON) throw std::runtime_error("op kind");
+        if (o.kind == OP_LIMB && (o.a >= c.num_slots || o.k1 < 1 || o.k1 > 16 || o.k0 > 64 || o.k0 + o.k1 > 64)) throw std::runtime_error("limb op");
+        if (o.kind > OP_LIMB) throw std::runtime_error("op kind");
     }
     for (auto s : c.wire_slot)
         if (s >= (int32_t)c.num_slots) throw std::runtime_error("wire slot range");

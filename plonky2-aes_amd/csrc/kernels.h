@@ -1034,6 +1034,11 @@ __global__ __launch_bounds__(512) void k_witness(WitnessArgs a) {
                         r = ent[u] & 0xFFFF;
                         atomicAdd(&mult[ent[u] >> 16], 1u);
                     }
+                } else if (kind == p2::OP_LIMB) {
+                    if (x[u] == UNSET)
+                        bad = 2;
+                    else
+                        r = (x[u] >> o[u].k0) & ((1ull << o[u].k1) - 1);  // witness_check.h limb_of
                 } else {
                     if (x[u] == UNSET || y[u] == UNSET)
                         bad = 2;

@@ -52,7 +52,7 @@ inline int op_operands(const Circuit& c, const Op& o, u32* d) {
     int nd = 0;
     if (o.kind == OP_ARITH) {
         d[nd++] = o.a, d[nd++] = o.b, d[nd++] = o.c;
-    } else if (o.kind == OP_LOOKUP) {
+    } else if (o.kind == OP_LOOKUP || o.kind == OP_LIMB) {
         d[nd++] = o.a;
     } else if (o.kind == OP_EQ || o.kind == OP_EQINV) {
         d[nd++] = o.a, d[nd++] = o.b;
@@ -183,6 +183,9 @@ WC_HD inline void poseidon_row_walk(const u64* in, u64 swap, Emit emit) {
     for (int i = 0; i < 12; i++) emit(PG_OUT + i, st[i]);
 }
 
+// OP_LIMB: bits [k0, k0 + k1) of a canonical value (load-time validation keeps 1 <= k1 <= 16 and k0 + k1 <= 64)
+WC_HD inline u64 limb_of(u64 x, u64 k0, u64 k1) { return (x >> k0) & ((1ull << k1) - 1); }
+
 struct WOpFault {
     int kind;  // P2_FAULT_NONE, P2_FAULT_LOOKUP_MISS or P2_FAULT_GENERATOR_CONFLICT
     u32 slot;  // the slot at fault: the lookup's input, or the output the generator lost
@@ -231,6 +234,8 @@ WC_HD inline WOpFault wcheck_op(const WCheckCtx& c, u32 i) {
         r = ent & 0xFFFF;
     } else if (o.kind == OP_EQ) {
         r = x == y ? 1 : 0;
+    } else if (o.kind == OP_LIMB) {
+        r = limb_of(x, o.k0, o.k1);
     } else {
         r = x == y ? 0 : gl::inv(gl::sub(x, y));
     }

@@ -62,7 +62,7 @@ inline WitnessSchedule schedule_witness(const Circuit& c, u32 max_chain, u32 sla
         int nd = 0;
         if (o.kind == OP_ARITH) {
             d[nd++] = o.a, d[nd++] = o.b, d[nd++] = o.c;
-        } else if (o.kind == OP_LOOKUP) {
+        } else if (o.kind == OP_LOOKUP || o.kind == OP_LIMB) {
             d[nd++] = o.a;
         } else if (o.kind == OP_EQ || o.kind == OP_EQINV) {
             d[nd++] = o.a, d[nd++] = o.b;
