@@ -446,6 +446,12 @@ pub mod plonk {
                 let rc = unsafe { ffi::p2_builder_range_check(self.h, x.0, n_log) };
                 assert!(rc == ffi::P2_OK, "{}", last_error());
             }
+            /// Not upstream's: `multiply_point` (and `public_key`, `elgamal_encrypt`, `hashed_elgamal_encrypt` through it) as 320
+            /// EcStepGate rows instead of arithmetic gates.  Off by default.
+            pub fn set_ec_gate(&mut self, on: bool) {
+                let rc = unsafe { ffi::p2_builder_set_ec_gate(self.h, on as std::os::raw::c_int) };
+                assert!(rc == ffi::P2_OK, "{}", last_error());
+            }
             pub fn num_gates(&self) -> usize { unsafe { ffi::p2_builder_num_gates(self.h) } }
             /// `build::<PoseidonGoldilocksConfig>()` (19 sites) or `build::<KeccakGoldilocksConfig>()`: compile on the host, then upload the circuit
             /// to HIP device P2AES_DEVICE (default 0) and commit constants | sigmas there.

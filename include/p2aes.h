@@ -207,6 +207,15 @@ void p2_builder_constant_point(p2_builder*, const uint64_t p[10], p2_target out[
 void p2_builder_add_virtual_biguint320_target(p2_builder*, p2_target bits[320]);
 int p2_builder_multiply_point(p2_builder*, const p2_target bits[320], const p2_target p[10], p2_target out[10]);
 void p2_builder_add_point(p2_builder*, const p2_target p[10], const p2_target q[10], p2_target out[10]);
+/* EcStepGate (csrc/ecstep_gate.h; not an upstream gate): one row holds one double-and-add step of a scalar multiplication,
+ *     mid = 2 acc,  out = mid + bit q,
+ * in (X:Z:U:T) coordinates, acc / mid / out = X | Z | U | T (4 x 5 elements), q = x | u (2 x 5).  `bit` is not made boolean.
+ *   set_ec_gate  on != 0: multiply_point -- and public_key, elgamal_encrypt, hashed_elgamal_encrypt through it -- emits 320 such
+ *                rows instead of arithmetic gates.  Off by default; a builder that leaves it off builds what it always built.
+ *   ec_step      one row; hinted != 0 attaches the generator that fills mid and out (witness op ECSTEP), hinted == 0 leaves
+ *                them to the caller, who sets the returned targets. */
+int p2_builder_set_ec_gate(p2_builder*, int on);
+int p2_builder_ec_step(p2_builder*, const p2_target acc[20], const p2_target q[10], p2_target bit, int hinted, p2_target mid[20], p2_target out[20]);
 /* CircuitBuilderECGFP5PublicKey::public_key (ecgfp5/src/circuit.rs:35) */
 int p2_builder_public_key(p2_builder*, const p2_target sk_bits[320], p2_target pk[10]);
 /* CircuitBuilderElGamal::elgamal_encrypt (elgamal/circuit.rs:28) */
@@ -248,6 +257,10 @@ int p2_host_partial_rounds(uint64_t* states, size_t count);
  * place on count x 12 words that may be ANY u64: from "round 3's twelve S-box outputs" to "the state carries round 26's constants"
  * (some representative of each word, not canonical).  p2_gpu_merged_middle is the same on the device. */
 int p2_host_merged_middle(uint64_t* states, size_t count);
+/* EcStepGate's 40 constraints on count rows of 80 canonical wires -> out [count][40]; the _ext form over GF(p^2): wires
+ * [count][80][2] (c0, c1) -> out [count][40][2].  The evaluator the verifiers and the quotient-side kernel share. */
+int p2_host_ecstep_constraints(const uint64_t* wires, size_t count, uint64_t* out);
+int p2_host_ecstep_constraints_ext(const uint64_t* wires, size_t count, uint64_t* out);
 /* k_hash_leaves' sponge on the host: data [min(active_cols, cols)][num_leaves] -> digests [num_leaves][4] */
 int p2_host_hash_leaves(const uint64_t* data, size_t cols, size_t active_cols, size_t num_leaves, uint64_t* digests);
 
@@ -407,7 +420,7 @@ int p2_witness_batch(p2_circuit*, size_t batch, const p2_assignment* inputs, con
  * kind == P2_FAULT_NONE iff *status == 0, kinds 1-4 iff *status == 1, kind 5 iff *status == 2. */
 typedef struct {
     int32_t kind;        /* P2_FAULT_* */
-    int32_t op_kind;     /* generator kind (csrc/circuit.h OP_*: 0 ARITH .. 5 POSEIDON, 6 LIMB = a bit or byte hint of split_le /
+    int32_t op_kind;     /* generator kind (csrc/circuit.h OP_*: 0 ARITH .. 5 POSEIDON, 7 ECSTEP, 6 LIMB = a bit or byte hint of split_le /
                           * split_bytes_le) at fault, -1 if none */
     int64_t input_index; /* entry of the assignment involved, -1 if none */
     p2_target target;    /* a target of the slot at fault: its lowest virtual target, else its lowest routed wire; UINT64_MAX if none */
@@ -514,6 +527,8 @@ int p2_gpu_hash_leaves(const uint64_t* data, size_t cols, size_t active_cols, si
 int p2_gpu_partial_rounds(uint64_t* states, size_t count, int device);
 /* p2_host_merged_middle on the device, the same way (tests/test_gpu_merged_middle.py) */
 int p2_gpu_merged_middle(uint64_t* states, size_t count, int device);
+/* p2_host_ecstep_constraints on the device: the base-field instantiation, one row per thread (tests/test_gpu_ecstep.py) */
+int p2_gpu_ecstep_constraints(const uint64_t* wires, size_t count, uint64_t* out, int device);
 /* child [batch][2 * num_parents][4] -> parent [batch][num_parents][4] */
 int p2_gpu_merkle_level(const uint64_t* child, size_t num_parents, size_t batch, uint64_t* parent, int device);
 /* vals [batch][2][len] -> digests [batch][len / arity][4] */

@@ -62,7 +62,7 @@ VERIFY_REASONS = {
 # p2_witness_explain / p2_host_witness fault kinds (include/p2aes.h P2_FAULT_*), by code
 FAULT_KINDS = ("NONE", "INPUT_NOT_CANONICAL", "INPUT_CONFLICT", "LOOKUP_MISS", "GENERATOR_CONFLICT", "NOT_SET")
 # witness generator kinds (csrc/circuit.h OP_*), by code
-OP_KINDS = ("ARITH", "CONST", "LOOKUP", "EQ", "EQINV", "POSEIDON", "LIMB")
+OP_KINDS = ("ARITH", "CONST", "LOOKUP", "EQ", "EQINV", "POSEIDON", "LIMB", "ECSTEP")
 VALUE_UNSET = 0xFFFFFFFFFFFFFFFF   # P2_VALUE_UNSET: "not assigned" on input, "the run did not determine it" on output
 
 u32p = C.POINTER(C.c_uint32)
@@ -229,6 +229,7 @@ def lib():
         "p2_builder_add_virtual_biguint320_target": (None, [vp, u64p]),
         "p2_builder_multiply_point": (C.c_int, [vp, u64p, u64p, u64p]), "p2_builder_add_point": (None, [vp, u64p, u64p, u64p]),
         "p2_builder_public_key": (C.c_int, [vp, u64p, u64p]),
+        "p2_builder_set_ec_gate": (C.c_int, [vp, C.c_int]), "p2_builder_ec_step": (C.c_int, [vp, u64p, u64p, u64, C.c_int, u64p, u64p]),
         "p2_builder_elgamal_encrypt": (C.c_int, [vp, u64p, u64p, u64p, u64p, u64p]),
         "p2_builder_hashed_elgamal_encrypt": (C.c_int, [vp, u64p, u64p, u64p, u64p, u64p]),
         "p2_selftest_host": (C.c_int, [u64, sz, sz]), "p2_selftest_device": (C.c_int, [u64, sz, C.c_int]),
@@ -278,6 +279,8 @@ def lib():
         "p2_gpu_partial_rounds": (C.c_int, [u64p, sz, C.c_int]),
         "p2_host_merged_middle": (C.c_int, [u64p, sz]),
         "p2_gpu_merged_middle": (C.c_int, [u64p, sz, C.c_int]),
+        "p2_host_ecstep_constraints": (C.c_int, [u64p, sz, u64p]), "p2_host_ecstep_constraints_ext": (C.c_int, [u64p, sz, u64p]),
+        "p2_gpu_ecstep_constraints": (C.c_int, [u64p, sz, u64p, C.c_int]),
         "p2_gpu_lde": (C.c_int, [u64p, sz, C.c_int, C.c_int, u64p, C.c_int]),
         "p2_gpu_intt": (C.c_int, [u64p, sz, C.c_int, u64p, C.c_int]),
         "p2_gpu_lde_round": (C.c_int, [u64p, sz, C.c_int, u32p, sz, sz, sz, sz, u64p, sz, C.c_int]),
@@ -309,10 +312,11 @@ def _arr(vals):
 
 
 class CircuitBuilder:
-    def __init__(self, zero_knowledge=False, hasher="poseidon"):
+    def __init__(self, zero_knowledge=False, hasher="poseidon", ec_gate=False):
         """CircuitBuilder::<F, D>::new(standard_recursion_config()) or, with zero_knowledge, standard_recursion_zk_config().
         hasher: "poseidon" (build::<PoseidonGoldilocksConfig>()) or "keccak" (build::<KeccakGoldilocksConfig>(): Keccak-256
-        Merkle trees and circuit digest); everything made from the circuit afterwards takes the hasher from it."""
+        Merkle trees and circuit digest); everything made from the circuit afterwards takes the hasher from it.
+        ec_gate: multiply_point (and public_key, elgamal_encrypt, hashed_elgamal_encrypt) as 320 EcStepGate rows."""
         if hasher not in HASHERS:
             raise P2Error("unknown hasher %r (known: %s)" % (hasher, ", ".join(sorted(HASHERS))))
         if hasher == "poseidon":
@@ -320,6 +324,8 @@ class CircuitBuilder:
         else:
             self._h = lib().p2_builder_new_config(1 if zero_knowledge else 0, HASHERS[hasher])
         if not self._h:
+            raise P2Error(_err())
+        if ec_gate and lib().p2_builder_set_ec_gate(self._h, 1):
             raise P2Error(_err())
 
     def __del__(self):
@@ -486,6 +492,16 @@ class CircuitBuilder:
         if lib().p2_builder_multiply_point(self._h, _arr(bits), _arr(point_target), out):
             raise P2Error(_err())
         return list(out)
+
+    def ec_step(self, acc, q, bit, hinted=True):
+        """One EcStepGate row: (mid, out) = (2 acc, 2 acc + bit q), acc / mid / out as X | Z | U | T (20 targets), q as x | u
+        (10).  hinted=False leaves mid and out to the caller's witness."""
+        if len(acc) != 20 or len(q) != 10:
+            raise P2Error("ec_step takes 20 accumulator targets and 10 point targets")
+        mid, out = (u64 * 20)(), (u64 * 20)()
+        if lib().p2_builder_ec_step(self._h, _arr(acc), _arr(q), bit, 1 if hinted else 0, mid, out):
+            raise P2Error(_err())
+        return list(mid), list(out)
 
     def add_point(self, p, q):
         out = (u64 * 10)()

@@ -254,6 +254,26 @@ class CircuitBuilder {
         }
     }
 
+    // ---- ecGFp5 scalar-multiplication step (ecstep_gate.h; not an upstream gate) ---------------------
+    // One EcStepGate row: mid = 2 acc, out = mid + bit Q in (X:Z:U:T) coordinates, acc = X | Z | U | T and Q = x | u.  `bit` is
+    // not made boolean here.  hinted = false leaves the row without a generator: the caller sets mid and out.
+    struct EcStep {
+        std::array<Target, 20> mid, out;
+    };
+    EcStep ec_step(const std::array<Target, 20>& acc, const std::array<Target, 10>& q, Target bit, bool hinted = true) {
+        u32 row = add_gate(G_ECSTEP);
+        for (u32 i = 0; i < 20; i++) connect(acc[i], wire_target(row, EG_ACC + i));
+        for (u32 i = 0; i < 10; i++) connect(q[i], wire_target(row, EG_Q + i));
+        connect(bit, wire_target(row, EG_BIT));
+        if (hinted) gens_.push_back(Gen{OP_ECSTEP, wire_target(row, EG_MID), (Target)row, 0, 0, 0, 0, 0});
+        EcStep r;
+        for (u32 i = 0; i < 20; i++) r.mid[i] = wire_target(row, EG_MID + i), r.out[i] = wire_target(row, EG_OUT + i);
+        return r;
+    }
+    // multiply_point (ecgfp5.h) as 320 EcStepGate rows instead of arithmetic gates; off by default
+    void set_ec_gate(bool on) { ec_gate_ = on; }
+    bool ec_gate() const { return ec_gate_; }
+
     // ---- build (plonky2 CircuitBuilder::build) ----------------------------------------------------
     Circuit build();
 
@@ -353,6 +373,7 @@ class CircuitBuilder {
     void add_all_lookups();
 
     Config cfg_;
+    bool ec_gate_ = false;
     u64 num_virtual_ = 0;
     std::vector<GateInstance> gate_instances_;
     std::vector<std::pair<Target, Target>> copy_constraints_;
@@ -497,6 +518,7 @@ inline Circuit CircuitBuilder::build() {
         if (present[G_CONSTANT]) types.push_back({G_CONSTANT, 0, "ConstantGate { num_consts: 2 }"});
         if (present[G_PUBLIC_INPUT]) types.push_back({G_PUBLIC_INPUT, 0, "PublicInputGate"});
         if (present[G_ARITHMETIC]) types.push_back({G_ARITHMETIC, 0, "ArithmeticGate { num_ops: 20 }"});
+        if (present[G_ECSTEP]) types.push_back({G_ECSTEP, 0, "EcStepGate"});
         if (present[G_POSEIDON]) types.push_back({G_POSEIDON, 0, "PoseidonGate(PhantomData<plonky2_field::goldilocks_field::GoldilocksField>)<WIDTH=12>"});
         std::sort(types.begin(), types.end(), [](const GateType& a, const GateType& b) {
             u32 da = gate_degree(a.kind), db = gate_degree(b.kind);
@@ -650,9 +672,15 @@ inline Circuit CircuitBuilder::build() {
             o.aux = (u32)c.poseidon_rows.size();
             c.poseidon_rows.push_back(row);
             for (u32 col = 0; col < R; col++) slot(wire_target(row, col));  // every routed wire of the row carries a value
+        } else if (g.kind == OP_ECSTEP) {
+            o.a = (u32)g.a;
         }
         ops[i] = o;
     }
+    // wires 0..70 of an EcStepGate row carry a value whether or not the row has a generator (an unhinted row's are set by the caller)
+    for (size_t row = 0; row < n; row++)
+        if (gate_instances_[row].kind == G_ECSTEP)
+            for (u32 col = 0; col < EG_WIRES; col++) slot(wire_target((u32)row, col));
     c.vt_slot.resize(V);
     for (u64 v = 0; v < V; v++) c.vt_slot[v] = (int32_t)slot((Target)v);
     for (Target t : public_inputs_) c.pi_slots.push_back(slot(t));  // routed PoseidonGate inputs: every one has a slot already
@@ -679,9 +707,17 @@ inline Circuit CircuitBuilder::build() {
                 in[12] = wslot(o.a, PG_SWAP);
                 return 13;
             }
+            if (o.kind == OP_ECSTEP) {
+                for (u32 k = 0; k < EG_MID; k++) in[k] = wslot(o.a, k);
+                return (int)EG_MID;
+            }
             return 0;
         };
         auto outputs = [&](const Op& o, u32* out) -> int {
+            if (o.kind == OP_ECSTEP) {
+                for (u32 col = EG_MID; col < EG_WIRES; col++) out[col - EG_MID] = wslot(o.a, col);
+                return (int)(EG_WIRES - EG_MID);
+            }
             if (o.kind != OP_POSEIDON) { out[0] = o.out; return 1; }
             int k = 0;
             for (u32 col = PG_OUT; col < R; col++)
@@ -696,7 +732,7 @@ inline Circuit CircuitBuilder::build() {
         std::vector<u32> pending(M, 0), level(M, 0), slot_level(num_slots, 0);
         std::vector<uint8_t> slot_ready(num_slots, 0);
         for (size_t i = 0; i < M; i++) {
-            u32 in[16];
+            u32 in[32];
             int k = inputs(ops[i], in);
             for (int j = 0; j < k; j++) {
                 bool dup = false;
@@ -721,7 +757,7 @@ inline Circuit CircuitBuilder::build() {
         for (;;) {
             while (done < queue.size()) {
                 u32 i = queue[done++];
-                u32 in[16], outs[80];
+                u32 in[32], outs[80];
                 int k = inputs(ops[i], in);
                 int ko = outputs(ops[i], outs);
                 u32 lv = ops[i].kind == OP_EQINV ? floor_level : 0;

@@ -159,6 +159,23 @@ int p2_builder_split_bytes_le(p2_builder* b, p2_target x, size_t num_bytes, size
 int p2_builder_is_less_than(p2_builder* b, p2_target x, p2_target y, size_t num_bits, p2_target* out) {
     return guarded([&] { *out = b->b.is_less_than(x, y, num_bits).target; });
 }
+int p2_builder_set_ec_gate(p2_builder* b, int on) {
+    if (!b) return set_error("p2_builder_set_ec_gate: null builder"), P2_ERR_INVALID;
+    b->b.set_ec_gate(on != 0);
+    return P2_OK;
+}
+int p2_builder_ec_step(p2_builder* b, const p2_target acc[20], const p2_target q[10], p2_target bit, int hinted, p2_target mid[20], p2_target out[20]) {
+    if (!b || !acc || !q || !mid || !out) return set_error("p2_builder_ec_step: null argument"), P2_ERR_INVALID;
+    return guarded([&] {
+        std::array<Target, 20> a;
+        std::array<Target, 10> qq;
+        std::copy(acc, acc + 20, a.begin());
+        std::copy(q, q + 10, qq.begin());
+        const CircuitBuilder::EcStep st = b->b.ec_step(a, qq, bit, hinted != 0);
+        std::copy(st.mid.begin(), st.mid.end(), mid);
+        std::copy(st.out.begin(), st.out.end(), out);
+    });
+}
 size_t p2_builder_num_gates(const p2_builder* b) { return guarded_sz([&]() -> size_t { return b->b.num_gates(); }); }
 int p2_builder_build(p2_builder* b, uint8_t** blob, size_t* len) {
     try {
@@ -563,6 +580,25 @@ int p2_host_merged_middle(uint64_t* states, size_t count) {
     for (size_t i = 0; i < count; i++) glf::merged_middle(states + 12 * i);
     return P2_OK;
 }
+// EcStepGate's 40 constraints (ecstep_gate_constraints<FBase>) of `count` rows of 80 wires, on arbitrary canonical words; the
+// _ext form is the <FExt> instantiation on (c0, c1) pairs.
+int p2_host_ecstep_constraints(const uint64_t* wires, size_t count, uint64_t* out) {
+    if (count && (!wires || !out)) return set_error("p2_host_ecstep_constraints: null argument"), P2_ERR_INVALID;
+    for (size_t i = 0; i < 80 * count; i++)
+        if (wires[i] >= gl::P) return set_error("p2_host_ecstep_constraints: non-canonical wire"), P2_ERR_INVALID;
+    for (size_t r = 0; r < count; r++)
+        ecstep_gate_constraints<FBase>([&](u32 i) { return wires[80 * r + i]; }, [&](int k, u64 c) { out[40 * r + k] = c; });
+    return P2_OK;
+}
+int p2_host_ecstep_constraints_ext(const uint64_t* wires, size_t count, uint64_t* out) {
+    if (count && (!wires || !out)) return set_error("p2_host_ecstep_constraints_ext: null argument"), P2_ERR_INVALID;
+    for (size_t i = 0; i < 160 * count; i++)
+        if (wires[i] >= gl::P) return set_error("p2_host_ecstep_constraints_ext: non-canonical wire"), P2_ERR_INVALID;
+    for (size_t r = 0; r < count; r++)
+        ecstep_gate_constraints<FExt>([&](u32 i) { return gl::e2(wires[160 * r + 2 * i], wires[160 * r + 2 * i + 1]); },
+                                      [&](int k, gl::E2 c) { out[80 * r + 2 * k] = c.a, out[80 * r + 2 * k + 1] = c.b; });
+    return P2_OK;
+}
 // k_hash_leaves on the host, with the same sponge steps (glf::sponge_permute): data [active][num_leaves] column-major, columns
 // >= active_cols are zero and not stored; digests [num_leaves][4].
 int p2_host_hash_leaves(const uint64_t* data, size_t cols, size_t active_cols, size_t num_leaves, uint64_t* digests) {
@@ -644,9 +680,13 @@ int p2_witness_schedule_check(const uint8_t* blob, size_t len, uint32_t fuse, ui
             else if (o.kind == OP_POSEIDON) {
                 for (u32 k = 0; k < 12; k++) d[nd++] = (u32)c.wire_slot[(size_t)(PG_IN + k) * n + o.a];
                 d[nd++] = (u32)c.wire_slot[(size_t)PG_SWAP * n + o.a];
+            } else if (o.kind == OP_ECSTEP) {
+                for (u32 col = 0; col < EG_MID; col++) d[nd++] = (u32)c.wire_slot[(size_t)col * n + o.a];
             }
             first_out = nd;
-            if (o.kind == OP_POSEIDON) {
+            if (o.kind == OP_ECSTEP) {
+                for (u32 col = EG_MID; col < EG_WIRES; col++) d[nd++] = (u32)c.wire_slot[(size_t)col * n + o.a];
+            } else if (o.kind == OP_POSEIDON) {
                 for (u32 col = PG_OUT; col < R; col++)
                     if (col != PG_SWAP) d[nd++] = (u32)c.wire_slot[(size_t)col * n + o.a];
             } else {
@@ -770,6 +810,18 @@ int p2_host_witness(const uint8_t* blob, size_t len, const p2_assignment* input,
                 poseidon_gate_witness(w);
                 for (u32 col = PG_OUT; col < c.cfg.num_routed_wires; col++)
                     if (col != PG_SWAP) put((u32)c.wire_slot[(size_t)col * n + o.a], w[col]);
+                continue;
+            }
+            if (o.kind == OP_ECSTEP) {
+                u64 w[EG_WIRES];
+                bool ready = true;
+                for (u32 col = 0; col < EG_MID; col++) ready &= (w[col] = val[c.wire_slot[(size_t)col * n + o.a]]) != W_UNSET;
+                if (!ready) {
+                    worst = std::max(worst, 2);
+                    continue;
+                }
+                ecstep_gate_witness(w);
+                for (u32 col = EG_MID; col < EG_WIRES; col++) put((u32)c.wire_slot[(size_t)col * n + o.a], w[col]);
                 continue;
             }
             u64 x = 0, y = 0, z = 0, r = 0;

@@ -66,19 +66,26 @@ enum GateKind : u32 {
     G_PUBLIC_INPUT = 4,  // PublicInputGate, degree 1
     G_ARITHMETIC = 5,    // ArithmeticGate{20 ops}, degree 3
     G_POSEIDON = 6,      // PoseidonGate (one permutation per row, all 135 wires), degree 7, 123 constraints
-    G_NUM_KINDS = 7
+    G_ECSTEP = 7,        // EcStepGate (one ecGFp5 double-and-add step per row, ecstep_gate.h), degree 6, 40 constraints.  Not an
+                         // upstream gate; numbered after the others so that their values stay, sorted between the two by degree
+    G_NUM_KINDS = 8
 };
-static inline u32 gate_degree(u32 k) { return k == G_POSEIDON ? 7 : k == G_ARITHMETIC ? 3 : (k == G_CONSTANT || k == G_PUBLIC_INPUT) ? 1 : 0; }
-static inline u32 gate_num_constraints(u32 k) { return k == G_POSEIDON ? 123 : k == G_ARITHMETIC ? 20 : k == G_CONSTANT ? 2 : k == G_PUBLIC_INPUT ? 4 : 0; }
+static inline u32 gate_degree(u32 k) { return k == G_POSEIDON ? 7 : k == G_ECSTEP ? 6 : k == G_ARITHMETIC ? 3 : (k == G_CONSTANT || k == G_PUBLIC_INPUT) ? 1 : 0; }
+static inline u32 gate_num_constraints(u32 k) { return k == G_POSEIDON ? 123 : k == G_ECSTEP ? 40 : k == G_ARITHMETIC ? 20 : k == G_CONSTANT ? 2 : k == G_PUBLIC_INPUT ? 4 : 0; }
+// place of a kind in the (degree, id) order of the `gates` list: the enum's order, but EcStepGate (6) before PoseidonGate (7)
+static inline u32 gate_order(u32 k) { return k == G_ECSTEP ? G_POSEIDON : k == G_POSEIDON ? G_ECSTEP : k; }
 // PoseidonGate wire layout (plonky2 gates/poseidon.rs): 12 in | 12 out | swap | 4 delta | 3x12 full-round
 // S-box inputs | 22 partial-round S-box inputs | 4x12 full-round S-box inputs = 135
 static const u32 PG_IN = 0, PG_OUT = 12, PG_SWAP = 24, PG_DELTA = 25, PG_FULL0 = 29, PG_PARTIAL = 65, PG_FULL1 = 87;
+// EcStepGate wire layout (all routed): acc (X, Z, U, T: 4 x 5) | Q (x, u: 2 x 5) | bit | mid = 2 acc (4 x 5) | out = mid + bit Q
+// (4 x 5) = 71; wires 71..79 unused and unconnected
+static const u32 EG_ACC = 0, EG_Q = 20, EG_BIT = 30, EG_MID = 31, EG_OUT = 51, EG_WIRES = 71;
 
 static const u32 LU_SLOTS = 40;   // LookupGate::num_slots = num_routed_wires / 2
 static const u32 LUT_SLOTS = 26;  // LookupTableGate::num_slots = num_routed_wires / 3
 static const u32 ARITH_OPS = 20;  // ArithmeticGate::num_ops = num_routed_wires / 4
 static const u32 UNUSED_SELECTOR = 0xFFFFFFFFu;
-static const u32 MAX_LUTS = 6, MAX_GATE_TYPES = 2 * MAX_LUTS + 5;  // per table: LookupGate + LookupTableGate; Noop, Constant, PublicInput, Arithmetic, Poseidon
+static const u32 MAX_LUTS = 6, MAX_GATE_TYPES = 2 * MAX_LUTS + 6;  // per table: LookupGate + LookupTableGate; Noop, Constant, PublicInput, Arithmetic, EcStep, Poseidon
 
 // Witness program: one op per generator, over "slots" (= copy-constraint partitions that carry a value).
 enum OpKind : u32 {
@@ -90,6 +97,8 @@ enum OpKind : u32 {
     OP_POSEIDON = 5,  // PoseidonGenerator of gate row `a`: reads wires 0..11 and 24 of the row, writes every other wire of
                       // the row (routed ones through their slots, wires >= 80 into advice block `aux`)
     OP_LIMB = 6,    // out = (a >> k0) & (2^k1 - 1) of the canonical value in slot a   (one limb of upstream's SplitGenerator)
+    OP_ECSTEP = 7,  // generator of EcStepGate row `a`: reads wires 0..30 of the row (acc, Q, bit) and writes wires 31..70 (mid, out),
+                    // all through their slots; `out` is the slot of wire 31
 };
 struct Op {
     u32 kind, out, a, b, c, aux;
@@ -295,7 +304,7 @@ static inline Circuit deserialize(const void* data, size_t len) {
     size_t n = c.n();
     if (c.gates.empty() || c.gates.size() > MAX_GATE_TYPES || c.groups.empty() || c.groups.size() > c.gates.size()) throw std::runtime_error("gate list");
     for (size_t i = 0; i < c.gates.size(); i++)
-        if (c.gates[i] >= G_NUM_KINDS || (i && (c.gates[i] < c.gates[i - 1] || (c.gates[i] == c.gates[i - 1] && c.gates[i] > G_LOOKUP_TABLE)))) throw std::runtime_error("gate kinds");
+        if (c.gates[i] >= G_NUM_KINDS || (i && (gate_order(c.gates[i]) < gate_order(c.gates[i - 1]) || (c.gates[i] == c.gates[i - 1] && c.gates[i] > G_LOOKUP_TABLE)))) throw std::runtime_error("gate kinds");
     for (auto& g : c.groups)
         if (g.first >= g.second || g.second > c.gates.size()) throw std::runtime_error("selector groups");
     for (size_t i = 0; i < c.selector_index.size(); i++)
@@ -333,7 +342,12 @@ static inline Circuit deserialize(const void* data, size_t len) {
         if ((o.kind == OP_EQ || o.kind == OP_EQINV) && (o.a >= c.num_slots || o.b >= c.num_slots)) throw std::runtime_error("eq op");
         if (o.kind == OP_POSEIDON && (o.a >= n || o.aux >= c.poseidon_rows.size() || c.poseidon_rows[o.aux] != o.a)) throw std::runtime_error("poseidon op");
         if (o.kind == OP_LIMB && (o.a >= c.num_slots || o.k1 < 1 || o.k1 > 16 || o.k0 > 64 || o.k0 + o.k1 > 64)) throw std::runtime_error("limb op");
-        if (o.kind > OP_LIMB) throw std::runtime_error("op kind");
+        if (o.kind == OP_ECSTEP) {
+            if (o.a >= n) throw std::runtime_error("ecstep op");
+            for (u32 col = 0; col < EG_WIRES; col++)
+                if (c.wire_slot[(size_t)col * n + o.a] < 0) throw std::runtime_error("ecstep row wire without slot");
+        }
+        if (o.kind > OP_ECSTEP) throw std::runtime_error("op kind");
     }
     for (auto s : c.wire_slot)
         if (s >= (int32_t)c.num_slots) throw std::runtime_error("wire slot range");

@@ -448,10 +448,22 @@ inline std::vector<BoolTarget> add_virtual_biguint320_target(CircuitBuilder& b) 
 }
 // bits * P.  A variable base costs a doubling and a mixed addition per bit (the addend is bit * (x, u): the neutral
 // when the bit is clear).  A constant base (the generator) needs no doublings: sum_i bit_i * (2^i P) with the
-// multiples precomputed on the host.
+// multiples precomputed on the host.  With CircuitBuilder::set_ec_gate both become 320 EcStepGate rows (ecstep_gate.h).
 inline PointTarget multiply_point(CircuitBuilder& b, const std::vector<BoolTarget>& bits, const PointTarget& p) {
     if (bits.size() != SCALAR_BITS) throw std::runtime_error("multiply_point takes 320 bits");
     ProjTarget acc = neutral_target(b);
+    if (b.ec_gate()) {
+        // one EcStepGate row per bit, most significant first: acc <- 2 acc + bit P, for a variable or a constant base alike
+        std::array<Target, 10> q;
+        for (int k = 0; k < 5; k++) q[k] = p.x[k], q[5 + k] = p.u[k];
+        for (size_t i = SCALAR_BITS; i-- > 0;) {
+            std::array<Target, 20> a;
+            for (int k = 0; k < 5; k++) a[k] = acc.X[k], a[5 + k] = acc.Z[k], a[10 + k] = acc.U[k], a[15 + k] = acc.T[k];
+            const CircuitBuilder::EcStep st = b.ec_step(a, q, bits[i].target);
+            for (int k = 0; k < 5; k++) acc.X[k] = st.out[k], acc.Z[k] = st.out[5 + k], acc.U[k] = st.out[10 + k], acc.T[k] = st.out[15 + k];
+        }
+        return to_affine(b, acc);
+    }
     Affine base;
     if (point_as_constant(b, p, &base)) {
         Point m = Point::from_affine(base);

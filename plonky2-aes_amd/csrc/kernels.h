@@ -14,6 +14,7 @@
 #include "gl.h"
 #include "poseidon_fast.h"
 #include "poseidon_gate.h"
+#include "ecstep_gate.h"
 #include "zk_prf.h"
 
 namespace p2k {
@@ -841,6 +842,27 @@ __device__ __noinline__ int witness_poseidon_op(const WitnessArgs& a, u64* val, 
     return bad;
 }
 
+// EcStepGate's generator: one thread computes the whole row (these ops form one sequential chain per scalar multiplication, like
+// sponge rows).  Everything is routed: wires 0..30 in, wires 31..70 out, through their slots.  0 ok, 1 conflict, 2 missing input
+__device__ __noinline__ int witness_ecstep_op(const WitnessArgs& a, u64* val, const p2::Op& o) {
+    const u32 row = o.a;
+    int bad = 0;
+    for (u32 c = 0; c < p2::EG_MID; c++)
+        if (val[a.wire_slot[(size_t)c * a.n + row]] == UNSET) bad = 2;
+    if (bad) return bad;
+    // every operand is set, and a set slot never changes: the walk reads each one when it needs it (the accumulator, then Q and
+    // the bit) instead of holding all 31 beside its products
+    p2::ecstep_row_walk([&](u32 c) { return val[a.wire_slot[(size_t)c * a.n + row]]; }, [&](u32 c, u64 v) {
+        const u32 sl = (u32)a.wire_slot[(size_t)c * a.n + row];
+        const u64 cur = val[sl];
+        if (cur == UNSET)
+            val[sl] = v;
+        else if (cur != v)
+            bad = 1;
+    });
+    return bad;
+}
+
 // Most ops per chain the kernel is unrolled for (witness_schedule.h is asked for chains no longer than this).
 static const int WITNESS_KMAX = 8;
 // Single ops a thread keeps in flight together: the kernel is latency bound (a dependent chain of memory round trips per op,
@@ -923,8 +945,9 @@ __device__ __forceinline__ int witness_exec_chain(const WitnessArgs& a, u64* val
 // CHAINS = false: the instantiation for schedules without chains (P2AES_WITNESS_FUSE=1, or a circuit whose critical path holds
 // nothing to fuse); it does not carry the chain executor's registers (252 -> ~100 VGPRs), so its 8 waves share a compute unit
 // with the other stream's hash waves instead of needing an empty one.
-template <bool HAS_POSEIDON, bool CHAINS>
-__global__ __launch_bounds__(512) void k_witness(WitnessArgs a) {
+// HAS_EC: the program may hold OP_ECSTEP row ops (k_ecwitness below); k_witness is the body without that branch.
+template <bool HAS_POSEIDON, bool CHAINS, bool HAS_EC>
+__device__ __forceinline__ void witness_body(const WitnessArgs& a) {
     __shared__ int s_status;
     const u32 proof = blockIdx.x;
     u64* val = a.values + (size_t)proof * a.num_slots;
@@ -995,7 +1018,7 @@ __global__ __launch_bounds__(512) void k_witness(WitnessArgs a) {
 #pragma unroll
             for (int u = 0; u < WITNESS_MLP; u++) {
                 x[u] = y[u] = z[u] = cur[u] = 0;
-                if (!act[u] || o[u].kind == p2::OP_POSEIDON) continue;
+                if (!act[u] || o[u].kind == p2::OP_POSEIDON || (HAS_EC && o[u].kind == p2::OP_ECSTEP)) continue;
                 const u32 kind = o[u].kind;
                 cur[u] = val[o[u].out];
                 if (kind != p2::OP_CONST) x[u] = val[o[u].a];
@@ -1015,6 +1038,11 @@ __global__ __launch_bounds__(512) void k_witness(WitnessArgs a) {
                 int bad = 0;
                 if (kind == p2::OP_POSEIDON) {
                     if (HAS_POSEIDON) bad = witness_poseidon_op(a, val, proof, o[u]);
+                    if (bad) worst = max(worst, bad == 1 ? 3 : 2);
+                    continue;
+                }
+                if (HAS_EC && kind == p2::OP_ECSTEP) {
+                    bad = witness_ecstep_op(a, val, o[u]);
                     if (bad) worst = max(worst, bad == 1 ? 3 : 2);
                     continue;
                 }
@@ -1060,6 +1088,15 @@ __global__ __launch_bounds__(512) void k_witness(WitnessArgs a) {
         __syncthreads();
     }
     if (threadIdx.x == 0) a.status[proof] = s_status == 3 ? 1 : s_status;
+}
+template <bool HAS_POSEIDON, bool CHAINS>
+__global__ __launch_bounds__(512) void k_witness(WitnessArgs a) {
+    witness_body<HAS_POSEIDON, CHAINS, false>(a);
+}
+// the same kernel for circuits with EcStepGate rows
+template <bool HAS_POSEIDON, bool CHAINS>
+__global__ __launch_bounds__(512) void k_ecwitness(WitnessArgs a) {
+    witness_body<HAS_POSEIDON, CHAINS, true>(a);
 }
 
 // wires[col][row] = value of the wire's partition (or 0 for unconnected wires)

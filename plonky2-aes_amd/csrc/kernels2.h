@@ -328,6 +328,53 @@ __global__ __launch_bounds__(256, 4) void k_quotient(QuotientArgs a) {
     out[(size_t)N] = gl::mul(A.acc[1].reduce(), zi);
 }
 
+// EcStepGate's share of the quotient, as a pass of its own behind k_quotient (which skips the kind) and before the inverse
+// transform; launched only for circuits that have the gate.  One thread per LDE point, the same bit-reversed p: the gate's
+// filter as k_quotient forms it, the 40 constraints over the base field, sum_k alpha_i^(idx_gate + k) filter c_k for both
+// challenges as exact sums, and zh_inv[coset] times that added to out[p], out[N + p].  The vanishing sum is linear in its terms,
+// so the result is what a fused evaluation would have stored.  The constraint walk asks for its wires in stages (acc; mid; Q and
+// bit; out), so at most two points and the products of one formula are live.
+struct EcQuotientArgs {
+    const u64* pre_lde;    // [ncc + R][8n]
+    const u64* wires_lde;  // [active][8n]
+    size_t wires_batch_stride;
+    const u64* zh_inv;  // [8] indexed by coset
+    const u64* apow;    // [batch][2][APOW_STRIDE]
+    u64* out;           // [batch][NC][8n], already holding k_quotient's values
+    size_t out_batch_stride;
+    u32 n, logn, rate_bits, nsel, idx_gate;
+    u32 gate, gate_sel, group_lo, group_hi;  // the EcStepGate's index in the gate list, its selector column and its group
+};
+__global__ __launch_bounds__(256) void k_ecstep_post(EcQuotientArgs a) {
+    const u32 N = a.n << a.rate_bits;
+    const u32 p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= N) return;
+    const u32 lde_bits = a.logn + a.rate_bits;
+    const u32 coset = (__brev(p) >> (32 - lde_bits)) & ((1u << a.rate_bits) - 1);
+    const u64 s = a.pre_lde[(size_t)a.gate_sel * N + p];
+    u64 filter = 1;
+    for (u32 j = a.group_lo; j < a.group_hi; j++)
+        if (j != a.gate) filter = gl::mul(filter, gl::sub(j, s));
+    if (a.nsel > 1) filter = gl::mul(filter, gl::sub(p2::UNUSED_SELECTOR, s));
+    const u64* W = a.wires_lde + (size_t)blockIdx.y * a.wires_batch_stride + p;
+    AlphaAcc A;
+    A.init(a.apow + (size_t)blockIdx.y * 2 * APOW_STRIDE);
+    p2::ecstep_gate_constraints<p2::FBase>([&](u32 i) { return W[(size_t)i * N]; }, [&](int k, u64 cst) { A.add(a.idx_gate + (u32)k, gl::mul(filter, cst)); });
+    const u64 zi = a.zh_inv[coset];
+    u64* out = a.out + (size_t)blockIdx.y * a.out_batch_stride + p;
+    out[0] = gl::add(out[0], gl::mul(A.acc[0].reduce(), zi));
+    out[(size_t)N] = gl::add(out[(size_t)N], gl::mul(A.acc[1].reduce(), zi));
+}
+
+// ecstep_gate_constraints<FBase> on rows of 80 wires (tests: p2_gpu_ecstep_constraints), one row per thread
+__global__ __launch_bounds__(256) void k_ecstep_selftest(const u64* __restrict__ wires /*[count][80]*/, size_t count, u64* __restrict__ out /*[count][40]*/) {
+    const size_t r = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= count) return;
+    const u64* w = wires + 80 * r;
+    u64* o = out + 40 * r;
+    p2::ecstep_gate_constraints<p2::FBase>([&](u32 i) { return w[i]; }, [&](int k, u64 cst) { o[k] = glf::canon(cst); });
+}
+
 // ------------------------------------------------------------------------------------------- openings
 // pows[k][i] = z_k^i (extension), k = 0: zeta, 1: g*zeta, 2: 1/zeta, 3: 1/(g*zeta).  layout [k][2][n] (c0 | c1)
 // Two levels: z^i = z^(i mod 256) * (z^256)^(i div 256).  k_zeta_tabs writes, per (proof, point), the 256 low powers as

@@ -251,7 +251,9 @@ __device__ __forceinline__ void vfy_opening_reductions(const VerifyArgs& a, u32 
     o[0] = r0.a, o[1] = r0.b, o[2] = r1.a, o[3] = r1.b, o[4] = gz.a, o[5] = gz.b, o[6] = ap.a, o[7] = ap.b;
 }
 
-__global__ __launch_bounds__(256) void k_vfy_vanishing(VerifyArgs a) {
+// HAS_EC: the gate list may hold an EcStepGate (k_vfy_ecvanishing below); k_vfy_vanishing is the body without that branch.
+template <bool HAS_EC>
+__device__ __forceinline__ void vfy_vanishing_body(const VerifyArgs& a) {
     __shared__ u64 red[256];
     __shared__ u64 lutacc[2][p2::MAX_LUTS];
     __shared__ E2 gate[VFY_MAX_GC];
@@ -372,7 +374,7 @@ __global__ __launch_bounds__(256) void k_vfy_vanishing(VerifyArgs a) {
     const u32 gc = a.o_const + 2 * (a.nsel + a.nls);
     for (u32 gi = 0; gi < a.num_gates; gi++) {
         const u32 kind = a.gate_kind[gi];
-        if (kind != p2::G_ARITHMETIC && kind != p2::G_CONSTANT && kind != p2::G_PUBLIC_INPUT && kind != p2::G_POSEIDON) continue;  // no constraints
+        if (kind != p2::G_ARITHMETIC && kind != p2::G_CONSTANT && kind != p2::G_PUBLIC_INPUT && kind != p2::G_POSEIDON && !(HAS_EC && kind == p2::G_ECSTEP)) continue;  // no constraints
         const E2 s = vfy_e2(w, a.o_const + 2 * a.gate_sel[gi]);
         E2 filter = gl::e2(1);
         for (u32 j = a.group_lo[gi]; j < a.group_hi[gi]; j++)
@@ -393,6 +395,8 @@ __global__ __launch_bounds__(256) void k_vfy_vanishing(VerifyArgs a) {
             }
         } else if (kind == p2::G_POSEIDON) {
             vfy_poseidon_gate(wire, [&](int k, E2 cst) { gate[k] = gl::add(gate[k], gl::mul(filter, cst)); }, pg_st, pg_tmp);
+        } else if (HAS_EC && kind == p2::G_ECSTEP) {
+            p2::ecstep_gate_constraints<p2::FExt>(wire, [&](int k, E2 cst) { gate[k] = gl::add(gate[k], gl::mul(filter, cst)); });
         }
     }
     for (u32 k = 0; k < a.ngc; k++) V.push(gate[k]);
@@ -402,6 +406,9 @@ __global__ __launch_bounds__(256) void k_vfy_vanishing(VerifyArgs a) {
         if (!gl::eq(i == 0 ? V.acc0 : V.acc1, gl::mul(zh, t))) atomicOr(&a.flags[p], (u32)VF_VANISH);
     }
 }
+__global__ __launch_bounds__(256) void k_vfy_vanishing(VerifyArgs a) { vfy_vanishing_body<false>(a); }
+// the same kernel for circuits with EcStepGate rows
+__global__ __launch_bounds__(256) void k_vfy_ecvanishing(VerifyArgs a) { vfy_vanishing_body<true>(a); }
 
 // ------------------------------------------------------------------------------------------- 4. queries
 // The tree hasher of the circuit's configuration, as the path walks of the verifier (vfy_merkle) and of the compressor

@@ -240,6 +240,13 @@ static void fill_gate_table(const Circuit& c, Args& a) {
     }
 }
 
+// index of the EcStepGate in the circuit's gate list, or -1: such circuits take k_ecwitness, k_ecstep_post and k_vfy_ecvanishing
+static int ecstep_gate_index(const Circuit& c) {
+    for (size_t g = 0; g < c.gates.size(); g++)
+        if (c.gates[g] == p2::G_ECSTEP) return (int)g;
+    return -1;
+}
+
 static inline dim3 g1(size_t work, u32 block, u32 y = 1, u32 z = 1) { return dim3((u32)((work + block - 1) / block), y, z); }
 
 // ---------------------------------------------------------------------------------- building blocks
@@ -906,7 +913,13 @@ static int prove_chunk(p2_circuit* C, Workspace& W, u32 B, u32 n_inputs, const u
         // the wide kernels -- and a deep circuit's witness time is never hidden.  Chained, chunk k+1's witness runs
         // under chunk k's commitments.
         if (C->witness_recorded) HIPCHECK(hipStreamWaitEvent(W.lane.stream, C->ev_witness, 0));
-        if (c.poseidon_rows.empty()) {
+        if (ecstep_gate_index(c) >= 0) {
+            const bool pos = !c.poseidon_rows.empty();
+            if (!pos && C->witness_chains) LAUNCH(W.lane, "witness", (k_ecwitness<false, true>), dim3(B), dim3(WITNESS_THREADS), 0, a);
+            if (!pos && !C->witness_chains) LAUNCH(W.lane, "witness", (k_ecwitness<false, false>), dim3(B), dim3(WITNESS_THREADS), 0, a);
+            if (pos && C->witness_chains) LAUNCH(W.lane, "witness", (k_ecwitness<true, true>), dim3(B), dim3(WITNESS_THREADS), 0, a);
+            if (pos && !C->witness_chains) LAUNCH(W.lane, "witness", (k_ecwitness<true, false>), dim3(B), dim3(WITNESS_THREADS), 0, a);
+        } else if (c.poseidon_rows.empty()) {
             if (C->witness_chains)
                 LAUNCH(W.lane, "witness", (k_witness<false, true>), dim3(B), dim3(WITNESS_THREADS), 0, a);
             else
@@ -1032,6 +1045,16 @@ static int prove_chunk(p2_circuit* C, Workspace& W, u32 B, u32 n_inputs, const u
             LAUNCH(W.lane, "quotient", (k_quotient<false, true>), g1(N, 256, B), dim3(256), 0, a);  // the wire columns read once
         else
             LAUNCH(W.lane, "quotient", k_quotient<true>, g1(N, 256, B), dim3(256), 0, a);
+        const int eg = ecstep_gate_index(c);
+        if (eg >= 0) {  // k_quotient skips the kind: its terms are added behind it (the stage's time is the sum of the two)
+            EcQuotientArgs e{};
+            e.pre_lde = a.pre_lde, e.wires_lde = a.wires_lde, e.wires_batch_stride = a.wires_batch_stride, e.zh_inv = a.zh_inv, e.apow = a.apow;
+            e.out = a.out, e.out_batch_stride = a.out_batch_stride;
+            e.n = a.n, e.logn = a.logn, e.rate_bits = a.rate_bits, e.nsel = a.nsel;
+            e.idx_gate = NC + NC * (npp + 1) + NC * (nlp ? 4 + (u32)c.luts.size() + 2 * nsldc : 0);
+            e.gate = (u32)eg, e.gate_sel = a.gate_sel[eg], e.group_lo = a.group_lo[eg], e.group_hi = a.group_hi[eg];
+            LAUNCH(W.lane, "quotient", k_ecstep_post, g1(N, 256, B), dim3(256), 0, e);
+        }
         if (quotient_chunks(W.lane, C->dom, W.d_qvals, W.d_qres, W.quot.coef, NC, (size_t)qc * n, B, C->d_shift_inv_pows, C->d_w8inv, C->d_qscale)) return P2_ERR_HIP;
     }
     if (commit_oracle(C, W, W.quot, 2, c.degree_bits, proof_base, B)) return P2_ERR_HIP;
@@ -1540,7 +1563,8 @@ static int proof_run(p2_circuit* C, VerifyWs* W, ProofOp op, size_t batch, const
             LAUNCH_ON(st, k_cmp_pack, words_grid, dim3(256), a);
         } else {
             const u32 slots = 4 + v.num_rounds + 1;
-            LAUNCH_ON(st, k_vfy_vanishing, dim3(B), dim3(256), v);
+            if (ecstep_gate_index(C->c) >= 0) LAUNCH_ON(st, k_vfy_ecvanishing, dim3(B), dim3(256), v);
+            else LAUNCH_ON(st, k_vfy_vanishing, dim3(B), dim3(256), v);
             const dim3 queries_grid((u32)(((size_t)B * v.num_queries + 63) / 64), slots);
             if (keccak) LAUNCH_ON(st, k_kcv_queries, queries_grid, dim3(64), v);
             else LAUNCH_ON(st, k_vfy_queries, queries_grid, dim3(64), v);
@@ -1725,10 +1749,15 @@ static int witness_put_slots(WitnessWs* W, u32** d, size_t* cap, std::vector<u32
 }
 static int launch_witness(p2_circuit* C, hipStream_t st, u32 B, const WitnessArgs& a) {
     const bool pos = !C->c.poseidon_rows.empty();
-    if (!pos && C->witness_chains) LAUNCH_ON(st, (k_witness<false, true>), dim3(B), dim3(512), a);
-    if (!pos && !C->witness_chains) LAUNCH_ON(st, (k_witness<false, false>), dim3(B), dim3(512), a);
-    if (pos && C->witness_chains) LAUNCH_ON(st, (k_witness<true, true>), dim3(B), dim3(512), a);
-    if (pos && !C->witness_chains) LAUNCH_ON(st, (k_witness<true, false>), dim3(B), dim3(512), a);
+    const bool ec = ecstep_gate_index(C->c) >= 0;
+    if (!ec && !pos && C->witness_chains) LAUNCH_ON(st, (k_witness<false, true>), dim3(B), dim3(512), a);
+    if (!ec && !pos && !C->witness_chains) LAUNCH_ON(st, (k_witness<false, false>), dim3(B), dim3(512), a);
+    if (!ec && pos && C->witness_chains) LAUNCH_ON(st, (k_witness<true, true>), dim3(B), dim3(512), a);
+    if (!ec && pos && !C->witness_chains) LAUNCH_ON(st, (k_witness<true, false>), dim3(B), dim3(512), a);
+    if (ec && !pos && C->witness_chains) LAUNCH_ON(st, (k_ecwitness<false, true>), dim3(B), dim3(512), a);
+    if (ec && !pos && !C->witness_chains) LAUNCH_ON(st, (k_ecwitness<false, false>), dim3(B), dim3(512), a);
+    if (ec && pos && C->witness_chains) LAUNCH_ON(st, (k_ecwitness<true, true>), dim3(B), dim3(512), a);
+    if (ec && pos && !C->witness_chains) LAUNCH_ON(st, (k_ecwitness<true, false>), dim3(B), dim3(512), a);
     return P2_OK;
 }
 // Enqueues witness generation of `batch` witnesses on `st`, a chunk of the workspace at a time: k_witness, the wired-slot
@@ -2791,6 +2820,20 @@ int p2_gpu_partial_rounds(uint64_t* states, size_t count, int device) {
     hipLaunchKernelGGL(k_partial_rounds, g1(count, 256), dim3(256), 0, 0, d, count);
     HIPCHECK(hipGetLastError());
     HIPCHECK(hipMemcpy(states, d, count * 96, hipMemcpyDeviceToHost));
+    return P2_OK;
+}
+// p2_host_ecstep_constraints on the device: the <FBase> instantiation the quotient-side kernel runs
+int p2_gpu_ecstep_constraints(const uint64_t* wires, size_t count, uint64_t* out, int device) {
+    if (count == 0 || count > (1u << 20) || !wires || !out) return set_error("count out of range"), P2_ERR_INVALID;
+    for (size_t i = 0; i < 80 * count; i++)
+        if (wires[i] >= gl::P) return set_error("p2_gpu_ecstep_constraints: non-canonical wire"), P2_ERR_INVALID;
+    if (int rc = pick_device(device)) return rc;
+    Allocs mem;
+    u64 *d_in, *d_out;
+    if (upload(mem, &d_in, (const u64*)wires, count * 80) || dalloc(mem, &d_out, count * 40)) return P2_ERR_HIP;
+    hipLaunchKernelGGL(k_ecstep_selftest, g1(count, 256), dim3(256), 0, 0, d_in, count, d_out);
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipMemcpy(out, d_out, count * 40 * 8, hipMemcpyDeviceToHost));
     return P2_OK;
 }
 int p2_gpu_merged_middle(uint64_t* states, size_t count, int device) {

@@ -9,6 +9,7 @@
 #include "circuit.h"
 #include "gl.h"
 #include "keccak_hash.h"
+#include "ecstep_gate.h"
 #include "poseidon_gate.h"
 
 namespace p2 {
@@ -498,6 +499,8 @@ inline std::string verify_parsed(const Circuit& C, const VerifierData& vd, const
             } else if (kind == G_POSEIDON) {
                 poseidon_gate_constraints<FExt>([&](u32 i) { return o_wires[i]; },
                                                 [&](int k, E2 cst) { gate[k] = add(gate[k], mul(filter, cst)); });
+            } else if (kind == G_ECSTEP) {
+                ecstep_gate_constraints<FExt>([&](u32 i) { return o_wires[i]; }, [&](int k, E2 cst) { gate[k] = add(gate[k], mul(filter, cst)); });
             }
         }
         for (auto* v : {&z1, &ppt, &lkt, &gate}) terms.insert(terms.end(), v->begin(), v->end());

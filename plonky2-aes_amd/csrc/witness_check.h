@@ -22,12 +22,26 @@
 #include "../../include/p2aes.h"
 #include "circuit.h"
 #include "gl.h"
+#include "ecstep_gate.h"
 #include "poseidon_gate.h"
 
 #if defined(__HIPCC__)
 #define WC_HD __host__ __device__
 #else
 #define WC_HD
+#endif
+// wcheck_op and wfault_report in device code: always inlined, a call would pass the context through scratch memory
+#if defined(__HIP_DEVICE_COMPILE__)
+#define WC_HD_INLINE __host__ __device__ __forceinline__
+#else
+#define WC_HD_INLINE WC_HD inline
+#endif
+// Device: no global load written below may be issued before `v` is computed (an empty asm that takes v and clobbers memory).
+// The loads of a check do not depend on the values they are compared with, and the compiler otherwise issues all of them first.
+#if defined(__HIP_DEVICE_COMPILE__)
+#define WC_LOADS_AFTER(v) asm volatile("" : "+v"(v) : : "memory")
+#else
+#define WC_LOADS_AFTER(v) (void)0
 #endif
 
 namespace p2 {
@@ -46,7 +60,7 @@ struct WitnessTables {
     std::vector<u64> lut_ent;       // [num_luts][65536] input -> (flat entry index << 16) | output, or ~0 (as the prover's table)
 };
 
-// operands of an op (Poseidon: the row's 12 inputs and its swap wire); returns their number
+// operands of an op (Poseidon: the row's 12 inputs and its swap wire; EcStep: the row's wires 0..30); returns their number
 inline int op_operands(const Circuit& c, const Op& o, u32* d) {
     const size_t n = c.n();
     int nd = 0;
@@ -59,6 +73,8 @@ inline int op_operands(const Circuit& c, const Op& o, u32* d) {
     } else if (o.kind == OP_POSEIDON) {
         for (u32 k = 0; k < 12; k++) d[nd++] = (u32)c.wire_slot[(size_t)(PG_IN + k) * n + o.a];
         d[nd++] = (u32)c.wire_slot[(size_t)PG_SWAP * n + o.a];
+    } else if (o.kind == OP_ECSTEP) {
+        for (u32 k = 0; k < EG_MID; k++) d[nd++] = (u32)c.wire_slot[(size_t)k * n + o.a];
     }
     return nd;
 }
@@ -103,13 +119,15 @@ inline WitnessTables witness_tables(const Circuit& c, bool with_lut = true) {
             t.slot_row[s] = (u32)row;
             if (t.slot_target[s] >> 63) t.slot_target[s] = (1ull << 63) | ((u64)row << 8) | col;  // no virtual target: lowest wire so far
         }
-    u32 d[16];
+    u32 d[32];
     for (const Op& o : c.ops) {
         const int nd = op_operands(c, o, d);
         for (int j = 0; j < nd; j++) needed[d[j]] = 1;
         if (o.kind == OP_POSEIDON) {
             for (u32 col = PG_OUT; col < R; col++)
                 if (col != PG_SWAP) produced[c.wire_slot[(size_t)col * n + o.a]] = 1;
+        } else if (o.kind == OP_ECSTEP) {
+            for (u32 col = EG_MID; col < EG_WIRES; col++) produced[c.wire_slot[(size_t)col * n + o.a]] = 1;
         } else {
             produced[o.out] = 1;
         }
@@ -194,7 +212,7 @@ struct WOpFault {
 
 // Generator `i` (blob order) against the final values.  A generator with an unset operand never ran and is no fault here;
 // neither is one whose output slot is unset (it can only be unset if the generator never ran when it was scheduled).
-WC_HD inline WOpFault wcheck_op(const WCheckCtx& c, u32 i) {
+WC_HD_INLINE WOpFault wcheck_op(const WCheckCtx& c, u32 i) {
     const Op o = c.ops[i];
     WOpFault f{P2_FAULT_NONE, 0, 0, 0};
     if (o.kind == OP_POSEIDON) {
@@ -213,6 +231,21 @@ WC_HD inline WOpFault wcheck_op(const WCheckCtx& c, u32 i) {
                 best_col = col;
                 f.kind = P2_FAULT_GENERATOR_CONFLICT, f.slot = sl, f.computed = v, f.found = cur;
             }
+        });
+        return f;
+    }
+    if (o.kind == OP_ECSTEP) {
+        for (u32 k = 0; k < EG_MID; k++)
+            if (c.val[c.wire_slot[(size_t)k * c.n + o.a]] == W_UNSET) return f;
+        // the walk reads each operand when it needs it, and visits the columns in ascending order: the first conflict is the
+        // one of the lowest column
+        // (the present values of the 20 mid slots are fetched once mid is computed, those of the out slots once out is: fetched
+        // up front, 40 slots and their indices would sit in registers beside the 18 products and spill)
+        ecstep_row_walk([&](u32 k) { return c.val[c.wire_slot[(size_t)k * c.n + o.a]]; }, [&](u32 col, u64 v) {
+            if (col == EG_MID || col == EG_OUT) WC_LOADS_AFTER(v);
+            const u32 sl = (u32)c.wire_slot[(size_t)col * c.n + o.a];
+            const u64 cur = c.val[sl];
+            if (cur != W_UNSET && cur != v && f.kind == P2_FAULT_NONE) f.kind = P2_FAULT_GENERATOR_CONFLICT, f.slot = sl, f.computed = v, f.found = cur;
         });
         return f;
     }
@@ -268,7 +301,7 @@ inline std::vector<u32> input_prev_links(const std::vector<u32>& slots, u32 num_
 // faulting generator, first unset free slot (positions in free_slots); W_NO_INDEX = none.  *slot receives the slot at fault
 // (W_NO_INDEX if none): the caller fills input_index with the lowest entry that sets it (winput_sets), which for the input
 // kinds is already in place.
-WC_HD inline void wfault_report(const WCheckCtx& c, const u32* prev, int status, u32 bad_input, u32 conflict_input, u32 bad_op, u32 unset_free,
+WC_HD_INLINE void wfault_report(const WCheckCtx& c, const u32* prev, int status, u32 bad_input, u32 conflict_input, u32 bad_op, u32 unset_free,
                                 p2_witness_fault* out, u32* slot) {
     p2_witness_fault f;
     f.kind = P2_FAULT_NONE, f.op_kind = -1, f.input_index = -1, f.target = ~0ull, f.gate_row = ~0u, f.computed = 0, f.found = 0;
@@ -296,7 +329,7 @@ WC_HD inline void wfault_report(const WCheckCtx& c, const u32* prev, int status,
     if (s != W_NO_INDEX) {
         f.target = c.slot_target[s];
         f.gate_row = c.slot_row[s];
-        if (f.op_kind == (int32_t)OP_POSEIDON) f.gate_row = c.ops[bad_op].a;
+        if (f.op_kind == (int32_t)OP_POSEIDON || f.op_kind == (int32_t)OP_ECSTEP) f.gate_row = c.ops[bad_op].a;
     }
     *out = f;
 }

@@ -69,9 +69,13 @@ inline WitnessSchedule schedule_witness(const Circuit& c, u32 max_chain, u32 sla
         } else if (o.kind == OP_POSEIDON) {
             for (u32 k = 0; k < 12; k++) d[nd++] = wslot(o.a, PG_IN + k);
             d[nd++] = wslot(o.a, PG_SWAP);
+        } else if (o.kind == OP_ECSTEP) {
+            for (u32 col = 0; col < EG_MID; col++) d[nd++] = wslot(o.a, col);
         }
         first_out = nd;
-        if (o.kind == OP_POSEIDON) {
+        if (o.kind == OP_ECSTEP) {
+            for (u32 col = EG_MID; col < EG_WIRES; col++) d[nd++] = wslot(o.a, col);
+        } else if (o.kind == OP_POSEIDON) {
             for (u32 col = PG_OUT; col < R; col++)
                 if (col != PG_SWAP) d[nd++] = wslot(o.a, col);
         } else {
