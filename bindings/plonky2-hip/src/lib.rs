@@ -452,6 +452,12 @@ pub mod plonk {
                 let rc = unsafe { ffi::p2_builder_set_ec_gate(self.h, on as std::os::raw::c_int) };
                 assert!(rc == ffi::P2_OK, "{}", last_error());
             }
+            /// Not upstream's: `AesGcmTarget::build` with a tag computes GHASH from carry-less multiply tables, `lanes` (1 to 16)
+            /// blocks per reduction; 0, the default, is the reference's bit-serial circuit.
+            pub fn set_ghash_tables(&mut self, lanes: usize) {
+                let rc = unsafe { ffi::p2_builder_set_ghash_tables(self.h, lanes as std::os::raw::c_int) };
+                assert!(rc == ffi::P2_OK, "{}", last_error());
+            }
             pub fn num_gates(&self) -> usize { unsafe { ffi::p2_builder_num_gates(self.h) } }
             /// `build::<PoseidonGoldilocksConfig>()` (19 sites) or `build::<KeccakGoldilocksConfig>()`: compile on the host, then upload the circuit
             /// to HIP device P2AES_DEVICE (default 0) and commit constants | sigmas there.

@@ -136,6 +136,10 @@ size_t p2_aes_byte_xor_lut(p2_builder*);
 size_t p2_aes_gf_2_8_mul_lut(p2_builder*);
 size_t p2_gcm_u8_unit_right_shift_lut(p2_builder*);
 size_t p2_gcm_u8_bitref_lut(p2_builder*);
+/* Carry-less byte products in GCM's bit order (a byte B stands for the polynomial rev8(B), the bit-reversed byte): with
+ * c = clmul(rev8(a), rev8(b)), (a << 8) + b -> rev8(c & 0xff) and -> rev8(c >> 8).  65 536 entries each; not in the reference. */
+size_t p2_gcm_clmul_lo_lut(p2_builder*);
+size_t p2_gcm_clmul_hi_lut(p2_builder*);
 p2_target p2_aes_add_virtual_byte_target(p2_builder*, size_t u8_table_idx);
 p2_target p2_aes_add_virtual_byte_target_unsafe(p2_builder*);
 /* States are 16 targets, element [4*i + j] = row i, column j (StateTarget.0[i][j]). */
@@ -155,6 +159,19 @@ void p2_gcm_gf_2_128_mul(p2_builder*, size_t xor_lut, size_t shift_lut, size_t b
                          const p2_target* y, p2_target* out);
 int p2_gcm_ghash(p2_builder*, size_t xor_lut, size_t shift_lut, size_t bitref_lut, const p2_target* h, const p2_target* x,
                  size_t len, p2_target* out);
+/* The same two functions from the carry-less multiply tables (csrc/aes_gadgets.h; not the reference's circuit, only its
+ * function): 16 x 16 table products per multiplication, summed by byte position in balanced XOR trees and folded with
+ * x^128 = 1 + x + x^2 + x^7 -- 800 arithmetic ops and 1072 lookups per GHASH block instead of 10 880 and 4 480.  Every input
+ * byte must be a range-checked byte target (a lookup output, p2_aes_add_virtual_byte_target, a byte constant).  lanes, 1 to 16:
+ * blocks taken per reduction, y <- (y ^ x_1) h^k ^ x_2 h^(k-1) ^ .. ^ x_k h; 1 is the plain chain. */
+int p2_gcm_gf_2_128_mul_tables(p2_builder*, size_t xor_lut, size_t clmul_lo_lut, size_t clmul_hi_lut, const p2_target* x,
+                               const p2_target* y, p2_target* out);
+int p2_gcm_ghash_tables(p2_builder*, size_t xor_lut, size_t clmul_lo_lut, size_t clmul_hi_lut, const p2_target* h,
+                        const p2_target* x, size_t len, p2_target* out, int lanes);
+/* lanes = 0 (the default): p2_aes_gcm_build with a tag builds the reference's bit-serial GHASH.  1 to 16: it builds
+ * p2_gcm_ghash_tables with that many lanes, and the two clmul tables instead of the shift and bit tables.  Anything else is an
+ * error.  The switch is a property of the builder, not of the blob: the circuit is gates either way. */
+int p2_builder_set_ghash_tables(p2_builder*, int lanes);
 /* AesGcmTarget<NK,4,NR,L,TAG>::build.  Outputs: key[4*nk], nonce[12], pt[L], ct[L], tag[16]. */
 int p2_aes_gcm_build(p2_builder*, int nk, int nr, size_t L, int with_tag, p2_target* key, p2_target* nonce, p2_target* pt,
                      p2_target* ct, p2_target* tag);

@@ -208,6 +208,10 @@ def lib():
         "p2_gcm_right_shift_one": (None, [vp, sz, u64p, u64p]), "p2_gcm_inc32": (None, [vp, u64p, u64p]),
         "p2_gcm_gf_2_128_mul": (None, [vp, sz, sz, sz, u64p, u64p, u64p]),
         "p2_gcm_ghash": (C.c_int, [vp, sz, sz, sz, u64p, u64p, sz, u64p]),
+        "p2_gcm_clmul_lo_lut": (sz, [vp]), "p2_gcm_clmul_hi_lut": (sz, [vp]),
+        "p2_gcm_gf_2_128_mul_tables": (C.c_int, [vp, sz, sz, sz, u64p, u64p, u64p]),
+        "p2_gcm_ghash_tables": (C.c_int, [vp, sz, sz, sz, u64p, u64p, sz, u64p, C.c_int]),
+        "p2_builder_set_ghash_tables": (C.c_int, [vp, C.c_int]),
         "p2_aes_gcm_build": (C.c_int, [vp, C.c_int, C.c_int, sz, C.c_int, u64p, u64p, u64p, u64p, u64p]),
         "p2_builder_hash_n_to_m_no_pad": (C.c_int, [vp, u64p, sz, u64p, sz]),
         "p2_poseidon_cipher_build": (C.c_int, [vp, sz, u64p, u64p, u64p, u64p]),
@@ -312,11 +316,12 @@ def _arr(vals):
 
 
 class CircuitBuilder:
-    def __init__(self, zero_knowledge=False, hasher="poseidon", ec_gate=False):
+    def __init__(self, zero_knowledge=False, hasher="poseidon", ec_gate=False, ghash_tables=0):
         """CircuitBuilder::<F, D>::new(standard_recursion_config()) or, with zero_knowledge, standard_recursion_zk_config().
         hasher: "poseidon" (build::<PoseidonGoldilocksConfig>()) or "keccak" (build::<KeccakGoldilocksConfig>(): Keccak-256
         Merkle trees and circuit digest); everything made from the circuit afterwards takes the hasher from it.
-        ec_gate: multiply_point (and public_key, elgamal_encrypt, hashed_elgamal_encrypt) as 320 EcStepGate rows."""
+        ec_gate: multiply_point (and public_key, elgamal_encrypt, hashed_elgamal_encrypt) as 320 EcStepGate rows.
+        ghash_tables: 0, or 1 to 16 lanes: AesGcmTarget.build with a tag computes GHASH from carry-less multiply tables."""
         if hasher not in HASHERS:
             raise P2Error("unknown hasher %r (known: %s)" % (hasher, ", ".join(sorted(HASHERS))))
         if hasher == "poseidon":
@@ -326,6 +331,8 @@ class CircuitBuilder:
         if not self._h:
             raise P2Error(_err())
         if ec_gate and lib().p2_builder_set_ec_gate(self._h, 1):
+            raise P2Error(_err())
+        if ghash_tables != 0 and lib().p2_builder_set_ghash_tables(self._h, ghash_tables):
             raise P2Error(_err())
 
     def __del__(self):
@@ -461,6 +468,27 @@ class CircuitBuilder:
     def ghash(self, xor_lut, shift_lut, bitref_lut, h, x):
         out = (u64 * 16)()
         if lib().p2_gcm_ghash(self._h, xor_lut, shift_lut, bitref_lut, _arr(h), _arr(x), len(x), out):
+            raise P2Error(_err())
+        return list(out)
+
+    def clmul_lo_lut(self): return lib().p2_gcm_clmul_lo_lut(self._h)
+    def clmul_hi_lut(self): return lib().p2_gcm_clmul_hi_lut(self._h)
+
+    def gf_2_128_mul_tables(self, xor_lut, lo_lut, hi_lut, x, y):
+        """x * y in GF(2^128) from the clmul tables; x and y are 16 range-checked byte targets each."""
+        if len(x) != 16 or len(y) != 16:
+            raise P2Error("gf_2_128_mul_tables takes two blocks of 16 byte targets")
+        out = (u64 * 16)()
+        if lib().p2_gcm_gf_2_128_mul_tables(self._h, xor_lut, lo_lut, hi_lut, _arr(x), _arr(y), out):
+            raise P2Error(_err())
+        return list(out)
+
+    def ghash_tables(self, xor_lut, lo_lut, hi_lut, h, x, lanes=1):
+        """GHASH_h(x) from the clmul tables, `lanes` (1 to 16) blocks per reduction."""
+        if len(h) != 16:
+            raise P2Error("ghash_tables takes h as 16 byte targets")
+        out = (u64 * 16)()
+        if lib().p2_gcm_ghash_tables(self._h, xor_lut, lo_lut, hi_lut, _arr(h), _arr(x), len(x), out, lanes):
             raise P2Error(_err())
         return list(out)
 

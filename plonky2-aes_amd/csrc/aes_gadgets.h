@@ -6,6 +6,10 @@
 // right_shift_one_target :327-348, inc32_target :350-368, LUTs :392-425).  Const generics <NK,NB,NR,L,TAG>
 // become run-time arguments (NB is always 4).  The native (non-circuit) cipher used to produce witness values
 // mirrors aes-gcm/src/native_aes.rs and native_gcm.rs.
+//
+// Not in the reference: GHASH from carry-less multiply tables (gcm_clmul_lo_lut / gcm_clmul_hi_lut, gf_2_128_mul_tables_target,
+// ghash_tables_target), which AesGcmTarget::build uses under CircuitBuilder::set_ghash_tables.  Its inputs must be range-checked
+// byte targets; the comment above the gadget says why and which targets of AesGcmTarget qualify.
 #pragma once
 #include <array>
 
@@ -220,6 +224,34 @@ inline size_t u8_bitref_lut(CircuitBuilder& b) {  // circuit_gcm.rs:407
         for (int i = 0; i < 8; i++) t.push_back({(u16)((x << 3) + i), (u16)((x >> i) & 1)});
     return b.add_lookup_table_from_pairs(t);
 }
+// Carry-less byte products in GCM's bit order (not in the reference; CircuitBuilder::set_ghash_tables).  Bit i of a GCM block is
+// bit 7 - i % 8 of byte i / 8 and the coefficient of x^i, so a byte B stands for the polynomial whose plain-integer form is the
+// bit-reversed byte rev8(B).  With c = clmul(rev8(a), rev8(b)), a 15-bit product, the two tables send (a << 8) + b to
+// rev8(c & 0xff) and rev8(c >> 8): the product's coefficients of x^0..x^7 and of x^8..x^14 as GCM bytes (the second one's low bit
+// is always 0).
+inline uint8_t rev8(uint8_t v) {
+    v = (uint8_t)((v >> 4) | (v << 4));
+    v = (uint8_t)(((v & 0xCC) >> 2) | ((v & 0x33) << 2));
+    return (uint8_t)(((v & 0xAA) >> 1) | ((v & 0x55) << 1));
+}
+inline u16 clmul8(uint8_t a, uint8_t b) {
+    u16 r = 0;
+    for (int i = 0; i < 8; i++)
+        if ((b >> i) & 1) r ^= (u16)((u16)a << i);
+    return r;
+}
+inline size_t gcm_clmul_lut(CircuitBuilder& b, bool high) {
+    std::vector<std::pair<u16, u16>> t;
+    t.reserve(65536);
+    for (int x = 0; x < 256; x++)
+        for (int y = 0; y < 256; y++) {
+            u16 c = clmul8(rev8((uint8_t)x), rev8((uint8_t)y));
+            t.push_back({(u16)((x << 8) + y), (u16)rev8((uint8_t)(high ? c >> 8 : c & 0xff))});
+        }
+    return b.add_lookup_table_from_pairs(t);
+}
+inline size_t gcm_clmul_lo_lut(CircuitBuilder& b) { return gcm_clmul_lut(b, false); }
+inline size_t gcm_clmul_hi_lut(CircuitBuilder& b) { return gcm_clmul_lut(b, true); }
 
 // ---------------------------------------------------------------- CircuitBuilderAESState (circuit_aes.rs:41-275)
 inline ByteTarget add_virtual_byte_target_unsafe(CircuitBuilder& b) { return b.add_virtual_target(); }
@@ -452,6 +484,106 @@ inline BlockTarget ghash_target(CircuitBuilder& b, size_t xor_lut, size_t shift_
     return y;
 }
 
+// ---------------------------------------------------------------- GHASH from carry-less multiply tables (not in the reference)
+// The same function as gf_2_128_mul_target / ghash_target in ArithmeticGate and LookupGate rows of another shape: a product in
+// GF(2^128) is 16 x 16 byte-by-byte carry-less products, each one entry of gcm_clmul_lo_lut and one of gcm_clmul_hi_lut, summed
+// by byte position into a 32-byte unreduced product and folded back with x^128 = 1 + x + x^2 + x^7 (the byte 0xE1, the
+// reference's r_first).  Per GHASH block 800 arithmetic ops and 1072 lookups instead of 10 880 and 4 480.
+//
+// Every input byte must be a range-checked ByteTarget (a lookup output, add_virtual_byte_target, or a byte constant), as for
+// byte_xor: a table index x * 256 + y names one pair (x, y) only when both are bytes.  AesGcmTarget's h and ciphertext bytes are
+// XOR-table outputs and its padding and length bytes constants, so they qualify.
+struct ClmulAccumulator {
+    std::array<std::vector<ByteTarget>, 32> early, late;  // per byte position: pieces of products known early / of the one on the chain
+};
+// x[p] * y[q] for all (p, q): the low byte of each product goes to position p + q, the high byte to p + q + 1
+inline void clmul_accumulate(CircuitBuilder& b, size_t lo_lut, size_t hi_lut, const BlockTarget& x, const BlockTarget& y,
+                             std::array<std::vector<ByteTarget>, 32>& pos) {
+    for (int p = 0; p < 16; p++)
+        for (int q = 0; q < 16; q++) {
+            Target idx = b.mul_const_add(1 << 8, x[p], y[q]);
+            pos[p + q].push_back(b.add_lookup_from_index(idx, lo_lut));
+            pos[p + q + 1].push_back(b.add_lookup_from_index(idx, hi_lut));
+        }
+}
+// XOR of v as a balanced pairwise tree, ceil(log2(size)) byte_xors deep: the witness runs level by level, and a running sum of
+// the 31 pieces of a middle position would be 30 deep.
+inline ByteTarget xor_tree(CircuitBuilder& b, size_t xor_lut, std::vector<ByteTarget> v) {
+    if (v.empty()) return zero_byte(b);
+    while (v.size() > 1) {
+        std::vector<ByteTarget> next;
+        next.reserve((v.size() + 1) / 2);
+        for (size_t i = 0; i + 1 < v.size(); i += 2) next.push_back(byte_xor(b, xor_lut, v[i], v[i + 1]));
+        if (v.size() & 1) next.push_back(v.back());
+        v.swap(next);
+    }
+    return v[0];
+}
+// The 32 sums, then the reduction: for k = 15 .. 1 and then 0, D[16 + k] * x^128 = D[16 + k] * 0xE1 goes to D[k] (low byte) and
+// D[k + 1] (high byte).  k = 15 writes D[16], which k = 0 reads; hence k = 0 last.
+inline BlockTarget clmul_fold(CircuitBuilder& b, size_t xor_lut, size_t lo_lut, size_t hi_lut, const ClmulAccumulator& acc) {
+    std::array<ByteTarget, 32> d;
+    for (int j = 0; j < 32; j++) {
+        // the pieces that wait for the chain get a tree of their own, one XOR away from the result
+        ByteTarget late = xor_tree(b, xor_lut, acc.late[j]);
+        if (acc.early[j].empty()) {
+            d[j] = late;
+            continue;
+        }
+        ByteTarget early = xor_tree(b, xor_lut, acc.early[j]);
+        d[j] = acc.late[j].empty() ? early : byte_xor(b, xor_lut, late, early);
+    }
+    ByteTarget r_first = byte_constant(b, 225);
+    std::array<std::vector<ByteTarget>, 17> fold;
+    auto reduce = [&](int k, ByteTarget top) {
+        Target idx = b.mul_const_add(1 << 8, top, r_first);
+        fold[k].push_back(b.add_lookup_from_index(idx, lo_lut));
+        fold[k + 1].push_back(b.add_lookup_from_index(idx, hi_lut));
+    };
+    for (int k = 15; k >= 1; k--) reduce(k, d[16 + k]);
+    fold[16].insert(fold[16].begin(), d[16]);
+    reduce(0, xor_tree(b, xor_lut, fold[16]));
+    BlockTarget z;
+    for (int k = 0; k < 16; k++) {
+        fold[k].insert(fold[k].begin(), d[k]);
+        z[k] = xor_tree(b, xor_lut, fold[k]);
+    }
+    return z;
+}
+inline BlockTarget gf_2_128_mul_tables_target(CircuitBuilder& b, size_t xor_lut, size_t lo_lut, size_t hi_lut, const BlockTarget& x, const BlockTarget& y) {
+    ClmulAccumulator acc;
+    clmul_accumulate(b, lo_lut, hi_lut, x, y, acc.late);
+    return clmul_fold(b, xor_lut, lo_lut, hi_lut, acc);
+}
+// GHASH_h(x).  lanes = 1 is the Horner chain y <- (y ^ x_i) * h.  With lanes = k the powers h^2 .. h^k are computed once and the
+// blocks taken k at a time, y <- (y ^ x_1) h^k ^ x_2 h^(k-1) ^ .. ^ x_k h, all k products in ONE unreduced accumulator with one
+// tree per position and one fold: the chain, which is what bounds witness generation for long inputs, is k times shorter.  A last
+// group of r < k blocks uses h^r .. h.
+inline BlockTarget ghash_tables_target(CircuitBuilder& b, size_t xor_lut, size_t lo_lut, size_t hi_lut, const BlockTarget& h,
+                                       const std::vector<ByteTarget>& x, int lanes) {
+    if (x.size() % 16 != 0) throw std::runtime_error("ghash input must be a multiple of 16 bytes");
+    if (lanes < 1 || lanes > 16) throw std::runtime_error("ghash_tables: lanes must be 1 to 16");
+    const size_t blocks = x.size() / 16;
+    std::vector<BlockTarget> pw(2, h);  // pw[i] = h^i, from the two halves of i
+    for (size_t i = 2; i <= std::min<size_t>((size_t)lanes, blocks); i++)
+        pw.push_back(gf_2_128_mul_tables_target(b, xor_lut, lo_lut, hi_lut, pw[(i + 1) / 2], pw[i / 2]));
+    ByteTarget zb = zero_byte(b);
+    BlockTarget y;
+    y.fill(zb);
+    for (size_t g = 0; g < blocks; g += (size_t)lanes) {
+        const size_t r = std::min<size_t>((size_t)lanes, blocks - g);
+        ClmulAccumulator acc;
+        for (size_t j = 0; j < r; j++) {
+            BlockTarget xj;
+            for (int k = 0; k < 16; k++) xj[k] = x[16 * (g + j) + k];
+            if (j == 0) xj = xor_blocks(b, xor_lut, y, xj);
+            clmul_accumulate(b, lo_lut, hi_lut, xj, pw[r - j], j == 0 ? acc.late : acc.early);
+        }
+        y = clmul_fold(b, xor_lut, lo_lut, hi_lut, acc);
+    }
+    return y;
+}
+
 // AesGcmTarget<NK, 4, NR, L, TAG> (circuit_gcm.rs:24-209)
 struct AesGcmTarget {
     int NK, NR;
@@ -488,8 +620,15 @@ struct AesGcmTarget {
         for (size_t i = 0; i < u; i++) gin.push_back(zb);
         for (int i = 0; i < 8; i++) gin.push_back(byte_constant(b, 0));
         for (int i = 7; i >= 0; i--) gin.push_back(byte_constant(b, (uint8_t)(clen >> (8 * i))));
-        size_t shl = u8_unit_right_shift_lut(b), brl = u8_bitref_lut(b);
-        BlockTarget s = ghash_target(b, xorl, shl, brl, h, gin);
+        BlockTarget s;
+        if (b.ghash_tables()) {
+            // the two clmul tables INSTEAD of the shift and bit tables: a table nobody looks into cannot be built
+            size_t lol = gcm_clmul_lo_lut(b), hil = gcm_clmul_hi_lut(b);
+            s = ghash_tables_target(b, xorl, lol, hil, h, gin, b.ghash_tables());
+        } else {
+            size_t shl = u8_unit_right_shift_lut(b), brl = u8_bitref_lut(b);
+            s = ghash_target(b, xorl, shl, brl, h, gin);
+        }
         std::vector<ByteTarget> sv(s.begin(), s.end());
         auto msb_input = gctr_target(b, NR, xorl, mull, sbox, mix, expanded_key, j0, sv);
         for (size_t i = 0; i < TAG_LEN / 8; i++) b.connect(t.tag[i], msb_input[i]);

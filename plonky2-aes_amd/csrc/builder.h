@@ -273,6 +273,13 @@ class CircuitBuilder {
     // multiply_point (ecgfp5.h) as 320 EcStepGate rows instead of arithmetic gates; off by default
     void set_ec_gate(bool on) { ec_gate_ = on; }
     bool ec_gate() const { return ec_gate_; }
+    // AesGcmTarget's GHASH from carry-less multiply tables (aes_gadgets.h ghash_tables_target) with `lanes` blocks per
+    // reduction, 1 to 16; 0, the default, is the reference's bit-serial circuit
+    void set_ghash_tables(int lanes) {
+        if (lanes < 0 || lanes > 16) throw std::runtime_error("set_ghash_tables: lanes must be 0 (off) or 1 to 16");
+        ghash_tables_ = lanes;
+    }
+    int ghash_tables() const { return ghash_tables_; }
 
     // ---- build (plonky2 CircuitBuilder::build) ----------------------------------------------------
     Circuit build();
@@ -374,6 +381,7 @@ class CircuitBuilder {
 
     Config cfg_;
     bool ec_gate_ = false;
+    int ghash_tables_ = 0;
     u64 num_virtual_ = 0;
     std::vector<GateInstance> gate_instances_;
     std::vector<std::pair<Target, Target>> copy_constraints_;

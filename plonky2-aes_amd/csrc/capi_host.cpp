@@ -176,6 +176,10 @@ int p2_builder_ec_step(p2_builder* b, const p2_target acc[20], const p2_target q
         std::copy(st.out.begin(), st.out.end(), out);
     });
 }
+int p2_builder_set_ghash_tables(p2_builder* b, int lanes) {
+    if (!b) return set_error("p2_builder_set_ghash_tables: null builder"), P2_ERR_INVALID;
+    return guarded([&] { b->b.set_ghash_tables(lanes); });
+}
 size_t p2_builder_num_gates(const p2_builder* b) { return guarded_sz([&]() -> size_t { return b->b.num_gates(); }); }
 int p2_builder_build(p2_builder* b, uint8_t** blob, size_t* len) {
     try {
@@ -220,6 +224,8 @@ size_t p2_aes_byte_xor_lut(p2_builder* b) { return guarded_sz([&]() -> size_t { 
 size_t p2_aes_gf_2_8_mul_lut(p2_builder* b) { return guarded_sz([&]() -> size_t { return aes::gf_2_8_mul_lut(b->b); }); }
 size_t p2_gcm_u8_unit_right_shift_lut(p2_builder* b) { return guarded_sz([&]() -> size_t { return aes::u8_unit_right_shift_lut(b->b); }); }
 size_t p2_gcm_u8_bitref_lut(p2_builder* b) { return guarded_sz([&]() -> size_t { return aes::u8_bitref_lut(b->b); }); }
+size_t p2_gcm_clmul_lo_lut(p2_builder* b) { return guarded_sz([&]() -> size_t { return aes::gcm_clmul_lo_lut(b->b); }); }
+size_t p2_gcm_clmul_hi_lut(p2_builder* b) { return guarded_sz([&]() -> size_t { return aes::gcm_clmul_hi_lut(b->b); }); }
 p2_target p2_aes_add_virtual_byte_target(p2_builder* b, size_t t) {
     try {
         return aes::add_virtual_byte_target(b->b, t);
@@ -287,6 +293,21 @@ int p2_gcm_ghash(p2_builder* b, size_t xl, size_t shl, size_t brl, const p2_targ
     } catch (std::exception& e) {
         return set_error(e.what()), P2_ERR_INVALID;
     }
+}
+int p2_gcm_gf_2_128_mul_tables(p2_builder* b, size_t xl, size_t lol, size_t hil, const p2_target* x, const p2_target* y, p2_target* out) {
+    if (!b || !x || !y || !out) return set_error("p2_gcm_gf_2_128_mul_tables: null argument"), P2_ERR_INVALID;
+    return guarded([&] {
+        auto r = aes::gf_2_128_mul_tables_target(b->b, xl, lol, hil, block_in(x), block_in(y));
+        for (int i = 0; i < 16; i++) out[i] = r[i];
+    });
+}
+int p2_gcm_ghash_tables(p2_builder* b, size_t xl, size_t lol, size_t hil, const p2_target* h, const p2_target* x, size_t len, p2_target* out, int lanes) {
+    if (!b || !h || (len && !x) || !out) return set_error("p2_gcm_ghash_tables: null argument"), P2_ERR_INVALID;
+    return guarded([&] {
+        std::vector<aes::ByteTarget> xv(x, x + len);
+        auto r = aes::ghash_tables_target(b->b, xl, lol, hil, block_in(h), xv, lanes);
+        for (int i = 0; i < 16; i++) out[i] = r[i];
+    });
 }
 int p2_aes_gcm_build(p2_builder* b, int nk, int nr, size_t L, int with_tag, p2_target* key, p2_target* nonce, p2_target* pt, p2_target* ct, p2_target* tag) {
     if (!((nk == 4 && nr == 10) || (nk == 6 && nr == 12) || (nk == 8 && nr == 14))) return set_error("unsupported (NK, NR)"), P2_ERR_INVALID;
