@@ -318,6 +318,16 @@ int p2_witness_schedule_check(const uint8_t* blob, size_t len, uint32_t fuse, ui
 /* verifier_data = constants_sigmas_cap (16 digests) || circuit_digest, 68 u64 -- from p2_circuit_verifier_data */
 int p2_verify(const uint8_t* blob, size_t blob_len, const uint64_t* verifier_data, size_t verifier_data_len,
               const uint8_t* proof, size_t proof_len);
+/* Test hook: the vanishing identity at zeta, the check p2_verify makes after the proof-of-work test, on openings and
+ * challenges the caller supplies.  openings: a buffer of the circuit's proof size of which only the opening set is read;
+ * challenges: betas[2] gammas[2] deltas[8] alphas[2] zeta[2] (the deltas are ignored without lookup tables); pi_hash: the
+ * public-inputs hash (taken as zero for a circuit without public inputs).  No transcript, proof-of-work response, Merkle path
+ * or FRI check is involved.  terms <- the flat term list, *n_terms extension elements of two words (cap: room in elements);
+ * sides[4 i ..] <- for challenge i the sum of term_k alpha_i^k and Z_H(zeta) t_i(zeta), two words each; *verdict <- P2_VERIFY_OK,
+ * P2_VERIFY_VANISHING, or P2_VERIFY_ZETA_IN_SUBGROUP (then *n_terms = 0 and the sides are zero).  P2_ERR_INVALID for a word
+ * that is not below p.  tests/vanishing_ref.py restates what it computes. */
+int p2_vanishing_terms(const uint8_t* blob, size_t blob_len, const uint8_t* openings, size_t len, const uint64_t challenges[16],
+                       const uint64_t pi_hash[4], uint64_t* terms, size_t cap, size_t* n_terms, uint64_t sides[8], int* verdict);
 /* Compressed proofs: ProofWithPublicInputs::compress, CompressedProofWithPublicInputs::decompress and
  * CircuitData::verify_compressed, on the host.  Same argument conventions as p2_verify; a compressed proof is never longer
  * than the full one (p2_blob_info's proof_bytes), so cap = proof_bytes always suffices.  *n_written receives the output's
@@ -477,6 +487,13 @@ int p2_verify_batch(p2_circuit*, size_t batch, const uint8_t* proofs, const uint
  * verify_batch_device on one stream needs no host round trip.  Asynchronous: synchronise `stream` before reading d_status. */
 int p2_verify_batch_device(p2_circuit*, size_t batch, const uint8_t* d_proofs, const uint64_t* verifier_data, size_t vd_len,
                            int* d_status, void* stream);
+/* Test hook: p2_vanishing_terms' verdict from the device verifier.  buffers [batch][proof size], challenges [batch][16] and
+ * pi_hashes [batch][4] as p2_vanishing_terms takes them, all in host memory.  Per chunk it unpacks the buffers, puts the
+ * caller's challenges and hashes where the transcript kernel would, and launches the vanishing kernel verify_batch launches
+ * for the circuit; flags[i] <- 8 if zeta is in the subgroup (the kernel goes on and may add 16), 16 if the identity fails, 0 if
+ * it holds.  Workspaces, chunks and thread safety are p2_verify_batch's. */
+int p2_gpu_vanishing_flags(p2_circuit*, size_t batch, const uint8_t* buffers, const uint64_t* challenges, const uint64_t* pi_hashes,
+                           uint32_t* flags);
 /* Compressed proofs in GPU batches (the conversions of p2_proof_compress / p2_proof_decompress / p2_verify_compressed; layout
  * and verdict order in DESIGN.md section 8).  Compressed proofs sit at a stride of p2_circuit_proof_bytes() (a compressed
  * proof is never longer than the full one) with lengths[i] their actual lengths; the bytes of a slot past its length are

@@ -249,6 +249,8 @@ def lib():
         "p2_blob_info": (C.c_int, [C.c_char_p, sz, C.POINTER(_Info)]),
         "p2_witness_schedule_check": (C.c_int, [C.c_char_p, sz, C.c_uint32, u32p]),
         "p2_verify": (C.c_int, [C.c_char_p, sz, u64p, sz, C.c_char_p, sz]),
+        "p2_vanishing_terms": (C.c_int, [C.c_char_p, sz, C.c_char_p, sz, u64p, u64p, u64p, sz, C.POINTER(sz), u64p, C.POINTER(C.c_int)]),
+        "p2_gpu_vanishing_flags": (C.c_int, [vp, sz, C.c_char_p, u64p, u64p, u32p]),
         "p2_proof_compress": (C.c_int, [C.c_char_p, sz, u64p, sz, C.c_char_p, sz, C.c_char_p, sz, C.POINTER(sz)]),
         "p2_proof_decompress": (C.c_int, [C.c_char_p, sz, u64p, sz, C.c_char_p, sz, C.c_char_p, sz, C.POINTER(sz)]),
         "p2_verify_compressed": (C.c_int, [C.c_char_p, sz, u64p, sz, C.c_char_p, sz]),

@@ -923,6 +923,54 @@ int p2_verify(const uint8_t* blob, size_t blob_len, const uint64_t* vd, size_t v
         return set_error(e.what()), P2_ERR_INVALID;
     }
 }
+// eval_vanishing (verifier.h) on openings and challenges the caller supplies; see include/p2aes.h.
+int p2_vanishing_terms(const uint8_t* blob, size_t blob_len, const uint8_t* openings, size_t len, const uint64_t challenges[16],
+                       const uint64_t pi_hash[4], uint64_t* terms, size_t cap, size_t* n_terms, uint64_t* sides, int* verdict) {
+    try {
+        if (!openings || !challenges || !pi_hash || !n_terms || !sides || !verdict || (cap && !terms))
+            return set_error("p2_vanishing_terms: null argument"), P2_ERR_INVALID;
+        Circuit c = deserialize(blob, blob_len);
+        const ProofLayout L = make_proof_layout(c);
+        const size_t NC = c.cfg.num_challenges;
+        if (len != L.bytes) return set_error("p2_vanishing_terms: the buffer must have the size of a proof of the circuit"), P2_ERR_INVALID;
+        if (NC != 2) return set_error("p2_vanishing_terms: num_challenges != 2"), P2_ERR_INVALID;
+        ParsedProof pp;
+        std::vector<gl::E2>* groups[OG_GROUPS];
+        groups[OG_CONSTANTS] = &pp.o_constants, groups[OG_SIGMAS] = &pp.o_sigmas, groups[OG_WIRES] = &pp.o_wires, groups[OG_ZS] = &pp.o_zs;
+        groups[OG_ZS_NEXT] = &pp.o_zs_next, groups[OG_LOOKUP_ZS] = &pp.o_lk, groups[OG_LOOKUP_ZS_NEXT] = &pp.o_lk_next;
+        groups[OG_PARTIAL_PRODUCTS] = &pp.o_pp, groups[OG_QUOTIENT] = &pp.o_quot;
+        bool canonical = true;
+        for (u32 g = 0; g < OG_GROUPS; g++)
+            for (size_t i = 0; i < L.open[g].len; i++) {
+                u64 w[2];
+                memcpy(w, openings + L.open[g].off + 16 * i, 16);
+                canonical = canonical && w[0] < gl::P && w[1] < gl::P;
+                groups[g]->push_back(gl::e2(w[0], w[1]));
+            }
+        for (int i = 0; i < 16; i++) canonical = canonical && challenges[i] < gl::P;
+        for (int i = 0; i < 4; i++) canonical = canonical && pi_hash[i] < gl::P;
+        if (!canonical) return set_error("p2_vanishing_terms: non-canonical field element"), P2_ERR_INVALID;
+        Transcript T;
+        T.betas.assign(challenges, challenges + 2);
+        T.gammas.assign(challenges + 2, challenges + 4);
+        T.deltas.assign(challenges + 4, challenges + 12);
+        T.alphas.assign(challenges + 12, challenges + 14);
+        T.zeta = gl::e2(challenges[14], challenges[15]);
+        for (int i = 0; i < 4; i++) T.pi_hash.e[i] = c.pi_slots.empty() ? 0 : pi_hash[i];
+        VanishingEval ev;
+        const std::string reason = eval_vanishing(c, pp, T, &ev);
+        *n_terms = ev.terms.size();
+        memset(sides, 0, 8 * sizeof(uint64_t));
+        if (reason == "Opening point is in the subgroup.") return *verdict = P2_VERIFY_ZETA_IN_SUBGROUP, P2_OK;
+        if (ev.terms.size() > cap) return set_error("p2_vanishing_terms: " + std::to_string(ev.terms.size()) + " terms, room for fewer"), P2_ERR_INVALID;
+        for (size_t k = 0; k < ev.terms.size(); k++) terms[2 * k] = ev.terms[k].a, terms[2 * k + 1] = ev.terms[k].b;
+        for (size_t i = 0; i < NC; i++) sides[4 * i] = ev.lhs[i].a, sides[4 * i + 1] = ev.lhs[i].b, sides[4 * i + 2] = ev.rhs[i].a, sides[4 * i + 3] = ev.rhs[i].b;
+        *verdict = reason.empty() ? P2_VERIFY_OK : P2_VERIFY_VANISHING;
+        return P2_OK;
+    } catch (std::exception& e) {
+        return set_error(e.what()), P2_ERR_INVALID;
+    }
+}
 int p2_proof_compress(const uint8_t* blob, size_t blob_len, const uint64_t* vd, size_t vd_len, const uint8_t* proof, size_t proof_len, uint8_t* out,
                       size_t cap, size_t* n_written) {
     return convert_proof(blob, blob_len, vd, vd_len, proof, proof_len, out, cap, n_written,

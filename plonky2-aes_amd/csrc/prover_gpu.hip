@@ -1614,6 +1614,63 @@ static int proof_batch_impl(p2_circuit* C, ProofOp op, size_t batch, const uint8
     return rc;
 }
 
+// p2_gpu_vanishing_flags: the vanishing kernel of OP_VERIFY on the caller's openings, challenges and public-input hashes.  Per
+// chunk: k_vfy_unpack, the challenge rows and hashes copied to where k_vfy_transcript leaves them (the rest of a row zero: the
+// opening reductions of the kernel's second wave read fri_alpha and write vq, which nothing here reads), the kernel, the flags.
+static int vanishing_flags_run(p2_circuit* C, VerifyWs* W, size_t batch, const uint8_t* buffers, const uint64_t* challenges, const uint64_t* pi_hashes,
+                               uint32_t* flags) {
+    const size_t pb = C->layout.bytes;
+    hipStream_t st = W->stream;
+    HIPCHECK(hipStreamWaitEvent(st, W->done, 0));  // the workspace's previous user
+    std::vector<u64> rows;
+    for (size_t done = 0; done < batch; done += W->chunk) {
+        const u32 B = (u32)std::min(W->chunk, batch - done);
+        VerifyArgs v = C->vfy_args;
+        v.batch = B;
+        v.words = W->d_words;
+        v.flags = W->d_flags;
+        v.qfail = W->d_qfail;
+        v.chal = W->d_chal;
+        v.vq = W->d_vq;
+        v.vd = W->d_vd;
+        v.pi_hash = W->d_pi_hash;
+        v.status = W->d_status;
+        v.proofs = W->d_proofs;
+        rows.assign((size_t)B * CH_WORDS, 0);
+        for (u32 p = 0; p < B; p++) memcpy(&rows[(size_t)p * CH_WORDS], challenges + (done + p) * 16, 16 * sizeof(u64));  // CH_BETAS .. CH_ZETA
+        HIPCHECK(hipMemcpyAsync(W->d_proofs, buffers + done * pb, B * pb, hipMemcpyHostToDevice, st));
+        HIPCHECK(hipMemcpyAsync(W->d_chal, rows.data(), rows.size() * sizeof(u64), hipMemcpyHostToDevice, st));
+        HIPCHECK(hipMemcpyAsync(W->d_pi_hash, pi_hashes + done * 4, (size_t)B * 4 * sizeof(u64), hipMemcpyHostToDevice, st));
+        HIPCHECK(hipMemsetAsync(W->d_flags, 0, (size_t)B * 4, st));
+        LAUNCH_ON(st, k_vfy_unpack, dim3((v.W + 255) / 256, B), dim3(256), v);
+        if (ecstep_gate_index(C->c) >= 0) LAUNCH_ON(st, k_vfy_ecvanishing, dim3(B), dim3(256), v);
+        else LAUNCH_ON(st, k_vfy_vanishing, dim3(B), dim3(256), v);
+        HIPCHECK(hipMemcpyAsync(flags + done, W->d_flags, (size_t)B * 4, hipMemcpyDeviceToHost, st));
+        HIPCHECK(hipStreamSynchronize(st));  // `rows` is refilled by the next chunk
+        for (u32 p = 0; p < B; p++) flags[done + p] &= (u32)(VF_ZETA | VF_VANISH);
+    }
+    HIPCHECK(hipEventRecord(W->done, st));
+    return P2_OK;
+}
+static int vanishing_flags_impl(p2_circuit* C, size_t batch, const uint8_t* buffers, const uint64_t* challenges, const uint64_t* pi_hashes, uint32_t* flags) {
+    if (!C) return set_error("p2_gpu_vanishing_flags: null circuit handle"), P2_ERR_INVALID;
+    if (!C->vfy_error.empty()) return set_error(C->vfy_error), P2_ERR_INVALID;
+    if (batch == 0) return P2_OK;
+    if (!buffers || !challenges || !pi_hashes || !flags) return set_error("p2_gpu_vanishing_flags: null buffer"), P2_ERR_INVALID;
+    static_assert(CH_BETAS == 0 && CH_GAMMAS == 2 && CH_DELTAS == 4 && CH_ALPHAS == 12 && CH_ZETA == 14, "the caller's 16 words are the head of a challenge row");
+    for (size_t i = 0; i < batch * 16; i++)
+        if (challenges[i] >= gl::P) return set_error("p2_gpu_vanishing_flags: non-canonical challenge"), P2_ERR_INVALID;
+    for (size_t i = 0; i < batch * 4; i++)
+        if (pi_hashes[i] >= gl::P) return set_error("p2_gpu_vanishing_flags: non-canonical public-inputs hash"), P2_ERR_INVALID;
+    HIPCHECK(hipSetDevice(C->device));
+    VerifyWs* W = verify_lease(C);
+    if (!W) return P2_ERR_HIP;
+    const int rc = vanishing_flags_run(C, W, batch, buffers, challenges, pi_hashes, flags);
+    if (rc != P2_OK) (void)hipStreamSynchronize(W->stream);  // what was enqueued before the failure may still use the workspace
+    verify_return(C, W);
+    return rc;
+}
+
 // ---------------------------------------------------------------------------------- witness-only runs, fault diagnosis
 // (kernels_witness_io.h)  A lean workspace, leased per call like the verification ones: per witness the slot values, the
 // multiplicity counters and the PoseidonGate advice block that k_witness writes -- megabytes where a proving workspace holds
@@ -2989,6 +3046,9 @@ int p2_verify_batch(p2_circuit* C, size_t batch, const uint8_t* proofs, const ui
 }
 int p2_verify_batch_device(p2_circuit* C, size_t batch, const uint8_t* d_proofs, const uint64_t* verifier_data, size_t vd_len, int* d_status, void* stream) {
     return guarded_rc([&] { return proof_batch_impl(C, OP_VERIFY, batch, d_proofs, nullptr, verifier_data, vd_len, nullptr, nullptr, d_status, (hipStream_t)stream, false); });
+}
+int p2_gpu_vanishing_flags(p2_circuit* C, size_t batch, const uint8_t* buffers, const uint64_t* challenges, const uint64_t* pi_hashes, uint32_t* flags) {
+    return guarded_rc([&] { return vanishing_flags_impl(C, batch, buffers, challenges, pi_hashes, flags); });
 }
 int p2_compress_batch(p2_circuit* C, size_t batch, const uint8_t* proofs, const uint64_t* vd, size_t vd_len, uint8_t* out, uint32_t* lengths, int* status) {
     return guarded_rc([&] { return proof_batch_impl(C, OP_COMPRESS, batch, proofs, nullptr, vd, vd_len, out, lengths, status, nullptr, true); });

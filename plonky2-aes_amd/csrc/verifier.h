@@ -386,26 +386,24 @@ inline gl::E2 fri_compute_evaluation(const std::vector<gl::E2>& evals, size_t x_
     return acc;
 }
 
-// The checks after the transcript: the vanishing identity at zeta, then FRI.
-inline std::string verify_parsed(const Circuit& C, const VerifierData& vd, const ParsedProof& pp, const Transcript& T) {
+// What eval_vanishing shows of the identity besides its verdict: the flat term list and, per challenge, the two sides
+// sum_k term_k alpha^k and Z_H(zeta) t(zeta) (p2_vanishing_terms).
+struct VanishingEval {
+    std::vector<gl::E2> terms, lhs, rhs;
+};
+// The vanishing identity at zeta (eval_vanishing_poly) on the opening set of pp and the challenges and public-inputs hash of
+// T: "" when it holds, else the reason.  `out`, when given, receives the terms and both sides (nothing if zeta is in the subgroup).
+inline std::string eval_vanishing(const Circuit& C, const ParsedProof& pp, const Transcript& T, VanishingEval* out = nullptr) {
     using namespace gl;
     const size_t NC = C.cfg.num_challenges, R = C.cfg.num_routed_wires, npp = C.num_partial_products(), nlp = C.num_lookup_polys();
     const size_t nsldc = C.num_sldc_polys(), qdf = C.cfg.quotient_degree_factor;
     const size_t nsel = C.num_selectors(), nls = C.num_lookup_selectors;
-    const size_t n = C.n(), lde_bits = C.degree_bits + C.cfg.rate_bits;
-    const std::vector<u32> arities = C.reduction_arity_bits();
-    const auto &wires_cap = pp.wires_cap, &zs_cap = pp.zs_cap, &quot_cap = pp.quot_cap;
+    const size_t n = C.n();
     const auto &o_constants = pp.o_constants, &o_sigmas = pp.o_sigmas, &o_wires = pp.o_wires, &o_zs = pp.o_zs, &o_zs_next = pp.o_zs_next;
     const auto &o_lk = pp.o_lk, &o_lk_next = pp.o_lk_next, &o_pp = pp.o_pp, &o_quot = pp.o_quot;
-    const auto& fri_caps = pp.fri_caps;
-    const auto& queries = pp.queries;
-    const auto& final_poly = pp.final_poly;
     const auto &betas = T.betas, &gammas = T.gammas, &deltas = T.deltas, &alphas = T.alphas;
-    const auto &batch0 = T.batch0, &batch1 = T.batch1, &fri_betas = T.fri_betas;
-    const auto& query_idx = T.query_idx;
-    const E2 zeta = T.zeta, fri_alpha = T.fri_alpha;
+    const E2 zeta = T.zeta;
     const Hash4 pi_hash = T.pi_hash;
-    // ---- vanishing polynomial at zeta (eval_vanishing_poly)
     E2 zeta_pow_n = exp_pow2(zeta, (int)C.degree_bits);
     E2 z_h_zeta = sub(zeta_pow_n, e2(1));
     if (eq(zeta_pow_n, e2(1))) return "Opening point is in the subgroup.";
@@ -505,13 +503,34 @@ inline std::string verify_parsed(const Circuit& C, const VerifierData& vd, const
         }
         for (auto* v : {&z1, &ppt, &lkt, &gate}) terms.insert(terms.end(), v->begin(), v->end());
     }
+    bool holds = true;
     for (size_t i = 0; i < NC; i++) {
         E2 vanishing = e2(0);
         for (size_t k = terms.size(); k-- > 0;) vanishing = add(mul(vanishing, alphas[i]), terms[k]);
         E2 t = e2(0);
         for (size_t c = qdf; c-- > 0;) t = add(mul(t, zeta_pow_n), o_quot[i * qdf + c]);
-        if (!eq(vanishing, mul(z_h_zeta, t))) return "vanishing polynomial identity does not hold at zeta";
+        holds = holds && eq(vanishing, mul(z_h_zeta, t));
+        if (out) out->lhs.push_back(vanishing), out->rhs.push_back(mul(z_h_zeta, t));
     }
+    if (out) out->terms = terms;
+    if (!holds) return "vanishing polynomial identity does not hold at zeta";
+    return "";
+}
+
+// The checks after the transcript: the vanishing identity at zeta, then FRI.
+inline std::string verify_parsed(const Circuit& C, const VerifierData& vd, const ParsedProof& pp, const Transcript& T) {
+    using namespace gl;
+    const size_t lde_bits = C.degree_bits + C.cfg.rate_bits;
+    const std::vector<u32> arities = C.reduction_arity_bits();
+    const auto &wires_cap = pp.wires_cap, &zs_cap = pp.zs_cap, &quot_cap = pp.quot_cap;
+    const auto& fri_caps = pp.fri_caps;
+    const auto& queries = pp.queries;
+    const auto& final_poly = pp.final_poly;
+    const auto &batch0 = T.batch0, &batch1 = T.batch1, &fri_betas = T.fri_betas;
+    const auto& query_idx = T.query_idx;
+    const E2 zeta = T.zeta, fri_alpha = T.fri_alpha;
+    const std::string vanishing = eval_vanishing(C, pp, T);
+    if (!vanishing.empty()) return vanishing;
 
     // ---- FRI (fri/verifier.rs)
     E2 g_zeta = mul(zeta, root_of_unity((int)C.degree_bits));

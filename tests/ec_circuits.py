@@ -1,5 +1,6 @@
-"""EcStepGate: a plain-Python restatement of its 40 constraint polynomials over the affine oracle's field helpers
-(oracle/oracle_ecgfp5.py: f_mul, f_add, f_sub), the rows and vectors the tests share, and the circuits built with the gate.
+"""EcStepGate: a plain-Python restatement of its 40 constraint polynomials, generic over the field the wires live in (Quintic;
+BASE agrees with the affine oracle's helpers, oracle/oracle_ecgfp5.py: f_mul, f_add, f_sub), the rows and vectors the tests
+share, and the circuits built with the gate.
 
 Wire layout of a row (csrc/circuit.h EG_*): acc X|Z|U|T (0..19), Q x|u (20..29), bit (30), mid (31..50), out (51..70)."""
 import os
@@ -14,47 +15,80 @@ B1 = 263
 ACC, Q, BIT, MID, OUT, WIRES = 0, 20, 30, 31, 51, 71
 
 
+class Quintic:
+    """GF(q)[z]/(z^5 - 3) over a base field given by its add, sub and mul and the embedding of a small integer: what the gate's
+    formulas need, so that they read the same over GF(p) (BASE) and over GF(p^2) (tests/vanishing_ref.py)."""
+
+    def __init__(self, add, sub, mul, const):
+        self.add, self.sub, self.mul, self.const = add, sub, mul, const
+
+    def f_add(self, a, b):
+        return tuple(self.add(x, y) for x, y in zip(a, b))
+
+    def f_sub(self, a, b):
+        return tuple(self.sub(x, y) for x, y in zip(a, b))
+
+    def f_mul(self, a, b):
+        c = [self.const(0)] * 9
+        for i in range(5):
+            for j in range(5):
+                c[i + j] = self.add(c[i + j], self.mul(a[i], b[j]))
+        three = self.const(3)
+        return tuple(self.add(c[k], self.mul(three, c[k + 5])) if k + 5 < 9 else c[k] for k in range(5))
+
+    def f_small(self, a, k):
+        return tuple(self.mul(x, self.const(k)) for x in a)
+
+    def mul_bz(self, a, k=B1):
+        """a * (k z)"""
+        return (self.mul(a[4], self.const(3 * k)),) + tuple(self.mul(a[i], self.const(k)) for i in range(4))
+
+
+BASE = Quintic(lambda x, y: (x + y) % P, lambda x, y: (x - y) % P, lambda x, y: x * y % P, lambda k: k % P)
+
+
 def mul_bz(a, k=B1):
     """a * (k z) in GF(p)[z]/(z^5 - 3)"""
-    return (3 * k * a[4] % P,) + tuple(k * a[i] % P for i in range(4))
+    return BASE.mul_bz(a, k)
 
 
-def _tail(t1, t2, t3, t4, t5, t6):
-    t7 = ec.f_add(mul_bz(t2), t1)
-    t8 = ec.f_mul(t4, t7)
-    w9 = ec.f_add(mul_bz(t5, 2 * B1), ec.f_small(t7, 2))
-    z = ec.f_sub(t8, ec.f_mul(t3, w9))
-    t = ec.f_sub(ec.f_small(t8, 2), z)
-    d = ec.f_sub(ec.f_mul(ec.f_add(ec.f_small(t3, 2), t4), ec.f_add(t5, t7)), t8)
-    return mul_bz(d), z, ec.f_mul(t6, ec.f_sub(mul_bz(t2), t1)), t
+def _tail(F, t1, t2, t3, t4, t5, t6):
+    t7 = F.f_add(F.mul_bz(t2), t1)
+    t8 = F.f_mul(t4, t7)
+    w9 = F.f_add(F.mul_bz(t5, 2 * B1), F.f_small(t7, 2))
+    z = F.f_sub(t8, F.f_mul(t3, w9))
+    t = F.f_sub(F.f_small(t8, 2), z)
+    d = F.f_sub(F.f_mul(F.f_add(F.f_small(t3, 2), t4), F.f_add(t5, t7)), t8)
+    return F.mul_bz(d), z, F.f_mul(t6, F.f_sub(F.mul_bz(t2), t1)), t
 
 
-def double(p):
+def double(p, F=BASE):
     """2 p for p = (X, Z, U, T): the unified addition of ecgfp5.h with both operands equal"""
     X, Z, U, T = p
-    return _tail(ec.f_mul(X, X), ec.f_mul(Z, Z), ec.f_mul(U, U), ec.f_mul(T, T), ec.f_small(ec.f_mul(X, Z), 2), ec.f_small(ec.f_mul(U, T), 2))
+    return _tail(F, F.f_mul(X, X), F.f_mul(Z, Z), F.f_mul(U, U), F.f_mul(T, T), F.f_small(F.f_mul(X, Z), 2), F.f_small(F.f_mul(U, T), 2))
 
 
-def add_mixed(p, qx, qu):
+def add_mixed(p, qx, qu, F=BASE):
     """p + (qx, qu), the second operand affine (Z2 = T2 = 1)"""
     X, Z, U, T = p
-    return _tail(ec.f_mul(X, qx), Z, ec.f_mul(U, qu), T, ec.f_add(ec.f_mul(Z, qx), X), ec.f_add(ec.f_mul(T, qu), U))
+    return _tail(F, F.f_mul(X, qx), Z, F.f_mul(U, qu), T, F.f_add(F.f_mul(Z, qx), X), F.f_add(F.f_mul(T, qu), U))
 
 
 def _point(w, first):
     return tuple(tuple(w[first + 5 * j + i] for i in range(5)) for j in range(4))
 
 
-def constraints(w):
-    """The 40 constraint values of one row of (at least 71) wires: 0..19 mid - 2 acc, 20..39 out - (mid + bit Q)."""
+def constraints(w, F=BASE):
+    """The 40 constraint values of one row of (at least 71) wires: 0..19 mid - 2 acc, 20..39 out - (mid + bit Q).  Over GF(p)
+    unless F names another base field for the wires."""
     acc, mid, out = _point(w, ACC), _point(w, MID), _point(w, OUT)
     bit = w[BIT]
-    qx = tuple(bit * v % P for v in w[Q:Q + 5])
-    qu = tuple(bit * v % P for v in w[Q + 5:Q + 10])
+    qx = tuple(F.mul(bit, v) for v in w[Q:Q + 5])
+    qu = tuple(F.mul(bit, v) for v in w[Q + 5:Q + 10])
     res = []
-    for have, want in ((mid, double(acc)), (out, add_mixed(mid, qx, qu))):
+    for have, want in ((mid, double(acc, F)), (out, add_mixed(mid, qx, qu, F))):
         for h, x in zip(have, want):
-            res.extend(ec.f_sub(h, x))
+            res.extend(F.f_sub(h, x))
     return res
 
 

@@ -7,8 +7,9 @@ in as a pair of functions (hash_no_pad(words [..., n]) -> [..., 4], two_to_one(l
 
 What the replay restates: the transcript (challenges, proof-of-work response, query indices), every Merkle path against its
 cap, canonical encoding, the reduced composition value of each query from the opened leaves and the opening set, every
-arity-16 fold and the final polynomial.  **What it does not restate: the vanishing identity at zeta** (the gate, permutation
-and lookup constraints evaluated on the opening set) -- the one check of the verifier that is left to csrc/verifier.h.
+arity-16 fold and the final polynomial.  The vanishing identity at zeta (the gate, permutation and lookup constraints evaluated
+on the opening set) is restated in tests/vanishing_ref.py, which needs the circuit's blob: `replay(..., blob=...)` runs it
+between the proof-of-work test and the Merkle checks, the host verifier's order; without a blob the replay leaves it out.
 
 Every check returns None when it holds and otherwise a string naming the first thing that failed (section, query, round)."""
 import ctypes as C
@@ -351,14 +352,20 @@ def check_fri(info, proof, challenges, indices):
     return None
 
 
-def replay(info, verifier_data, proof, hasher):
-    """All of it on the proof alone (public-inputs hash from the trailer): None, or the first failure."""
+def replay(info, verifier_data, proof, hasher, blob=None):
+    """All of it on the proof alone (public-inputs hash from the trailer): None, or the first failure.  With the circuit's
+    blob also the vanishing identity at zeta (vanishing_ref.check_vanishing)."""
     bad = check_canonical(info, proof)
     if bad:
         return bad
     t = replay_transcript(info, verifier_data, proof, hash_public_inputs(trailer_values(info, proof)))
     if not t["pow_ok"]:
         return "pow_witness: the response %#x has fewer than %d leading zeros" % (t["pow_response"], POW_BITS)
+    if blob is not None:
+        import vanishing_ref   # it imports this module
+        bad = vanishing_ref.check_vanishing(info, blob, proof, t)
+        if bad:
+            return bad
     return check_merkle(info, verifier_data, proof, t["query_indices"], hasher) or check_fri(info, proof, t, t["query_indices"])
 
 

@@ -145,12 +145,13 @@ def test_elgamal_proof_replays(gpu, elgamal, monkeypatch):
     monkeypatch.setattr(replay, "_build", lambda pkg_view, name: (gpu.CircuitData(data.blob), maps))
     p = replay.Proven(gpu, gpu, "poseidon", "elgamal_ecstep")
     assert p.proof == proofs[2]
-    assert R.replay(p.info, p.vd, p.proof, R.memoised(p.hasher)) is None
+    assert R.replay(p.info, p.vd, p.proof, R.memoised(p.hasher), blob=data.blob) is None
     replay.test_transcript(p)
     replay.test_caps_and_merkle_paths(p)
     replay.test_wires_leaves(p)
     replay.test_openings(p)
     replay.test_fri(p)
+    replay.test_vanishing_identity(p)
 
 
 @pytest.mark.parametrize("kw", ({"hasher": "keccak"}, {"zero_knowledge": True}), ids=("keccak", "zk"))

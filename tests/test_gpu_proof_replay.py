@@ -1,8 +1,8 @@
 """Keccak and public-input proofs held to the independent proof replay of tests/proof_ref.py.  The CPU oracle hashes with
 Poseidon and hard-codes the public-inputs hash 0^4, so it cannot follow these proofs past the wires commitment; the replay
 (pinned on the oracle's own proofs by tests/test_proof_ref_host.py) can: transcript, caps, Merkle paths, opened leaves,
-openings and FRI of the last proof of a batch of three are compared with it exactly.  The vanishing identity at zeta is the
-one stage it does not restate; that one stays with the two verifiers."""
+openings and FRI of the last proof of a batch of three are compared with it exactly, and the vanishing identity at zeta holds
+as tests/vanishing_ref.py restates it."""
 import ctypes as C
 
 import numpy as np
@@ -12,6 +12,7 @@ import circuits
 import keccak_circuits
 import oracle_lib
 import proof_ref as R
+import vanishing_ref
 
 pytestmark = pytest.mark.gpu
 
@@ -218,13 +219,21 @@ def test_fri(proven):
         assert R.words(p.proof, p.S, "final_poly") == [int(w) for w in p.fri_in.T.reshape(-1)]
 
 
+# ---------------------------------------------------------------------------------------------- vanishing identity
+def test_vanishing_identity(proven):
+    """k_quotient (k_ecstep_post) and the openings: the quotient the device committed to satisfies the identity as
+    tests/vanishing_ref.py restates it, under the replayed challenges -- not only as the product's verifiers evaluate it."""
+    p = proven
+    assert vanishing_ref.check_vanishing(p.info, p.data.blob, p.proof, p.t) is None
+
+
 # ---------------------------------------------------------------------------------------------- both verifiers
 def test_tampers_replay_host_and_gpu(gpu, kpkg):
     """The teeth list of the host tests on one Keccak proof (n = 2^13), one batch through verify_batch and one host call per
     case: the GPU verdict equals the host's, and neither accepts what the replay rejects."""
     p = _proven(gpu, kpkg, ("keccak", "aes_gcm_13"))
     hasher = R.memoised(p.hasher)
-    assert R.replay(p.info, p.vd, p.proof, hasher) is None
+    assert R.replay(p.info, p.vd, p.proof, hasher, blob=p.data.blob) is None
     cases = R.tamper_cases(p.info, p.proof)
     assert len(cases) == 3 + 9 + 2 + 2 + 3 * (12 + 3 * 2)
     got = p.data.verify_batch([c[1] for c in cases] + [p.proof])

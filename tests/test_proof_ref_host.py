@@ -62,7 +62,7 @@ def test_replay_reproduces_the_oracle_trace(pkg, orc, name):
     hasher = proof_ref.poseidon_hasher()
     assert proof_ref.check_merkle(info, vd, proof, t["query_indices"], hasher) is None
     assert proof_ref.check_fri(info, proof, t, t["query_indices"]) is None
-    assert proof_ref.replay(info, vd, proof, hasher) is None
+    assert proof_ref.replay(info, vd, proof, hasher, blob=blob) is None
     assert host_reason(pkg, blob, vd, proof) == ""
     # the other tree hasher does not fit these trees
     assert "Merkle path" in proof_ref.check_merkle(info, vd, proof, t["query_indices"], proof_ref.keccak_hasher())
