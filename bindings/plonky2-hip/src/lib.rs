@@ -83,11 +83,68 @@ pub mod hash {
     pub mod hash_types {
         pub trait RichField: crate::field::types::Field64 {}
         impl RichField for crate::field::goldilocks_field::GoldilocksField {}
+        use crate::iop::target::Target;
+        /// `HashOut<F>`: four field elements.
+        pub type HashOut = [crate::field::goldilocks_field::GoldilocksField; 4];
+        #[derive(Copy, Clone, Debug)]
+        pub struct HashOutTarget { pub elements: [Target; 4] }
+        #[derive(Clone, Debug)]
+        pub struct MerkleCapTarget(pub Vec<HashOutTarget>);
     }
     pub mod poseidon {
         /// Marker for `builder.hash_n_to_m_no_pad::<PoseidonHash>` (poseidon-cipher/src/circuit.rs:123).
         pub struct PoseidonHash;
         pub struct PoseidonPermutation<F>(core::marker::PhantomData<F>);
+    }
+    pub mod merkle_proofs {
+        use super::hash_types::{HashOut, HashOutTarget};
+        use crate::field::goldilocks_field::GoldilocksField as F;
+        #[derive(Clone, Debug)]
+        pub struct MerkleProof { pub siblings: Vec<HashOut> }
+        #[derive(Clone, Debug)]
+        pub struct MerkleProofTarget { pub siblings: Vec<HashOutTarget> }
+        /// `verify_merkle_proof_to_cap::<F, PoseidonHash>` on the host (p2_native_merkle_verify).
+        pub fn verify_merkle_proof_to_cap(leaf_data: &[F], leaf_index: usize, merkle_cap: &[HashOut], proof: &MerkleProof) -> Result<(), String> {
+            let leaf: Vec<u64> = leaf_data.iter().map(|x| x.0).collect();
+            let cap: Vec<u64> = merkle_cap.iter().flat_map(|h| h.iter().map(|x| x.0)).collect();
+            let sib: Vec<u64> = proof.siblings.iter().flat_map(|h| h.iter().map(|x| x.0)).collect();
+            let mut status: std::os::raw::c_int = -1;
+            let rc = unsafe { crate::ffi::p2_native_merkle_verify(leaf.as_ptr(), leaf.len(), leaf_index, sib.as_ptr(), proof.siblings.len(), cap.as_ptr(), merkle_cap.len().trailing_zeros() as std::os::raw::c_int, &mut status) };
+            if rc != crate::ffi::P2_OK { return Err(crate::last_error()); }
+            if status == 0 { Ok(()) } else { Err("Invalid Merkle proof.".into()) }
+        }
+    }
+    pub mod merkle_tree {
+        use super::hash_types::HashOut;
+        use super::merkle_proofs::MerkleProof;
+        use crate::field::goldilocks_field::GoldilocksField as F;
+        /// `MerkleTree::<F, PoseidonHash>::new(leaves, cap_height)`: built and kept on HIP device 0 (p2_merkle_tree_new).
+        pub struct MerkleTree { h: *mut std::os::raw::c_void, depth: usize, pub cap: Vec<HashOut> }
+        impl Drop for MerkleTree {
+            fn drop(&mut self) { unsafe { crate::ffi::p2_merkle_tree_free(self.h) } }
+        }
+        impl MerkleTree {
+            pub fn new(leaves: Vec<Vec<F>>, cap_height: usize) -> Self {
+                let leaf_len = leaves.first().map_or(0, |l| l.len());
+                assert!(leaves.iter().all(|l| l.len() == leaf_len), "leaves of unequal length");
+                let flat: Vec<u64> = leaves.iter().flat_map(|l| l.iter().map(|x| x.0)).collect();
+                let mut h: *mut std::os::raw::c_void = core::ptr::null_mut();
+                let rc = unsafe { crate::ffi::p2_merkle_tree_new(flat.as_ptr(), leaves.len(), leaf_len, cap_height as std::os::raw::c_int, 0, &mut h) };
+                assert!(rc == crate::ffi::P2_OK, "{}", crate::last_error());
+                let mut cap = vec![0u64; 4 << cap_height];
+                let rc = unsafe { crate::ffi::p2_merkle_tree_cap(h, cap.as_mut_ptr(), cap.len()) };
+                assert!(rc == crate::ffi::P2_OK, "{}", crate::last_error());
+                let depth = leaves.len().trailing_zeros() as usize - cap_height;
+                MerkleTree { h, depth, cap: cap.chunks(4).map(|c| core::array::from_fn(|i| F(c[i]))).collect() }
+            }
+            pub fn prove(&self, leaf_index: usize) -> MerkleProof {
+                let idx = [leaf_index as u64];
+                let mut out = vec![0u64; 4 * self.depth.max(1)];
+                let rc = unsafe { crate::ffi::p2_merkle_tree_prove_batch(self.h, idx.as_ptr(), 1, out.as_mut_ptr()) };
+                assert!(rc == crate::ffi::P2_OK, "{}", crate::last_error());
+                MerkleProof { siblings: out[..4 * self.depth].chunks(4).map(|c| core::array::from_fn(|i| F(c[i]))).collect() }
+            }
+        }
     }
     pub mod hashing {
         use crate::field::goldilocks_field::GoldilocksField as F;
@@ -360,6 +417,8 @@ pub mod plonk {
     pub mod circuit_builder {
         use super::circuit_data::{CircuitConfig, CircuitData};
         use crate::field::types::Field;
+        use crate::hash::hash_types::{HashOutTarget, MerkleCapTarget};
+        use crate::hash::merkle_proofs::MerkleProofTarget;
         use crate::iop::target::{BoolTarget, Target};
         use crate::{ffi, last_error};
         use core::marker::PhantomData;
@@ -445,6 +504,55 @@ pub mod plonk {
             pub fn range_check(&mut self, x: Target, n_log: usize) {
                 let rc = unsafe { ffi::p2_builder_range_check(self.h, x.0, n_log) };
                 assert!(rc == ffi::P2_OK, "{}", last_error());
+            }
+            /// `permute_swapped::<PoseidonHash>`: one PoseidonGate row; the first two quarters of `inputs` are exchanged where swap = 1.
+            pub fn permute_swapped(&mut self, inputs: [Target; 12], swap: BoolTarget) -> [Target; 12] {
+                let inp: [u64; 12] = core::array::from_fn(|i| inputs[i].0);
+                let mut out = [0u64; 12];
+                let rc = unsafe { ffi::p2_builder_permute_swapped(self.h, inp.as_ptr(), swap.target.0, out.as_mut_ptr()) };
+                assert!(rc == ffi::P2_OK, "{}", last_error());
+                out.map(Target)
+            }
+            /// `hash_or_noop::<PoseidonHash>`: up to four targets zero-padded as they are, more hashed.
+            pub fn hash_or_noop<H>(&mut self, inputs: Vec<Target>) -> HashOutTarget {
+                let inp: Vec<u64> = inputs.iter().map(|t| t.0).collect();
+                let mut out = [0u64; 4];
+                let rc = unsafe { ffi::p2_builder_hash_or_noop(self.h, inp.as_ptr(), inp.len(), out.as_mut_ptr()) };
+                assert!(rc == ffi::P2_OK, "{}", last_error());
+                HashOutTarget { elements: out.map(Target) }
+            }
+            pub fn add_virtual_hash(&mut self) -> HashOutTarget {
+                let mut out = [0u64; 4];
+                let rc = unsafe { ffi::p2_builder_add_virtual_hash(self.h, out.as_mut_ptr()) };
+                assert!(rc == ffi::P2_OK, "{}", last_error());
+                HashOutTarget { elements: out.map(Target) }
+            }
+            pub fn add_virtual_cap(&mut self, cap_height: usize) -> MerkleCapTarget {
+                assert!(cap_height <= 16, "add_virtual_cap: cap_height must be 0 to 16");
+                let mut out = vec![0u64; 4 << cap_height];
+                let rc = unsafe { ffi::p2_builder_add_virtual_cap(self.h, cap_height as std::os::raw::c_int, out.as_mut_ptr()) };
+                assert!(rc == ffi::P2_OK, "{}", last_error());
+                MerkleCapTarget(out.chunks(4).map(|c| HashOutTarget { elements: core::array::from_fn(|i| Target(c[i])) }).collect())
+            }
+            pub fn connect_hashes(&mut self, x: HashOutTarget, y: HashOutTarget) {
+                let (a, b): ([u64; 4], [u64; 4]) = (x.elements.map(|t| t.0), y.elements.map(|t| t.0));
+                let rc = unsafe { ffi::p2_builder_connect_hashes(self.h, a.as_ptr(), b.as_ptr()) };
+                assert!(rc == ffi::P2_OK, "{}", last_error());
+            }
+            /// `verify_merkle_proof_to_cap::<PoseidonHash>`: leaf_data is the leaf at the index the little-endian bits spell.  The
+            /// cap entry is chosen by a mux tree of `select` (upstream: a RandomAccessGate); the cap-index bits are made boolean here.
+            pub fn verify_merkle_proof_to_cap<H>(&mut self, leaf_data: Vec<Target>, leaf_index_bits: &[BoolTarget], merkle_cap: &MerkleCapTarget, proof: &MerkleProofTarget) {
+                let leaf: Vec<u64> = leaf_data.iter().map(|t| t.0).collect();
+                let bits: Vec<u64> = leaf_index_bits.iter().map(|b| b.target.0).collect();
+                let cap: Vec<u64> = merkle_cap.0.iter().flat_map(|h| h.elements.iter().map(|t| t.0)).collect();
+                let sib: Vec<u64> = proof.siblings.iter().flat_map(|h| h.elements.iter().map(|t| t.0)).collect();
+                let h = merkle_cap.0.len().trailing_zeros() as std::os::raw::c_int;
+                assert!(merkle_cap.0.len().is_power_of_two(), "the cap must hold a power of two of hashes");
+                let rc = unsafe { ffi::p2_builder_verify_merkle_proof_to_cap(self.h, leaf.as_ptr(), leaf.len(), bits.as_ptr(), bits.len(), cap.as_ptr(), h, sib.as_ptr(), proof.siblings.len()) };
+                assert!(rc == ffi::P2_OK, "{}", last_error());
+            }
+            pub fn verify_merkle_proof<H>(&mut self, leaf_data: Vec<Target>, leaf_index_bits: &[BoolTarget], merkle_root: HashOutTarget, proof: &MerkleProofTarget) {
+                self.verify_merkle_proof_to_cap::<H>(leaf_data, leaf_index_bits, &MerkleCapTarget(vec![merkle_root]), proof)
             }
             /// Not upstream's: `multiply_point` (and `public_key`, `elgamal_encrypt`, `hashed_elgamal_encrypt` through it) as 320
             /// EcStepGate rows instead of arithmetic gates.  Off by default.

@@ -17,6 +17,8 @@
  *   data.verify(proof)                                                       p2_verify (host),
  *     aes-gcm/src/circuit_gcm.rs:782 (19 sites)                              p2_verify_batch (GPU, batched)
  *   native_gcm::encrypt (witness values)  aes-gcm/src/native_gcm.rs:16       p2_native_aes_gcm_encrypt
+ *   MerkleTree::new / prove, verify_merkle_proof_to_cap (upstream plonky2;   p2_merkle_tree_*, p2_merkle_verify_batch,
+ *     not called by the reference: committed sets for pod2-style users)      p2_builder_verify_merkle_proof_to_cap
  *
  * Conventions: plain pointers and sizes only; every function that can fail returns 0 on success and a
  * non-zero code otherwise, with a thread-local message available from p2_last_error().  The caller owns
@@ -179,6 +181,38 @@ int p2_aes_gcm_build(p2_builder*, int nk, int nr, size_t L, int with_tag, p2_tar
 /* ------------------------------------------------------------------ Poseidon hashing / poseidon-cipher (host) */
 /* builder.hash_n_to_m_no_pad::<PoseidonHash>(inputs, m)  (poseidon-cipher/src/circuit.rs:123): PoseidonGate rows */
 int p2_builder_hash_n_to_m_no_pad(p2_builder*, const p2_target* inputs, size_t n, p2_target* outputs, size_t m);
+/* Merkle membership in a circuit (plonky2 hash/merkle_proofs.rs verify_merkle_proof_to_cap; gadgets/hash.rs permute_swapped;
+ * hash/hash_types.rs add_virtual_hash / add_virtual_cap / connect_hashes; hashing.rs hash_or_noop).  A hash is four targets,
+ * a cap of height h is 2^h hashes = 4 * 2^h targets.  Poseidon by construction, whatever the circuit's tree hasher.
+ *   permute_swapped   one PoseidonGate row: the permutation of inputs[4..8] | inputs[0..4] | inputs[8..12] where swap = 1, of
+ *                     `inputs` where swap = 0.  The gate itself constrains swap (swap - 1) = 0.  hash_n_to_m_no_pad's rows are
+ *                     this with swap = zero(), gate for gate what they were
+ *   hash_or_noop      n <= 4 targets: themselves, zero-padded; more: hash_n_to_m_no_pad(inputs, 4)
+ *   verify_merkle_proof_to_cap   leaf[leaf_len] is the leaf at index sum index_bits[i] 2^i of a tree with this cap:
+ *                     state = hash_or_noop(leaf), then per sibling state = permute_swapped(state | sibling | 0^4, bit)[0..4], then
+ *                     state = cap[the remaining cap_height bits].  n_bits must be n_siblings + cap_height (P2_ERR_INVALID otherwise).
+ *                     The path bits are made boolean by the gate; the cap-index bits select through a mux tree of `select`
+ *                     ((2^cap_height - 1) * 4 of them, where upstream uses a RandomAccessGate) and are made boolean here with
+ *                     assert_bool.  Gate counts differ from upstream's by construction
+ *   verify_merkle_proof   the same against a root (cap_height 0) */
+int p2_builder_permute_swapped(p2_builder*, const p2_target inputs[12], p2_target swap, p2_target out[12]);
+int p2_builder_hash_or_noop(p2_builder*, const p2_target* inputs, size_t n, p2_target out[4]);
+int p2_builder_add_virtual_hash(p2_builder*, p2_target out[4]);
+int p2_builder_add_virtual_cap(p2_builder*, int cap_height, p2_target* out); /* 0 <= cap_height <= 16 */
+int p2_builder_connect_hashes(p2_builder*, const p2_target x[4], const p2_target y[4]);
+int p2_builder_verify_merkle_proof_to_cap(p2_builder*, const p2_target* leaf, size_t leaf_len, const p2_target* index_bits, size_t n_bits,
+                                          const p2_target* cap, int cap_height, const p2_target* siblings, size_t n_siblings);
+int p2_builder_verify_merkle_proof(p2_builder*, const p2_target* leaf, size_t leaf_len, const p2_target* index_bits, size_t n_bits,
+                                   const p2_target root[4], const p2_target* siblings, size_t n_siblings);
+/* Native Poseidon Merkle trees on the host (MerkleTree::new(leaves, cap_height).cap, tree.prove(i), verify_merkle_proof_to_cap):
+ * the twin of the p2_merkle_tree_* calls below, for hosts without a device.  leaves: [num_leaves][leaf_len] canonical words,
+ * row-major; the shape rules are p2_merkle_tree_new's.  cap: 4 * 2^cap_height words; siblings: 4 * (log2(num_leaves) -
+ * cap_height) words, the lowest level first.  _cap and _prove build the whole tree on every call.  _verify: *status <- 0
+ * accepted, 1 rejected, 2 a leaf, sibling or cap word that is not below p; cap_height 0 to 16, depth + cap_height at most 32. */
+int p2_native_merkle_cap(const uint64_t* leaves, size_t num_leaves, size_t leaf_len, int cap_height, uint64_t* cap);
+int p2_native_merkle_prove(const uint64_t* leaves, size_t num_leaves, size_t leaf_len, int cap_height, size_t index, uint64_t* siblings);
+int p2_native_merkle_verify(const uint64_t* leaf, size_t leaf_len, size_t index, const uint64_t* siblings, size_t depth, const uint64_t* cap,
+                            int cap_height, int* status);
 /* PoseidonEncryptTarget::<L>::build (poseidon-cipher/src/circuit.rs:49).  ks: 10 targets (x then u), m: 5*L,
  * nonce: 2, ct: 5*(L+1) */
 int p2_poseidon_cipher_build(p2_builder*, size_t L, p2_target* ks, p2_target* m, p2_target* nonce, p2_target* ct);
@@ -531,6 +565,46 @@ typedef struct {
 } p2_kernel_time;
 int p2_circuit_set_timing(p2_circuit*, int enable);
 size_t p2_circuit_get_timing(p2_circuit*, p2_kernel_time* out, size_t cap);
+
+/* ------------------------------------------------------------------ Merkle trees on the GPU (independent of any circuit) */
+/* MerkleTree::new(leaves, cap_height) with PoseidonHash: commits a set.  leaves: [num_leaves][leaf_len] canonical words,
+ * row-major (a Vec<Vec<F>> of equal lengths); num_leaves a power of two >= 1, 0 <= cap_height <= log2(num_leaves), leaf_len >= 1.
+ * A leaf of at most four words is its own digest, zero-padded (hash_or_noop); a longer one is hash_no_pad of it.  Anything
+ * else is P2_ERR_INVALID with a message: a bad shape, a null pointer, a word >= p (host form; the device form takes the words
+ * as canonical), a tree that does not fit in the free device memory.  *tree <- the handle, passed as void* like the streams
+ * (see p2_witness_explain); it holds every digest level on the device, 64 * num_leaves bytes, and not the leaves (while it
+ * is being built also a column-major copy of them).  num_leaves at most 2^32, leaf_len at most 2^20.
+ * _new returns with the tree built.  _new_device reads d_leaves (a device pointer) in kernels enqueued on `stream` (NULL = the
+ * default stream) behind the work already there and returns at once: d_leaves must stay untouched until they have run; every
+ * later call on the handle orders itself behind them.  Only caps and paths are interface, not the digests' order in memory. */
+int p2_merkle_tree_new(const uint64_t* leaves, size_t num_leaves, size_t leaf_len, int cap_height, int device, void** tree);
+int p2_merkle_tree_new_device(const uint64_t* d_leaves, size_t num_leaves, size_t leaf_len, int cap_height, int device, void* stream,
+                              void** tree);
+void p2_merkle_tree_free(void* tree);
+/* tree.cap: 4 * 2^cap_height words to host memory (cap_words: room in words); waits for the build */
+int p2_merkle_tree_cap(void* tree, uint64_t* cap, size_t cap_words);
+/* tree.prove(i) for n indices: siblings [n][log2(num_leaves) - cap_height][4], the lowest level first.  Host form: an index
+ * >= num_leaves is P2_ERR_INVALID and nothing is written.  Device form: path i goes to d_out[i * out_stride_words ..], so a
+ * caller can write paths straight into the [batch][n_targets] matrix of p2_prove_batch_device (d_out = the matrix plus the
+ * column of the first sibling target, out_stride_words = n_targets); the words between paths are left alone.  d_status[i] <- 0,
+ * or 1 for an index >= num_leaves, whose row is left untouched.  Asynchronous on `stream`, like p2_prove_batch_device. */
+int p2_merkle_tree_prove_batch(void* tree, const uint64_t* indices, size_t n, uint64_t* siblings);
+int p2_merkle_tree_prove_batch_device(void* tree, const uint64_t* d_indices, size_t n, uint64_t* d_out, size_t out_stride_words, int* d_status,
+                                      void* stream);
+/* verify_merkle_proof_to_cap for n paths against one cap: leaves [n][leaf_len], indices [n], siblings [n][depth][4], cap
+ * 4 * 2^cap_height words.  status[i] <- 0 accepted, 1 rejected (also an index that names no leaf), 2 a leaf, sibling or cap word
+ * that is not below p -- what p2_native_merkle_verify gives path for path.  cap_height 0 to 16, depth + cap_height at most 32.
+ * Device form: every buffer in device memory, asynchronous on `stream`. */
+int p2_merkle_verify_batch(const uint64_t* leaves, size_t leaf_len, const uint64_t* indices, const uint64_t* siblings, size_t depth,
+                           const uint64_t* cap, int cap_height, size_t n, int* status, int device);
+int p2_merkle_verify_batch_device(const uint64_t* d_leaves, size_t leaf_len, const uint64_t* d_indices, const uint64_t* d_siblings, size_t depth,
+                                  const uint64_t* d_cap, int cap_height, size_t n, int* d_status, int device, void* stream);
+/* Benchmark hook (tools/gpu_merkle_bench.py): one tree build on buffers the caller owns.  d_dig: 8 * num_leaves words (the
+ * digest levels); with_transpose == 0: the column-major build of p2_gpu_merkle_cap on d_scratch [leaf_len][num_leaves];
+ * otherwise the transpose kernel from the row-major d_leaves into d_scratch in front of it, the build of p2_merkle_tree_new.
+ * Asynchronous on `stream`. */
+int p2_gpu_merkle_build_device(const uint64_t* d_leaves, size_t num_leaves, size_t leaf_len, int cap_height, int with_transpose,
+                               uint64_t* d_scratch, uint64_t* d_dig, int device, void* stream);
 
 /* ------------------------------------------------------------------ GPU primitives (parity tests / microbench) */
 int p2_gpu_device_count(void);

@@ -294,6 +294,22 @@ def lib():
         "p2_gpu_merkle_cap": (C.c_int, [u64p, sz, sz, C.c_int, u64p, C.c_int]),
         "p2_gpu_zeta_pows": (C.c_int, [u64p, sz, u64p, C.c_int]),
         "p2_circuit_debug_read": (C.c_int, [vp, C.c_char_p, sz, u64p, sz, C.POINTER(sz)]),
+        "p2_builder_permute_swapped": (C.c_int, [vp, u64p, u64, u64p]), "p2_builder_hash_or_noop": (C.c_int, [vp, u64p, sz, u64p]),
+        "p2_builder_add_virtual_hash": (C.c_int, [vp, u64p]), "p2_builder_add_virtual_cap": (C.c_int, [vp, C.c_int, u64p]),
+        "p2_builder_connect_hashes": (C.c_int, [vp, u64p, u64p]),
+        "p2_builder_verify_merkle_proof_to_cap": (C.c_int, [vp, u64p, sz, u64p, sz, u64p, C.c_int, u64p, sz]),
+        "p2_builder_verify_merkle_proof": (C.c_int, [vp, u64p, sz, u64p, sz, u64p, u64p, sz]),
+        "p2_native_merkle_cap": (C.c_int, [u64p, sz, sz, C.c_int, u64p]),
+        "p2_native_merkle_prove": (C.c_int, [u64p, sz, sz, C.c_int, sz, u64p]),
+        "p2_native_merkle_verify": (C.c_int, [u64p, sz, sz, u64p, sz, u64p, C.c_int, C.POINTER(C.c_int)]),
+        "p2_merkle_tree_new": (C.c_int, [u64p, sz, sz, C.c_int, C.c_int, C.POINTER(vp)]),
+        "p2_merkle_tree_new_device": (C.c_int, [vp, sz, sz, C.c_int, C.c_int, vp, C.POINTER(vp)]),
+        "p2_merkle_tree_free": (None, [vp]), "p2_merkle_tree_cap": (C.c_int, [vp, u64p, sz]),
+        "p2_merkle_tree_prove_batch": (C.c_int, [vp, u64p, sz, u64p]),
+        "p2_merkle_tree_prove_batch_device": (C.c_int, [vp, vp, sz, vp, sz, vp, vp]),
+        "p2_merkle_verify_batch": (C.c_int, [u64p, sz, u64p, u64p, sz, u64p, C.c_int, sz, C.POINTER(C.c_int), C.c_int]),
+        "p2_merkle_verify_batch_device": (C.c_int, [vp, sz, vp, vp, sz, vp, C.c_int, sz, vp, C.c_int, vp]),
+        "p2_gpu_merkle_build_device": (C.c_int, [vp, sz, sz, C.c_int, C.c_int, vp, vp, C.c_int, vp]),
     }
     missing = []
     for name, (res, args) in sig.items():
@@ -500,6 +516,55 @@ class CircuitBuilder:
             raise P2Error(_err())
         return list(out)
 
+    # ---- Merkle membership (plonky2 hash/merkle_proofs.rs, gadgets/hash.rs).  A hash is a list of four targets, a cap a list of
+    # 2^cap_height hashes; include/p2aes.h has the rules.
+    def permute_swapped(self, inputs, swap):
+        """One PoseidonGate row: the permutation of `inputs` (12 targets) with its first two quarters exchanged where swap = 1."""
+        if len(inputs) != 12:
+            raise P2Error("permute_swapped takes 12 input targets")
+        out = (u64 * 12)()
+        if lib().p2_builder_permute_swapped(self._h, _arr(inputs), swap, out):
+            raise P2Error(_err())
+        return list(out)
+
+    def hash_or_noop(self, targets):
+        out = (u64 * 4)()
+        if lib().p2_builder_hash_or_noop(self._h, _arr(targets) if targets else None, len(targets), out):
+            raise P2Error(_err())
+        return list(out)
+
+    def add_virtual_hash(self):
+        out = (u64 * 4)()
+        if lib().p2_builder_add_virtual_hash(self._h, out):
+            raise P2Error(_err())
+        return list(out)
+
+    def add_virtual_cap(self, cap_height):
+        if not 0 <= cap_height <= 16:
+            raise P2Error("add_virtual_cap: cap_height must be 0 to 16")
+        out = (u64 * (4 << cap_height))()
+        if lib().p2_builder_add_virtual_cap(self._h, cap_height, out):
+            raise P2Error(_err())
+        return [list(out[4 * i:4 * i + 4]) for i in range(1 << cap_height)]
+
+    def connect_hashes(self, x, y):
+        if len(x) != 4 or len(y) != 4 or lib().p2_builder_connect_hashes(self._h, _arr(x), _arr(y)):
+            raise P2Error("connect_hashes takes two hashes of four targets" if len(x) != 4 or len(y) != 4 else _err())
+
+    def verify_merkle_proof_to_cap(self, leaf_data, index_bits, cap, siblings):
+        """leaf_data is the leaf at index sum index_bits[i] 2^i of the tree with this cap (a list of 2^h hashes); siblings: one
+        hash per path level, the lowest first; len(index_bits) must be len(siblings) + h."""
+        n_cap = len(cap)
+        if n_cap == 0 or n_cap & (n_cap - 1) or n_cap > 1 << 16 or any(len(h) != 4 for h in list(cap) + list(siblings)):
+            raise P2Error("verify_merkle_proof_to_cap: the cap is 2^h hashes (h <= 16) and every hash four targets")
+        flat = lambda hs: _arr([t for h in hs for t in h]) if hs else None  # noqa: E731
+        if lib().p2_builder_verify_merkle_proof_to_cap(self._h, _arr(leaf_data) if leaf_data else None, len(leaf_data), _arr(index_bits) if index_bits else None,
+                                                       len(index_bits), flat(cap), n_cap.bit_length() - 1, flat(siblings), len(siblings)):
+            raise P2Error(_err())
+
+    def verify_merkle_proof(self, leaf_data, index_bits, root, siblings):
+        self.verify_merkle_proof_to_cap(leaf_data, index_bits, [root], siblings)
+
     # ---- pod2 CircuitBuilderElliptic / CircuitBuilderBits and the ecgfp5 crate's builder traits.  A PointTarget is its ten
     # targets (x then u), a BigUInt320Target its 320 little-endian bit targets.
     def add_virtual_point_target(self):
@@ -597,6 +662,25 @@ class PartialWitness:
 
     def set_secret_key_target(self, target, sk):          # ecgfp5/src/circuit.rs:52
         self.set_biguint320_target(target, sk.value)
+
+    def set_hash_target(self, target, words):
+        self.set_target_arr(target, _hash4(words))
+
+    def set_cap_target(self, targets, cap):               # plonky2 WitnessHashes::set_cap_target
+        if len(targets) != len(cap):
+            raise P2Error("the cap has %d hashes, its target %d" % (len(cap), len(targets)))
+        for t, h in zip(targets, cap):
+            self.set_hash_target(t, h)
+
+    def set_merkle_proof_target(self, targets, index, siblings):
+        """targets = (index_bits, sibling hashes) as verify_merkle_proof_to_cap took them: the little-endian bits of `index`
+        and one hash per level."""
+        bits, sibs = targets
+        if len(sibs) != len(siblings) or not 0 <= index < 1 << len(bits):
+            raise P2Error("the path has %d siblings and the index %d bits" % (len(sibs), len(bits)))
+        self.set_target_arr(bits, [(index >> i) & 1 for i in range(len(bits))])
+        for t, h in zip(sibs, siblings):
+            self.set_hash_target(t, h)
 
     def set_byte_target(self, target, value): self.set_target(target, value & 0xFF if isinstance(value, int) else int(value))
     def set_state_target(self, targets, state16):
@@ -983,6 +1067,152 @@ class PoseidonEncryptTarget:
         pw.set_target_arr(self.m, [v for fq in m for v in fq])
         pw.set_target_arr(self.nonce, nonce)
         pw.set_target_arr(self.ct, [v for fq in ct for v in fq])
+
+
+def _hash4(words):
+    words = [int(w) for w in words]
+    if len(words) != 4:
+        raise P2Error("a hash is four field elements")
+    return words
+
+
+def _rows(rows, what):
+    """[n][k] as (flat u64 array or None, n, k); every row of one length"""
+    rows = [list(r) for r in rows]
+    k = len(rows[0]) if rows else 0
+    if any(len(r) != k for r in rows):
+        raise P2Error("%s must all have one length" % what)
+    flat = [int(v) for r in rows for v in r]
+    if any(not 0 <= v < 1 << 64 for v in flat):
+        raise P2Error("%s hold 64-bit words" % what)
+    return (_arr(flat) if flat else None), len(rows), k
+
+
+class MerkleTree:
+    """plonky2 MerkleTree::new(leaves, cap_height) with PoseidonHash.  leaves: a list of equally long lists of canonical field
+    elements, a power of two of them.  device = an index: the tree is built and kept on that GPU (p2_merkle_tree_*; .cap,
+    .prove, .prove_batch and the device forms); device = None: the host twin (p2_native_merkle_*), which keeps the leaves and
+    rebuilds the tree on every call -- for hosts without a device.  Only caps and paths are interface."""
+
+    def __init__(self, leaves, cap_height=0, device=0):
+        self._h = None
+        self.device, self.cap_height = device, cap_height
+        flat, self.num_leaves, self.leaf_len = _rows(leaves, "leaves")
+        if self.num_leaves == 0 or self.num_leaves & (self.num_leaves - 1):
+            raise P2Error("num_leaves must be a power of two, at least 1")
+        self.depth = self.num_leaves.bit_length() - 1 - cap_height
+        if device is None:
+            self._leaves = flat
+            self.cap     # validates the shape and the words
+        else:
+            h = C.c_void_p()
+            if lib().p2_merkle_tree_new(flat, self.num_leaves, self.leaf_len, cap_height, device, C.byref(h)):
+                raise P2Error("p2_merkle_tree_new failed: " + _err())
+            self._h = h
+
+    @classmethod
+    def from_device(cls, d_leaves, num_leaves, leaf_len, cap_height=0, device=0, stream=None):
+        """p2_merkle_tree_new_device: `d_leaves` a raw device pointer to [num_leaves][leaf_len] u64 (e.g. a torch tensor's
+        data_ptr()), read by kernels enqueued on `stream`; keep the buffer untouched until they have run."""
+        t = cls.__new__(cls)
+        t._h = None
+        t.device, t.cap_height, t.num_leaves, t.leaf_len = device, cap_height, num_leaves, leaf_len
+        h = C.c_void_p()
+        if lib().p2_merkle_tree_new_device(d_leaves, num_leaves, leaf_len, cap_height, device, stream, C.byref(h)):
+            raise P2Error("p2_merkle_tree_new_device failed: " + _err())
+        t._h = h
+        t.depth = num_leaves.bit_length() - 1 - cap_height
+        return t
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            lib().p2_merkle_tree_free(self._h)
+            self._h = None
+
+    @property
+    def cap(self):
+        """2^cap_height hashes, each a list of four field elements"""
+        n = 4 << max(self.cap_height, 0)
+        out = (u64 * n)()
+        if self._h is None:
+            if lib().p2_native_merkle_cap(self._leaves, self.num_leaves, self.leaf_len, self.cap_height, out):
+                raise P2Error("p2_native_merkle_cap failed: " + _err())
+        elif lib().p2_merkle_tree_cap(self._h, out, n):
+            raise P2Error("p2_merkle_tree_cap failed: " + _err())
+        return [list(out[4 * i:4 * i + 4]) for i in range(n // 4)]
+
+    def prove_batch(self, indices):
+        """tree.prove(i) for every index: one list of sibling hashes (lowest level first) per index"""
+        idx = [int(i) for i in indices]
+        d = self.depth
+        if self._h is None:
+            out = []
+            buf = (u64 * max(4 * d, 1))()
+            for i in idx:
+                if not 0 <= i < 1 << 64 or lib().p2_native_merkle_prove(self._leaves, self.num_leaves, self.leaf_len, self.cap_height, i, buf):
+                    raise P2Error("p2_native_merkle_prove failed: " + (_err() if 0 <= i < 1 << 64 else "index out of range"))
+                out.append([list(buf[4 * l:4 * l + 4]) for l in range(d)])
+            return out
+        if any(not 0 <= i < 1 << 64 for i in idx):
+            raise P2Error("index out of range")
+        buf = (u64 * max(len(idx) * 4 * d, 1))()
+        if lib().p2_merkle_tree_prove_batch(self._h, _arr(idx) if idx else None, len(idx), buf):
+            raise P2Error("p2_merkle_tree_prove_batch failed: " + _err())
+        return [[list(buf[(k * d + l) * 4:(k * d + l) * 4 + 4]) for l in range(d)] for k in range(len(idx))]
+
+    def prove(self, index):
+        return self.prove_batch([index])[0]
+
+    def prove_batch_device(self, d_indices, n, d_out, out_stride_words, d_status, stream=None):
+        """Device-resident openings: `d_indices` u64[n], `d_out` (path i at d_out + 8 * i * out_stride_words bytes: 4 * depth words) and
+        `d_status` int32[n] are raw device pointers; asynchronous on `stream` like prove_batch_device of a circuit."""
+        if self._h is None:
+            raise P2Error("a host tree has no device forms")
+        if lib().p2_merkle_tree_prove_batch_device(self._h, d_indices, n, d_out, out_stride_words, d_status, stream):
+            raise P2Error("p2_merkle_tree_prove_batch_device failed: " + _err())
+
+
+class merkle:
+    """verify_merkle_proof_to_cap outside a circuit: statuses 0 accepted, 1 rejected, 2 a word that is not below p."""
+
+    @staticmethod
+    def verify_batch(leaves, indices, siblings, cap, device=0):
+        """leaves [n][leaf_len], indices [n], siblings [n][depth] hashes, cap 2^h hashes -> n statuses.  device = an index: on
+        that GPU (p2_merkle_verify_batch); None: a host loop over p2_native_merkle_verify."""
+        lf, n, leaf_len = _rows(leaves, "leaves")
+        idx = [int(i) for i in indices]
+        sibs = [[w for h in path for w in _hash4(h)] for path in siblings]
+        sb, n_s, sib_words = _rows(sibs, "paths")
+        capw, n_cap, _ = _rows([_hash4(h) for h in cap], "cap hashes")
+        if len(idx) != n or (n_s != n) or n_cap == 0 or n_cap & (n_cap - 1) or any(not 0 <= i < 1 << 64 for i in idx):
+            raise P2Error("verify_batch: one index and one path per leaf, a cap of 2^h hashes")
+        if n == 0:
+            return []
+        if leaf_len == 0:
+            raise P2Error("verify_batch: empty leaves")
+        depth, cap_height = sib_words // 4, n_cap.bit_length() - 1
+        status = (C.c_int * n)()
+        if device is None:
+            st = C.c_int()
+            for i in range(n):
+                leaf = C.cast(C.byref(lf, 8 * i * leaf_len), u64p)
+                path = C.cast(C.byref(sb, 8 * i * sib_words), u64p) if depth else None
+                if lib().p2_native_merkle_verify(leaf, leaf_len, idx[i], path, depth, capw, cap_height, C.byref(st)):
+                    raise P2Error("p2_native_merkle_verify failed: " + _err())
+                status[i] = st.value
+        elif lib().p2_merkle_verify_batch(lf, leaf_len, _arr(idx), sb, depth, capw, cap_height, n, status, device):
+            raise P2Error("p2_merkle_verify_batch failed: " + _err())
+        return list(status)
+
+    @staticmethod
+    def verify(leaf, index, siblings, cap, device=0):
+        return merkle.verify_batch([leaf], [index], [siblings], cap, device)[0]
+
+    @staticmethod
+    def verify_batch_device(d_leaves, leaf_len, d_indices, d_siblings, depth, d_cap, cap_height, n, d_status, device=0, stream=None):
+        """Every buffer a raw device pointer (p2_merkle_verify_batch_device); asynchronous on `stream`."""
+        if lib().p2_merkle_verify_batch_device(d_leaves, leaf_len, d_indices, d_siblings, depth, d_cap, cap_height, n, d_status, device, stream):
+            raise P2Error("p2_merkle_verify_batch_device failed: " + _err())
 
 
 class keccak_native:

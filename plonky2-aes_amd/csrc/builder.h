@@ -227,9 +227,12 @@ class CircuitBuilder {
 
     // ---- hashing (plonky2 gadgets/hash.rs, hash/poseidon.rs AlgebraicHasher::permute_swapped) --------
     // One PoseidonGate row; swap = false.
-    std::array<Target, 12> permute(const std::array<Target, 12>& inputs) {
+    std::array<Target, 12> permute(const std::array<Target, 12>& inputs) { return permute_swapped(inputs, BoolTarget{zero()}); }
+    // One PoseidonGate row that permutes inputs[4..8] | inputs[0..4] | inputs[8..12] where swap = 1 and `inputs` where swap = 0.
+    // The gate's own constraint swap (swap - 1) = 0 makes `swap` boolean: no assert_bool is needed for it.
+    std::array<Target, 12> permute_swapped(const std::array<Target, 12>& inputs, BoolTarget swap) {
         u32 row = add_gate(G_POSEIDON);
-        connect(zero(), wire_target(row, PG_SWAP));
+        connect(swap.target, wire_target(row, PG_SWAP));
         for (u32 i = 0; i < 12; i++) connect(inputs[i], wire_target(row, PG_IN + i));
         gens_.push_back(Gen{OP_POSEIDON, wire_target(row, PG_OUT), (Target)row, 0, 0, 0, 0, 0});
         std::array<Target, 12> out;
@@ -252,6 +255,68 @@ class CircuitBuilder {
             }
             state = permute(state);
         }
+    }
+
+    // ---- Merkle membership (plonky2 hash/merkle_proofs.rs, gadgets/hash.rs) ---------------------------------------
+    // Same names and meaning as upstream; the cap entry is chosen by a mux tree of `select` instead of a RandomAccessGate, so
+    // gate counts differ by construction.  Per path level: one PoseidonGate row.  Per proof with cap height h: h assert_bool
+    // ops and (2^h - 1) * 4 selects (two ArithmeticGate ops each), then four copy constraints.
+    typedef std::array<Target, 4> HashOutTarget;
+    HashOutTarget add_virtual_hash() { return HashOutTarget{add_virtual_target(), add_virtual_target(), add_virtual_target(), add_virtual_target()}; }
+    std::vector<HashOutTarget> add_virtual_cap(u32 cap_height) {
+        if (cap_height > 16) throw std::runtime_error("add_virtual_cap: cap_height must be 0 to 16");
+        std::vector<HashOutTarget> cap((size_t)1 << cap_height);
+        for (auto& h : cap) h = add_virtual_hash();
+        return cap;
+    }
+    void connect_hashes(const HashOutTarget& x, const HashOutTarget& y) {
+        for (u32 i = 0; i < 4; i++) connect(x[i], y[i]);
+    }
+    // The digest of a leaf: up to four elements zero-padded as they are, more through hash_n_to_hash_no_pad.
+    HashOutTarget hash_or_noop(const std::vector<Target>& inputs) {
+        HashOutTarget h;
+        if (inputs.size() <= 4) {
+            for (u32 i = 0; i < 4; i++) h[i] = i < inputs.size() ? inputs[i] : zero();
+            return h;
+        }
+        std::vector<Target> o = hash_n_to_m_no_pad(inputs, 4);
+        for (u32 i = 0; i < 4; i++) h[i] = o[i];
+        return h;
+    }
+    // leaf_data is the leaf at index sum index_bits[i] 2^i of a tree with the given cap: the low siblings.size() bits walk the
+    // path, the bits above them (log2 of the cap's size of them) choose the cap entry.  The path bits are made boolean by the
+    // PoseidonGate's swap constraint; the cap-index bits reach only `select`, which constrains nothing, so they are made
+    // boolean here with assert_bool.
+    void verify_merkle_proof_to_cap(const std::vector<Target>& leaf_data, const std::vector<BoolTarget>& index_bits, const std::vector<HashOutTarget>& cap,
+                                    const std::vector<HashOutTarget>& siblings) {
+        u32 cap_height = 0;
+        while (((size_t)1 << cap_height) < cap.size()) cap_height++;
+        if (cap.empty() || ((size_t)1 << cap_height) != cap.size()) throw std::runtime_error("verify_merkle_proof_to_cap: the cap must hold a power of two of hashes");
+        if (leaf_data.empty()) throw std::runtime_error("verify_merkle_proof_to_cap: empty leaf");
+        if (index_bits.size() != siblings.size() + cap_height)
+            throw std::runtime_error("verify_merkle_proof_to_cap: " + std::to_string(index_bits.size()) + " index bits for " + std::to_string(siblings.size()) +
+                                     " siblings and cap height " + std::to_string(cap_height));
+        HashOutTarget state = hash_or_noop(leaf_data);
+        for (size_t l = 0; l < siblings.size(); l++) {
+            std::array<Target, 12> in;
+            for (u32 i = 0; i < 4; i++) in[i] = state[i], in[4 + i] = siblings[l][i], in[8 + i] = zero();
+            std::array<Target, 12> out = permute_swapped(in, index_bits[l]);
+            for (u32 i = 0; i < 4; i++) state[i] = out[i];
+        }
+        std::vector<HashOutTarget> entries = cap;
+        for (u32 j = 0; j < cap_height; j++) {
+            BoolTarget bit = index_bits[siblings.size() + j];
+            assert_bool(bit.target);
+            std::vector<HashOutTarget> half(entries.size() / 2);
+            for (size_t i = 0; i < half.size(); i++)
+                for (u32 w = 0; w < 4; w++) half[i][w] = select(bit, entries[2 * i + 1][w], entries[2 * i][w]);
+            entries.swap(half);
+        }
+        connect_hashes(state, entries[0]);
+    }
+    void verify_merkle_proof(const std::vector<Target>& leaf_data, const std::vector<BoolTarget>& index_bits, const HashOutTarget& root,
+                             const std::vector<HashOutTarget>& siblings) {
+        verify_merkle_proof_to_cap(leaf_data, index_bits, {root}, siblings);
     }
 
     // ---- ecGFp5 scalar-multiplication step (ecstep_gate.h; not an upstream gate) ---------------------

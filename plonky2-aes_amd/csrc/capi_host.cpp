@@ -7,6 +7,7 @@
 #include "capi_common.h"
 #include "compress.h"
 #include "ecgfp5.h"
+#include "merkle_host.h"
 #include "poseidon_cipher.h"
 #include "poseidon_fast.h"
 #include "verifier.h"
@@ -333,6 +334,80 @@ int p2_builder_hash_n_to_m_no_pad(p2_builder* b, const p2_target* inputs, size_t
     } catch (std::exception& e) {
         return set_error(e.what()), P2_ERR_INVALID;
     }
+}
+// ---- Merkle membership
+static CircuitBuilder::HashOutTarget hash_at(const p2_target* h) { return CircuitBuilder::HashOutTarget{h[0], h[1], h[2], h[3]}; }
+static std::vector<CircuitBuilder::HashOutTarget> hashes_at(const p2_target* h, size_t n) {
+    std::vector<CircuitBuilder::HashOutTarget> v(n);
+    for (size_t i = 0; i < n; i++) v[i] = hash_at(h + 4 * i);
+    return v;
+}
+int p2_builder_permute_swapped(p2_builder* b, const p2_target inputs[12], p2_target swap, p2_target out[12]) {
+    return guarded([&] {
+        std::array<Target, 12> in;
+        std::copy(inputs, inputs + 12, in.begin());
+        auto o = b->b.permute_swapped(in, BoolTarget{swap});
+        std::copy(o.begin(), o.end(), out);
+    });
+}
+int p2_builder_hash_or_noop(p2_builder* b, const p2_target* inputs, size_t n, p2_target out[4]) {
+    return guarded([&] {
+        auto h = b->b.hash_or_noop(std::vector<Target>(inputs, inputs + n));
+        std::copy(h.begin(), h.end(), out);
+    });
+}
+int p2_builder_add_virtual_hash(p2_builder* b, p2_target out[4]) {
+    return guarded([&] {
+        auto h = b->b.add_virtual_hash();
+        std::copy(h.begin(), h.end(), out);
+    });
+}
+int p2_builder_add_virtual_cap(p2_builder* b, int cap_height, p2_target* out) {
+    return guarded([&] {
+        if (cap_height < 0) throw std::runtime_error("add_virtual_cap: cap_height must be 0 to 16");
+        auto cap = b->b.add_virtual_cap((u32)cap_height);
+        for (size_t i = 0; i < cap.size(); i++) std::copy(cap[i].begin(), cap[i].end(), out + 4 * i);
+    });
+}
+int p2_builder_connect_hashes(p2_builder* b, const p2_target x[4], const p2_target y[4]) {
+    return guarded([&] { b->b.connect_hashes(hash_at(x), hash_at(y)); });
+}
+int p2_builder_verify_merkle_proof_to_cap(p2_builder* b, const p2_target* leaf, size_t leaf_len, const p2_target* index_bits, size_t n_bits, const p2_target* cap,
+                                          int cap_height, const p2_target* siblings, size_t n_siblings) {
+    return guarded([&] {
+        if (cap_height < 0 || cap_height > 16) throw std::runtime_error("verify_merkle_proof_to_cap: cap_height must be 0 to 16");
+        std::vector<BoolTarget> bits(n_bits);
+        for (size_t i = 0; i < n_bits; i++) bits[i] = BoolTarget{index_bits[i]};
+        b->b.verify_merkle_proof_to_cap(std::vector<Target>(leaf, leaf + leaf_len), bits, hashes_at(cap, (size_t)1 << cap_height), hashes_at(siblings, n_siblings));
+    });
+}
+int p2_builder_verify_merkle_proof(p2_builder* b, const p2_target* leaf, size_t leaf_len, const p2_target* index_bits, size_t n_bits, const p2_target root[4],
+                                   const p2_target* siblings, size_t n_siblings) {
+    return p2_builder_verify_merkle_proof_to_cap(b, leaf, leaf_len, index_bits, n_bits, root, 0, siblings, n_siblings);
+}
+// Native trees on the host (merkle_host.h): the twin of the p2_merkle_tree_* calls for the CPU suite
+int p2_native_merkle_cap(const uint64_t* leaves, size_t num_leaves, size_t leaf_len, int cap_height, uint64_t* cap) {
+    return guarded([&] {
+        mt::HostTree t(leaves, num_leaves, leaf_len, cap_height);
+        const auto& top = t.levels[t.bits - t.cap_height];
+        memcpy(cap, top.data(), top.size() * sizeof(Hash4));
+    });
+}
+int p2_native_merkle_prove(const uint64_t* leaves, size_t num_leaves, size_t leaf_len, int cap_height, size_t index, uint64_t* siblings) {
+    return guarded([&] {
+        mt::HostTree t(leaves, num_leaves, leaf_len, cap_height);
+        if (index >= num_leaves) throw std::runtime_error("leaf index " + std::to_string(index) + " is not below num_leaves");
+        for (u32 l = 0; l < t.bits - t.cap_height; l++) memcpy(siblings + 4 * l, t.levels[l][(index >> l) ^ 1].e, 32);
+    });
+}
+int p2_native_merkle_verify(const uint64_t* leaf, size_t leaf_len, size_t index, const uint64_t* siblings, size_t depth, const uint64_t* cap, int cap_height,
+                            int* status) {
+    return guarded([&] {
+        if (!leaf || !cap || !status || (depth && !siblings)) throw std::runtime_error("null argument");
+        if (leaf_len < 1 || leaf_len > 0xFFFFFFFFull || cap_height < 0 || cap_height > 16 || depth + (size_t)cap_height > 32)
+            throw std::runtime_error("leaf_len >= 1, cap_height 0 to 16, siblings + cap_height at most 32");
+        *status = mt::host_verify(leaf, leaf_len, index, siblings, depth, cap, (u32)cap_height);
+    });
 }
 int p2_poseidon_cipher_build(p2_builder* b, size_t L, p2_target* ks, p2_target* m, p2_target* nonce, p2_target* ct) {
     try {

@@ -7,6 +7,7 @@
 
 #include <algorithm>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <random>
 #include <string>
@@ -18,7 +19,9 @@
 #include "kernels2.h"
 #include "kernels_compress.h"
 #include "kernels_keccak.h"
+#include "kernels_merkle.h"
 #include "kernels_witness_io.h"
+#include "merkle_host.h"
 #include "verifier.h"
 
 using namespace p2;
@@ -3038,6 +3041,207 @@ int p2_gpu_merkle_cap_hasher(const uint64_t* cols_major, size_t cols, size_t num
     HIPCHECK(hipStreamSynchronize(ctx.lane.stream));
     HIPCHECK(hipMemcpy(cap, t.dig + cap_off(t, (u32)cap_height), ((size_t)4 << cap_height) * 8, hipMemcpyDeviceToHost));
     return P2_OK;
+}
+
+// ---- stand-alone Merkle trees (kernels_merkle.h, merkle_host.h)
+// A tree independent of any circuit: every digest level on the device in merkle_build's layout; the leaves are not kept.
+struct MerkleTreeHandle {
+    int device = 0;
+    u32 leaf_len = 0, cap_height = 0;
+    Tree t;
+    Allocs mem;
+    Allocs scratch;              // the column-major copy of the leaves: needed until the build has run
+    Lane lane;                   // the stream of the host forms
+    hipEvent_t built = nullptr;  // recorded behind the last kernel of the build, on whichever stream ran it
+    void drop_scratch(bool wait) {
+        if (scratch.empty() || (wait ? hipEventSynchronize(built) : hipEventQuery(built)) != hipSuccess) return;
+        for (void* p : scratch) (void)hipFree(p);
+        scratch.clear();
+    }
+    ~MerkleTreeHandle() {
+        if (built) (void)hipEventSynchronize(built), (void)hipEventDestroy(built);
+        if (lane.stream) (void)hipStreamSynchronize(lane.stream), (void)hipStreamDestroy(lane.stream);
+    }
+    u32 depth() const { return t.bits - cap_height; }
+};
+// row-major leaves -> column-major, then merkle_build (leaf digests and the levels up to the cap), on `stream`; records `built`
+static int mt_transpose(Lane& L, const u64* d_leaves, size_t num_leaves, u32 leaf_len, u64* d_cols) {
+    LAUNCH(L, "mt_transpose", k_mt_transpose, dim3((u32)((num_leaves + 31) / 32), (leaf_len + 31) / 32), dim3(256), 0, d_leaves, num_leaves, leaf_len, d_cols);
+    return 0;
+}
+static int mt_build(MerkleTreeHandle& T, const u64* d_leaves, hipStream_t stream) {
+    Lane L;
+    L.stream = stream;
+    Domain D;
+    D.cap_height = T.cap_height;
+    const size_t leaves = (size_t)1 << T.t.bits;
+    u64* d_cols;
+    if (dalloc(T.scratch, &d_cols, leaves * T.leaf_len) || mt_transpose(L, d_leaves, leaves, T.leaf_len, d_cols)) return P2_ERR_HIP;
+    if (merkle_build(L, D, d_cols, T.leaf_len, T.leaf_len, leaves, 0, T.t, 1)) return P2_ERR_HIP;
+    HIPCHECK(hipEventRecord(T.built, stream));
+    return P2_OK;
+}
+static int mt_new(const u64* leaves, bool on_device, size_t num_leaves, size_t leaf_len, int cap_height, int device, hipStream_t stream, void** tree) {
+    if (!tree) return set_error("null tree pointer"), P2_ERR_INVALID;
+    *tree = nullptr;
+    const u32 bits = mt::check_shape(num_leaves, leaf_len, cap_height);  // throws: P2_ERR_INVALID
+    if (!leaves) return set_error("null leaves"), P2_ERR_INVALID;
+    const size_t words = num_leaves * leaf_len;
+    if (!on_device) {
+        const size_t bad = mt::first_non_canonical(leaves, words);
+        if (bad != words) return set_error("word " + std::to_string(bad % leaf_len) + " of leaf " + std::to_string(bad / leaf_len) + " is not below p"), P2_ERR_INVALID;
+    }
+    if (int rc = pick_device(device)) return rc;
+    std::unique_ptr<MerkleTreeHandle> T(new MerkleTreeHandle());
+    T->device = device;
+    T->leaf_len = (u32)leaf_len;
+    T->cap_height = (u32)cap_height;
+    T->t.bits = bits;
+    size_t free_b = 0, total_b = 0;
+    HIPCHECK(hipMemGetInfo(&free_b, &total_b));
+    const size_t need = 8 * T->t.stride() + 8 * words + (on_device ? 0 : 8 * words);  // digests, the column-major copy, the upload
+    if (need > free_b) return set_error("the tree needs " + std::to_string(need) + " bytes of device memory, " + std::to_string(free_b) + " are free"), P2_ERR_INVALID;
+    HIPCHECK(hipStreamCreateWithFlags(&T->lane.stream, hipStreamNonBlocking));
+    HIPCHECK(hipEventCreateWithFlags(&T->built, hipEventDisableTiming));
+    if (dalloc(T->mem, &T->t.dig, T->t.stride())) return P2_ERR_HIP;
+    if (on_device) {
+        if (int rc = mt_build(*T, leaves, stream)) return rc;
+    } else {
+        Allocs tmp;  // the uploaded leaves go when the build has run
+        u64* d_leaves;
+        if (upload(tmp, &d_leaves, leaves, words)) return P2_ERR_HIP;
+        if (int rc = mt_build(*T, d_leaves, T->lane.stream)) return rc;
+        HIPCHECK(hipStreamSynchronize(T->lane.stream));
+        T->drop_scratch(true);
+    }
+    *tree = T.release();
+    return P2_OK;
+}
+static int mt_handle(void* tree, MerkleTreeHandle** T) {
+    if (!tree) return set_error("null tree handle"), P2_ERR_INVALID;
+    *T = (MerkleTreeHandle*)tree;
+    HIPCHECK(hipSetDevice((*T)->device));
+    (*T)->drop_scratch(false);
+    return P2_OK;
+}
+static int mt_paths(MerkleTreeHandle& T, const u64* d_indices, size_t n, u64* d_out, size_t out_stride, int* d_status, hipStream_t stream) {
+    if (n == 0) return P2_OK;
+    if (!d_indices || !d_status || (T.depth() && !d_out)) return set_error("null argument"), P2_ERR_INVALID;
+    if (out_stride < 4 * (size_t)T.depth()) return set_error("out_stride_words is smaller than a path (" + std::to_string(4 * T.depth()) + " words)"), P2_ERR_INVALID;
+    HIPCHECK(hipStreamWaitEvent(stream, T.built, 0));
+    const size_t threads = n * std::max<u32>(T.depth(), 1);
+    hipLaunchKernelGGL(k_mt_paths, g1(threads, 256), dim3(256), 0, stream, T.t.dig, T.t.bits, T.depth(), d_indices, n, d_out, out_stride, d_status);
+    HIPCHECK(hipGetLastError());
+    return P2_OK;
+}
+static int mt_verify_shape(size_t leaf_len, size_t depth, int cap_height) {
+    if (leaf_len < 1 || leaf_len > 0xFFFFFFFFull || cap_height < 0 || cap_height > 16 || depth + (size_t)cap_height > 32)
+        return set_error("leaf_len >= 1, cap_height 0 to 16, siblings + cap_height at most 32"), P2_ERR_INVALID;
+    return P2_OK;
+}
+static int mt_verify(const u64* d_leaves, size_t leaf_len, const u64* d_indices, const u64* d_siblings, size_t depth, const u64* d_cap, int cap_height, size_t n,
+                     int* d_status, hipStream_t stream) {
+    hipLaunchKernelGGL(k_mt_verify, g1(n, 64), dim3(64), 0, stream, d_leaves, (u32)leaf_len, d_indices, d_siblings, (u32)depth, d_cap, (u32)cap_height, n, d_status);
+    HIPCHECK(hipGetLastError());
+    return P2_OK;
+}
+
+int p2_merkle_tree_new(const uint64_t* leaves, size_t num_leaves, size_t leaf_len, int cap_height, int device, void** tree) {
+    return guarded_rc([&] { return mt_new((const u64*)leaves, false, num_leaves, leaf_len, cap_height, device, nullptr, tree); });
+}
+int p2_merkle_tree_new_device(const uint64_t* d_leaves, size_t num_leaves, size_t leaf_len, int cap_height, int device, void* stream, void** tree) {
+    return guarded_rc([&] { return mt_new((const u64*)d_leaves, true, num_leaves, leaf_len, cap_height, device, (hipStream_t)stream, tree); });
+}
+void p2_merkle_tree_free(void* tree) {
+    if (!tree) return;
+    (void)hipSetDevice(((MerkleTreeHandle*)tree)->device);
+    delete (MerkleTreeHandle*)tree;
+}
+int p2_merkle_tree_cap(void* tree, uint64_t* cap, size_t cap_words) {
+    return guarded_rc([&]() -> int {
+        MerkleTreeHandle* T;
+        if (int rc = mt_handle(tree, &T)) return rc;
+        const size_t words = (size_t)4 << T->cap_height;
+        if (!cap || cap_words < words) return set_error("the cap holds " + std::to_string(words) + " words"), P2_ERR_INVALID;
+        HIPCHECK(hipEventSynchronize(T->built));
+        T->drop_scratch(true);
+        HIPCHECK(hipMemcpy(cap, T->t.dig + cap_off(T->t, T->cap_height), words * 8, hipMemcpyDeviceToHost));
+        return (int)P2_OK;
+    });
+}
+int p2_merkle_tree_prove_batch(void* tree, const uint64_t* indices, size_t n, uint64_t* siblings) {
+    return guarded_rc([&]() -> int {
+        MerkleTreeHandle* T;
+        if (int rc = mt_handle(tree, &T)) return rc;
+        if (n == 0) return (int)P2_OK;
+        if (!indices || (T->depth() && !siblings)) return set_error("null argument"), P2_ERR_INVALID;
+        for (size_t i = 0; i < n; i++)
+            if (indices[i] >> T->t.bits) return set_error("leaf index " + std::to_string(indices[i]) + " (entry " + std::to_string(i) + ") is not below num_leaves"), P2_ERR_INVALID;
+        const size_t stride = 4 * (size_t)T->depth();
+        Allocs tmp;
+        u64 *d_idx, *d_out;
+        int* d_st;
+        if (upload(tmp, &d_idx, (const u64*)indices, n) || dalloc(tmp, &d_out, n * stride) || dalloc(tmp, &d_st, n)) return P2_ERR_HIP;
+        if (int rc = mt_paths(*T, d_idx, n, d_out, stride, d_st, T->lane.stream)) return rc;
+        HIPCHECK(hipStreamSynchronize(T->lane.stream));
+        if (stride) HIPCHECK(hipMemcpy(siblings, d_out, n * stride * 8, hipMemcpyDeviceToHost));
+        return (int)P2_OK;
+    });
+}
+int p2_merkle_tree_prove_batch_device(void* tree, const uint64_t* d_indices, size_t n, uint64_t* d_out, size_t out_stride_words, int* d_status, void* stream) {
+    return guarded_rc([&]() -> int {
+        MerkleTreeHandle* T;
+        if (int rc = mt_handle(tree, &T)) return rc;
+        return mt_paths(*T, (const u64*)d_indices, n, (u64*)d_out, out_stride_words, d_status, (hipStream_t)stream);
+    });
+}
+int p2_merkle_verify_batch(const uint64_t* leaves, size_t leaf_len, const uint64_t* indices, const uint64_t* siblings, size_t depth, const uint64_t* cap, int cap_height,
+                           size_t n, int* status, int device) {
+    return guarded_rc([&]() -> int {
+        if (int rc = mt_verify_shape(leaf_len, depth, cap_height)) return rc;
+        if (n == 0) return (int)P2_OK;
+        if (!leaves || !indices || !cap || !status || (depth && !siblings)) return set_error("null argument"), P2_ERR_INVALID;
+        if (int rc = pick_device(device)) return rc;
+        Allocs tmp;
+        u64 *d_leaves, *d_idx, *d_sib, *d_cap;
+        int* d_st;
+        if (upload(tmp, &d_leaves, (const u64*)leaves, n * leaf_len) || upload(tmp, &d_idx, (const u64*)indices, n) || upload(tmp, &d_sib, (const u64*)siblings, n * 4 * depth) ||
+            upload(tmp, &d_cap, (const u64*)cap, (size_t)4 << cap_height) || dalloc(tmp, &d_st, n))
+            return P2_ERR_HIP;
+        if (int rc = mt_verify(d_leaves, leaf_len, d_idx, d_sib, depth, d_cap, cap_height, n, d_st, nullptr)) return rc;
+        HIPCHECK(hipMemcpy(status, d_st, n * sizeof(int), hipMemcpyDeviceToHost));
+        return (int)P2_OK;
+    });
+}
+int p2_merkle_verify_batch_device(const uint64_t* d_leaves, size_t leaf_len, const uint64_t* d_indices, const uint64_t* d_siblings, size_t depth, const uint64_t* d_cap,
+                                  int cap_height, size_t n, int* d_status, int device, void* stream) {
+    return guarded_rc([&]() -> int {
+        if (int rc = mt_verify_shape(leaf_len, depth, cap_height)) return rc;
+        if (n == 0) return (int)P2_OK;
+        if (!d_leaves || !d_indices || !d_cap || !d_status || (depth && !d_siblings)) return set_error("null argument"), P2_ERR_INVALID;
+        if (int rc = pick_device(device)) return rc;
+        return mt_verify((const u64*)d_leaves, leaf_len, (const u64*)d_indices, (const u64*)d_siblings, depth, (const u64*)d_cap, cap_height, n, d_status, (hipStream_t)stream);
+    });
+}
+// Bench hook (tools/gpu_merkle_bench.py): one tree build on buffers the caller owns.  d_dig: 8 * num_leaves words, the level
+// layout.  with_transpose = 0: merkle_build on d_scratch, column-major [leaf_len][num_leaves] (the build of p2_gpu_merkle_cap);
+// otherwise k_mt_transpose of the row-major d_leaves into d_scratch first (the build of p2_merkle_tree_new).
+int p2_gpu_merkle_build_device(const uint64_t* d_leaves, size_t num_leaves, size_t leaf_len, int cap_height, int with_transpose, uint64_t* d_scratch, uint64_t* d_dig,
+                               int device, void* stream) {
+    return guarded_rc([&]() -> int {
+        const u32 bits = mt::check_shape(num_leaves, leaf_len, cap_height);
+        if ((with_transpose && !d_leaves) || !d_scratch || !d_dig) return set_error("null argument"), P2_ERR_INVALID;
+        if (int rc = pick_device(device)) return rc;
+        Lane L;
+        L.stream = (hipStream_t)stream;
+        Domain D;
+        D.cap_height = (u32)cap_height;
+        Tree t;
+        t.bits = bits;
+        t.dig = (u64*)d_dig;
+        if (with_transpose && mt_transpose(L, (const u64*)d_leaves, num_leaves, (u32)leaf_len, (u64*)d_scratch)) return P2_ERR_HIP;
+        return merkle_build(L, D, (const u64*)d_scratch, (u32)leaf_len, (u32)leaf_len, num_leaves, 0, t, 1);
+    });
 }
 
 // ---- batched verification
