@@ -463,7 +463,9 @@ pub mod plonk {
             pub fn add_lookup_table_from_pairs(&mut self, table: Arc<Vec<(u16, u16)>>) -> usize {
                 // (u16, u16) has no guaranteed layout (repr(Rust)): flatten to the [in, out, in, out, ...] array the C ABI reads
                 let flat: Vec<u16> = table.iter().flat_map(|&(a, b)| [a, b]).collect();
-                unsafe { ffi::p2_builder_add_lookup_table_from_pairs(self.h, flat.as_ptr(), table.len()) }
+                let i = unsafe { ffi::p2_builder_add_lookup_table_from_pairs(self.h, flat.as_ptr(), table.len()) };
+                assert!(i != usize::MAX, "{}", last_error());   // an empty table (upstream panics too)
+                i
             }
             /// circuit_aes.rs:182,193,250,357; circuit_gcm.rs:403,424.
             pub fn add_lookup_from_index(&mut self, looking_in: Target, lut_index: usize) -> Target {

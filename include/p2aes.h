@@ -123,7 +123,8 @@ int p2_builder_is_less_than(p2_builder*, p2_target x, p2_target y, size_t num_bi
  * circuit ends with the trailer u64 k || k x u64 value.  A circuit with none is built exactly as before.  P2_ERR_INVALID
  * for a target the builder never handed out. */
 int p2_builder_register_public_input(p2_builder*, p2_target t);
-/* pairs = n_pairs * (input u16, output u16); returns the LUT index (an identical table is re-used) */
+/* pairs = n_pairs * (input u16, output u16); returns the LUT index (an identical table is re-used);
+ * an empty table (n_pairs = 0) is refused: (size_t)-1, p2_last_error set */
 size_t p2_builder_add_lookup_table_from_pairs(p2_builder*, const uint16_t* pairs, size_t n_pairs);
 /* returns the looked-up output target; (size_t)-1 lut index is an error -> returns UINT64_MAX */
 p2_target p2_builder_add_lookup_from_index(p2_builder*, p2_target looking_in, size_t lut_index);

@@ -231,6 +231,8 @@ class Builder:
     # ---- gadgets/lookup.rs
     def add_lookup_table_from_pairs(self, table):
         table = [tuple(p) for p in table]
+        if not table:
+            raise ValueError("lookup table is empty")
         if table in self.luts:
             return self.luts.index(table)
         self.luts.append(table)

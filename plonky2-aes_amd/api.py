@@ -419,7 +419,10 @@ class CircuitBuilder:
 
     def add_lookup_table_from_pairs(self, pairs):
         flat = (C.c_uint16 * (2 * len(pairs)))(*[v for p in pairs for v in p])
-        return lib().p2_builder_add_lookup_table_from_pairs(self._h, flat, len(pairs))
+        i = lib().p2_builder_add_lookup_table_from_pairs(self._h, flat, len(pairs))
+        if i == C.c_size_t(-1).value:
+            raise P2Error(_err())
+        return i
 
     def add_lookup_from_index(self, looking_in, lut_index):
         t = lib().p2_builder_add_lookup_from_index(self._h, looking_in, lut_index)

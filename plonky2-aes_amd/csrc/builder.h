@@ -211,6 +211,8 @@ class CircuitBuilder {
 
     // ---- lookups (plonky2 gadgets/lookup.rs) ------------------------------------------------------
     size_t add_lookup_table_from_pairs(const std::vector<std::pair<u16, u16>>& table) {
+        // an empty table has no LookupTableGate row to stand on: (size() - 1) / LUT_SLOTS + 1 in add_all_lookups would wrap
+        if (table.empty()) throw std::runtime_error("lookup table is empty");
         for (size_t i = 0; i < luts_.size(); i++)
             if (luts_[i] == table) return i;
         luts_.push_back(table);

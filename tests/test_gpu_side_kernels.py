@@ -11,6 +11,7 @@ import random
 import pytest
 
 import circuits
+from edge_circuits import chain_ops as _chain, chain_value as _chain_value
 
 pytestmark = pytest.mark.gpu
 P = 0xFFFFFFFF00000001
@@ -25,21 +26,6 @@ def gpu(pkg):
 
 
 # ---------------------------------------------------------------------------------------------- whole proofs
-def _chain(b, x, y, n_ops):
-    """A dependent chain of arithmetic operations: one row's worth of padding per operation or so (the sizes are asserted)."""
-    acc = x
-    for k in range(n_ops):
-        acc = b.mul_const_add(k + 3, acc, y) if k & 1 else b.mul(acc, y)
-    return acc
-
-
-def _chain_value(xv, yv, n_ops):
-    acc = xv
-    for k in range(n_ops):
-        acc = ((k + 3) * acc + yv) % P if k & 1 else acc * yv % P
-    return acc
-
-
 def _padded(pkg, luts, n_ops, seeds):
     """`luts` small lookup tables (0: none, 1: the S-box, 2: S-box and the one-bit right shift) next to an arithmetic chain that
     sets the number of rows; the chain's end value is asserted in the witness."""
