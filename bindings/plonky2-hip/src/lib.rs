@@ -679,6 +679,75 @@ pub mod pod2 {
             }
         }
     }
+    /// Schnorr signatures on ecGFp5 with a Poseidon challenge (csrc/schnorr.h; this project's own scheme, UNPINNED against pod2's
+    /// signature bytes): `p2_schnorr_*` on the host and the `verify_schnorr_signature` gadget.
+    pub mod schnorr {
+        use super::curve::{BigUInt320Target, Point, PointTarget};
+        use crate::ffi;
+        use crate::field::types::Field;
+        use crate::hash::hash_types::HashOutTarget;
+        use crate::iop::target::{BoolTarget, Target};
+        use crate::plonk::circuit_builder::CircuitBuilder;
+
+        /// s as five little-endian limbs, then the four challenge words.
+        #[derive(Copy, Clone, Debug, Eq, PartialEq)]
+        pub struct Signature { pub s: [u64; 5], pub e: [u64; 4] }
+        #[derive(Copy, Clone, Debug, Eq, PartialEq)]
+        pub enum Verdict { Accepted, Rejected, Malformed }
+        fn pack(p: &Point) -> [u64; 10] { let mut o = [0u64; 10]; o[..5].copy_from_slice(&p.x); o[5..].copy_from_slice(&p.u); o }
+        /// (a b + c) mod the group order for arbitrary 320-bit operands.
+        pub fn scalar_muladd(a: &[u64; 5], b: &[u64; 5], c: &[u64; 5]) -> [u64; 5] {
+            let mut o = [0u64; 5];
+            unsafe { ffi::p2_ecgfp5_scalar_muladd(a.as_ptr(), b.as_ptr(), c.as_ptr(), o.as_mut_ptr()) };
+            o
+        }
+        /// Sign with a caller-supplied nonce in [1, n); `Err` for a key or nonce outside [1, n) or a message word not below p.
+        pub fn sign(sk: &[u64; 5], msg: &[u64], nonce: &[u64; 5]) -> Result<Signature, String> {
+            let mut sig = [0u64; 9];
+            let mut status: std::os::raw::c_int = -1;
+            let rc = unsafe { ffi::p2_schnorr_sign(sk.as_ptr(), nonce.as_ptr(), msg.as_ptr(), msg.len(), sig.as_mut_ptr(), core::ptr::null_mut(), &mut status) };
+            if rc != ffi::P2_OK { return Err(crate::last_error()); }
+            if status != 0 { return Err("secret key and nonce must be in [1, n), message words below p".into()); }
+            Ok(Signature { s: core::array::from_fn(|i| sig[i]), e: core::array::from_fn(|i| sig[5 + i]) })
+        }
+        pub fn verify(pk: &Point, msg: &[u64], sig: &Signature) -> Result<Verdict, String> {
+            let mut w = [0u64; 9];
+            w[..5].copy_from_slice(&sig.s);
+            w[5..].copy_from_slice(&sig.e);
+            let mut status: std::os::raw::c_int = -1;
+            let rc = unsafe { ffi::p2_schnorr_verify(pack(pk).as_ptr(), msg.as_ptr(), msg.len(), w.as_ptr(), &mut status) };
+            if rc != ffi::P2_OK { return Err(crate::last_error()); }
+            Ok(match status { 0 => Verdict::Accepted, 1 => Verdict::Rejected, _ => Verdict::Malformed })
+        }
+        #[derive(Clone, Debug)]
+        pub struct SignatureTarget { pub s: BigUInt320Target, pub e: HashOutTarget }
+        pub trait CircuitBuilderSchnorr {
+            fn add_virtual_schnorr_signature_target(&mut self) -> SignatureTarget;
+            /// Constrains hash(R' | pk | msg) = e for R' = s G + e (-pk) and returns R'.  Not checked in the circuit: s below the
+            /// group order, pk in the group.
+            fn verify_schnorr_signature(&mut self, pk: &PointTarget, msg: &[Target], sig: &SignatureTarget) -> PointTarget;
+        }
+        impl<F: Field, const D: usize> CircuitBuilderSchnorr for CircuitBuilder<F, D> {
+            fn add_virtual_schnorr_signature_target(&mut self) -> SignatureTarget {
+                let mut bits = [0u64; 320];
+                let mut e = [0u64; 4];
+                let rc = unsafe { ffi::p2_builder_add_virtual_schnorr_signature(self.h, bits.as_mut_ptr(), e.as_mut_ptr()) };
+                assert!(rc == ffi::P2_OK, "{}", crate::last_error());
+                SignatureTarget { s: BigUInt320Target { bits: bits.iter().map(|t| BoolTarget::new_unsafe(Target(*t))).collect() }, e: HashOutTarget { elements: e.map(Target) } }
+            }
+            fn verify_schnorr_signature(&mut self, pk: &PointTarget, msg: &[Target], sig: &SignatureTarget) -> PointTarget {
+                let p: [u64; 10] = core::array::from_fn(|i| pk.0[i].0);
+                let m: Vec<u64> = msg.iter().map(|t| t.0).collect();
+                let b: Vec<u64> = sig.s.bits.iter().map(|t| t.target.0).collect();
+                assert!(b.len() == 320, "a signature holds 320 bits of s");
+                let e: [u64; 4] = core::array::from_fn(|i| sig.e.elements[i].0);
+                let mut r = [0u64; 10];
+                let rc = unsafe { ffi::p2_builder_verify_schnorr_signature(self.h, p.as_ptr(), m.as_ptr(), m.len(), b.as_ptr(), e.as_ptr(), r.as_mut_ptr()) };
+                assert!(rc == ffi::P2_OK, "{}", crate::last_error());
+                PointTarget(r.map(Target))
+            }
+        }
+    }
 }
 
 #[allow(unused)]

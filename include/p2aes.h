@@ -277,6 +277,31 @@ int p2_builder_elgamal_encrypt(p2_builder*, const p2_target pk[10], const p2_tar
 int p2_builder_hashed_elgamal_encrypt(p2_builder*, const p2_target pk[10], const p2_target nonce_bits[320], const p2_target msg[5],
                                       p2_target c0[10], p2_target ct[5]);
 
+/* ------------------------------------------------------------------ Schnorr signatures on ecGFp5 (host) */
+/* The scheme (csrc/schnorr.h; this project's own, UNPINNED against pod2's signature bytes):
+ *   keys       sk in [1, n), pk = sk G
+ *   challenge  e_words[4] = hash_n_to_hash_no_pad(R.x | R.u | pk.x | pk.u | msg), e = sum e_words[i] 2^(64 i)
+ *   sign       R = nonce G for a caller-supplied nonce in [1, n), s = (nonce + e sk) mod n; sig[9] = s (5 limbs) | e_words
+ *   verify     status 2 (malformed): s >= n, a word of e_words, msg or pk not below p, pk outside the group, pk neutral;
+ *              otherwise R' = s G + e (-pk): status 0 (accepted) iff the challenge of R' is e_words, else 1 (rejected).
+ * msg: msg_len canonical field elements, 0 <= msg_len <= 1024 (P2_ERR_INVALID above that).  The return value tells whether the
+ * call could run; *status is the scheme's answer.
+ *   scalar_muladd  out = (a b + c) mod n for arbitrary 320-bit a, b, c (five little-endian limbs each)
+ *   sign           *status 0, or 2 with sig (and pk) zeroed: sk or nonce outside [1, n), a message word not below p.  pk: NULL, or
+ *                  receives sk G. */
+void p2_ecgfp5_scalar_muladd(const uint64_t a[5], const uint64_t b[5], const uint64_t c[5], uint64_t out[5]);
+int p2_schnorr_challenge(const uint64_t r[10], const uint64_t pk[10], const uint64_t* msg, size_t msg_len, uint64_t e[4]);
+int p2_schnorr_sign(const uint64_t sk[5], const uint64_t nonce[5], const uint64_t* msg, size_t msg_len, uint64_t sig[9], uint64_t pk[10], int* status);
+int p2_schnorr_verify(const uint64_t pk[10], const uint64_t* msg, size_t msg_len, const uint64_t sig[9], int* status);
+/* The gadget: no new gate.  add_virtual_schnorr_signature: s as 320 boolean bit targets (add_virtual_biguint320_target) and the
+ * four challenge words.  verify_schnorr_signature constrains hash(R' | pk | msg) = e for R' = s G + e (-pk), with e's bits from
+ * the canonical 64-bit split_le of every word; r: NULL, or receives the targets of R'.  Works with set_ec_gate on and off; pk is
+ * any point target.  NOT checked in the circuit: s < n, and that pk is in the group (add_virtual_point_target checks the curve
+ * equation only) -- a circuit that takes pk as a public input relies on p2_schnorr_verify's checks outside. */
+int p2_builder_add_virtual_schnorr_signature(p2_builder*, p2_target s_bits[320], p2_target e[4]);
+int p2_builder_verify_schnorr_signature(p2_builder*, const p2_target pk[10], const p2_target* msg, size_t msg_len, const p2_target s_bits[320],
+                                        const p2_target e[4], p2_target r[10]);
+
 /* ------------------------------------------------------------------ self-test (host) */
 /* Checks the host build of the arithmetic the kernels share with it: the carry-chain reduction against 128-bit
  * arithmetic (random and extreme inputs), and the restructured Poseidon (poseidon_fast.h: lazy reduction, sparse partial
@@ -606,6 +631,28 @@ int p2_merkle_verify_batch_device(const uint64_t* d_leaves, size_t leaf_len, con
  * Asynchronous on `stream`. */
 int p2_gpu_merkle_build_device(const uint64_t* d_leaves, size_t num_leaves, size_t leaf_len, int cap_height, int with_transpose,
                                uint64_t* d_scratch, uint64_t* d_dig, int device, void* stream);
+
+/* ------------------------------------------------------------------ native ecGFp5 and Schnorr signatures in GPU batches */
+/* One thread per item (csrc/kernels_schnorr.h); rows are contiguous: scalars [count][5], points [count][10], messages
+ * [count][msg_len] (one msg_len per call, at most 1024), signatures [count][9]; status int[count].  The host-pointer forms copy
+ * in and out and return when done; the _device forms take raw device pointers and are asynchronous on `stream` (NULL: the
+ * default stream).  Secret keys and nonces given to p2_schnorr_sign_batch_device live in device memory the caller owns;
+ * zeroising it is the caller's business.
+ *   mul_batch     out[i] = k[i] P[i] for any 320-bit k[i]; status 2 (row zeroed) for a P[i] with a word not below p or outside
+ *                 the group, else 0 -- p2_ecgfp5_mul item for item
+ *   sign_batch    p2_schnorr_sign item for item; pk: NULL, or receives the public keys
+ *   verify_batch  p2_schnorr_verify item for item */
+int p2_ecgfp5_mul_batch(const uint64_t* k, const uint64_t* p, size_t count, uint64_t* out, int* status, int device);
+int p2_ecgfp5_mul_batch_device(const uint64_t* d_k, const uint64_t* d_p, size_t count, uint64_t* d_out, int* d_status, int device, void* stream);
+int p2_schnorr_sign_batch(const uint64_t* sk, const uint64_t* nonce, const uint64_t* msg, size_t msg_len, size_t count, uint64_t* sig, uint64_t* pk,
+                          int* status, int device);
+int p2_schnorr_sign_batch_device(const uint64_t* d_sk, const uint64_t* d_nonce, const uint64_t* d_msg, size_t msg_len, size_t count, uint64_t* d_sig,
+                                 uint64_t* d_pk, int* d_status, int device, void* stream);
+int p2_schnorr_verify_batch(const uint64_t* pk, const uint64_t* msg, size_t msg_len, const uint64_t* sig, size_t count, int* status, int device);
+int p2_schnorr_verify_batch_device(const uint64_t* d_pk, const uint64_t* d_msg, size_t msg_len, const uint64_t* d_sig, size_t count, int* d_status,
+                                   int device, void* stream);
+/* test entry: out[i] = (a[i] b[i] + c[i]) mod n on the device, one thread per triple */
+int p2_gpu_ecgfp5_scalar_muladd(const uint64_t* a, const uint64_t* b, const uint64_t* c, size_t count, uint64_t* out, int device);
 
 /* ------------------------------------------------------------------ GPU primitives (parity tests / microbench) */
 int p2_gpu_device_count(void);

@@ -310,6 +310,19 @@ def lib():
         "p2_merkle_verify_batch": (C.c_int, [u64p, sz, u64p, u64p, sz, u64p, C.c_int, sz, C.POINTER(C.c_int), C.c_int]),
         "p2_merkle_verify_batch_device": (C.c_int, [vp, sz, vp, vp, sz, vp, C.c_int, sz, vp, C.c_int, vp]),
         "p2_gpu_merkle_build_device": (C.c_int, [vp, sz, sz, C.c_int, C.c_int, vp, vp, C.c_int, vp]),
+        "p2_ecgfp5_scalar_muladd": (None, [u64p, u64p, u64p, u64p]),
+        "p2_gpu_ecgfp5_scalar_muladd": (C.c_int, [u64p, u64p, u64p, sz, u64p, C.c_int]),
+        "p2_schnorr_challenge": (C.c_int, [u64p, u64p, u64p, sz, u64p]),
+        "p2_schnorr_sign": (C.c_int, [u64p, u64p, u64p, sz, u64p, u64p, C.POINTER(C.c_int)]),
+        "p2_schnorr_verify": (C.c_int, [u64p, u64p, sz, u64p, C.POINTER(C.c_int)]),
+        "p2_builder_add_virtual_schnorr_signature": (C.c_int, [vp, u64p, u64p]),
+        "p2_builder_verify_schnorr_signature": (C.c_int, [vp, u64p, u64p, sz, u64p, u64p, u64p]),
+        "p2_ecgfp5_mul_batch": (C.c_int, [u64p, u64p, sz, u64p, C.POINTER(C.c_int), C.c_int]),
+        "p2_ecgfp5_mul_batch_device": (C.c_int, [vp, vp, sz, vp, vp, C.c_int, vp]),
+        "p2_schnorr_sign_batch": (C.c_int, [u64p, u64p, u64p, sz, sz, u64p, u64p, C.POINTER(C.c_int), C.c_int]),
+        "p2_schnorr_sign_batch_device": (C.c_int, [vp, vp, vp, sz, sz, vp, vp, vp, C.c_int, vp]),
+        "p2_schnorr_verify_batch": (C.c_int, [u64p, u64p, sz, u64p, sz, C.POINTER(C.c_int), C.c_int]),
+        "p2_schnorr_verify_batch_device": (C.c_int, [vp, vp, sz, vp, sz, vp, C.c_int, vp]),
     }
     missing = []
     for name, (res, args) in sig.items():
@@ -626,6 +639,25 @@ class CircuitBuilder:
             raise P2Error(_err())
         return list(c0), list(ct)
 
+    # ---- Schnorr signatures on ecGFp5 (csrc/schnorr.h).  A signature target is (s_bits, e): 320 bit targets and a hash.
+    def add_virtual_schnorr_signature_target(self):
+        bits, e = (u64 * 320)(), (u64 * 4)()
+        if lib().p2_builder_add_virtual_schnorr_signature(self._h, bits, e):
+            raise P2Error(_err())
+        return list(bits), list(e)
+
+    def verify_schnorr_signature(self, pk, msg, sig):
+        """Constrains hash(R' | pk | msg) = e for R' = s G + e (-pk) and returns R' (ten targets).  pk: any point target; msg: a
+        list of targets; sig: what add_virtual_schnorr_signature_target gave.  Not checked in the circuit: s below the group
+        order, pk in the group (see include/p2aes.h)."""
+        bits, e = sig
+        if len(pk) != 10 or len(bits) != 320 or len(e) != 4:
+            raise P2Error("verify_schnorr_signature takes a point of 10 targets and a signature of 320 bits and 4 words")
+        r = (u64 * 10)()
+        if lib().p2_builder_verify_schnorr_signature(self._h, _arr(pk), _arr(msg) if msg else None, len(msg), _arr(bits), _arr(e), r):
+            raise P2Error(_err())
+        return list(r)
+
     def build(self):
         blob, n = u8p(), sz()
         if lib().p2_builder_build(self._h, C.byref(blob), C.byref(n)):
@@ -668,6 +700,12 @@ class PartialWitness:
 
     def set_hash_target(self, target, words):
         self.set_target_arr(target, _hash4(words))
+
+    def set_schnorr_signature_target(self, target, sig):
+        """target = (s_bits, e) of add_virtual_schnorr_signature_target; sig = (s, e_words) as schnorr.sign returns it"""
+        s, e = sig
+        self.set_biguint320_target(target[0], s)
+        self.set_hash_target(target[1], e)
 
     def set_cap_target(self, targets, cap):               # plonky2 WitnessHashes::set_cap_target
         if len(targets) != len(cap):
@@ -1404,6 +1442,154 @@ class ecgfp5:
         if lib().p2_hashed_elgamal_decrypt(_sc(sk.value), _pt(ct[0]), _arr(list(ct[1])), out):
             raise P2Error(_err())
         return tuple(out)
+
+    @staticmethod
+    def scalar_muladd(a, b, c):
+        """(a b + c) mod the group order for any a, b, c below 2^320"""
+        out = (u64 * 5)()
+        lib().p2_ecgfp5_scalar_muladd(_sc(a), _sc(b), _sc(c), out)
+        return _int5(out)
+
+    @staticmethod
+    def mul_batch(scalars, points, device=0):
+        """[k P for k, P in zip(scalars, points)] on a GPU (p2_ecgfp5_mul_batch), with one status per item: 0, or 2 (and the
+        neutral as output) for a point with a word not below p or outside the group.  device=None: a host loop."""
+        ks, n, _ = _rows([_sc_words(k) for k in scalars], "scalars")
+        ps, n_p, _ = _rows([list(p[0]) + list(p[1]) for p in points], "points")
+        if n != n_p:
+            raise P2Error("mul_batch: one point per scalar")
+        if n == 0:
+            return [], []
+        out, status = (u64 * (10 * n))(), (C.c_int * n)()
+        if device is None:
+            for i in range(n):
+                pt = _pt_out(ps[10 * i:10 * i + 10])
+                ok = all(w < P for w in pt[0] + pt[1]) and ecgfp5.is_in_subgroup(pt)
+                status[i] = 0 if ok else 2
+                if ok:
+                    out[10 * i:10 * i + 10] = list(sum(ecgfp5.mul(_int5(ks[5 * i:5 * i + 5]), pt), ()))
+        elif lib().p2_ecgfp5_mul_batch(ks, ps, n, out, status, device):
+            raise P2Error("p2_ecgfp5_mul_batch failed: " + _err())
+        return [_pt_out(out[10 * i:10 * i + 10]) for i in range(n)], list(status)
+
+    @staticmethod
+    def mul_batch_device(d_k, d_p, count, d_out, d_status, device=0, stream=None):
+        """Every buffer a raw device pointer (p2_ecgfp5_mul_batch_device); asynchronous on `stream`."""
+        if lib().p2_ecgfp5_mul_batch_device(d_k, d_p, count, d_out, d_status, device, stream):
+            raise P2Error("p2_ecgfp5_mul_batch_device failed: " + _err())
+
+
+def _int5(words):
+    return sum(int(words[i]) << (64 * i) for i in range(5))
+
+
+def _sc_words(k):
+    k = int(k)
+    if not 0 <= k < 1 << 320:
+        raise P2Error("a scalar is below 2^320")
+    return [(k >> (64 * i)) & (2**64 - 1) for i in range(5)]
+
+
+class schnorr:
+    """Schnorr signatures on ecGFp5 with a Poseidon challenge (csrc/schnorr.h; UNPINNED against pod2).
+    A secret key and a nonce are Python ints in [1, n); a public key is a Point; a message a list of canonical field elements
+    (at most 1024); a signature is (s, (e0, e1, e2, e3)).  Statuses: 0 accepted, 1 rejected, 2 malformed."""
+
+    ACCEPTED, REJECTED, MALFORMED = 0, 1, 2
+
+    @staticmethod
+    def _sig_words(sig):
+        s, e = sig
+        return _sc_words(s) + [int(w) for w in _hash4(e)]
+
+    @staticmethod
+    def _sig_out(buf):
+        return _int5(buf), tuple(int(w) for w in buf[5:9])
+
+    @staticmethod
+    def challenge(r, pk, msg):
+        msg = [int(w) for w in msg]
+        e = (u64 * 4)()
+        if lib().p2_schnorr_challenge(_pt(r), _pt(pk), _arr(msg) if msg else None, len(msg), e):
+            raise P2Error(_err())
+        return tuple(e)
+
+    @staticmethod
+    def sign(sk, msg, nonce=None):
+        """nonce=None draws one from ecgfp5.random_scalar() (the OS CSPRNG); a nonce must never sign two messages"""
+        if nonce is None:
+            nonce = ecgfp5.random_scalar()
+            while nonce == 0:
+                nonce = ecgfp5.random_scalar()
+        msg = [int(w) for w in msg]
+        sig, st = (u64 * 9)(), C.c_int()
+        if lib().p2_schnorr_sign(_arr(_sc_words(sk)), _arr(_sc_words(nonce)), _arr(msg) if msg else None, len(msg), sig, None, C.byref(st)):
+            raise P2Error(_err())
+        if st.value:
+            raise P2Error("schnorr.sign: the secret key and the nonce must be in [1, n), message words below p")
+        return schnorr._sig_out(sig)
+
+    @staticmethod
+    def verify(pk, msg, sig):
+        return schnorr.verify_batch([pk], [msg], [sig], device=None)[0]
+
+    @staticmethod
+    def sign_batch(sks, msgs, nonces, device=0):
+        """-> (signatures, public keys, statuses); a row with status 2 holds zeros.  device=None: the host twin."""
+        sk, n, _ = _rows([_sc_words(k) for k in sks], "secret keys")
+        ks, n_k, _ = _rows([_sc_words(k) for k in nonces], "nonces")
+        mg, n_m, msg_len = _rows(msgs, "messages")
+        if n != n_k or n != n_m:
+            raise P2Error("sign_batch: one nonce and one message per secret key")
+        if n == 0:
+            return [], [], []
+        sig, pk, status = (u64 * (9 * n))(), (u64 * (10 * n))(), (C.c_int * n)()
+        if device is None:
+            st = C.c_int()
+            for i in range(n):
+                m = C.cast(C.byref(mg, 8 * i * msg_len), u64p) if msg_len else None
+                if lib().p2_schnorr_sign(C.cast(C.byref(sk, 40 * i), u64p), C.cast(C.byref(ks, 40 * i), u64p), m, msg_len, C.cast(C.byref(sig, 72 * i), u64p),
+                                         C.cast(C.byref(pk, 80 * i), u64p), C.byref(st)):
+                    raise P2Error("p2_schnorr_sign failed: " + _err())
+                status[i] = st.value
+        elif lib().p2_schnorr_sign_batch(sk, ks, mg, msg_len, n, sig, pk, status, device):
+            raise P2Error("p2_schnorr_sign_batch failed: " + _err())
+        return ([schnorr._sig_out(sig[9 * i:9 * i + 9]) for i in range(n)], [_pt_out(pk[10 * i:10 * i + 10]) for i in range(n)], list(status))
+
+    @staticmethod
+    def verify_batch(pks, msgs, sigs, device=0):
+        """-> statuses.  Words of pk, msg and e may be any 64-bit value (such rows are malformed); s any value below 2^320.
+        device=None: the host twin."""
+        pk, n, _ = _rows([list(p[0]) + list(p[1]) for p in pks], "public keys")
+        mg, n_m, msg_len = _rows(msgs, "messages")
+        sg, n_s, _ = _rows([_sc_words(s[0]) + [int(w) for w in s[1]] for s in sigs], "signatures")
+        if n != n_m or n != n_s:
+            raise P2Error("verify_batch: one message and one signature per public key")
+        if n == 0:
+            return []
+        status = (C.c_int * n)()
+        if device is None:
+            st = C.c_int()
+            for i in range(n):
+                m = C.cast(C.byref(mg, 8 * i * msg_len), u64p) if msg_len else None
+                if lib().p2_schnorr_verify(C.cast(C.byref(pk, 80 * i), u64p), m, msg_len, C.cast(C.byref(sg, 72 * i), u64p), C.byref(st)):
+                    raise P2Error("p2_schnorr_verify failed: " + _err())
+                status[i] = st.value
+        elif lib().p2_schnorr_verify_batch(pk, mg, msg_len, sg, n, status, device):
+            raise P2Error("p2_schnorr_verify_batch failed: " + _err())
+        return list(status)
+
+    @staticmethod
+    def sign_batch_device(d_sk, d_nonce, d_msg, msg_len, count, d_sig, d_pk, d_status, device=0, stream=None):
+        """Every buffer a raw device pointer (p2_schnorr_sign_batch_device; d_pk may be None); asynchronous on `stream`.  The
+        secret keys and nonces stay in device memory the caller owns."""
+        if lib().p2_schnorr_sign_batch_device(d_sk, d_nonce, d_msg, msg_len, count, d_sig, d_pk, d_status, device, stream):
+            raise P2Error("p2_schnorr_sign_batch_device failed: " + _err())
+
+    @staticmethod
+    def verify_batch_device(d_pk, d_msg, msg_len, d_sig, count, d_status, device=0, stream=None):
+        if lib().p2_schnorr_verify_batch_device(d_pk, d_msg, msg_len, d_sig, count, d_status, device, stream):
+            raise P2Error("p2_schnorr_verify_batch_device failed: " + _err())
 
 
 class ECGFP5SecretKey:

@@ -10,6 +10,7 @@
 #include "merkle_host.h"
 #include "poseidon_cipher.h"
 #include "poseidon_fast.h"
+#include "schnorr.h"
 #include "verifier.h"
 #include "witness_check.h"
 #include "witness_schedule.h"
@@ -603,6 +604,45 @@ int p2_builder_hashed_elgamal_encrypt(p2_builder* b, const p2_target pk[10], con
     } catch (std::exception& e) {
         return set_error(e.what()), P2_ERR_INVALID;
     }
+}
+
+// ---- Schnorr signatures on ecGFp5 (schnorr.h): the host twins of p2_schnorr_*_batch, and the gadget
+void p2_ecgfp5_scalar_muladd(const uint64_t a[5], const uint64_t b[5], const uint64_t c[5], uint64_t out[5]) { ecsc::sc_muladd(a, b, c, out); }
+int p2_schnorr_challenge(const uint64_t r[10], const uint64_t pk[10], const uint64_t* msg, size_t msg_len, uint64_t e[4]) {
+    return guarded([&] {
+        if (msg_len > schnorr::MAX_MSG_LEN || (msg_len && !msg)) throw std::runtime_error("msg_len is at most 1024 words");
+        schnorr::challenge(pt_at(r), pt_at(pk), msg, msg_len, e);
+    });
+}
+int p2_schnorr_sign(const uint64_t sk[5], const uint64_t nonce[5], const uint64_t* msg, size_t msg_len, uint64_t sig[9], uint64_t pk[10], int* status) {
+    return guarded([&] {
+        if (!status || msg_len > schnorr::MAX_MSG_LEN || (msg_len && !msg)) throw std::runtime_error("msg_len is at most 1024 words, status not null");
+        ecgfp5::Affine pub;
+        *status = schnorr::sign(sc_at(sk), sc_at(nonce), msg, msg_len, sig, pk ? &pub : nullptr);
+        if (pk) pt_put(pub, pk);
+    });
+}
+int p2_schnorr_verify(const uint64_t pk[10], const uint64_t* msg, size_t msg_len, const uint64_t sig[9], int* status) {
+    return guarded([&] {
+        if (!status || msg_len > schnorr::MAX_MSG_LEN || (msg_len && !msg)) throw std::runtime_error("msg_len is at most 1024 words, status not null");
+        *status = schnorr::verify(pt_at(pk), msg, msg_len, sig);
+    });
+}
+int p2_builder_add_virtual_schnorr_signature(p2_builder* b, p2_target s_bits[320], p2_target e[4]) {
+    return guarded([&] {
+        const schnorr::SignatureTarget t = schnorr::add_virtual_signature_target(b->b);
+        for (size_t i = 0; i < t.s_bits.size(); i++) s_bits[i] = t.s_bits[i].target;
+        std::copy(t.e.begin(), t.e.end(), e);
+    });
+}
+int p2_builder_verify_schnorr_signature(p2_builder* b, const p2_target pk[10], const p2_target* msg, size_t msg_len, const p2_target s_bits[320], const p2_target e[4],
+                                        p2_target r[10]) {
+    return guarded([&] {
+        if (msg_len && !msg) throw std::runtime_error("null message");
+        const schnorr::SignatureTarget t{bits_at(s_bits), hash_at(e)};
+        const ecgfp5::PointTarget rp = schnorr::verify_signature_target(b->b, ptt_at(pk), std::vector<Target>(msg, msg + msg_len), t);
+        if (r) ptt_put(rp, r);
+    });
 }
 
 // ---- self-test

@@ -20,6 +20,7 @@
 #include "kernels_compress.h"
 #include "kernels_keccak.h"
 #include "kernels_merkle.h"
+#include "kernels_schnorr.h"
 #include "kernels_witness_io.h"
 #include "merkle_host.h"
 #include "verifier.h"
@@ -3241,6 +3242,127 @@ int p2_gpu_merkle_build_device(const uint64_t* d_leaves, size_t num_leaves, size
         t.dig = (u64*)d_dig;
         if (with_transpose && mt_transpose(L, (const u64*)d_leaves, num_leaves, (u32)leaf_len, (u64*)d_scratch)) return P2_ERR_HIP;
         return merkle_build(L, D, (const u64*)d_scratch, (u32)leaf_len, (u32)leaf_len, num_leaves, 0, t, 1);
+    });
+}
+
+// ---- native ecGFp5 in batches: scalar multiplication and Schnorr signatures (kernels_schnorr.h; the host twins are in schnorr.h)
+static const size_t SCHNORR_MAX_MSG_LEN = 1024;  // schnorr::MAX_MSG_LEN
+static EcWords ec_generator_words() {
+    EcWords g;
+    p2_ecgfp5_generator(g.w);
+    return g;
+}
+static int schnorr_shape(size_t msg_len) {
+    if (msg_len > SCHNORR_MAX_MSG_LEN) return set_error("msg_len is at most 1024 words"), P2_ERR_INVALID;
+    return P2_OK;
+}
+static int ec_mul_launch(const u64* d_k, const u64* d_p, size_t count, u64* d_out, int* d_status, hipStream_t stream) {
+    hipLaunchKernelGGL(k_ec_mul_batch, g1(count, 64), dim3(64), 0, stream, d_k, d_p, count, d_out, d_status);
+    HIPCHECK(hipGetLastError());
+    return P2_OK;
+}
+static int schnorr_sign_launch(const u64* d_sk, const u64* d_nonce, const u64* d_msg, size_t msg_len, size_t count, u64* d_sig, u64* d_pk, int* d_status, hipStream_t stream) {
+    hipLaunchKernelGGL(k_schnorr_sign, g1(count, 64), dim3(64), 0, stream, d_sk, d_nonce, d_msg, (u32)msg_len, count, ec_generator_words(), d_sig, d_pk, d_status);
+    HIPCHECK(hipGetLastError());
+    return P2_OK;
+}
+static int schnorr_verify_launch(const u64* d_pk, const u64* d_msg, size_t msg_len, const u64* d_sig, size_t count, int* d_status, hipStream_t stream) {
+    hipLaunchKernelGGL(k_schnorr_verify, g1(count, 64), dim3(64), 0, stream, d_pk, d_msg, (u32)msg_len, d_sig, count, ec_generator_words(), d_status);
+    HIPCHECK(hipGetLastError());
+    return P2_OK;
+}
+int p2_ecgfp5_mul_batch(const uint64_t* k, const uint64_t* p, size_t count, uint64_t* out, int* status, int device) {
+    return guarded_rc([&]() -> int {
+        if (count == 0) return (int)P2_OK;
+        if (!k || !p || !out || !status) return set_error("null argument"), P2_ERR_INVALID;
+        if (int rc = pick_device(device)) return rc;
+        Allocs tmp;
+        u64 *d_k, *d_p, *d_out;
+        int* d_st;
+        if (upload(tmp, &d_k, (const u64*)k, 5 * count) || upload(tmp, &d_p, (const u64*)p, 10 * count) || dalloc(tmp, &d_out, 10 * count) || dalloc(tmp, &d_st, count)) return P2_ERR_HIP;
+        if (int rc = ec_mul_launch(d_k, d_p, count, d_out, d_st, nullptr)) return rc;
+        HIPCHECK(hipMemcpy(out, d_out, 10 * count * 8, hipMemcpyDeviceToHost));
+        HIPCHECK(hipMemcpy(status, d_st, count * sizeof(int), hipMemcpyDeviceToHost));
+        return (int)P2_OK;
+    });
+}
+int p2_ecgfp5_mul_batch_device(const uint64_t* d_k, const uint64_t* d_p, size_t count, uint64_t* d_out, int* d_status, int device, void* stream) {
+    return guarded_rc([&]() -> int {
+        if (count == 0) return (int)P2_OK;
+        if (!d_k || !d_p || !d_out || !d_status) return set_error("null argument"), P2_ERR_INVALID;
+        if (int rc = pick_device(device)) return rc;
+        return ec_mul_launch((const u64*)d_k, (const u64*)d_p, count, (u64*)d_out, d_status, (hipStream_t)stream);
+    });
+}
+int p2_schnorr_sign_batch(const uint64_t* sk, const uint64_t* nonce, const uint64_t* msg, size_t msg_len, size_t count, uint64_t* sig, uint64_t* pk, int* status, int device) {
+    return guarded_rc([&]() -> int {
+        if (int rc = schnorr_shape(msg_len)) return rc;
+        if (count == 0) return (int)P2_OK;
+        if (!sk || !nonce || !sig || !status || (msg_len && !msg)) return set_error("null argument"), P2_ERR_INVALID;
+        if (int rc = pick_device(device)) return rc;
+        Allocs tmp;
+        u64 *d_sk, *d_k, *d_msg, *d_sig, *d_pk = nullptr;
+        int* d_st;
+        if (upload(tmp, &d_sk, (const u64*)sk, 5 * count) || upload(tmp, &d_k, (const u64*)nonce, 5 * count) || upload(tmp, &d_msg, (const u64*)msg, msg_len * count) ||
+            dalloc(tmp, &d_sig, 9 * count) || (pk && dalloc(tmp, &d_pk, 10 * count)) || dalloc(tmp, &d_st, count))
+            return P2_ERR_HIP;
+        if (int rc = schnorr_sign_launch(d_sk, d_k, d_msg, msg_len, count, d_sig, d_pk, d_st, nullptr)) return rc;
+        HIPCHECK(hipMemcpy(sig, d_sig, 9 * count * 8, hipMemcpyDeviceToHost));
+        if (pk) HIPCHECK(hipMemcpy(pk, d_pk, 10 * count * 8, hipMemcpyDeviceToHost));
+        HIPCHECK(hipMemcpy(status, d_st, count * sizeof(int), hipMemcpyDeviceToHost));
+        return (int)P2_OK;
+    });
+}
+int p2_schnorr_sign_batch_device(const uint64_t* d_sk, const uint64_t* d_nonce, const uint64_t* d_msg, size_t msg_len, size_t count, uint64_t* d_sig, uint64_t* d_pk,
+                                 int* d_status, int device, void* stream) {
+    return guarded_rc([&]() -> int {
+        if (int rc = schnorr_shape(msg_len)) return rc;
+        if (count == 0) return (int)P2_OK;
+        if (!d_sk || !d_nonce || !d_sig || !d_status || (msg_len && !d_msg)) return set_error("null argument"), P2_ERR_INVALID;
+        if (int rc = pick_device(device)) return rc;
+        return schnorr_sign_launch((const u64*)d_sk, (const u64*)d_nonce, (const u64*)d_msg, msg_len, count, (u64*)d_sig, (u64*)d_pk, d_status, (hipStream_t)stream);
+    });
+}
+int p2_schnorr_verify_batch(const uint64_t* pk, const uint64_t* msg, size_t msg_len, const uint64_t* sig, size_t count, int* status, int device) {
+    return guarded_rc([&]() -> int {
+        if (int rc = schnorr_shape(msg_len)) return rc;
+        if (count == 0) return (int)P2_OK;
+        if (!pk || !sig || !status || (msg_len && !msg)) return set_error("null argument"), P2_ERR_INVALID;
+        if (int rc = pick_device(device)) return rc;
+        Allocs tmp;
+        u64 *d_pk, *d_msg, *d_sig;
+        int* d_st;
+        if (upload(tmp, &d_pk, (const u64*)pk, 10 * count) || upload(tmp, &d_msg, (const u64*)msg, msg_len * count) || upload(tmp, &d_sig, (const u64*)sig, 9 * count) ||
+            dalloc(tmp, &d_st, count))
+            return P2_ERR_HIP;
+        if (int rc = schnorr_verify_launch(d_pk, d_msg, msg_len, d_sig, count, d_st, nullptr)) return rc;
+        HIPCHECK(hipMemcpy(status, d_st, count * sizeof(int), hipMemcpyDeviceToHost));
+        return (int)P2_OK;
+    });
+}
+int p2_schnorr_verify_batch_device(const uint64_t* d_pk, const uint64_t* d_msg, size_t msg_len, const uint64_t* d_sig, size_t count, int* d_status, int device, void* stream) {
+    return guarded_rc([&]() -> int {
+        if (int rc = schnorr_shape(msg_len)) return rc;
+        if (count == 0) return (int)P2_OK;
+        if (!d_pk || !d_sig || !d_status || (msg_len && !d_msg)) return set_error("null argument"), P2_ERR_INVALID;
+        if (int rc = pick_device(device)) return rc;
+        return schnorr_verify_launch((const u64*)d_pk, (const u64*)d_msg, msg_len, (const u64*)d_sig, count, d_status, (hipStream_t)stream);
+    });
+}
+// test entry: out[i] = (a[i] b[i] + c[i]) mod n, one thread per triple
+int p2_gpu_ecgfp5_scalar_muladd(const uint64_t* a, const uint64_t* b, const uint64_t* c, size_t count, uint64_t* out, int device) {
+    return guarded_rc([&]() -> int {
+        if (count == 0) return (int)P2_OK;
+        if (!a || !b || !c || !out) return set_error("null argument"), P2_ERR_INVALID;
+        if (int rc = pick_device(device)) return rc;
+        Allocs tmp;
+        u64 *d_a, *d_b, *d_c, *d_out;
+        if (upload(tmp, &d_a, (const u64*)a, 5 * count) || upload(tmp, &d_b, (const u64*)b, 5 * count) || upload(tmp, &d_c, (const u64*)c, 5 * count) || dalloc(tmp, &d_out, 5 * count))
+            return P2_ERR_HIP;
+        hipLaunchKernelGGL(k_ec_scalar_muladd, g1(count, 64), dim3(64), 0, nullptr, d_a, d_b, d_c, count, d_out);
+        HIPCHECK(hipGetLastError());
+        HIPCHECK(hipMemcpy(out, d_out, 5 * count * 8, hipMemcpyDeviceToHost));
+        return (int)P2_OK;
     });
 }
 
