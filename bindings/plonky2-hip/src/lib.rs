@@ -556,6 +556,25 @@ pub mod plonk {
             pub fn verify_merkle_proof<H>(&mut self, leaf_data: Vec<Target>, leaf_index_bits: &[BoolTarget], merkle_root: HashOutTarget, proof: &MerkleProofTarget) {
                 self.verify_merkle_proof_to_cap::<H>(leaf_data, leaf_index_bits, &MerkleCapTarget(vec![merkle_root]), proof)
             }
+            /// Not upstream's: the tree with cap `old_cap` holds `old_leaf` at the index; returns the cap of the same tree with
+            /// `new_leaf` there.  Two walks over the same siblings and bits; the siblings are one item of `p2_merkle_tree_update`'s trace.
+            pub fn merkle_update_to_cap<H>(&mut self, old_leaf: Vec<Target>, new_leaf: Vec<Target>, leaf_index_bits: &[BoolTarget], old_cap: &MerkleCapTarget, proof: &MerkleProofTarget) -> MerkleCapTarget {
+                assert!(old_cap.0.len().is_power_of_two(), "the cap must hold a power of two of hashes");
+                assert!(old_leaf.len() == new_leaf.len(), "the old and the new leaf must have one length");
+                let old: Vec<u64> = old_leaf.iter().map(|t| t.0).collect();
+                let new: Vec<u64> = new_leaf.iter().map(|t| t.0).collect();
+                let bits: Vec<u64> = leaf_index_bits.iter().map(|b| b.target.0).collect();
+                let cap: Vec<u64> = old_cap.0.iter().flat_map(|h| h.elements.iter().map(|t| t.0)).collect();
+                let sib: Vec<u64> = proof.siblings.iter().flat_map(|h| h.elements.iter().map(|t| t.0)).collect();
+                let h = old_cap.0.len().trailing_zeros() as std::os::raw::c_int;
+                let mut out = vec![0u64; cap.len()];
+                let rc = unsafe { ffi::p2_builder_merkle_update_to_cap(self.h, old.as_ptr(), new.as_ptr(), old.len(), bits.as_ptr(), bits.len(), cap.as_ptr(), h, sib.as_ptr(), proof.siblings.len(), out.as_mut_ptr()) };
+                assert!(rc == ffi::P2_OK, "{}", last_error());
+                MerkleCapTarget(out.chunks(4).map(|c| HashOutTarget { elements: core::array::from_fn(|i| Target(c[i])) }).collect())
+            }
+            pub fn merkle_update<H>(&mut self, old_leaf: Vec<Target>, new_leaf: Vec<Target>, leaf_index_bits: &[BoolTarget], old_root: HashOutTarget, proof: &MerkleProofTarget) -> HashOutTarget {
+                self.merkle_update_to_cap::<H>(old_leaf, new_leaf, leaf_index_bits, &MerkleCapTarget(vec![old_root]), proof).0[0]
+            }
             /// Not upstream's: `multiply_point` (and `public_key`, `elgamal_encrypt`, `hashed_elgamal_encrypt` through it) as 320
             /// EcStepGate rows instead of arithmetic gates.  Off by default.
             pub fn set_ec_gate(&mut self, on: bool) {

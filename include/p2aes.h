@@ -205,6 +205,18 @@ int p2_builder_verify_merkle_proof_to_cap(p2_builder*, const p2_target* leaf, si
                                           const p2_target* cap, int cap_height, const p2_target* siblings, size_t n_siblings);
 int p2_builder_verify_merkle_proof(p2_builder*, const p2_target* leaf, size_t leaf_len, const p2_target* index_bits, size_t n_bits,
                                    const p2_target root[4], const p2_target* siblings, size_t n_siblings);
+/* A leaf update as a state transition (not upstream's): the tree with cap old_cap holds old_leaf at the index, and new_cap
+ * (4 * 2^cap_height targets, out) is the cap of the same tree with new_leaf there.  No new gate, witness op or kernel: the old walk
+ * is verify_merkle_proof_to_cap (cap-index bits made boolean with assert_bool), the new walk climbs from hash_or_noop(new_leaf)
+ * over the SAME siblings and index bits (one more PoseidonGate row per level), and new_cap[i] = select(i == cap index, new root,
+ * old_cap[i]) with indicators from a demux tree over the cap-index bits: 2 (2^h - 1) + 8 * 2^h more arithmetic ops for cap
+ * height h >= 1, none for a root.  Both leaves have leaf_len targets; the other lengths follow verify_merkle_proof_to_cap's rule
+ * (P2_ERR_INVALID otherwise, with nothing added).  The siblings a witness sets are item j's of p2_merkle_tree_update's trace.
+ *   merkle_update   the same from root to root */
+int p2_builder_merkle_update_to_cap(p2_builder*, const p2_target* old_leaf, const p2_target* new_leaf, size_t leaf_len, const p2_target* index_bits,
+                                    size_t n_bits, const p2_target* old_cap, int cap_height, const p2_target* siblings, size_t n_siblings, p2_target* new_cap);
+int p2_builder_merkle_update(p2_builder*, const p2_target* old_leaf, const p2_target* new_leaf, size_t leaf_len, const p2_target* index_bits, size_t n_bits,
+                             const p2_target old_root[4], const p2_target* siblings, size_t n_siblings, p2_target new_root[4]);
 /* Native Poseidon Merkle trees on the host (MerkleTree::new(leaves, cap_height).cap, tree.prove(i), verify_merkle_proof_to_cap):
  * the twin of the p2_merkle_tree_* calls below, for hosts without a device.  leaves: [num_leaves][leaf_len] canonical words,
  * row-major; the shape rules are p2_merkle_tree_new's.  cap: 4 * 2^cap_height words; siblings: 4 * (log2(num_leaves) -
@@ -214,6 +226,15 @@ int p2_native_merkle_cap(const uint64_t* leaves, size_t num_leaves, size_t leaf_
 int p2_native_merkle_prove(const uint64_t* leaves, size_t num_leaves, size_t leaf_len, int cap_height, size_t index, uint64_t* siblings);
 int p2_native_merkle_verify(const uint64_t* leaf, size_t leaf_len, size_t index, const uint64_t* siblings, size_t depth, const uint64_t* cap,
                             int cap_height, int* status);
+/* MerkleTree.update_batch on the host, and the DEFINITION of an update: the k writes leaves[indices[j]] <- new_leaves[j] one after
+ * the other, item j on the tree left by the items before it (duplicate indices are legal, the last write wins).  `leaves` is
+ * the whole set as p2_native_merkle_cap takes it and is updated in place; the tree is rebuilt from it on every call.  With
+ * siblings != NULL item j records [depth][4] words, the path siblings of indices[j] BEFORE its write (p2_native_merkle_prove at that
+ * moment), with root_after != NULL four words, cap entry indices[j] >> depth right AFTER it: cap j + 1 is cap j with that one
+ * entry replaced.  All or nothing: an index >= num_leaves or a word >= p is P2_ERR_INVALID, names the entry and changes
+ * nothing.  k = 0 is a no-op. */
+int p2_native_merkle_update(uint64_t* leaves, size_t num_leaves, size_t leaf_len, int cap_height, const uint64_t* indices, const uint64_t* new_leaves,
+                            size_t k, uint64_t* siblings, uint64_t* root_after);
 /* PoseidonEncryptTarget::<L>::build (poseidon-cipher/src/circuit.rs:49).  ks: 10 targets (x then u), m: 5*L,
  * nonce: 2, ct: 5*(L+1) */
 int p2_poseidon_cipher_build(p2_builder*, size_t L, p2_target* ks, p2_target* m, p2_target* nonce, p2_target* ct);
@@ -617,6 +638,24 @@ int p2_merkle_tree_cap(void* tree, uint64_t* cap, size_t cap_words);
 int p2_merkle_tree_prove_batch(void* tree, const uint64_t* indices, size_t n, uint64_t* siblings);
 int p2_merkle_tree_prove_batch_device(void* tree, const uint64_t* d_indices, size_t n, uint64_t* d_out, size_t out_stride_words, int* d_status,
                                       void* stream);
+/* tree.update: k ordered writes, leaf indices[j] <- leaves[j] ([k][leaf_len] words), with p2_native_merkle_update's semantics word
+ * for word; the shape of the tree does not change.  The trace (siblings [k][depth][4] as the path of indices[j] was before item j,
+ * root_after [k][4], cap entry indices[j] >> depth right after it) costs k * depth hashes, all of one level independent of each
+ * other; without it every changed node is hashed once.  All or nothing.  Host form: the trace is on iff siblings or root_after is
+ * non-null; a bad item is P2_ERR_INVALID, names the entry and is found on the host before anything is enqueued; returns with
+ * the update applied.  Device form: the trace is on iff d_siblings is non-null; item j's siblings go to d_siblings[j *
+ * sib_stride_words ..] and its root to d_root_after[j * root_stride_words ..] (may be NULL) with the strides of
+ * p2_merkle_tree_prove_batch_device, so a trace lands in the [batch][n_targets] matrix of p2_prove_batch_device; d_status[j] <- 0, 1
+ * (the index names no leaf; looked at first) or 2 (a word not below p), and where any is not 0 the tree and the trace buffers stay
+ * as they were -- a device flag turns the later kernels of the call into no-ops, the host does not synchronise.  Asynchronous on
+ * `stream`, behind the build and earlier updates; later _cap, _prove* and _update* calls order themselves behind it.  k < 2^32;
+ * k = 0 is a no-op.  Temporaries live in a block on the handle that only grows (growing it waits for the last update).
+ * Concurrent calls on ONE handle from several host threads are not supported.
+ * _last_update_hashes: the two_to_one calls of the last update (0 before the first), counted on the device; waits for it. */
+int p2_merkle_tree_update(void* tree, const uint64_t* indices, const uint64_t* leaves, size_t k, uint64_t* siblings, uint64_t* root_after);
+int p2_merkle_tree_update_device(void* tree, const uint64_t* d_indices, const uint64_t* d_leaves, size_t k, uint64_t* d_siblings, size_t sib_stride_words,
+                                 uint64_t* d_root_after, size_t root_stride_words, int* d_status, void* stream);
+int p2_merkle_tree_last_update_hashes(void* tree, uint64_t* hashes);
 /* verify_merkle_proof_to_cap for n paths against one cap: leaves [n][leaf_len], indices [n], siblings [n][depth][4], cap
  * 4 * 2^cap_height words.  status[i] <- 0 accepted, 1 rejected (also an index that names no leaf), 2 a leaf, sibling or cap word
  * that is not below p -- what p2_native_merkle_verify gives path for path.  cap_height 0 to 16, depth + cap_height at most 32.

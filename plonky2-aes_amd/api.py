@@ -310,6 +310,12 @@ def lib():
         "p2_merkle_verify_batch": (C.c_int, [u64p, sz, u64p, u64p, sz, u64p, C.c_int, sz, C.POINTER(C.c_int), C.c_int]),
         "p2_merkle_verify_batch_device": (C.c_int, [vp, sz, vp, vp, sz, vp, C.c_int, sz, vp, C.c_int, vp]),
         "p2_gpu_merkle_build_device": (C.c_int, [vp, sz, sz, C.c_int, C.c_int, vp, vp, C.c_int, vp]),
+        "p2_native_merkle_update": (C.c_int, [u64p, sz, sz, C.c_int, u64p, u64p, sz, u64p, u64p]),
+        "p2_merkle_tree_update": (C.c_int, [vp, u64p, u64p, sz, u64p, u64p]),
+        "p2_merkle_tree_update_device": (C.c_int, [vp, vp, vp, sz, vp, sz, vp, sz, vp, vp]),
+        "p2_merkle_tree_last_update_hashes": (C.c_int, [vp, u64p]),
+        "p2_builder_merkle_update_to_cap": (C.c_int, [vp, u64p, u64p, sz, u64p, sz, u64p, C.c_int, u64p, sz, u64p]),
+        "p2_builder_merkle_update": (C.c_int, [vp, u64p, u64p, sz, u64p, sz, u64p, u64p, sz, u64p]),
         "p2_ecgfp5_scalar_muladd": (None, [u64p, u64p, u64p, u64p]),
         "p2_gpu_ecgfp5_scalar_muladd": (C.c_int, [u64p, u64p, u64p, sz, u64p, C.c_int]),
         "p2_schnorr_challenge": (C.c_int, [u64p, u64p, u64p, sz, u64p]),
@@ -580,6 +586,25 @@ class CircuitBuilder:
 
     def verify_merkle_proof(self, leaf_data, index_bits, root, siblings):
         self.verify_merkle_proof_to_cap(leaf_data, index_bits, [root], siblings)
+
+    def merkle_update_to_cap(self, old_leaf, new_leaf, index_bits, old_cap, siblings):
+        """The tree with cap old_cap holds old_leaf at the index; returns the cap (a list of 2^h hashes) of the same tree with
+        new_leaf there.  siblings: one hash per path level as MerkleTree.update_batch(..., trace=True) records them."""
+        n_cap = len(old_cap)
+        if n_cap == 0 or n_cap & (n_cap - 1) or n_cap > 1 << 16 or any(len(h) != 4 for h in list(old_cap) + list(siblings)):
+            raise P2Error("merkle_update_to_cap: the cap is 2^h hashes (h <= 16) and every hash four targets")
+        if len(old_leaf) != len(new_leaf):
+            raise P2Error("merkle_update_to_cap: the old leaf has %d targets, the new one %d" % (len(old_leaf), len(new_leaf)))
+        flat = lambda hs: _arr([t for h in hs for t in h]) if hs else None  # noqa: E731
+        out = (u64 * (4 * n_cap))()
+        if lib().p2_builder_merkle_update_to_cap(self._h, _arr(old_leaf) if old_leaf else None, _arr(new_leaf) if new_leaf else None, len(old_leaf),
+                                                 _arr(index_bits) if index_bits else None, len(index_bits), flat(old_cap), n_cap.bit_length() - 1, flat(siblings),
+                                                 len(siblings), out):
+            raise P2Error(_err())
+        return [list(out[4 * i:4 * i + 4]) for i in range(n_cap)]
+
+    def merkle_update(self, old_leaf, new_leaf, index_bits, old_root, siblings):
+        return self.merkle_update_to_cap(old_leaf, new_leaf, index_bits, [old_root], siblings)[0]
 
     # ---- pod2 CircuitBuilderElliptic / CircuitBuilderBits and the ecgfp5 crate's builder traits.  A PointTarget is its ten
     # targets (x then u), a BigUInt320Target its 320 little-endian bit targets.
@@ -1204,6 +1229,52 @@ class MerkleTree:
     def prove(self, index):
         return self.prove_batch([index])[0]
 
+    def update_batch(self, indices, leaves, trace=False):
+        """The writes leaf indices[j] <- leaves[j] in order: item j acts on the tree left by the items before it, duplicates are
+        legal and the last write wins.  All or nothing: an index that names no leaf or a word not below p raises and changes
+        nothing.  trace=True returns a MerkleUpdateTrace (the siblings each item saw, the cap entry it left), else None."""
+        idx = [int(i) for i in indices]
+        flat, k, leaf_len = _rows(leaves, "leaves")
+        if k != len(idx) or any(not 0 <= i < 1 << 64 for i in idx):
+            raise P2Error("update_batch: one leaf per index, indices of 64 bits")
+        if k == 0:
+            return MerkleUpdateTrace(self, [], [], []) if trace else None
+        if leaf_len != self.leaf_len:
+            raise P2Error("update_batch: the tree's leaves have %d words, these %d" % (self.leaf_len, leaf_len))
+        d = self.depth
+        sib, roots = ((u64 * max(k * 4 * d, 1))(), (u64 * (4 * k))()) if trace else (None, None)
+        if self._h is None:
+            if lib().p2_native_merkle_update(self._leaves, self.num_leaves, self.leaf_len, self.cap_height, _arr(idx), flat, k, sib, roots):
+                raise P2Error("p2_native_merkle_update failed: " + _err())
+        elif lib().p2_merkle_tree_update(self._h, _arr(idx), flat, k, sib, roots):
+            raise P2Error("p2_merkle_tree_update failed: " + _err())
+        if not trace:
+            return None
+        return MerkleUpdateTrace(self, idx, [[list(sib[(j * d + l) * 4:(j * d + l) * 4 + 4]) for l in range(d)] for j in range(k)],
+                                 [list(roots[4 * j:4 * j + 4]) for j in range(k)])
+
+    def update(self, index, leaf, trace=False):
+        return self.update_batch([index], [leaf], trace)
+
+    def update_batch_device(self, d_indices, d_leaves, k, d_siblings, sib_stride_words, d_root_after, root_stride_words, d_status, stream=None):
+        """Device-resident updates (p2_merkle_tree_update_device): `d_indices` u64[k], `d_leaves` u64[k][leaf_len], `d_status` int32[k]
+        and, for a trace, `d_siblings` (item j at d_siblings + 8 * j * sib_stride_words bytes) and `d_root_after` are raw device
+        pointers; d_siblings = None: no trace.  Asynchronous on `stream`."""
+        if self._h is None:
+            raise P2Error("a host tree has no device forms")
+        if lib().p2_merkle_tree_update_device(self._h, d_indices, d_leaves, k, d_siblings, sib_stride_words, d_root_after, root_stride_words, d_status, stream):
+            raise P2Error("p2_merkle_tree_update_device failed: " + _err())
+
+    @property
+    def last_update_hashes(self):
+        """two_to_one calls of the last update on the device (0 before the first; a host tree does not count)"""
+        if self._h is None:
+            raise P2Error("a host tree does not count its hashes")
+        out = u64()
+        if lib().p2_merkle_tree_last_update_hashes(self._h, C.byref(out)):
+            raise P2Error("p2_merkle_tree_last_update_hashes failed: " + _err())
+        return out.value
+
     def prove_batch_device(self, d_indices, n, d_out, out_stride_words, d_status, stream=None):
         """Device-resident openings: `d_indices` u64[n], `d_out` (path i at d_out + 8 * i * out_stride_words bytes: 4 * depth words) and
         `d_status` int32[n] are raw device pointers; asynchronous on `stream` like prove_batch_device of a circuit."""
@@ -1211,6 +1282,23 @@ class MerkleTree:
             raise P2Error("a host tree has no device forms")
         if lib().p2_merkle_tree_prove_batch_device(self._h, d_indices, n, d_out, out_stride_words, d_status, stream):
             raise P2Error("p2_merkle_tree_prove_batch_device failed: " + _err())
+
+
+class MerkleUpdateTrace:
+    """What MerkleTree.update_batch(indices, leaves, trace=True) recorded: siblings[j] the path of indices[j] (one hash per level,
+    the lowest first) in the tree BEFORE item j, roots_after[j] cap entry indices[j] >> depth right AFTER it."""
+
+    def __init__(self, tree, indices, siblings, roots_after):
+        self.indices, self.siblings, self.roots_after, self._depth = indices, siblings, roots_after, tree.depth
+
+    def caps(self, initial_cap):
+        """the k + 1 caps: initial_cap, then the cap after every item"""
+        out = [[list(h) for h in initial_cap]]
+        for i, root in zip(self.indices, self.roots_after):
+            cap = [list(h) for h in out[-1]]
+            cap[i >> self._depth] = list(root)
+            out.append(cap)
+        return out
 
 
 class merkle:

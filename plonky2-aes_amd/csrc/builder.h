@@ -320,6 +320,43 @@ class CircuitBuilder {
                              const std::vector<HashOutTarget>& siblings) {
         verify_merkle_proof_to_cap(leaf_data, index_bits, {root}, siblings);
     }
+    // The tree with cap old_cap holds old_leaf at the index; the returned cap is that of the same tree with new_leaf there: the
+    // state transition of one item of MerkleTree.update_batch, whose trace gives `siblings` (not an upstream gadget).  The old walk
+    // is verify_merkle_proof_to_cap itself, assert_bool of the cap-index bits included; the new walk climbs from
+    // hash_or_noop(new_leaf) over the SAME siblings and bits, one more PoseidonGate row per level.  new_cap[i] = select(i == cap
+    // index, new root, old_cap[i]): the indicators come from a demux tree over the cap-index bits, the highest first
+    // (2 (2^h - 1) ops: t = ind * bit - 0, ind - t), boolean because the bits are; then 4 * 2^h selects.  A cap of one is the new root.
+    std::vector<HashOutTarget> merkle_update_to_cap(const std::vector<Target>& old_leaf, const std::vector<Target>& new_leaf, const std::vector<BoolTarget>& index_bits,
+                                                    const std::vector<HashOutTarget>& old_cap, const std::vector<HashOutTarget>& siblings) {
+        if (new_leaf.empty()) throw std::runtime_error("merkle_update_to_cap: empty leaf");
+        if (new_leaf.size() != old_leaf.size()) throw std::runtime_error("merkle_update_to_cap: the old leaf has " + std::to_string(old_leaf.size()) + " targets, the new one " + std::to_string(new_leaf.size()));
+        verify_merkle_proof_to_cap(old_leaf, index_bits, old_cap, siblings);  // throws on every other length mismatch, before anything is added
+        HashOutTarget state = hash_or_noop(new_leaf);
+        for (size_t l = 0; l < siblings.size(); l++) {
+            std::array<Target, 12> in;
+            for (u32 i = 0; i < 4; i++) in[i] = state[i], in[4 + i] = siblings[l][i], in[8 + i] = zero();
+            std::array<Target, 12> out = permute_swapped(in, index_bits[l]);
+            for (u32 i = 0; i < 4; i++) state[i] = out[i];
+        }
+        if (old_cap.size() == 1) return {state};
+        std::vector<Target> ind{one()};
+        for (size_t j = index_bits.size(); j-- > siblings.size();) {
+            std::vector<Target> next(2 * ind.size());
+            for (size_t i = 0; i < ind.size(); i++) {
+                next[2 * i + 1] = mul_sub(ind[i], index_bits[j].target, zero());  // the selects' constants: the ops share their gates
+                next[2 * i] = sub(ind[i], next[2 * i + 1]);
+            }
+            ind.swap(next);
+        }
+        std::vector<HashOutTarget> new_cap(old_cap.size());
+        for (size_t i = 0; i < old_cap.size(); i++)
+            for (u32 w = 0; w < 4; w++) new_cap[i][w] = select(BoolTarget{ind[i]}, state[w], old_cap[i][w]);
+        return new_cap;
+    }
+    HashOutTarget merkle_update(const std::vector<Target>& old_leaf, const std::vector<Target>& new_leaf, const std::vector<BoolTarget>& index_bits,
+                                const HashOutTarget& old_root, const std::vector<HashOutTarget>& siblings) {
+        return merkle_update_to_cap(old_leaf, new_leaf, index_bits, {old_root}, siblings)[0];
+    }
 
     // ---- ecGFp5 scalar-multiplication step (ecstep_gate.h; not an upstream gate) ---------------------
     // One EcStepGate row: mid = 2 acc, out = mid + bit Q in (X:Z:U:T) coordinates, acc = X | Z | U | T and Q = x | u.  `bit` is

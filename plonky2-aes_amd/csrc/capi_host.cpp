@@ -386,6 +386,21 @@ int p2_builder_verify_merkle_proof(p2_builder* b, const p2_target* leaf, size_t 
                                    const p2_target* siblings, size_t n_siblings) {
     return p2_builder_verify_merkle_proof_to_cap(b, leaf, leaf_len, index_bits, n_bits, root, 0, siblings, n_siblings);
 }
+int p2_builder_merkle_update_to_cap(p2_builder* b, const p2_target* old_leaf, const p2_target* new_leaf, size_t leaf_len, const p2_target* index_bits, size_t n_bits,
+                                    const p2_target* old_cap, int cap_height, const p2_target* siblings, size_t n_siblings, p2_target* new_cap) {
+    return guarded([&] {
+        if (cap_height < 0 || cap_height > 16) throw std::runtime_error("merkle_update_to_cap: cap_height must be 0 to 16");
+        std::vector<BoolTarget> bits(n_bits);
+        for (size_t i = 0; i < n_bits; i++) bits[i] = BoolTarget{index_bits[i]};
+        auto cap = b->b.merkle_update_to_cap(std::vector<Target>(old_leaf, old_leaf + leaf_len), std::vector<Target>(new_leaf, new_leaf + leaf_len), bits,
+                                             hashes_at(old_cap, (size_t)1 << cap_height), hashes_at(siblings, n_siblings));
+        for (size_t i = 0; i < cap.size(); i++) std::copy(cap[i].begin(), cap[i].end(), new_cap + 4 * i);
+    });
+}
+int p2_builder_merkle_update(p2_builder* b, const p2_target* old_leaf, const p2_target* new_leaf, size_t leaf_len, const p2_target* index_bits, size_t n_bits,
+                             const p2_target old_root[4], const p2_target* siblings, size_t n_siblings, p2_target new_root[4]) {
+    return p2_builder_merkle_update_to_cap(b, old_leaf, new_leaf, leaf_len, index_bits, n_bits, old_root, 0, siblings, n_siblings, new_root);
+}
 // Native trees on the host (merkle_host.h): the twin of the p2_merkle_tree_* calls for the CPU suite
 int p2_native_merkle_cap(const uint64_t* leaves, size_t num_leaves, size_t leaf_len, int cap_height, uint64_t* cap) {
     return guarded([&] {
@@ -399,6 +414,18 @@ int p2_native_merkle_prove(const uint64_t* leaves, size_t num_leaves, size_t lea
         mt::HostTree t(leaves, num_leaves, leaf_len, cap_height);
         if (index >= num_leaves) throw std::runtime_error("leaf index " + std::to_string(index) + " is not below num_leaves");
         for (u32 l = 0; l < t.bits - t.cap_height; l++) memcpy(siblings + 4 * l, t.levels[l][(index >> l) ^ 1].e, 32);
+    });
+}
+int p2_native_merkle_update(uint64_t* leaves, size_t num_leaves, size_t leaf_len, int cap_height, const uint64_t* indices, const uint64_t* new_leaves, size_t k,
+                            uint64_t* siblings, uint64_t* root_after) {
+    return guarded([&] {
+        mt::HostTree t(leaves, num_leaves, leaf_len, cap_height);
+        if (k == 0) return;
+        if (!indices || !new_leaves) throw std::runtime_error("null argument");
+        const std::string bad = mt::first_bad_item(indices, new_leaves, k, num_leaves, leaf_len);
+        if (!bad.empty()) throw std::runtime_error(bad);
+        mt::host_update(t, leaf_len, indices, new_leaves, k, siblings, root_after);
+        for (size_t j = 0; j < k; j++) memcpy(leaves + indices[j] * leaf_len, new_leaves + j * leaf_len, 8 * leaf_len);
     });
 }
 int p2_native_merkle_verify(const uint64_t* leaf, size_t leaf_len, size_t index, const uint64_t* siblings, size_t depth, const uint64_t* cap, int cap_height,

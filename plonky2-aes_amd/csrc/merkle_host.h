@@ -49,6 +49,32 @@ struct HostTree {
     }
 };
 
+// The first item of an update that cannot be applied, as a message, or "" (p2_native_merkle_update, p2_merkle_tree_update): the
+// index is looked at before the words.  An update with such an item changes nothing.
+inline std::string first_bad_item(const u64* indices, const u64* leaves, size_t k, size_t num_leaves, size_t leaf_len) {
+    for (size_t j = 0; j < k; j++) {
+        if (indices[j] >= num_leaves) return "leaf index " + std::to_string(indices[j]) + " (entry " + std::to_string(j) + ") is not below num_leaves";
+        const size_t bad = first_non_canonical(leaves + j * leaf_len, leaf_len);
+        if (bad != leaf_len) return "word " + std::to_string(bad) + " of the leaf of entry " + std::to_string(j) + " is not below p";
+    }
+    return "";
+}
+// MerkleTree.update_batch as it is DEFINED: the k writes one after the other, item j on the tree left by the items before it
+// (duplicates are legal, the last write wins).  Before its write item j records the siblings of its path (siblings [k][depth][4],
+// the lowest level first: tree.prove(indices[j]) at that moment), after it cap entry indices[j] >> depth (root_after [k][4]);
+// either may be null.  depth + 1 hashes of the verifier's per item; the device does the same in k * depth independent ones.
+inline void host_update(HostTree& t, size_t leaf_len, const u64* indices, const u64* leaves, size_t k, u64* siblings, u64* root_after) {
+    const u32 depth = t.bits - t.cap_height;
+    for (size_t j = 0; j < k; j++) {
+        size_t n = indices[j];
+        if (siblings)
+            for (u32 l = 0; l < depth; l++) memcpy(siblings + 4 * (j * depth + l), t.levels[l][(n >> l) ^ 1].e, 32);
+        t.levels[0][n] = h_hash_or_noop(leaves + j * leaf_len, leaf_len, HASHER_POSEIDON);
+        for (u32 l = 0; l < depth; l++, n >>= 1) t.levels[l + 1][n >> 1] = h_two_to_one(t.levels[l][n & ~(size_t)1], t.levels[l][n | 1], HASHER_POSEIDON);
+        if (root_after) memcpy(root_after + 4 * j, t.levels[depth][n].e, 32);
+    }
+}
+
 // One path: 0 accepted, 1 rejected, 2 a word (leaf, sibling or cap) that is not below p
 inline int host_verify(const u64* leaf, size_t leaf_len, size_t index, const u64* siblings, size_t depth, const u64* cap, u32 cap_height) {
     const size_t cap_n = (size_t)1 << cap_height;

@@ -5,6 +5,8 @@
 #include <chrono>
 #include <cstring>
 
+#include <rocprim/device/device_radix_sort.hpp>
+
 #include <algorithm>
 #include <map>
 #include <memory>
@@ -20,6 +22,7 @@
 #include "kernels_compress.h"
 #include "kernels_keccak.h"
 #include "kernels_merkle.h"
+#include "kernels_merkle_update.h"
 #include "kernels_schnorr.h"
 #include "kernels_witness_io.h"
 #include "merkle_host.h"
@@ -3053,7 +3056,12 @@ struct MerkleTreeHandle {
     Allocs mem;
     Allocs scratch;              // the column-major copy of the leaves: needed until the build has run
     Lane lane;                   // the stream of the host forms
-    hipEvent_t built = nullptr;  // recorded behind the last kernel of the build, on whichever stream ran it
+    hipEvent_t built = nullptr;  // recorded behind the last kernel of the build and of every update, on whichever stream ran it
+    // updates (mt_update): a grow-only block for keys, node versions and the sort, never freed under a running kernel, and the
+    // hash counter and the bad-item flag of the last update
+    u64* upd = nullptr;
+    size_t upd_words = 0;
+    u64* upd_ctl = nullptr;  // [0] the counter, [1] the flag (its low word)
     void drop_scratch(bool wait) {
         if (scratch.empty() || (wait ? hipEventSynchronize(built) : hipEventQuery(built)) != hipSuccess) return;
         for (void* p : scratch) (void)hipFree(p);
@@ -3062,6 +3070,7 @@ struct MerkleTreeHandle {
     ~MerkleTreeHandle() {
         if (built) (void)hipEventSynchronize(built), (void)hipEventDestroy(built);
         if (lane.stream) (void)hipStreamSynchronize(lane.stream), (void)hipStreamDestroy(lane.stream);
+        if (upd) (void)hipFree(upd);
     }
     u32 depth() const { return t.bits - cap_height; }
 };
@@ -3135,6 +3144,62 @@ static int mt_paths(MerkleTreeHandle& T, const u64* d_indices, size_t n, u64* d_
     HIPCHECK(hipGetLastError());
     return P2_OK;
 }
+// ---- ordered leaf updates (kernels_merkle_update.h): validate and hash the leaves, sort the keys, then one launch per level.
+// trace = d_sib != nullptr.  Everything is enqueued on `stream` behind the handle's event, which is recorded again at the end.
+static int mt_update_launch(MerkleTreeHandle& T, const u64* d_indices, const u64* d_leaves, size_t k, u64* d_sib, size_t sib_stride, u64* d_root, size_t root_stride,
+                            int* d_status, hipStream_t stream, u64* keys_a, u64* keys_b, u64* v_a, u64* v_b, void* sort_tmp, size_t sort_bytes) {
+    const u32 bits = T.t.bits, depth = T.depth();
+    u64* counter = T.upd_ctl;
+    u32* flag = (u32*)(T.upd_ctl + 1);
+    const dim3 grid = g1(k, 256), block(256);
+    HIPCHECK(hipMemsetAsync(T.upd_ctl, 0, 16, stream));
+    hipLaunchKernelGGL(k_mu_leaves, grid, block, 0, stream, d_indices, d_leaves, T.leaf_len, bits, k, keys_a, v_a, d_status, flag);
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(rocprim::radix_sort_keys(sort_tmp, sort_bytes, keys_a, keys_b, k, 0u, 32u + bits, stream));
+    if (!d_sib || depth == 0) {
+        hipLaunchKernelGGL(k_mu_fast_leaf, grid, block, 0, stream, keys_b, v_a, k, T.t.dig, flag);
+        for (u32 l = 1; l <= depth; l++)
+            hipLaunchKernelGGL(k_mu_fast_level, grid, block, 0, stream, keys_b, k, l, T.t.dig + level_off(bits, l - 1), T.t.dig + level_off(bits, l), flag, counter);
+        if (d_sib && d_root) hipLaunchKernelGGL(k_mu_roots, grid, block, 0, stream, v_a, k, d_root, root_stride, flag);
+    } else {
+        hipLaunchKernelGGL(k_mu_gather, g1(k * depth, 256), block, 0, stream, T.t.dig, bits, depth, d_indices, k, d_sib, sib_stride, flag);
+        u64 *a_in = keys_b, *a_out = keys_a, *v_in = v_a, *v_out = v_b;
+        for (u32 l = 0; l < depth; l++) {
+            hipLaunchKernelGGL(k_mu_step, grid, block, 0, stream, a_in, v_in, k, l, l == 0 ? 1u : 0u, l + 1 == depth ? 1u : 0u, a_out, v_out, T.t.dig, bits, d_sib, sib_stride,
+                               d_root, root_stride, flag, counter);
+            std::swap(a_in, a_out);
+            if (l == 0) v_in = v_b, v_out = v_a;
+            else std::swap(v_in, v_out);
+        }
+    }
+    HIPCHECK(hipGetLastError());
+    return P2_OK;
+}
+static int mt_update(MerkleTreeHandle& T, const u64* d_indices, const u64* d_leaves, size_t k, u64* d_sib, size_t sib_stride, u64* d_root, size_t root_stride, int* d_status,
+                     hipStream_t stream) {
+    if (k == 0) return P2_OK;
+    if (!d_indices || !d_leaves || !d_status) return set_error("null argument"), P2_ERR_INVALID;
+    if (k >> 32) return set_error("an update takes fewer than 2^32 items"), P2_ERR_INVALID;
+    if (d_sib && sib_stride < 4 * (size_t)T.depth()) return set_error("sib_stride_words is smaller than a path (" + std::to_string(4 * T.depth()) + " words)"), P2_ERR_INVALID;
+    if (d_sib && d_root && root_stride < 4) return set_error("root_stride_words is smaller than a hash (4 words)"), P2_ERR_INVALID;
+    size_t sort_bytes = 0;
+    HIPCHECK(rocprim::radix_sort_keys(nullptr, sort_bytes, (u64*)nullptr, (u64*)nullptr, k, 0u, 32u + T.t.bits, stream));
+    const size_t sort_off = (10 * k + 31) & ~(size_t)31;  // keys A | keys B | v A | v B, then the sort's block on a 256-byte boundary
+    const size_t need = sort_off + (sort_bytes + 7) / 8;
+    if (!T.upd_ctl && dalloc(T.mem, &T.upd_ctl, 2)) return P2_ERR_HIP;
+    if (need > T.upd_words) {  // grow: the last update may still be reading the old block
+        HIPCHECK(hipEventSynchronize(T.built));
+        if (T.upd) HIPCHECK(hipFree(T.upd));
+        T.upd = nullptr, T.upd_words = 0;
+        HIPCHECK(hipMalloc((void**)&T.upd, need * 8));
+        T.upd_words = need;
+    }
+    HIPCHECK(hipStreamWaitEvent(stream, T.built, 0));
+    const int rc = mt_update_launch(T, d_indices, d_leaves, k, d_sib, sib_stride, d_root, root_stride, d_status, stream, T.upd, T.upd + k, T.upd + 2 * k, T.upd + 6 * k,
+                                    T.upd + sort_off, sort_bytes);
+    HIPCHECK(hipEventRecord(T.built, stream));  // also behind a launch that failed half-way: what was enqueued still runs
+    return rc;
+}
 static int mt_verify_shape(size_t leaf_len, size_t depth, int cap_height) {
     if (leaf_len < 1 || leaf_len > 0xFFFFFFFFull || cap_height < 0 || cap_height > 16 || depth + (size_t)cap_height > 32)
         return set_error("leaf_len >= 1, cap_height 0 to 16, siblings + cap_height at most 32"), P2_ERR_INVALID;
@@ -3194,6 +3259,50 @@ int p2_merkle_tree_prove_batch_device(void* tree, const uint64_t* d_indices, siz
         MerkleTreeHandle* T;
         if (int rc = mt_handle(tree, &T)) return rc;
         return mt_paths(*T, (const u64*)d_indices, n, (u64*)d_out, out_stride_words, d_status, (hipStream_t)stream);
+    });
+}
+int p2_merkle_tree_update(void* tree, const uint64_t* indices, const uint64_t* leaves, size_t k, uint64_t* siblings, uint64_t* root_after) {
+    return guarded_rc([&]() -> int {
+        MerkleTreeHandle* T;
+        if (int rc = mt_handle(tree, &T)) return rc;
+        if (k == 0) return (int)P2_OK;
+        if (!indices || !leaves) return set_error("null argument"), P2_ERR_INVALID;
+        const std::string bad = mt::first_bad_item((const u64*)indices, (const u64*)leaves, k, (size_t)1 << T->t.bits, T->leaf_len);
+        if (!bad.empty()) return set_error(bad), P2_ERR_INVALID;
+        const bool trace = siblings || root_after;
+        const size_t stride = 4 * (size_t)T->depth();
+        Allocs tmp;
+        u64 *d_idx, *d_leaves, *d_sib = nullptr, *d_root = nullptr;
+        int* d_st;
+        if (upload(tmp, &d_idx, (const u64*)indices, k) || upload(tmp, &d_leaves, (const u64*)leaves, k * T->leaf_len) || dalloc(tmp, &d_st, k)) return P2_ERR_HIP;
+        if (trace && (dalloc(tmp, &d_sib, k * stride) || dalloc(tmp, &d_root, 4 * k))) return P2_ERR_HIP;
+        const int rc = mt_update(*T, d_idx, d_leaves, k, d_sib, stride, d_root, 4, d_st, T->lane.stream);
+        HIPCHECK(hipStreamSynchronize(T->lane.stream));  // before tmp goes, whatever rc says
+        if (rc) return rc;
+        if (siblings && stride) HIPCHECK(hipMemcpy(siblings, d_sib, k * stride * 8, hipMemcpyDeviceToHost));
+        if (root_after) HIPCHECK(hipMemcpy(root_after, d_root, k * 32, hipMemcpyDeviceToHost));
+        return (int)P2_OK;
+    });
+}
+int p2_merkle_tree_update_device(void* tree, const uint64_t* d_indices, const uint64_t* d_leaves, size_t k, uint64_t* d_siblings, size_t sib_stride_words,
+                                 uint64_t* d_root_after, size_t root_stride_words, int* d_status, void* stream) {
+    return guarded_rc([&]() -> int {
+        MerkleTreeHandle* T;
+        if (int rc = mt_handle(tree, &T)) return rc;
+        return mt_update(*T, (const u64*)d_indices, (const u64*)d_leaves, k, (u64*)d_siblings, sib_stride_words, (u64*)d_root_after, root_stride_words, d_status,
+                         (hipStream_t)stream);
+    });
+}
+int p2_merkle_tree_last_update_hashes(void* tree, uint64_t* hashes) {
+    return guarded_rc([&]() -> int {
+        MerkleTreeHandle* T;
+        if (int rc = mt_handle(tree, &T)) return rc;
+        if (!hashes) return set_error("null argument"), P2_ERR_INVALID;
+        *hashes = 0;
+        if (!T->upd_ctl) return (int)P2_OK;
+        HIPCHECK(hipEventSynchronize(T->built));
+        HIPCHECK(hipMemcpy(hashes, T->upd_ctl, 8, hipMemcpyDeviceToHost));
+        return (int)P2_OK;
     });
 }
 int p2_merkle_verify_batch(const uint64_t* leaves, size_t leaf_len, const uint64_t* indices, const uint64_t* siblings, size_t depth, const uint64_t* cap, int cap_height,
