@@ -1,5 +1,6 @@
 """Compressed proofs on the host (no GPU): p2_proof_compress / p2_proof_decompress / p2_verify_compressed (csrc/compress.h)
-against an independent compressor written here from the layout of DESIGN.md section 8, on proofs made by the CPU oracle."""
+against the independent compressor of tests/compress_cases.py, written from the layout of DESIGN.md section 8, on proofs made by
+the CPU oracle."""
 import ctypes as C
 import random
 import struct
@@ -9,98 +10,9 @@ import pytest
 import circuits
 import pi_circuits
 import verify_layout
+from compress_cases import _body_info, _flip, _put, coset_collision, kept_levels, py_compress  # noqa: F401 (the independent compressor)
 
 P = 0xFFFFFFFF00000001
-ARITY_BITS, CAP_HEIGHT = 4, 4
-
-
-# ------------------------------------------------------------------------------------------------ independent compressor
-def _body_info(info):
-    k = info["num_public_inputs"]
-    return dict(info, proof_bytes=info["proof_bytes"] - (8 + 8 * k if k else 0))
-
-
-def kept_levels(leaves, q, depth):
-    """The levels at which query q stores its sibling: the sibling is on no query's path, and no earlier query shares q's
-    node at that level (which would have stored it already).  (A closed form of upstream's walk over a set of known nodes.)"""
-    out = []
-    for lvl in range(depth):
-        node = leaves[q] >> lvl
-        if any((x >> lvl) == node ^ 1 for x in leaves):
-            continue
-        if any((leaves[e] >> lvl) == node for e in range(q)):
-            continue
-        out.append(lvl)
-    return out
-
-
-def py_compress(info, proof, idx):
-    """(compressed bytes, {name: byte offset}) for a full proof and its drawn query indices."""
-    S = verify_layout.sections(_body_info(info))
-    lde_bits, rounds, Q = info["degree_bits"] + 3, info["num_fri_rounds"], len(idx)
-    prefix_end, tail_start = S["q0_init0_leaf"][0], S["final_poly"][0]
-    out = bytearray(proof[:prefix_end])
-    at = {"indices": len(out)}
-    out += struct.pack("<%dI" % Q, *idx)
-
-    def firsts(leaves):
-        seen = {}
-        for q, v in enumerate(leaves):
-            seen.setdefault(v, q)
-        return [seen[v] for v in sorted(seen)]
-
-    def sib(name, lvl):
-        off = S[name][0]
-        return proof[off + 32 * lvl: off + 32 * lvl + 32]
-
-    depth0 = lde_bits - CAP_HEIGHT
-    for q in firsts(idx):
-        kept = kept_levels(idx, q, depth0)
-        for o in range(4):
-            off, n, _ = S["q%d_init%d_leaf" % (q, o)]
-            at["init_leaf_%d_%d" % (q, o)] = len(out)
-            out += proof[off:off + n]
-            at["init_count_%d_%d" % (q, o)] = len(out)
-            out.append(len(kept))
-            if kept:
-                at["init_sib_%d_%d" % (q, o)] = len(out)
-            for lvl in kept:
-                out += sib("q%d_init%d_siblings" % (q, o), lvl)
-    for r in range(rounds):
-        leaves = [x >> (ARITY_BITS * (r + 1)) for x in idx]
-        depth = lde_bits - ARITY_BITS * (r + 1) - CAP_HEIGHT
-        for q in firsts(leaves):
-            left_out = (idx[q] >> (ARITY_BITS * r)) & 15
-            off = S["q%d_round%d_evals" % (q, r)][0]
-            at["evals_%d_%d" % (r, q)] = len(out)
-            for k in range(16):
-                if k != left_out:
-                    out += proof[off + 16 * k: off + 16 * k + 16]
-            kept = kept_levels(leaves, q, depth)
-            at["round_count_%d_%d" % (r, q)] = len(out)
-            out.append(len(kept))
-            if kept:
-                at["round_sib_%d_%d" % (r, q)] = len(out)
-            for lvl in kept:
-                out += sib("q%d_round%d_siblings" % (q, r), lvl)
-    at["final_poly"] = len(out)
-    at["pow_witness"] = len(out) + (S["pow_witness"][0] - tail_start)
-    if info["num_public_inputs"]:
-        at["pi_values"] = at["pow_witness"] + 16
-    out += proof[tail_start:]
-    return bytes(out), at
-
-
-def coset_collision(info, idx):
-    """A pair of queries in the same coset of the last FRI round, at different positions within it."""
-    r = info["num_fri_rounds"] - 1
-    if r < 0:
-        return None
-    for a in range(len(idx)):
-        for b in range(a + 1, len(idx)):
-            if idx[a] >> (4 * r + 4) == idx[b] >> (4 * r + 4) and (idx[a] >> 4 * r) & 15 != (idx[b] >> 4 * r) & 15:
-                return a, b
-    return None
 
 
 # ------------------------------------------------------------------------------------------------ library wrappers
@@ -263,16 +175,6 @@ def test_the_coset_collision_case_is_exercised(pkg, orc):
                 assert decompress(pkg, data, vd, c)[0] == proof
                 assert verify_compressed_reason(pkg, data, vd, c) == ""
     assert hits
-
-
-def _flip(word_bytes):
-    v = struct.unpack("<Q", word_bytes)[0]
-    w = v ^ 1 if v ^ 1 < P else v ^ 2
-    return struct.pack("<Q", w)
-
-
-def _put(c, off, b):
-    return c[:off] + b + c[off + len(b):]
 
 
 def test_rejections(pkg, orc, case):

@@ -80,8 +80,8 @@ def _tampered(info, proof):
     for q in (0, last):
         names += [n for n in sec if n.startswith("q%d_" % q)]
     out = []
-    off0 = sec["q0_round0_evals"][0]
-    for e in range(16):   # one of the sixteen is the element the round-0 fold check compares
+    off0 = sec["q0_round0_evals"][0] if "q0_round0_evals" in sec else 0
+    for e in range(16 if off0 else 0):   # one of the sixteen is the element the round-0 fold check compares
         b = bytearray(proof)
         b[off0 + 16 * e + 2] ^= 0x04
         out.append(("q0_round0_evals element %d flip" % e, bytes(b)))
