@@ -697,6 +697,40 @@ pub mod pod2 {
                 PointTarget(o.map(Target))
             }
         }
+        /// Verifiable decryption (not in the reference, whose circuits only encrypt): no new gate.  The caller ties the key to a
+        /// public key with `connect(public_key(sk), pk)`.  Not checked in the circuit: `c0` and `c1` in the group, `sk` below the
+        /// group order.
+        pub trait CircuitBuilderElGamalDecrypt {
+            fn neg_point(&mut self, p: &PointTarget) -> PointTarget;
+            /// `msg = c1 - sk c0` (elgamal.rs:19).
+            fn elgamal_decrypt(&mut self, sk: &BigUInt320Target, c0: &PointTarget, c1: &PointTarget) -> PointTarget;
+            /// `msg[i] = ct[i] - hash_n_to_m_no_pad(as_fields(sk c0), 5)[i]` (hashed_elgamal.rs:28).
+            fn hashed_elgamal_decrypt(&mut self, sk: &BigUInt320Target, c0: &PointTarget, ct: &[Target; 5]) -> [Target; 5];
+        }
+        impl<F: Field, const D: usize> CircuitBuilderElGamalDecrypt for CircuitBuilder<F, D> {
+            fn neg_point(&mut self, p: &PointTarget) -> PointTarget {
+                let mut o = [0u64; 10];
+                let rc = unsafe { ffi::p2_builder_neg_point(self.h, raw::<10>(&p.0).as_ptr(), o.as_mut_ptr()) };
+                assert!(rc == ffi::P2_OK, "{}", crate::last_error());
+                PointTarget(o.map(Target))
+            }
+            fn elgamal_decrypt(&mut self, sk: &BigUInt320Target, c0: &PointTarget, c1: &PointTarget) -> PointTarget {
+                let b: Vec<u64> = sk.bits.iter().map(|t| t.target.0).collect();
+                assert!(b.len() == 320, "a secret key holds 320 bits");
+                let mut o = [0u64; 10];
+                let rc = unsafe { ffi::p2_builder_elgamal_decrypt(self.h, b.as_ptr(), raw::<10>(&c0.0).as_ptr(), raw::<10>(&c1.0).as_ptr(), o.as_mut_ptr()) };
+                assert!(rc == ffi::P2_OK, "{}", crate::last_error());
+                PointTarget(o.map(Target))
+            }
+            fn hashed_elgamal_decrypt(&mut self, sk: &BigUInt320Target, c0: &PointTarget, ct: &[Target; 5]) -> [Target; 5] {
+                let b: Vec<u64> = sk.bits.iter().map(|t| t.target.0).collect();
+                assert!(b.len() == 320, "a secret key holds 320 bits");
+                let mut o = [0u64; 5];
+                let rc = unsafe { ffi::p2_builder_hashed_elgamal_decrypt(self.h, b.as_ptr(), raw::<10>(&c0.0).as_ptr(), raw::<5>(ct).as_ptr(), o.as_mut_ptr()) };
+                assert!(rc == ffi::P2_OK, "{}", crate::last_error());
+                o.map(Target)
+            }
+        }
     }
     /// Schnorr signatures on ecGFp5 with a Poseidon challenge (csrc/schnorr.h; this project's own scheme, UNPINNED against pod2's
     /// signature bytes): `p2_schnorr_*` on the host and the `verify_schnorr_signature` gadget.

@@ -297,6 +297,20 @@ int p2_builder_elgamal_encrypt(p2_builder*, const p2_target pk[10], const p2_tar
 /* CircuitBuilderHashedElGamal::hashed_elgamal_encrypt (hashed_elgamal/circuit.rs:33) */
 int p2_builder_hashed_elgamal_encrypt(p2_builder*, const p2_target pk[10], const p2_target nonce_bits[320], const p2_target msg[5],
                                       p2_target c0[10], p2_target ct[5]);
+/* encode_binary (lib.rs:48) with the random high halves supplied by the caller, hence deterministic: attempt a tries
+ * w[i] = limbs[i] + (pad[5 a + i] << 32), an attempt with a word not below p is skipped, the first that decodes gives out and
+ * *used.  P2_ERR_INVALID (*used = attempts, out untouched) when none does.  The reference draws r < p - limb and keeps r >> 32;
+ * uniform 32-bit halves differ from that by less than 2^-32.  The host twin of p2_ecgfp5_encode_binary_batch. */
+int p2_ecgfp5_encode_binary_padded(const uint32_t limbs[5], const uint32_t* pad, size_t attempts, uint64_t out[10], uint32_t* used);
+/* Verifiable decryption (not in the reference, whose circuits only encrypt): no new gate.
+ *   neg_point               negates the five u targets
+ *   elgamal_decrypt         msg = c1 - sk c0: add_point(c1, neg_point(multiply_point(sk_bits, c0)))
+ *   hashed_elgamal_decrypt  msg[i] = ct[i] - hash_n_to_m_no_pad(multiply_point(sk_bits, c0), 5)[i]
+ * The caller ties the key to a public key with connect(public_key(sk_bits), pk).  Works with set_ec_gate on and off.  NOT checked
+ * in the circuit: that c0 and c1 are in the group (add_virtual_point_target checks the curve equation only) and that sk < n. */
+int p2_builder_neg_point(p2_builder*, const p2_target p[10], p2_target out[10]);
+int p2_builder_elgamal_decrypt(p2_builder*, const p2_target sk_bits[320], const p2_target c0[10], const p2_target c1[10], p2_target msg[10]);
+int p2_builder_hashed_elgamal_decrypt(p2_builder*, const p2_target sk_bits[320], const p2_target c0[10], const p2_target ct[5], p2_target msg[5]);
 
 /* ------------------------------------------------------------------ Schnorr signatures on ecGFp5 (host) */
 /* The scheme (csrc/schnorr.h; this project's own, UNPINNED against pod2's signature bytes):
@@ -692,6 +706,45 @@ int p2_schnorr_verify_batch_device(const uint64_t* d_pk, const uint64_t* d_msg, 
                                    int device, void* stream);
 /* test entry: out[i] = (a[i] b[i] + c[i]) mod n on the device, one thread per triple */
 int p2_gpu_ecgfp5_scalar_muladd(const uint64_t* a, const uint64_t* b, const uint64_t* c, size_t count, uint64_t* out, int device);
+
+/* ------------------------------------------------------------------ ElGamal on ecGFp5 in GPU batches */
+/* One thread per item (csrc/kernels_elgamal.h), the call shape of the section above: contiguous rows, every array per item (a
+ * caller with one key repeats it), host-pointer forms that copy in and out, _device forms that take raw device pointers and are
+ * asynchronous on `stream`.  Compressed points and hashed messages are [count][5] words.  status[i]:
+ *   0  done
+ *   1  no result: the row is zeroed (decompress: w[i] encodes no group element; encode_binary: no attempt decodes)
+ *   2  malformed, every output row of the item zeroed: a word not below p, a scalar not below n, a point outside the group (the
+ *      neutral is inside)
+ * Outputs are the host's word for word (p2_ecgfp5_decompress, p2_ecgfp5_encode_binary_padded, p2_elgamal_*, p2_hashed_elgamal_*).
+ *   decompress_batch      out[i] = decompress_into_subgroup(w[i])
+ *   encode_binary_batch   limbs uint32 [count][5], pad uint32 [count][attempts][5], 1 <= attempts <= 256; used[i]: the number of
+ *                         the attempt taken, `attempts` with status 1
+ *   elgamal_encrypt       c0[i] = nonce[i] G, c1[i] = msg[i] + nonce[i] pk[i]
+ *   elgamal_decrypt       msg[i] = c1[i] - sk[i] c0[i]
+ *   hashed_elgamal_*      the same with the message five field elements under hash_n_to_m_no_pad(as_fields(nonce pk), 5)
+ *   scalar_bits_device    d_out[i stride + j] = bit j of d_k[i], j < 320 <= stride (words): a scalar's row segment of the prover's
+ *                         value matrix.  Secret keys and nonces stay in device memory the caller owns. */
+int p2_ecgfp5_decompress_batch(const uint64_t* w, size_t count, uint64_t* out, int* status, int device);
+int p2_ecgfp5_decompress_batch_device(const uint64_t* d_w, size_t count, uint64_t* d_out, int* d_status, int device, void* stream);
+int p2_ecgfp5_encode_binary_batch(const uint32_t* limbs, const uint32_t* pad, size_t attempts, size_t count, uint64_t* out, uint32_t* used, int* status,
+                                  int device);
+int p2_ecgfp5_encode_binary_batch_device(const uint32_t* d_limbs, const uint32_t* d_pad, size_t attempts, size_t count, uint64_t* d_out, uint32_t* d_used,
+                                         int* d_status, int device, void* stream);
+int p2_elgamal_encrypt_batch(const uint64_t* pk, const uint64_t* nonce, const uint64_t* msg, size_t count, uint64_t* c0, uint64_t* c1, int* status,
+                             int device);
+int p2_elgamal_encrypt_batch_device(const uint64_t* d_pk, const uint64_t* d_nonce, const uint64_t* d_msg, size_t count, uint64_t* d_c0, uint64_t* d_c1,
+                                    int* d_status, int device, void* stream);
+int p2_elgamal_decrypt_batch(const uint64_t* sk, const uint64_t* c0, const uint64_t* c1, size_t count, uint64_t* msg, int* status, int device);
+int p2_elgamal_decrypt_batch_device(const uint64_t* d_sk, const uint64_t* d_c0, const uint64_t* d_c1, size_t count, uint64_t* d_msg, int* d_status,
+                                    int device, void* stream);
+int p2_hashed_elgamal_encrypt_batch(const uint64_t* pk, const uint64_t* nonce, const uint64_t* msg, size_t count, uint64_t* c0, uint64_t* ct, int* status,
+                                    int device);
+int p2_hashed_elgamal_encrypt_batch_device(const uint64_t* d_pk, const uint64_t* d_nonce, const uint64_t* d_msg, size_t count, uint64_t* d_c0,
+                                           uint64_t* d_ct, int* d_status, int device, void* stream);
+int p2_hashed_elgamal_decrypt_batch(const uint64_t* sk, const uint64_t* c0, const uint64_t* ct, size_t count, uint64_t* msg, int* status, int device);
+int p2_hashed_elgamal_decrypt_batch_device(const uint64_t* d_sk, const uint64_t* d_c0, const uint64_t* d_ct, size_t count, uint64_t* d_msg,
+                                           int* d_status, int device, void* stream);
+int p2_ecgfp5_scalar_bits_device(const uint64_t* d_k, size_t count, uint64_t* d_out, size_t stride, int device, void* stream);
 
 /* ------------------------------------------------------------------ GPU primitives (parity tests / microbench) */
 int p2_gpu_device_count(void);

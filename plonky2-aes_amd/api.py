@@ -329,6 +329,23 @@ def lib():
         "p2_schnorr_sign_batch_device": (C.c_int, [vp, vp, vp, sz, sz, vp, vp, vp, C.c_int, vp]),
         "p2_schnorr_verify_batch": (C.c_int, [u64p, u64p, sz, u64p, sz, C.POINTER(C.c_int), C.c_int]),
         "p2_schnorr_verify_batch_device": (C.c_int, [vp, vp, sz, vp, sz, vp, C.c_int, vp]),
+        "p2_ecgfp5_encode_binary_padded": (C.c_int, [u32p, u32p, sz, u64p, u32p]),
+        "p2_builder_neg_point": (C.c_int, [vp, u64p, u64p]),
+        "p2_builder_elgamal_decrypt": (C.c_int, [vp, u64p, u64p, u64p, u64p]),
+        "p2_builder_hashed_elgamal_decrypt": (C.c_int, [vp, u64p, u64p, u64p, u64p]),
+        "p2_ecgfp5_decompress_batch": (C.c_int, [u64p, sz, u64p, C.POINTER(C.c_int), C.c_int]),
+        "p2_ecgfp5_decompress_batch_device": (C.c_int, [vp, sz, vp, vp, C.c_int, vp]),
+        "p2_ecgfp5_encode_binary_batch": (C.c_int, [u32p, u32p, sz, sz, u64p, u32p, C.POINTER(C.c_int), C.c_int]),
+        "p2_ecgfp5_encode_binary_batch_device": (C.c_int, [vp, vp, sz, sz, vp, vp, vp, C.c_int, vp]),
+        "p2_elgamal_encrypt_batch": (C.c_int, [u64p, u64p, u64p, sz, u64p, u64p, C.POINTER(C.c_int), C.c_int]),
+        "p2_elgamal_encrypt_batch_device": (C.c_int, [vp, vp, vp, sz, vp, vp, vp, C.c_int, vp]),
+        "p2_elgamal_decrypt_batch": (C.c_int, [u64p, u64p, u64p, sz, u64p, C.POINTER(C.c_int), C.c_int]),
+        "p2_elgamal_decrypt_batch_device": (C.c_int, [vp, vp, vp, sz, vp, vp, C.c_int, vp]),
+        "p2_hashed_elgamal_encrypt_batch": (C.c_int, [u64p, u64p, u64p, sz, u64p, u64p, C.POINTER(C.c_int), C.c_int]),
+        "p2_hashed_elgamal_encrypt_batch_device": (C.c_int, [vp, vp, vp, sz, vp, vp, vp, C.c_int, vp]),
+        "p2_hashed_elgamal_decrypt_batch": (C.c_int, [u64p, u64p, u64p, sz, u64p, C.POINTER(C.c_int), C.c_int]),
+        "p2_hashed_elgamal_decrypt_batch_device": (C.c_int, [vp, vp, vp, sz, vp, vp, C.c_int, vp]),
+        "p2_ecgfp5_scalar_bits_device": (C.c_int, [vp, sz, vp, sz, C.c_int, vp]),
     }
     missing = []
     for name, (res, args) in sig.items():
@@ -663,6 +680,37 @@ class CircuitBuilder:
         if lib().p2_builder_hashed_elgamal_encrypt(self._h, _arr(pk), _arr(nonce), _arr(msg), c0, ct):
             raise P2Error(_err())
         return list(c0), list(ct)
+
+    # ---- verifiable decryption (not in the reference, whose circuits only encrypt).  The caller ties the key with
+    # connect(public_key(sk_bits), pk) target by target.  Not checked in the circuit: c0 and c1 in the group, sk below the order.
+    @staticmethod
+    def _decrypt_args(sk_bits, c0, second, n_second):
+        if len(sk_bits) != 320 or len(c0) != 10 or len(second) != n_second:
+            raise P2Error("a decryption takes 320 key bits, a point of 10 targets and %d ciphertext targets" % n_second)
+
+    def neg_point(self, p):
+        if len(p) != 10:
+            raise P2Error("neg_point takes a point of 10 targets")
+        out = (u64 * 10)()
+        if lib().p2_builder_neg_point(self._h, _arr(p), out):
+            raise P2Error(_err())
+        return list(out)
+
+    def elgamal_decrypt(self, sk_bits, c0, c1):
+        """msg = c1 - sk c0 (elgamal.rs:19) as ten targets"""
+        self._decrypt_args(sk_bits, c0, c1, 10)
+        out = (u64 * 10)()
+        if lib().p2_builder_elgamal_decrypt(self._h, _arr(sk_bits), _arr(c0), _arr(c1), out):
+            raise P2Error(_err())
+        return list(out)
+
+    def hashed_elgamal_decrypt(self, sk_bits, c0, ct):
+        """msg[i] = ct[i] - hash_n_to_m_no_pad(as_fields(sk c0), 5)[i] (hashed_elgamal.rs:28) as five targets"""
+        self._decrypt_args(sk_bits, c0, ct, 5)
+        out = (u64 * 5)()
+        if lib().p2_builder_hashed_elgamal_decrypt(self._h, _arr(sk_bits), _arr(c0), _arr(ct), out):
+            raise P2Error(_err())
+        return list(out)
 
     # ---- Schnorr signatures on ecGFp5 (csrc/schnorr.h).  A signature target is (s_bits, e): 320 bit targets and a hash.
     def add_virtual_schnorr_signature_target(self):
@@ -1565,6 +1613,190 @@ class ecgfp5:
         """Every buffer a raw device pointer (p2_ecgfp5_mul_batch_device); asynchronous on `stream`."""
         if lib().p2_ecgfp5_mul_batch_device(d_k, d_p, count, d_out, d_status, device, stream):
             raise P2Error("p2_ecgfp5_mul_batch_device failed: " + _err())
+
+    # ---- ElGamal in GPU batches (csrc/kernels_elgamal.h).  Every list is per item; a caller with one key repeats it.  Statuses:
+    # 0 done, 1 no result, 2 malformed (a word not below p, a scalar not below n, a point outside the group); a row whose status
+    # is not 0 holds zeros.  device=None: a host loop over the single-item entry points with the same checks.
+    DONE, NO_RESULT, MALFORMED = 0, 1, 2
+
+    @staticmethod
+    def _point_rows(points, what):
+        arr, n, k = _rows([list(p[0]) + list(p[1]) for p in points], what)
+        if n and k != 10:
+            raise P2Error("%s are points of ten words" % what)
+        return arr, n
+
+    @staticmethod
+    def _word_rows(rows, what):
+        arr, n, k = _rows(rows, what)
+        if n and k != 5:
+            raise P2Error("%s are rows of five words" % what)
+        return arr, n
+
+    @staticmethod
+    def _point_ok(arr, i):
+        return all(w < P for w in arr[10 * i:10 * i + 10]) and bool(lib().p2_ecgfp5_is_in_subgroup(_at(arr, 10 * i)))
+
+    @staticmethod
+    def _scalar_ok(arr, i):
+        return _int5(arr[5 * i:5 * i + 5]) < ecgfp5.group_order()
+
+    @staticmethod
+    def _cipher_batch(name, ins, out_widths, device, ok, host):
+        """ins: three (array, n); -> ([flat output arrays], statuses).  The host loop calls host(i, outs) where ok(i)."""
+        n = ins[0][1]
+        if any(m != n for _, m in ins):
+            raise P2Error(name + ": every list has one entry per item")
+        if n == 0:
+            return [[] for _ in out_widths], []
+        outs, status = [(u64 * (w * n))() for w in out_widths], (C.c_int * n)()
+        if device is None:
+            for i in range(n):
+                if not ok(i):
+                    status[i] = ecgfp5.MALFORMED
+                elif host(i, outs):
+                    raise P2Error(name + " (host) failed: " + _err())
+        elif getattr(lib(), "p2_" + name)(*[a for a, _ in ins], n, *outs, status, device):
+            raise P2Error("p2_%s failed: %s" % (name, _err()))
+        return outs, list(status)
+
+    @staticmethod
+    def decompress_batch(ws, device=0):
+        """-> (points, statuses): decompress_into_subgroup per item; status 1 where w encodes no group element"""
+        w, n = ecgfp5._word_rows(ws, "compressed points")
+        if n == 0:
+            return [], []
+        out, status = (u64 * (10 * n))(), (C.c_int * n)()
+        if device is None:
+            for i in range(n):
+                if any(v >= P for v in w[5 * i:5 * i + 5]):
+                    status[i] = ecgfp5.MALFORMED
+                else:
+                    status[i] = ecgfp5.NO_RESULT if lib().p2_ecgfp5_decompress(_at(w, 5 * i), _at(out, 10 * i)) else ecgfp5.DONE
+        elif lib().p2_ecgfp5_decompress_batch(w, n, out, status, device):
+            raise P2Error("p2_ecgfp5_decompress_batch failed: " + _err())
+        return _points_out(out, n), list(status)
+
+    @staticmethod
+    def _encode_args(xs, pads):
+        xs, pads = [int(x) for x in xs], [[list(a) for a in p] for p in pads]
+        n, attempts = len(xs), len(pads[0]) if pads else 0
+        if len(pads) != n or any(len(p) != attempts or any(len(a) != 5 for a in p) for p in pads):
+            raise P2Error("encode_binary_batch: per item one message and one list of `attempts` rows of five 32-bit pad words")
+        flat = [int(v) for p in pads for a in p for v in a]
+        if any(not 0 <= x < 1 << 160 for x in xs) or any(not 0 <= v < 1 << 32 for v in flat):
+            raise P2Error("encode_binary_batch: messages are below 2^160, pad words below 2^32")
+        limbs = (C.c_uint32 * (5 * n))(*[(x >> (32 * j)) & 0xFFFFFFFF for x in xs for j in range(5)])
+        return limbs, (C.c_uint32 * max(len(flat), 1))(*flat), n, attempts
+
+    @staticmethod
+    def encode_binary_batch(xs, pads, device=0):
+        """encode_binary (lib.rs:48) with the random high halves supplied: xs are messages below 2^160, pads[i] a list of `attempts`
+        rows of five 32-bit words (draw them from a CSPRNG: they hide nothing, but a fixed list makes encodings recognisable).
+        -> (points, used, statuses): used[i] the number of the attempt taken; status 1 and used = attempts where none decodes."""
+        limbs, pad, n, attempts = ecgfp5._encode_args(xs, pads)
+        if n == 0:
+            return [], [], []
+        out, used, status = (u64 * (10 * n))(), (C.c_uint32 * n)(), (C.c_int * n)()
+        if device is None:
+            if not 1 <= attempts <= 256:
+                raise P2Error("attempts is between 1 and 256")
+            u = C.c_uint32()
+            for i in range(n):
+                rc = lib().p2_ecgfp5_encode_binary_padded(C.cast(C.byref(limbs, 20 * i), u32p), C.cast(C.byref(pad, 20 * attempts * i), u32p), attempts, _at(out, 10 * i),
+                                                         C.byref(u))
+                used[i], status[i] = u.value, ecgfp5.NO_RESULT if rc else ecgfp5.DONE
+        elif lib().p2_ecgfp5_encode_binary_batch(limbs, pad, attempts, n, out, used, status, device):
+            raise P2Error("p2_ecgfp5_encode_binary_batch failed: " + _err())
+        return _points_out(out, n), list(used), list(status)
+
+    @staticmethod
+    def decode_binary_batch(points):
+        """decode_binary (lib.rs:80) per point, on the host: the low halves of u"""
+        return [sum((int(p[1][j]) & 0xFFFFFFFF) << (32 * j) for j in range(5)) for p in points]
+
+    @staticmethod
+    def elgamal_encrypt_batch(pks, nonces, msgs, device=0):
+        """-> (c0s, c1s, statuses): c0 = nonce G, c1 = msg + nonce pk (elgamal.rs:11)"""
+        pk, k, m = ecgfp5._point_rows(pks, "public keys"), _rows([_sc_words(x) for x in nonces], "nonces")[:2], ecgfp5._point_rows(msgs, "messages")
+        outs, st = ecgfp5._cipher_batch(
+            "elgamal_encrypt_batch", [pk, k, m], (10, 10), device, lambda i: ecgfp5._scalar_ok(k[0], i) and ecgfp5._point_ok(pk[0], i) and ecgfp5._point_ok(m[0], i),
+            lambda i, o: lib().p2_elgamal_encrypt(_at(pk[0], 10 * i), _at(k[0], 5 * i), _at(m[0], 10 * i), _at(o[0], 10 * i), _at(o[1], 10 * i)))
+        return _points_out(outs[0], len(st)), _points_out(outs[1], len(st)), st
+
+    @staticmethod
+    def elgamal_decrypt_batch(sks, c0s, c1s, device=0):
+        """-> (msgs, statuses): msg = c1 - sk c0 (elgamal.rs:19); sks are Python ints"""
+        k, a, b = _rows([_sc_words(x) for x in sks], "secret keys")[:2], ecgfp5._point_rows(c0s, "c0"), ecgfp5._point_rows(c1s, "c1")
+        outs, st = ecgfp5._cipher_batch(
+            "elgamal_decrypt_batch", [k, a, b], (10,), device, lambda i: ecgfp5._scalar_ok(k[0], i) and ecgfp5._point_ok(a[0], i) and ecgfp5._point_ok(b[0], i),
+            lambda i, o: lib().p2_elgamal_decrypt(_at(k[0], 5 * i), _at(a[0], 10 * i), _at(b[0], 10 * i), _at(o[0], 10 * i)))
+        return _points_out(outs[0], len(st)), st
+
+    @staticmethod
+    def hashed_elgamal_encrypt_batch(pks, nonces, msgs, device=0):
+        """-> (c0s, cts, statuses): messages and ciphertexts are five field elements (hashed_elgamal.rs:19)"""
+        pk, k, m = ecgfp5._point_rows(pks, "public keys"), _rows([_sc_words(x) for x in nonces], "nonces")[:2], ecgfp5._word_rows(msgs, "messages")
+        outs, st = ecgfp5._cipher_batch(
+            "hashed_elgamal_encrypt_batch", [pk, k, m], (10, 5), device,
+            lambda i: ecgfp5._scalar_ok(k[0], i) and all(w < P for w in m[0][5 * i:5 * i + 5]) and ecgfp5._point_ok(pk[0], i),
+            lambda i, o: lib().p2_hashed_elgamal_encrypt(_at(pk[0], 10 * i), _at(k[0], 5 * i), _at(m[0], 5 * i), _at(o[0], 10 * i), _at(o[1], 5 * i)))
+        return _points_out(outs[0], len(st)), [tuple(outs[1][5 * i:5 * i + 5]) for i in range(len(st))], st
+
+    @staticmethod
+    def hashed_elgamal_decrypt_batch(sks, c0s, cts, device=0):
+        """-> (msgs, statuses) (hashed_elgamal.rs:28)"""
+        k, a, c = _rows([_sc_words(x) for x in sks], "secret keys")[:2], ecgfp5._point_rows(c0s, "c0"), ecgfp5._word_rows(cts, "ciphertexts")
+        outs, st = ecgfp5._cipher_batch(
+            "hashed_elgamal_decrypt_batch", [k, a, c], (5,), device,
+            lambda i: ecgfp5._scalar_ok(k[0], i) and all(w < P for w in c[0][5 * i:5 * i + 5]) and ecgfp5._point_ok(a[0], i),
+            lambda i, o: lib().p2_hashed_elgamal_decrypt(_at(k[0], 5 * i), _at(a[0], 10 * i), _at(c[0], 5 * i), _at(o[0], 5 * i)))
+        return [tuple(outs[0][5 * i:5 * i + 5]) for i in range(len(st))], st
+
+    # the _device forms: every buffer a raw device pointer, asynchronous on `stream`; keys and nonces stay in device memory
+    @staticmethod
+    def _device_call(name, *args):
+        if getattr(lib(), name)(*args):
+            raise P2Error("%s failed: %s" % (name, _err()))
+
+    @staticmethod
+    def decompress_batch_device(d_w, count, d_out, d_status, device=0, stream=None):
+        ecgfp5._device_call("p2_ecgfp5_decompress_batch_device", d_w, count, d_out, d_status, device, stream)
+
+    @staticmethod
+    def encode_binary_batch_device(d_limbs, d_pad, attempts, count, d_out, d_used, d_status, device=0, stream=None):
+        ecgfp5._device_call("p2_ecgfp5_encode_binary_batch_device", d_limbs, d_pad, attempts, count, d_out, d_used, d_status, device, stream)
+
+    @staticmethod
+    def elgamal_encrypt_batch_device(d_pk, d_nonce, d_msg, count, d_c0, d_c1, d_status, device=0, stream=None):
+        ecgfp5._device_call("p2_elgamal_encrypt_batch_device", d_pk, d_nonce, d_msg, count, d_c0, d_c1, d_status, device, stream)
+
+    @staticmethod
+    def elgamal_decrypt_batch_device(d_sk, d_c0, d_c1, count, d_msg, d_status, device=0, stream=None):
+        ecgfp5._device_call("p2_elgamal_decrypt_batch_device", d_sk, d_c0, d_c1, count, d_msg, d_status, device, stream)
+
+    @staticmethod
+    def hashed_elgamal_encrypt_batch_device(d_pk, d_nonce, d_msg, count, d_c0, d_ct, d_status, device=0, stream=None):
+        ecgfp5._device_call("p2_hashed_elgamal_encrypt_batch_device", d_pk, d_nonce, d_msg, count, d_c0, d_ct, d_status, device, stream)
+
+    @staticmethod
+    def hashed_elgamal_decrypt_batch_device(d_sk, d_c0, d_ct, count, d_msg, d_status, device=0, stream=None):
+        ecgfp5._device_call("p2_hashed_elgamal_decrypt_batch_device", d_sk, d_c0, d_ct, count, d_msg, d_status, device, stream)
+
+    @staticmethod
+    def scalar_bits_device(d_k, count, d_out, stride, device=0, stream=None):
+        """d_out[i stride + j] = bit j of scalar i (j < 320 <= stride, in words): a scalar's 320 bit targets in a row of the value
+        matrix that prove_batch_device reads, without the host spelling the bits"""
+        ecgfp5._device_call("p2_ecgfp5_scalar_bits_device", d_k, count, d_out, stride, device, stream)
+
+
+def _at(arr, words):
+    """pointer to word `words` of a u64 array"""
+    return C.cast(C.byref(arr, 8 * words), u64p)
+
+
+def _points_out(buf, n):
+    return [_pt_out(buf[10 * i:10 * i + 10]) for i in range(n)]
 
 
 def _int5(words):

@@ -632,6 +632,35 @@ int p2_builder_hashed_elgamal_encrypt(p2_builder* b, const p2_target pk[10], con
         return set_error(e.what()), P2_ERR_INVALID;
     }
 }
+// the host twin of p2_ecgfp5_encode_binary_batch, and the decryption gadgets (ecgfp5.h)
+int p2_ecgfp5_encode_binary_padded(const uint32_t limbs[5], const uint32_t* pad, size_t attempts, uint64_t out[10], uint32_t* used) {
+    if (!limbs || !out || !used || (attempts && !pad)) return set_error("null argument"), P2_ERR_INVALID;
+    ecgfp5::Affine a;
+    const size_t n = ecgfp5::encode_binary_padded(limbs, pad, attempts, &a);
+    *used = (uint32_t)n;
+    if (n == attempts) return set_error("no attempt decodes to a group element"), P2_ERR_INVALID;
+    pt_put(a, out);
+    return P2_OK;
+}
+int p2_builder_neg_point(p2_builder* b, const p2_target p[10], p2_target out[10]) {
+    return guarded([&] { ptt_put(ecgfp5::neg_point(b->b, ptt_at(p)), out); });
+}
+int p2_builder_elgamal_decrypt(p2_builder* b, const p2_target sk_bits[320], const p2_target c0[10], const p2_target c1[10], p2_target msg[10]) {
+    try {
+        ptt_put(ecgfp5::elgamal_decrypt_target(b->b, bits_at(sk_bits), ptt_at(c0), ptt_at(c1)), msg);
+        return P2_OK;
+    } catch (std::exception& e) {
+        return set_error(e.what()), P2_ERR_INVALID;
+    }
+}
+int p2_builder_hashed_elgamal_decrypt(p2_builder* b, const p2_target sk_bits[320], const p2_target c0[10], const p2_target ct[5], p2_target msg[5]) {
+    try {
+        ecgfp5::hashed_elgamal_decrypt_target(b->b, bits_at(sk_bits), ptt_at(c0), ct, msg);
+        return P2_OK;
+    } catch (std::exception& e) {
+        return set_error(e.what()), P2_ERR_INVALID;
+    }
+}
 
 // ---- Schnorr signatures on ecGFp5 (schnorr.h): the host twins of p2_schnorr_*_batch, and the gadget
 void p2_ecgfp5_scalar_muladd(const uint64_t a[5], const uint64_t b[5], const uint64_t c[5], uint64_t out[5]) { ecsc::sc_muladd(a, b, c, out); }

@@ -251,6 +251,22 @@ inline Affine encode_binary(const u32 limbs[5], Rng& rng) {
         if (decompress_into_subgroup(w, &a)) return a;
     }
 }
+// encode_binary with the random high halves supplied by the caller (the host twin of k_ec_encode_binary): attempt a tries
+// w[i] = limbs[i] + (pad[5 a + i] << 32); an attempt with a word not below p is skipped.  Returns the number of the first attempt
+// that decodes, or `attempts` when none does (*out is then untouched).  The reference draws r < p - limb and keeps r >> 32;
+// uniform 32-bit halves differ from that by less than 2^-32.
+inline size_t encode_binary_padded(const u32 limbs[5], const u32* pad, size_t attempts, Affine* out) {
+    for (size_t a = 0; a < attempts; a++) {
+        Fq w;
+        bool canonical = true;
+        for (int i = 0; i < 5; i++) {
+            w[i] = (u64)limbs[i] + ((u64)pad[5 * a + i] << 32);
+            canonical &= w[i] < gl::P;
+        }
+        if (canonical && decompress_into_subgroup(w, out)) return a;
+    }
+    return attempts;
+}
 inline void decode_binary(const Affine& p, u32 limbs[5]) {  // lib.rs:80
     Fq w = compress_from_subgroup(p);
     for (int i = 0; i < 5; i++) limbs[i] = (u32)w[i];
@@ -512,6 +528,27 @@ inline void hashed_elgamal_encrypt_target(CircuitBuilder& b, const PointTarget& 
     in.insert(in.end(), npk.u.begin(), npk.u.end());
     auto h = b.hash_n_to_m_no_pad(in, 5);
     for (int i = 0; i < 5; i++) ct[i] = b.add(msg[i], h[i]);
+}
+
+// Verifiable decryption (not in the reference, whose circuits only encrypt).  The caller ties the key to a public key with
+// connect(public_key_target(sk_bits), pk).  NOT checked here: that c0 and c1 are in the group (add_virtual_point_target checks the
+// curve equation only) and that sk is below the group order.
+inline PointTarget neg_point(CircuitBuilder& b, const PointTarget& p) {
+    PointTarget r = p;
+    for (auto& t : r.u) t = b.mul_const(NEG1, t);
+    return r;
+}
+// msg = c1 - sk c0 (elgamal.rs:19)
+inline PointTarget elgamal_decrypt_target(CircuitBuilder& b, const std::vector<BoolTarget>& sk_bits, const PointTarget& c0, const PointTarget& c1) {
+    return add_point(b, c1, neg_point(b, multiply_point(b, sk_bits, c0)));
+}
+// msg[i] = ct[i] - hash_n_to_m_no_pad(as_fields(sk c0), 5)[i] (hashed_elgamal.rs:28)
+inline void hashed_elgamal_decrypt_target(CircuitBuilder& b, const std::vector<BoolTarget>& sk_bits, const PointTarget& c0, const Target ct[5], Target msg[5]) {
+    PointTarget s = multiply_point(b, sk_bits, c0);
+    std::vector<Target> in(s.x.begin(), s.x.end());
+    in.insert(in.end(), s.u.begin(), s.u.end());
+    auto h = b.hash_n_to_m_no_pad(in, 5);
+    for (int i = 0; i < 5; i++) msg[i] = b.sub(ct[i], h[i]);
 }
 
 }  // namespace ecgfp5

@@ -23,6 +23,7 @@
 #include "kernels_keccak.h"
 #include "kernels_merkle.h"
 #include "kernels_merkle_update.h"
+#include "kernels_elgamal.h"
 #include "kernels_schnorr.h"
 #include "kernels_witness_io.h"
 #include "merkle_host.h"
@@ -3471,6 +3472,159 @@ int p2_gpu_ecgfp5_scalar_muladd(const uint64_t* a, const uint64_t* b, const uint
         hipLaunchKernelGGL(k_ec_scalar_muladd, g1(count, 64), dim3(64), 0, nullptr, d_a, d_b, d_c, count, d_out);
         HIPCHECK(hipGetLastError());
         HIPCHECK(hipMemcpy(out, d_out, 5 * count * 8, hipMemcpyDeviceToHost));
+        return (int)P2_OK;
+    });
+}
+
+// ---- ElGamal on ecGFp5 in batches (kernels_elgamal.h; the host twins are in ecgfp5.h)
+static const size_t ENCODE_MAX_ATTEMPTS = 256;
+static int ec_decompress_launch(const u64* d_w, size_t count, u64* d_out, int* d_status, hipStream_t stream) {
+    hipLaunchKernelGGL(k_ec_decompress_batch, g1(count, 64), dim3(64), 0, stream, d_w, count, d_out, d_status);
+    HIPCHECK(hipGetLastError());
+    return P2_OK;
+}
+static int ec_encode_shape(size_t attempts) {
+    if (attempts == 0 || attempts > ENCODE_MAX_ATTEMPTS) return set_error("attempts is between 1 and 256"), P2_ERR_INVALID;
+    return P2_OK;
+}
+static int ec_encode_launch(const u32* d_limbs, const u32* d_pad, size_t attempts, size_t count, u64* d_out, u32* d_used, int* d_status, hipStream_t stream) {
+    hipLaunchKernelGGL(k_ec_encode_binary, g1(count, 64), dim3(64), 0, stream, d_limbs, d_pad, (u32)attempts, count, d_out, d_used, d_status);
+    HIPCHECK(hipGetLastError());
+    return P2_OK;
+}
+// The four ciphers share one call shape: three input arrays and one or two output arrays of fixed row widths (words).
+enum EgOp { EG_ENCRYPT, EG_DECRYPT, EG_HASHED_ENCRYPT, EG_HASHED_DECRYPT };
+struct EgShape {
+    size_t in[3], out[2];
+};
+static const EgShape EG_SHAPES[4] = {{{10, 5, 10}, {10, 10}}, {{5, 10, 10}, {10, 0}}, {{10, 5, 5}, {10, 5}}, {{5, 10, 5}, {5, 0}}};
+static int eg_launch(EgOp op, const u64* d_a, const u64* d_b, const u64* d_c, size_t count, u64* d_o0, u64* d_o1, int* d_status, hipStream_t stream) {
+    const dim3 grid = g1(count, 64), block(64);
+    switch (op) {
+    case EG_ENCRYPT: hipLaunchKernelGGL(k_elgamal_encrypt, grid, block, 0, stream, d_a, d_b, d_c, count, ec_generator_words(), d_o0, d_o1, d_status); break;
+    case EG_DECRYPT: hipLaunchKernelGGL(k_elgamal_decrypt, grid, block, 0, stream, d_a, d_b, d_c, count, d_o0, d_status); break;
+    case EG_HASHED_ENCRYPT: hipLaunchKernelGGL(k_hashed_elgamal_encrypt, grid, block, 0, stream, d_a, d_b, d_c, count, ec_generator_words(), d_o0, d_o1, d_status); break;
+    case EG_HASHED_DECRYPT: hipLaunchKernelGGL(k_hashed_elgamal_decrypt, grid, block, 0, stream, d_a, d_b, d_c, count, d_o0, d_status); break;
+    }
+    HIPCHECK(hipGetLastError());
+    return P2_OK;
+}
+static int eg_batch(EgOp op, const uint64_t* a, const uint64_t* b, const uint64_t* c, size_t count, uint64_t* o0, uint64_t* o1, int* status, int device) {
+    return guarded_rc([&]() -> int {
+        const EgShape& s = EG_SHAPES[op];
+        if (count == 0) return (int)P2_OK;
+        if (!a || !b || !c || !o0 || (s.out[1] && !o1) || !status) return set_error("null argument"), P2_ERR_INVALID;
+        if (int rc = pick_device(device)) return rc;
+        Allocs tmp;
+        u64 *d_a, *d_b, *d_c, *d_o0, *d_o1 = nullptr;
+        int* d_st;
+        if (upload(tmp, &d_a, (const u64*)a, s.in[0] * count) || upload(tmp, &d_b, (const u64*)b, s.in[1] * count) || upload(tmp, &d_c, (const u64*)c, s.in[2] * count) ||
+            dalloc(tmp, &d_o0, s.out[0] * count) || (s.out[1] && dalloc(tmp, &d_o1, s.out[1] * count)) || dalloc(tmp, &d_st, count))
+            return P2_ERR_HIP;
+        if (int rc = eg_launch(op, d_a, d_b, d_c, count, d_o0, d_o1, d_st, nullptr)) return rc;
+        HIPCHECK(hipMemcpy(o0, d_o0, s.out[0] * count * 8, hipMemcpyDeviceToHost));
+        if (s.out[1]) HIPCHECK(hipMemcpy(o1, d_o1, s.out[1] * count * 8, hipMemcpyDeviceToHost));
+        HIPCHECK(hipMemcpy(status, d_st, count * sizeof(int), hipMemcpyDeviceToHost));
+        return (int)P2_OK;
+    });
+}
+static int eg_batch_device(EgOp op, const uint64_t* d_a, const uint64_t* d_b, const uint64_t* d_c, size_t count, uint64_t* d_o0, uint64_t* d_o1, int* d_status, int device,
+                           void* stream) {
+    return guarded_rc([&]() -> int {
+        if (count == 0) return (int)P2_OK;
+        if (!d_a || !d_b || !d_c || !d_o0 || (EG_SHAPES[op].out[1] && !d_o1) || !d_status) return set_error("null argument"), P2_ERR_INVALID;
+        if (int rc = pick_device(device)) return rc;
+        return eg_launch(op, (const u64*)d_a, (const u64*)d_b, (const u64*)d_c, count, (u64*)d_o0, (u64*)d_o1, d_status, (hipStream_t)stream);
+    });
+}
+int p2_ecgfp5_decompress_batch(const uint64_t* w, size_t count, uint64_t* out, int* status, int device) {
+    return guarded_rc([&]() -> int {
+        if (count == 0) return (int)P2_OK;
+        if (!w || !out || !status) return set_error("null argument"), P2_ERR_INVALID;
+        if (int rc = pick_device(device)) return rc;
+        Allocs tmp;
+        u64 *d_w, *d_out;
+        int* d_st;
+        if (upload(tmp, &d_w, (const u64*)w, 5 * count) || dalloc(tmp, &d_out, 10 * count) || dalloc(tmp, &d_st, count)) return P2_ERR_HIP;
+        if (int rc = ec_decompress_launch(d_w, count, d_out, d_st, nullptr)) return rc;
+        HIPCHECK(hipMemcpy(out, d_out, 10 * count * 8, hipMemcpyDeviceToHost));
+        HIPCHECK(hipMemcpy(status, d_st, count * sizeof(int), hipMemcpyDeviceToHost));
+        return (int)P2_OK;
+    });
+}
+int p2_ecgfp5_decompress_batch_device(const uint64_t* d_w, size_t count, uint64_t* d_out, int* d_status, int device, void* stream) {
+    return guarded_rc([&]() -> int {
+        if (count == 0) return (int)P2_OK;
+        if (!d_w || !d_out || !d_status) return set_error("null argument"), P2_ERR_INVALID;
+        if (int rc = pick_device(device)) return rc;
+        return ec_decompress_launch((const u64*)d_w, count, (u64*)d_out, d_status, (hipStream_t)stream);
+    });
+}
+int p2_ecgfp5_encode_binary_batch(const uint32_t* limbs, const uint32_t* pad, size_t attempts, size_t count, uint64_t* out, uint32_t* used, int* status, int device) {
+    return guarded_rc([&]() -> int {
+        if (int rc = ec_encode_shape(attempts)) return rc;
+        if (count == 0) return (int)P2_OK;
+        if (!limbs || !pad || !out || !used || !status) return set_error("null argument"), P2_ERR_INVALID;
+        if (int rc = pick_device(device)) return rc;
+        Allocs tmp;
+        u32 *d_limbs, *d_pad, *d_used;
+        u64* d_out;
+        int* d_st;
+        if (upload(tmp, &d_limbs, (const u32*)limbs, 5 * count) || upload(tmp, &d_pad, (const u32*)pad, 5 * attempts * count) || dalloc(tmp, &d_out, 10 * count) ||
+            dalloc(tmp, &d_used, count) || dalloc(tmp, &d_st, count))
+            return P2_ERR_HIP;
+        if (int rc = ec_encode_launch(d_limbs, d_pad, attempts, count, d_out, d_used, d_st, nullptr)) return rc;
+        HIPCHECK(hipMemcpy(out, d_out, 10 * count * 8, hipMemcpyDeviceToHost));
+        HIPCHECK(hipMemcpy(used, d_used, count * sizeof(u32), hipMemcpyDeviceToHost));
+        HIPCHECK(hipMemcpy(status, d_st, count * sizeof(int), hipMemcpyDeviceToHost));
+        return (int)P2_OK;
+    });
+}
+int p2_ecgfp5_encode_binary_batch_device(const uint32_t* d_limbs, const uint32_t* d_pad, size_t attempts, size_t count, uint64_t* d_out, uint32_t* d_used, int* d_status,
+                                         int device, void* stream) {
+    return guarded_rc([&]() -> int {
+        if (int rc = ec_encode_shape(attempts)) return rc;
+        if (count == 0) return (int)P2_OK;
+        if (!d_limbs || !d_pad || !d_out || !d_used || !d_status) return set_error("null argument"), P2_ERR_INVALID;
+        if (int rc = pick_device(device)) return rc;
+        return ec_encode_launch((const u32*)d_limbs, (const u32*)d_pad, attempts, count, (u64*)d_out, (u32*)d_used, d_status, (hipStream_t)stream);
+    });
+}
+int p2_elgamal_encrypt_batch(const uint64_t* pk, const uint64_t* nonce, const uint64_t* msg, size_t count, uint64_t* c0, uint64_t* c1, int* status, int device) {
+    return eg_batch(EG_ENCRYPT, pk, nonce, msg, count, c0, c1, status, device);
+}
+int p2_elgamal_encrypt_batch_device(const uint64_t* d_pk, const uint64_t* d_nonce, const uint64_t* d_msg, size_t count, uint64_t* d_c0, uint64_t* d_c1, int* d_status,
+                                    int device, void* stream) {
+    return eg_batch_device(EG_ENCRYPT, d_pk, d_nonce, d_msg, count, d_c0, d_c1, d_status, device, stream);
+}
+int p2_elgamal_decrypt_batch(const uint64_t* sk, const uint64_t* c0, const uint64_t* c1, size_t count, uint64_t* msg, int* status, int device) {
+    return eg_batch(EG_DECRYPT, sk, c0, c1, count, msg, nullptr, status, device);
+}
+int p2_elgamal_decrypt_batch_device(const uint64_t* d_sk, const uint64_t* d_c0, const uint64_t* d_c1, size_t count, uint64_t* d_msg, int* d_status, int device, void* stream) {
+    return eg_batch_device(EG_DECRYPT, d_sk, d_c0, d_c1, count, d_msg, nullptr, d_status, device, stream);
+}
+int p2_hashed_elgamal_encrypt_batch(const uint64_t* pk, const uint64_t* nonce, const uint64_t* msg, size_t count, uint64_t* c0, uint64_t* ct, int* status, int device) {
+    return eg_batch(EG_HASHED_ENCRYPT, pk, nonce, msg, count, c0, ct, status, device);
+}
+int p2_hashed_elgamal_encrypt_batch_device(const uint64_t* d_pk, const uint64_t* d_nonce, const uint64_t* d_msg, size_t count, uint64_t* d_c0, uint64_t* d_ct,
+                                           int* d_status, int device, void* stream) {
+    return eg_batch_device(EG_HASHED_ENCRYPT, d_pk, d_nonce, d_msg, count, d_c0, d_ct, d_status, device, stream);
+}
+int p2_hashed_elgamal_decrypt_batch(const uint64_t* sk, const uint64_t* c0, const uint64_t* ct, size_t count, uint64_t* msg, int* status, int device) {
+    return eg_batch(EG_HASHED_DECRYPT, sk, c0, ct, count, msg, nullptr, status, device);
+}
+int p2_hashed_elgamal_decrypt_batch_device(const uint64_t* d_sk, const uint64_t* d_c0, const uint64_t* d_ct, size_t count, uint64_t* d_msg, int* d_status, int device,
+                                           void* stream) {
+    return eg_batch_device(EG_HASHED_DECRYPT, d_sk, d_c0, d_ct, count, d_msg, nullptr, d_status, device, stream);
+}
+int p2_ecgfp5_scalar_bits_device(const uint64_t* d_k, size_t count, uint64_t* d_out, size_t stride, int device, void* stream) {
+    return guarded_rc([&]() -> int {
+        if (stride < 320) return set_error("stride is at least 320 words"), P2_ERR_INVALID;
+        if (count == 0) return (int)P2_OK;
+        if (!d_k || !d_out) return set_error("null argument"), P2_ERR_INVALID;
+        if (int rc = pick_device(device)) return rc;
+        hipLaunchKernelGGL(k_ec_scalar_bits, g1(count, 64), dim3(64), 0, (hipStream_t)stream, (const u64*)d_k, count, (u64*)d_out, stride);
+        HIPCHECK(hipGetLastError());
         return (int)P2_OK;
     });
 }
