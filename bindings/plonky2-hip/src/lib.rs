@@ -731,6 +731,34 @@ pub mod pod2 {
                 o.map(Target)
             }
         }
+        /// The Poseidon sponge cipher (poseidon-cipher/src/lib.rs:41, :75) on targets the caller supplies, so that the key can be
+        /// `multiply_point(sk, R)`: with `connect(public_key(sk), pk)` that states "this ciphertext decrypts, under the secret key of
+        /// this public key, to that message".  An Fq element is five targets; `L` is a multiple of 3; a ciphertext has `L + 1`
+        /// elements, the last one the tag.  No new gate.  Not constrained: `ks` on the curve.
+        pub trait CircuitBuilderPoseidonCipher {
+            /// The loop of `PoseidonEncryptTarget::build` (circuit.rs:66-86).
+            fn poseidon_encrypt(&mut self, ks: &PointTarget, nonce: &[Target; 2], m: &[[Target; 5]]) -> Vec<[Target; 5]>;
+            /// `m = ct - s[1..3]` per block; the tag is connected to the closing state, so a wrong one is an unsatisfiable witness.
+            fn poseidon_decrypt(&mut self, ks: &PointTarget, nonce: &[Target; 2], ct: &[[Target; 5]]) -> Vec<[Target; 5]>;
+        }
+        impl<F: Field, const D: usize> CircuitBuilderPoseidonCipher for CircuitBuilder<F, D> {
+            fn poseidon_encrypt(&mut self, ks: &PointTarget, nonce: &[Target; 2], m: &[[Target; 5]]) -> Vec<[Target; 5]> {
+                assert!(m.len() % 3 == 0, "L must be a multiple of 3");
+                let i: Vec<u64> = m.iter().flat_map(|e| e.iter().map(|t| t.0)).collect();
+                let mut o = vec![0u64; 5 * (m.len() + 1)];
+                let rc = unsafe { ffi::p2_builder_poseidon_encrypt(self.h, raw::<10>(&ks.0).as_ptr(), raw::<2>(nonce).as_ptr(), i.as_ptr(), m.len(), o.as_mut_ptr()) };
+                assert!(rc == ffi::P2_OK, "{}", crate::last_error());
+                o.chunks(5).map(|c| core::array::from_fn(|j| Target(c[j]))).collect()
+            }
+            fn poseidon_decrypt(&mut self, ks: &PointTarget, nonce: &[Target; 2], ct: &[[Target; 5]]) -> Vec<[Target; 5]> {
+                assert!(ct.len() % 3 == 1, "a ciphertext has L + 1 elements, L a multiple of 3");
+                let i: Vec<u64> = ct.iter().flat_map(|e| e.iter().map(|t| t.0)).collect();
+                let mut o = vec![0u64; 5 * (ct.len() - 1)];
+                let rc = unsafe { ffi::p2_builder_poseidon_decrypt(self.h, raw::<10>(&ks.0).as_ptr(), raw::<2>(nonce).as_ptr(), i.as_ptr(), ct.len() - 1, o.as_mut_ptr()) };
+                assert!(rc == ffi::P2_OK, "{}", crate::last_error());
+                o.chunks(5).map(|c| core::array::from_fn(|j| Target(c[j]))).collect()
+            }
+        }
     }
     /// Schnorr signatures on ecGFp5 with a Poseidon challenge (csrc/schnorr.h; this project's own scheme, UNPINNED against pod2's
     /// signature bytes): `p2_schnorr_*` on the host and the `verify_schnorr_signature` gadget.

@@ -238,7 +238,18 @@ int p2_native_merkle_update(uint64_t* leaves, size_t num_leaves, size_t leaf_len
 /* PoseidonEncryptTarget::<L>::build (poseidon-cipher/src/circuit.rs:49).  ks: 10 targets (x then u), m: 5*L,
  * nonce: 2, ct: 5*(L+1) */
 int p2_poseidon_cipher_build(p2_builder*, size_t L, p2_target* ks, p2_target* m, p2_target* nonce, p2_target* ct);
-/* native hash / cipher (poseidon-cipher/src/lib.rs:41,75,113).  msg: 5*n_msg words; ct: 5*(ceil3(n_msg)+1) words */
+/* The cipher on targets the caller supplies, so that the key can come out of another gadget: ks = multiply_point(sk_bits, R),
+ * connect(public_key(sk_bits), pk), m = poseidon_decrypt(ks, nonce, ct) states "this ciphertext decrypts, under the secret key of
+ * this public key, to that message".  L a multiple of 3 (P2_ERR_INVALID otherwise); m: 5*L targets, ct: 5*(L+1), the last five
+ * the tag.  No new gate.
+ *   poseidon_encrypt  the loop of PoseidonEncryptTarget::build (circuit.rs:66-86); p2_poseidon_cipher_build is built on it
+ *   poseidon_decrypt  per block hash_state, m = ct - s[1..3], s[1..3] = ct; then the closing hash_state and connect(tag, s[1]) word
+ *                     by word: a wrong tag is an unsatisfiable witness
+ * Not constrained: ks on the curve. */
+int p2_builder_poseidon_encrypt(p2_builder*, const p2_target ks[10], const p2_target nonce[2], const p2_target* m, size_t L, p2_target* ct);
+int p2_builder_poseidon_decrypt(p2_builder*, const p2_target ks[10], const p2_target nonce[2], const p2_target* ct, size_t L, p2_target* m);
+/* native hash / cipher (poseidon-cipher/src/lib.rs:41,75,113).  msg: 5*n_msg words; ct: 5*(ceil3(n_msg)+1) words.  decrypt: n_ct
+ * is 3 k + 1 and l <= n_ct - 1 (P2_ERR_INVALID otherwise; the reference panics); P2_ERR_VERIFY where the reference's asserts fail */
 void p2_native_hash_n_to_m_no_pad(const uint64_t* in, size_t n, uint64_t* out, size_t m);
 void p2_native_poseidon_encrypt(const uint64_t* ks10, const uint64_t* msg, size_t n_msg, const uint64_t* nonce2, uint64_t* ct);
 int p2_native_poseidon_decrypt(const uint64_t* ks10, const uint64_t* ct, size_t n_ct, const uint64_t* nonce2, size_t l, uint64_t* msg);
@@ -361,6 +372,9 @@ int p2_selftest_ntt_device(uint64_t seed, size_t threads, int device);
  * as 0 (the words declared zero are not read); rows bit r = output word r is kept (canonical), the others are unspecified;
  * parts 0 = the round loops as the kernels run them, 1 = first round, middle and last round as separate functions. */
 int p2_host_poseidon_known(uint64_t* states, size_t n_perm, int kind, uint32_t rows, int parts);
+/* The host build of the cipher kernels' sponge step (csrc/kernels_pcipher.h): out = hash_state(in) = hash_n_to_m_no_pad(in, 20) on
+ * twenty canonical words.  last != 0: the closing form, which computes only out[5..10), the tag; the other words come back as 0. */
+int p2_host_pcipher_hash_state(const uint64_t in[20], int last, uint64_t out[20]);
 /* The partial-round section of that permutation alone, in place on count x 12 words that may be ANY u64: from "the state carries
  * round 4's constants" to "the state carries round 26's" (some representative of each word, not canonical).  After four full
  * rounds a test cannot steer what reaches the folds of the section; through this entry point, and p2_gpu_partial_rounds, it can. */
@@ -745,6 +759,22 @@ int p2_hashed_elgamal_decrypt_batch(const uint64_t* sk, const uint64_t* c0, cons
 int p2_hashed_elgamal_decrypt_batch_device(const uint64_t* d_sk, const uint64_t* d_c0, const uint64_t* d_ct, size_t count, uint64_t* d_msg,
                                            int* d_status, int device, void* stream);
 int p2_ecgfp5_scalar_bits_device(const uint64_t* d_k, size_t count, uint64_t* d_out, size_t stride, int device, void* stream);
+
+/* ------------------------------------------------------------------ Poseidon cipher in GPU batches */
+/* One thread per message (csrc/kernels_pcipher.h), the call shape of the sections above.  l, the number of Fq elements of a message,
+ * is one value per call, 0 <= l <= 3072 (P2_ERR_INVALID beyond, before any launch).  Rows: ks [count][10] (x then u of the shared
+ * point, used as words only: no group test, as the host twin), nonce [count][2], msg [count][l][5], ct [count][pad3(l)+1][5] with
+ * pad3(l) = l rounded up to a multiple of 3.  status[i]:
+ *   0  done
+ *   1  decrypt only, the row zeroed: the tag does not match, or a padding element is not zero where the reference asserts it (l > 3)
+ *   2  the row zeroed: a word of ks, nonce, msg or ct not below p
+ * Outputs are p2_native_poseidon_encrypt's and _decrypt's word for word. */
+int p2_poseidon_encrypt_batch(const uint64_t* ks, const uint64_t* nonce, const uint64_t* msg, size_t l, size_t count, uint64_t* ct, int* status, int device);
+int p2_poseidon_encrypt_batch_device(const uint64_t* d_ks, const uint64_t* d_nonce, const uint64_t* d_msg, size_t l, size_t count, uint64_t* d_ct, int* d_status,
+                                     int device, void* stream);
+int p2_poseidon_decrypt_batch(const uint64_t* ks, const uint64_t* nonce, const uint64_t* ct, size_t l, size_t count, uint64_t* msg, int* status, int device);
+int p2_poseidon_decrypt_batch_device(const uint64_t* d_ks, const uint64_t* d_nonce, const uint64_t* d_ct, size_t l, size_t count, uint64_t* d_msg, int* d_status,
+                                     int device, void* stream);
 
 /* ------------------------------------------------------------------ GPU primitives (parity tests / microbench) */
 int p2_gpu_device_count(void);

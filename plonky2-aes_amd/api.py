@@ -346,6 +346,13 @@ def lib():
         "p2_hashed_elgamal_decrypt_batch": (C.c_int, [u64p, u64p, u64p, sz, u64p, C.POINTER(C.c_int), C.c_int]),
         "p2_hashed_elgamal_decrypt_batch_device": (C.c_int, [vp, vp, vp, sz, vp, vp, C.c_int, vp]),
         "p2_ecgfp5_scalar_bits_device": (C.c_int, [vp, sz, vp, sz, C.c_int, vp]),
+        "p2_host_pcipher_hash_state": (C.c_int, [u64p, C.c_int, u64p]),
+        "p2_builder_poseidon_encrypt": (C.c_int, [vp, u64p, u64p, u64p, sz, u64p]),
+        "p2_builder_poseidon_decrypt": (C.c_int, [vp, u64p, u64p, u64p, sz, u64p]),
+        "p2_poseidon_encrypt_batch": (C.c_int, [u64p, u64p, u64p, sz, sz, u64p, C.POINTER(C.c_int), C.c_int]),
+        "p2_poseidon_encrypt_batch_device": (C.c_int, [vp, vp, vp, sz, sz, vp, vp, C.c_int, vp]),
+        "p2_poseidon_decrypt_batch": (C.c_int, [u64p, u64p, u64p, sz, sz, u64p, C.POINTER(C.c_int), C.c_int]),
+        "p2_poseidon_decrypt_batch_device": (C.c_int, [vp, vp, vp, sz, sz, vp, vp, C.c_int, vp]),
     }
     missing = []
     for name, (res, args) in sig.items():
@@ -711,6 +718,33 @@ class CircuitBuilder:
         if lib().p2_builder_hashed_elgamal_decrypt(self._h, _arr(sk_bits), _arr(c0), _arr(ct), out):
             raise P2Error(_err())
         return list(out)
+
+    # ---- the Poseidon cipher on targets the caller supplies (csrc/poseidon_cipher.h): ks a point of 10 targets, nonce 2, a message
+    # 5 L targets with L a multiple of 3, a ciphertext 5 (L + 1), the last five the tag.  The sealed-message statement is
+    # ks = multiply_point(sk_bits, R); connect(public_key(sk_bits), pk); m = poseidon_decrypt(ks, nonce, ct).  Not checked in the
+    # circuit: ks or R in the group, sk below the order.
+    @staticmethod
+    def _pcipher_args(ks, nonce, rows, extra):
+        if len(ks) != 10 or len(nonce) != 2 or len(rows) % 5 or (len(rows) // 5 - extra) % 3 or len(rows) // 5 < extra:
+            raise P2Error("the cipher takes a key of 10 targets, a nonce of 2 and 5 targets per element, L a multiple of 3")
+        return len(rows) // 5 - extra
+
+    def poseidon_encrypt(self, ks, nonce, m):
+        """ct = encrypt(ks, m, nonce) (lib.rs:41): the loop of PoseidonEncryptTarget::build, as 5 (L + 1) targets"""
+        L = self._pcipher_args(ks, nonce, m, 0)
+        out = (u64 * (5 * (L + 1)))()
+        if lib().p2_builder_poseidon_encrypt(self._h, _arr(ks), _arr(nonce), _arr(m) if L else (u64 * 1)(), L, out):
+            raise P2Error(_err())
+        return list(out)
+
+    def poseidon_decrypt(self, ks, nonce, ct):
+        """m = decrypt(ks, ct, nonce) (lib.rs:75) as 5 L targets; the tag is connected to the closing state, so a wrong one is an
+        unsatisfiable witness"""
+        L = self._pcipher_args(ks, nonce, ct, 1)
+        out = (u64 * max(5 * L, 1))()
+        if lib().p2_builder_poseidon_decrypt(self._h, _arr(ks), _arr(nonce), _arr(ct), L, out):
+            raise P2Error(_err())
+        return list(out)[:5 * L]
 
     # ---- Schnorr signatures on ecGFp5 (csrc/schnorr.h).  A signature target is (s_bits, e): 320 bit targets and a hash.
     def add_virtual_schnorr_signature_target(self):
@@ -1447,6 +1481,119 @@ class poseidon_native:
         if lib().p2_native_poseidon_decrypt(_arr([v for fq in ks for v in fq]), _arr([v for fq in ct for v in fq]), len(ct), _arr(nonce), l, msg):
             raise P2Error(_err())
         return [tuple(msg[5 * i:5 * i + 5]) for i in range(l)]
+
+    # ---- the cipher in GPU batches (csrc/kernels_pcipher.h).  Every list is per item; a key is the shared point ks = r K = k R
+    # (new_key / expanded_key), used as its ten words; a nonce two words; a message l Fq elements of five words, l one value per
+    # call and at most 3072; a ciphertext pad3(l) + 1 elements.  Statuses: 0 done, 1 (decrypt) the tag or the padding is wrong,
+    # 2 a word not below p; a row whose status is not 0 holds zeros.  device=None: a host loop over encrypt / decrypt's entry
+    # points with the same checks.
+    DONE, REJECTED, MALFORMED = 0, 1, 2
+    MAX_LEN = 3072
+
+    @staticmethod
+    def _batch_args(name, kss, nonces, rows, elems):
+        """-> (ks, nonce, flat rows or a one-word dummy, n); rows: per item `elems` Fq elements"""
+        ks, n, k = _rows([list(p[0]) + list(p[1]) for p in kss], "keys")
+        nn, n_n, k_n = _rows(nonces, "nonces")
+        flat, n_r, k_r = _rows([[v for fq in row for v in fq] for row in rows], "messages and ciphertexts")
+        if n != n_n or n != n_r:
+            raise P2Error(name + ": every list has one entry per item")
+        if n and (k != 10 or k_n != 2 or k_r != 5 * elems):
+            raise P2Error("%s: keys are points of ten words, nonces two words, rows %d elements of five words" % (name, elems))
+        return ks, nn, flat if flat is not None else (u64 * 1)(), n
+
+    @staticmethod
+    def _pad3(l):
+        return (l + 2) // 3 * 3
+
+    @staticmethod
+    def _elements(buf, n, elems):
+        return [[tuple(buf[5 * (elems * i + j):5 * (elems * i + j) + 5]) for j in range(elems)] for i in range(n)]
+
+    @staticmethod
+    def _check_len(l):
+        if not 0 <= l <= poseidon_native.MAX_LEN:
+            raise P2Error("l is at most 3072 elements")
+
+    @staticmethod
+    def encrypt_batch(kss, nonces, msgs, device=0):
+        """-> (cts, statuses): cts[i] = encrypt(kss[i], msgs[i], nonces[i]) (lib.rs:41), every message of one length"""
+        msgs = [list(m) for m in msgs]
+        l = len(msgs[0]) if msgs else 0
+        ks, nn, m, n = poseidon_native._batch_args("encrypt_batch", kss, nonces, msgs, l)
+        if n == 0:
+            return [], []
+        nct = poseidon_native._pad3(l) + 1
+        ct, status = (u64 * (5 * nct * n))(), (C.c_int * n)()
+        if device is None:
+            poseidon_native._check_len(l)
+            for i in range(n):
+                if any(w >= P for w in ks[10 * i:10 * i + 10]) or any(w >= P for w in nn[2 * i:2 * i + 2]) or any(w >= P for w in m[5 * l * i:5 * l * (i + 1)]):
+                    status[i] = poseidon_native.MALFORMED
+                else:
+                    lib().p2_native_poseidon_encrypt(_at(ks, 10 * i), _at(m, 5 * l * i), l, _at(nn, 2 * i), _at(ct, 5 * nct * i))
+        elif lib().p2_poseidon_encrypt_batch(ks, nn, m, l, n, ct, status, device):
+            raise P2Error("p2_poseidon_encrypt_batch failed: " + _err())
+        return poseidon_native._elements(ct, n, nct), list(status)
+
+    @staticmethod
+    def decrypt_batch(kss, nonces, cts, l, device=0):
+        """-> (msgs, statuses): msgs[i] = decrypt(kss[i], cts[i], nonces[i], l) (lib.rs:75); status 1 and l zero elements where the
+        reference's asserts fail.  Its rule for the padding elements holds: they are looked at only when l > 3."""
+        nct = poseidon_native._pad3(l) + 1
+        ks, nn, ct, n = poseidon_native._batch_args("decrypt_batch", kss, nonces, cts, nct)
+        if n == 0:
+            return [], []
+        msg, status = (u64 * max(5 * l * n, 1))(), (C.c_int * n)()
+        if device is None:
+            poseidon_native._check_len(l)
+            one = (u64 * max(5 * l, 1))()
+            for i in range(n):
+                if any(w >= P for w in ks[10 * i:10 * i + 10]) or any(w >= P for w in nn[2 * i:2 * i + 2]) or any(w >= P for w in ct[5 * nct * i:5 * nct * (i + 1)]):
+                    status[i] = poseidon_native.MALFORMED
+                elif lib().p2_native_poseidon_decrypt(_at(ks, 10 * i), _at(ct, 5 * nct * i), nct, _at(nn, 2 * i), l, one):
+                    status[i] = poseidon_native.REJECTED
+                else:
+                    msg[5 * l * i:5 * l * (i + 1)] = one[:5 * l]
+        elif lib().p2_poseidon_decrypt_batch(ks, nn, ct, l, n, msg, status, device):
+            raise P2Error("p2_poseidon_decrypt_batch failed: " + _err())
+        return poseidon_native._elements(msg, n, l), list(status)
+
+    @staticmethod
+    def encrypt_batch_device(d_ks, d_nonce, d_msg, l, count, d_ct, d_status, device=0, stream=None):
+        """Every buffer a raw device pointer (p2_poseidon_encrypt_batch_device); asynchronous on `stream`."""
+        if lib().p2_poseidon_encrypt_batch_device(d_ks, d_nonce, d_msg, l, count, d_ct, d_status, device, stream):
+            raise P2Error("p2_poseidon_encrypt_batch_device failed: " + _err())
+
+    @staticmethod
+    def decrypt_batch_device(d_ks, d_nonce, d_ct, l, count, d_msg, d_status, device=0, stream=None):
+        if lib().p2_poseidon_decrypt_batch_device(d_ks, d_nonce, d_ct, l, count, d_msg, d_status, device, stream):
+            raise P2Error("p2_poseidon_decrypt_batch_device failed: " + _err())
+
+    @staticmethod
+    def seal_batch(pks, rs, nonces, msgs, device=0):
+        """A message of any length to the holder of a public key: R = r G, ks = r pk (two ecgfp5.mul_batch), ct = encrypt(ks, msg,
+        nonce).  -> (Rs, cts, statuses); a mul_batch status other than 0 (a pk outside the group: 2) is the item's, its rows zeros."""
+        msgs = [list(m) for m in msgs]
+        n, l = len(msgs), len(msgs[0]) if msgs else 0
+        Rs, st_r = ecgfp5.mul_batch(rs, [ecgfp5.generator()] * n, device)
+        kss, st_k = ecgfp5.mul_batch(rs, pks, device)
+        cts, st = poseidon_native.encrypt_batch(kss, nonces, msgs, device)
+        zero_ct = [(0,) * 5] * (poseidon_native._pad3(l) + 1)
+        for i in range(n):
+            if st_r[i] or st_k[i]:
+                st[i], cts[i], Rs[i] = st_r[i] or st_k[i], list(zero_ct), ((0,) * 5, (0,) * 5)
+        return Rs, cts, st
+
+    @staticmethod
+    def open_batch(sks, Rs, nonces, cts, l, device=0):
+        """The receiving side of seal_batch: ks = sk R (one mul_batch), msg = decrypt(ks, ct, nonce, l).  -> (msgs, statuses)"""
+        kss, st_k = ecgfp5.mul_batch(sks, Rs, device)
+        msgs, st = poseidon_native.decrypt_batch(kss, nonces, cts, l, device)
+        for i in range(len(st)):
+            if st_k[i]:
+                st[i], msgs[i] = st_k[i], [(0,) * 5] * l
+        return msgs, st
 
 
 def _pt(point):

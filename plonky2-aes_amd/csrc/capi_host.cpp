@@ -8,6 +8,8 @@
 #include "compress.h"
 #include "ecgfp5.h"
 #include "merkle_host.h"
+#define P2_PCIPHER_SPONGE_ONLY
+#include "kernels_pcipher.h"
 #include "poseidon_cipher.h"
 #include "poseidon_fast.h"
 #include "schnorr.h"
@@ -455,6 +457,29 @@ int p2_poseidon_cipher_build(p2_builder* b, size_t L, p2_target* ks, p2_target* 
         return set_error(e.what()), P2_ERR_INVALID;
     }
 }
+static pcipher::FqT fqt_at(const p2_target* p) { return pcipher::FqT{(Target)p[0], (Target)p[1], (Target)p[2], (Target)p[3], (Target)p[4]}; }
+// the two cipher gadgets share one call shape: `in` and `out` are the message and the ciphertext, in this or the other order
+static int pcipher_gadget(p2_builder* b, bool decrypt, const p2_target* ks, const p2_target* nonce, const p2_target* in, size_t L, p2_target* out) {
+    try {
+        if (!b || !ks || !nonce || !in || !out) throw std::runtime_error("null argument");
+        if (L % 3 != 0) throw std::runtime_error("L must be a multiple of 3");
+        const Target n[2] = {(Target)nonce[0], (Target)nonce[1]};
+        std::vector<pcipher::FqT> v(decrypt ? L + 1 : L);
+        for (size_t i = 0; i < v.size(); i++) v[i] = fqt_at(in + 5 * i);
+        const auto o = decrypt ? pcipher::poseidon_decrypt(b->b, fqt_at(ks), fqt_at(ks + 5), n, v) : pcipher::poseidon_encrypt(b->b, fqt_at(ks), fqt_at(ks + 5), n, v);
+        for (size_t i = 0; i < o.size(); i++)
+            for (int j = 0; j < 5; j++) out[5 * i + j] = o[i][j];
+        return P2_OK;
+    } catch (std::exception& e) {
+        return set_error(e.what()), P2_ERR_INVALID;
+    }
+}
+int p2_builder_poseidon_encrypt(p2_builder* b, const p2_target ks[10], const p2_target nonce[2], const p2_target* m, size_t L, p2_target* ct) {
+    return pcipher_gadget(b, false, ks, nonce, m, L, ct);
+}
+int p2_builder_poseidon_decrypt(p2_builder* b, const p2_target ks[10], const p2_target nonce[2], const p2_target* ct, size_t L, p2_target* m) {
+    return pcipher_gadget(b, true, ks, nonce, ct, L, m);
+}
 void p2_native_hash_n_to_m_no_pad(const uint64_t* in, size_t n, uint64_t* out, size_t m) {
     (void)guarded([&] {
         auto o = pcipher::hash_n_to_m_no_pad(std::vector<u64>(in, in + n), m);
@@ -474,9 +499,11 @@ void p2_native_poseidon_encrypt(const uint64_t* ks, const uint64_t* msg, size_t 
     });
 }
 int p2_native_poseidon_decrypt(const uint64_t* ks, const uint64_t* ct, size_t n_ct, const uint64_t* nonce, size_t l, uint64_t* msg) {
+    // pcipher::decrypt walks whole blocks of three: any other shape would write past m, and the reference panics there
+    if (n_ct % 3 != 1) return set_error("poseidon decrypt: a ciphertext has 3 k + 1 elements"), P2_ERR_INVALID;
     std::vector<pcipher::Fq> c(n_ct), m;
     for (size_t i = 0; i < n_ct; i++) c[i] = fq_at(ct + 5 * i);
-    if (n_ct < 1 || l > n_ct - 1 || !pcipher::decrypt(fq_at(ks), fq_at(ks + 5), c, nonce, l, &m)) return set_error("poseidon decrypt: authentication failed"), P2_ERR_VERIFY;
+    if ( l > n_ct - 1 || !pcipher::decrypt(fq_at(ks), fq_at(ks + 5), c, nonce, l, &m)) return set_error("poseidon decrypt: authentication failed"), P2_ERR_VERIFY;
     for (size_t i = 0; i < m.size(); i++) memcpy(msg + 5 * i, m[i].data(), 40);
     return P2_OK;
 }
@@ -760,6 +787,18 @@ int p2_host_poseidon_known(uint64_t* states, size_t n_perm, int kind, uint32_t r
             glf::permute_known_any(s, (u32)kind, rows);
         }
     }
+    return P2_OK;
+}
+// pcipher::hash_state as the cipher kernels run it (p2k::pcipher_hash_state, kernels_pcipher.h).  last != 0: only out[5..10) is
+// defined, the other words come back as 0.
+int p2_host_pcipher_hash_state(const uint64_t in[20], int last, uint64_t out[20]) {
+    if (!in || !out) return set_error("p2_host_pcipher_hash_state: null argument"), P2_ERR_INVALID;
+    for (int i = 0; i < 20; i++)
+        if (in[i] >= gl::P) return set_error("p2_host_pcipher_hash_state: non-canonical word"), P2_ERR_INVALID;
+    u64 s[20];
+    memcpy(s, in, sizeof s);
+    p2k::pcipher_hash_state(s, last != 0);
+    for (int i = 0; i < 20; i++) out[i] = (last && (i < 5 || i >= 10)) ? 0 : s[i];
     return P2_OK;
 }
 // The 22 partial rounds alone (glf::partial_block), on arbitrary u64 words: what reaches its folds is the caller's choice.

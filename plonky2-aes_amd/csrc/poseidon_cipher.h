@@ -99,6 +99,48 @@ inline FqT nnf_add(CircuitBuilder& b, const FqT& x, const FqT& y) {
     for (int i = 0; i < 5; i++) r[i] = b.add(x[i], y[i]);
     return r;
 }
+// The loop of PoseidonEncryptTarget::build (circuit.rs:66-86) on targets the caller supplies: ct has m.size() + 1 elements, the
+// last one the tag.  m.size() is a multiple of 3, as build asserts; the padding of a ragged length is a native matter.
+inline std::vector<FqT> poseidon_encrypt(CircuitBuilder& b, const FqT& ks_x, const FqT& ks_u, const Target nonce[2], const std::vector<FqT>& m) {
+    const size_t L = m.size();
+    if (L % 3 != 0) throw std::runtime_error("L must be a multiple of 3");
+    Target z = b.constant(0);
+    FqT fzero = {z, z, z, z, z};
+    std::vector<FqT> ct(L + 1, fzero);
+    FqT n_l = {nonce[0], nonce[1], b.constant((u64)L), z, z};
+    FqT s[4] = {fzero, ks_x, ks_u, n_l};
+    for (size_t i = 0; i < L / 3; i++) {
+        hash_state_target(b, s);
+        for (int k = 0; k < 3; k++) {
+            s[1 + k] = nnf_add(b, s[1 + k], m[3 * i + k]);
+            ct[3 * i + k] = s[1 + k];
+        }
+    }
+    hash_state_target(b, s);
+    ct[L] = s[1];
+    return ct;
+}
+// lib.rs:75 in a circuit: per block hash_state, m = ct - s[1..3] component-wise, s[1..3] = ct; then the closing hash_state and
+// connect(ct[L], s[1]) word by word, so a wrong tag is an unsatisfiable witness.  ct has L + 1 elements, L a multiple of 3.
+inline std::vector<FqT> poseidon_decrypt(CircuitBuilder& b, const FqT& ks_x, const FqT& ks_u, const Target nonce[2], const std::vector<FqT>& ct) {
+    if (ct.empty() || (ct.size() - 1) % 3 != 0) throw std::runtime_error("L must be a multiple of 3");
+    const size_t L = ct.size() - 1;
+    Target z = b.constant(0);
+    FqT fzero = {z, z, z, z, z};
+    std::vector<FqT> m(L, fzero);
+    FqT n_l = {nonce[0], nonce[1], b.constant((u64)L), z, z};
+    FqT s[4] = {fzero, ks_x, ks_u, n_l};
+    for (size_t i = 0; i < L / 3; i++) {
+        hash_state_target(b, s);
+        for (int k = 0; k < 3; k++) {
+            for (int j = 0; j < 5; j++) m[3 * i + k][j] = b.sub(ct[3 * i + k][j], s[1 + k][j]);
+            s[1 + k] = ct[3 * i + k];
+        }
+    }
+    hash_state_target(b, s);
+    for (int j = 0; j < 5; j++) b.connect(ct[L][j], s[1][j]);
+    return m;
+}
 struct PoseidonEncryptTarget {  // circuit.rs:35
     size_t L;
     FqT ks_x, ks_u;
@@ -108,7 +150,7 @@ struct PoseidonEncryptTarget {  // circuit.rs:35
         if (L % 3 != 0) throw std::runtime_error("L must be a multiple of 3");
         PoseidonEncryptTarget t;
         t.L = L;
-        Target z = b.constant(0);
+        b.constant(0);  // the zero of circuit.rs:55 comes before the virtual targets
         for (auto& x : t.ks_x) x = b.add_virtual_target();
         for (auto& x : t.ks_u) x = b.add_virtual_target();
         t.m.resize(L);
@@ -116,19 +158,7 @@ struct PoseidonEncryptTarget {  // circuit.rs:35
             for (auto& x : e) x = b.add_virtual_target();
         t.nonce[0] = b.add_virtual_target();
         t.nonce[1] = b.add_virtual_target();
-        FqT fzero = {z, z, z, z, z};
-        t.ct.assign(L + 1, fzero);
-        FqT n_l = {t.nonce[0], t.nonce[1], b.constant((u64)L), z, z};
-        FqT s[4] = {fzero, t.ks_x, t.ks_u, n_l};
-        for (size_t i = 0; i < L / 3; i++) {
-            hash_state_target(b, s);
-            for (int k = 0; k < 3; k++) {
-                s[1 + k] = nnf_add(b, s[1 + k], t.m[3 * i + k]);
-                t.ct[3 * i + k] = s[1 + k];
-            }
-        }
-        hash_state_target(b, s);
-        t.ct[L] = s[1];
+        t.ct = poseidon_encrypt(b, t.ks_x, t.ks_u, t.nonce, t.m);
         return t;
     }
 };

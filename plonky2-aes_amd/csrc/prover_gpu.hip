@@ -24,6 +24,7 @@
 #include "kernels_merkle.h"
 #include "kernels_merkle_update.h"
 #include "kernels_elgamal.h"
+#include "kernels_pcipher.h"
 #include "kernels_schnorr.h"
 #include "kernels_witness_io.h"
 #include "merkle_host.h"
@@ -3627,6 +3628,69 @@ int p2_ecgfp5_scalar_bits_device(const uint64_t* d_k, size_t count, uint64_t* d_
         HIPCHECK(hipGetLastError());
         return (int)P2_OK;
     });
+}
+
+// ---- the Poseidon cipher in batches (kernels_pcipher.h; the host twins are in poseidon_cipher.h).  Encryption and decryption
+// share one call shape: ks, nonce, one input row and one output row per item, of 5 l and 5 (pad3(l) + 1) words in this or the
+// other order.
+static const size_t PCIPHER_MAX_LEN = 3072;
+static int pcipher_shape(size_t l) {
+    if (l > PCIPHER_MAX_LEN) return set_error("l is at most 3072 elements"), P2_ERR_INVALID;
+    return P2_OK;
+}
+static size_t pcipher_msg_words(size_t l) { return 5 * l; }
+static size_t pcipher_ct_words(size_t l) { return 5 * ((l + 2) / 3 * 3 + 1); }
+static int pcipher_launch(bool decrypt, const u64* d_ks, const u64* d_nonce, const u64* d_in, size_t l, size_t count, u64* d_out, int* d_status, hipStream_t stream) {
+    if (decrypt)
+        hipLaunchKernelGGL(k_pcipher_decrypt, g1(count, 64), dim3(64), 0, stream, d_ks, d_nonce, d_in, (u32)l, count, d_out, d_status);
+    else
+        hipLaunchKernelGGL(k_pcipher_encrypt, g1(count, 64), dim3(64), 0, stream, d_ks, d_nonce, d_in, (u32)l, count, d_out, d_status);
+    HIPCHECK(hipGetLastError());
+    return P2_OK;
+}
+static int pcipher_batch(bool decrypt, const uint64_t* ks, const uint64_t* nonce, const uint64_t* in, size_t l, size_t count, uint64_t* out, int* status, int device) {
+    return guarded_rc([&]() -> int {
+        if (int rc = pcipher_shape(l)) return rc;
+        if (count == 0) return (int)P2_OK;
+        const size_t n_in = decrypt ? pcipher_ct_words(l) : pcipher_msg_words(l), n_out = decrypt ? pcipher_msg_words(l) : pcipher_ct_words(l);
+        if (!ks || !nonce || !status || (n_in && !in) || (n_out && !out)) return set_error("null argument"), P2_ERR_INVALID;
+        if (int rc = pick_device(device)) return rc;
+        Allocs tmp;
+        u64 *d_ks, *d_nonce, *d_in, *d_out;
+        int* d_st;
+        if (upload(tmp, &d_ks, (const u64*)ks, 10 * count) || upload(tmp, &d_nonce, (const u64*)nonce, 2 * count) || upload(tmp, &d_in, (const u64*)in, n_in * count) ||
+            dalloc(tmp, &d_out, n_out * count) || dalloc(tmp, &d_st, count))
+            return P2_ERR_HIP;
+        if (int rc = pcipher_launch(decrypt, d_ks, d_nonce, d_in, l, count, d_out, d_st, nullptr)) return rc;
+        if (n_out) HIPCHECK(hipMemcpy(out, d_out, n_out * count * 8, hipMemcpyDeviceToHost));
+        HIPCHECK(hipMemcpy(status, d_st, count * sizeof(int), hipMemcpyDeviceToHost));
+        return (int)P2_OK;
+    });
+}
+static int pcipher_batch_device(bool decrypt, const uint64_t* d_ks, const uint64_t* d_nonce, const uint64_t* d_in, size_t l, size_t count, uint64_t* d_out, int* d_status,
+                                int device, void* stream) {
+    return guarded_rc([&]() -> int {
+        if (int rc = pcipher_shape(l)) return rc;
+        if (count == 0) return (int)P2_OK;
+        const size_t n_in = decrypt ? pcipher_ct_words(l) : pcipher_msg_words(l), n_out = decrypt ? pcipher_msg_words(l) : pcipher_ct_words(l);
+        if (!d_ks || !d_nonce || !d_status || (n_in && !d_in) || (n_out && !d_out)) return set_error("null argument"), P2_ERR_INVALID;
+        if (int rc = pick_device(device)) return rc;
+        return pcipher_launch(decrypt, (const u64*)d_ks, (const u64*)d_nonce, (const u64*)d_in, l, count, (u64*)d_out, d_status, (hipStream_t)stream);
+    });
+}
+int p2_poseidon_encrypt_batch(const uint64_t* ks, const uint64_t* nonce, const uint64_t* msg, size_t l, size_t count, uint64_t* ct, int* status, int device) {
+    return pcipher_batch(false, ks, nonce, msg, l, count, ct, status, device);
+}
+int p2_poseidon_encrypt_batch_device(const uint64_t* d_ks, const uint64_t* d_nonce, const uint64_t* d_msg, size_t l, size_t count, uint64_t* d_ct, int* d_status, int device,
+                                     void* stream) {
+    return pcipher_batch_device(false, d_ks, d_nonce, d_msg, l, count, d_ct, d_status, device, stream);
+}
+int p2_poseidon_decrypt_batch(const uint64_t* ks, const uint64_t* nonce, const uint64_t* ct, size_t l, size_t count, uint64_t* msg, int* status, int device) {
+    return pcipher_batch(true, ks, nonce, ct, l, count, msg, status, device);
+}
+int p2_poseidon_decrypt_batch_device(const uint64_t* d_ks, const uint64_t* d_nonce, const uint64_t* d_ct, size_t l, size_t count, uint64_t* d_msg, int* d_status, int device,
+                                     void* stream) {
+    return pcipher_batch_device(true, d_ks, d_nonce, d_ct, l, count, d_msg, d_status, device, stream);
 }
 
 // ---- batched verification
