@@ -1236,6 +1236,30 @@ def _rows(rows, what):
     return (_arr(flat) if flat else None), len(rows), k
 
 
+def _device_call(name, *args):
+    """a _device form: every buffer a raw device pointer, asynchronous on the stream"""
+    if getattr(lib(), name)(*args):
+        raise P2Error("%s failed: %s" % (name, _err()))
+
+
+def _batch_call(name, counts, mismatch, outs, device, host, call):
+    """One per-item batch call.  counts: the lengths of the input lists, which agree or `mismatch` is raised; outs: one (ctype,
+    elements per item) per output array.  -> (flat output arrays, statuses), all empty for an empty batch.  device=None: the host
+    loop, host(i, outs, status) per item; otherwise call(fn, n, outs, status) makes the library call fn = `name`."""
+    n = counts[0]
+    if any(m != n for m in counts):
+        raise P2Error(mismatch)
+    if n == 0:
+        return [[] for _ in outs], []
+    outs, status = [(t * max(w * n, 1))() for t, w in outs], (C.c_int * n)()
+    if device is None:
+        for i in range(n):
+            host(i, outs, status)
+    elif call(getattr(lib(), name), n, outs, status):
+        raise P2Error("%s failed: %s" % (name, _err()))
+    return outs, list(status)
+
+
 class MerkleTree:
     """plonky2 MerkleTree::new(leaves, cap_height) with PoseidonHash.  leaves: a list of equally long lists of canonical field
     elements, a power of two of them.  device = an index: the tree is built and kept on that GPU (p2_merkle_tree_*; .cap,
@@ -1422,8 +1446,7 @@ class merkle:
     @staticmethod
     def verify_batch_device(d_leaves, leaf_len, d_indices, d_siblings, depth, d_cap, cap_height, n, d_status, device=0, stream=None):
         """Every buffer a raw device pointer (p2_merkle_verify_batch_device); asynchronous on `stream`."""
-        if lib().p2_merkle_verify_batch_device(d_leaves, leaf_len, d_indices, d_siblings, depth, d_cap, cap_height, n, d_status, device, stream):
-            raise P2Error("p2_merkle_verify_batch_device failed: " + _err())
+        _device_call("p2_merkle_verify_batch_device", d_leaves, leaf_len, d_indices, d_siblings, depth, d_cap, cap_height, n, d_status, device, stream)
 
 
 class keccak_native:
@@ -1492,15 +1515,13 @@ class poseidon_native:
 
     @staticmethod
     def _batch_args(name, kss, nonces, rows, elems):
-        """-> (ks, nonce, flat rows or a one-word dummy, n); rows: per item `elems` Fq elements"""
+        """-> (ks, nonce, flat rows or a one-word dummy, the three list lengths); rows: per item `elems` Fq elements"""
         ks, n, k = _rows([list(p[0]) + list(p[1]) for p in kss], "keys")
         nn, n_n, k_n = _rows(nonces, "nonces")
         flat, n_r, k_r = _rows([[v for fq in row for v in fq] for row in rows], "messages and ciphertexts")
-        if n != n_n or n != n_r:
-            raise P2Error(name + ": every list has one entry per item")
-        if n and (k != 10 or k_n != 2 or k_r != 5 * elems):
+        if n == n_n == n_r != 0 and (k != 10 or k_n != 2 or k_r != 5 * elems):
             raise P2Error("%s: keys are points of ten words, nonces two words, rows %d elements of five words" % (name, elems))
-        return ks, nn, flat if flat is not None else (u64 * 1)(), n
+        return ks, nn, flat if flat is not None else (u64 * 1)(), [n, n_n, n_r]
 
     @staticmethod
     def _pad3(l):
@@ -1520,55 +1541,47 @@ class poseidon_native:
         """-> (cts, statuses): cts[i] = encrypt(kss[i], msgs[i], nonces[i]) (lib.rs:41), every message of one length"""
         msgs = [list(m) for m in msgs]
         l = len(msgs[0]) if msgs else 0
-        ks, nn, m, n = poseidon_native._batch_args("encrypt_batch", kss, nonces, msgs, l)
-        if n == 0:
-            return [], []
+        ks, nn, m, counts = poseidon_native._batch_args("encrypt_batch", kss, nonces, msgs, l)
         nct = poseidon_native._pad3(l) + 1
-        ct, status = (u64 * (5 * nct * n))(), (C.c_int * n)()
-        if device is None:
+
+        def host(i, outs, status):
             poseidon_native._check_len(l)
-            for i in range(n):
-                if any(w >= P for w in ks[10 * i:10 * i + 10]) or any(w >= P for w in nn[2 * i:2 * i + 2]) or any(w >= P for w in m[5 * l * i:5 * l * (i + 1)]):
-                    status[i] = poseidon_native.MALFORMED
-                else:
-                    lib().p2_native_poseidon_encrypt(_at(ks, 10 * i), _at(m, 5 * l * i), l, _at(nn, 2 * i), _at(ct, 5 * nct * i))
-        elif lib().p2_poseidon_encrypt_batch(ks, nn, m, l, n, ct, status, device):
-            raise P2Error("p2_poseidon_encrypt_batch failed: " + _err())
-        return poseidon_native._elements(ct, n, nct), list(status)
+            if any(w >= P for w in ks[10 * i:10 * i + 10]) or any(w >= P for w in nn[2 * i:2 * i + 2]) or any(w >= P for w in m[5 * l * i:5 * l * (i + 1)]):
+                status[i] = poseidon_native.MALFORMED
+            else:
+                lib().p2_native_poseidon_encrypt(_at(ks, 10 * i), _at(m, 5 * l * i), l, _at(nn, 2 * i), _at(outs[0], 5 * nct * i))
+        (ct,), st = _batch_call("p2_poseidon_encrypt_batch", counts, "encrypt_batch: every list has one entry per item", [(u64, 5 * nct)], device, host,
+                                lambda fn, n, outs, status: fn(ks, nn, m, l, n, outs[0], status, device))
+        return poseidon_native._elements(ct, len(st), nct), st
 
     @staticmethod
     def decrypt_batch(kss, nonces, cts, l, device=0):
         """-> (msgs, statuses): msgs[i] = decrypt(kss[i], cts[i], nonces[i], l) (lib.rs:75); status 1 and l zero elements where the
         reference's asserts fail.  Its rule for the padding elements holds: they are looked at only when l > 3."""
         nct = poseidon_native._pad3(l) + 1
-        ks, nn, ct, n = poseidon_native._batch_args("decrypt_batch", kss, nonces, cts, nct)
-        if n == 0:
-            return [], []
-        msg, status = (u64 * max(5 * l * n, 1))(), (C.c_int * n)()
-        if device is None:
+        ks, nn, ct, counts = poseidon_native._batch_args("decrypt_batch", kss, nonces, cts, nct)
+
+        def host(i, outs, status):
             poseidon_native._check_len(l)
             one = (u64 * max(5 * l, 1))()
-            for i in range(n):
-                if any(w >= P for w in ks[10 * i:10 * i + 10]) or any(w >= P for w in nn[2 * i:2 * i + 2]) or any(w >= P for w in ct[5 * nct * i:5 * nct * (i + 1)]):
-                    status[i] = poseidon_native.MALFORMED
-                elif lib().p2_native_poseidon_decrypt(_at(ks, 10 * i), _at(ct, 5 * nct * i), nct, _at(nn, 2 * i), l, one):
-                    status[i] = poseidon_native.REJECTED
-                else:
-                    msg[5 * l * i:5 * l * (i + 1)] = one[:5 * l]
-        elif lib().p2_poseidon_decrypt_batch(ks, nn, ct, l, n, msg, status, device):
-            raise P2Error("p2_poseidon_decrypt_batch failed: " + _err())
-        return poseidon_native._elements(msg, n, l), list(status)
+            if any(w >= P for w in ks[10 * i:10 * i + 10]) or any(w >= P for w in nn[2 * i:2 * i + 2]) or any(w >= P for w in ct[5 * nct * i:5 * nct * (i + 1)]):
+                status[i] = poseidon_native.MALFORMED
+            elif lib().p2_native_poseidon_decrypt(_at(ks, 10 * i), _at(ct, 5 * nct * i), nct, _at(nn, 2 * i), l, one):
+                status[i] = poseidon_native.REJECTED
+            else:
+                outs[0][5 * l * i:5 * l * (i + 1)] = one[:5 * l]
+        (msg,), st = _batch_call("p2_poseidon_decrypt_batch", counts, "decrypt_batch: every list has one entry per item", [(u64, 5 * l)], device, host,
+                                 lambda fn, n, outs, status: fn(ks, nn, ct, l, n, outs[0], status, device))
+        return poseidon_native._elements(msg, len(st), l), st
 
     @staticmethod
     def encrypt_batch_device(d_ks, d_nonce, d_msg, l, count, d_ct, d_status, device=0, stream=None):
         """Every buffer a raw device pointer (p2_poseidon_encrypt_batch_device); asynchronous on `stream`."""
-        if lib().p2_poseidon_encrypt_batch_device(d_ks, d_nonce, d_msg, l, count, d_ct, d_status, device, stream):
-            raise P2Error("p2_poseidon_encrypt_batch_device failed: " + _err())
+        _device_call("p2_poseidon_encrypt_batch_device", d_ks, d_nonce, d_msg, l, count, d_ct, d_status, device, stream)
 
     @staticmethod
     def decrypt_batch_device(d_ks, d_nonce, d_ct, l, count, d_msg, d_status, device=0, stream=None):
-        if lib().p2_poseidon_decrypt_batch_device(d_ks, d_nonce, d_ct, l, count, d_msg, d_status, device, stream):
-            raise P2Error("p2_poseidon_decrypt_batch_device failed: " + _err())
+        _device_call("p2_poseidon_decrypt_batch_device", d_ks, d_nonce, d_ct, l, count, d_msg, d_status, device, stream)
 
     @staticmethod
     def seal_batch(pks, rs, nonces, msgs, device=0):
@@ -1739,27 +1752,21 @@ class ecgfp5:
         neutral as output) for a point with a word not below p or outside the group.  device=None: a host loop."""
         ks, n, _ = _rows([_sc_words(k) for k in scalars], "scalars")
         ps, n_p, _ = _rows([list(p[0]) + list(p[1]) for p in points], "points")
-        if n != n_p:
-            raise P2Error("mul_batch: one point per scalar")
-        if n == 0:
-            return [], []
-        out, status = (u64 * (10 * n))(), (C.c_int * n)()
-        if device is None:
-            for i in range(n):
-                pt = _pt_out(ps[10 * i:10 * i + 10])
-                ok = all(w < P for w in pt[0] + pt[1]) and ecgfp5.is_in_subgroup(pt)
-                status[i] = 0 if ok else 2
-                if ok:
-                    out[10 * i:10 * i + 10] = list(sum(ecgfp5.mul(_int5(ks[5 * i:5 * i + 5]), pt), ()))
-        elif lib().p2_ecgfp5_mul_batch(ks, ps, n, out, status, device):
-            raise P2Error("p2_ecgfp5_mul_batch failed: " + _err())
-        return [_pt_out(out[10 * i:10 * i + 10]) for i in range(n)], list(status)
+
+        def host(i, outs, status):
+            pt = _pt_out(ps[10 * i:10 * i + 10])
+            ok = all(w < P for w in pt[0] + pt[1]) and ecgfp5.is_in_subgroup(pt)
+            status[i] = 0 if ok else 2
+            if ok:
+                outs[0][10 * i:10 * i + 10] = list(sum(ecgfp5.mul(_int5(ks[5 * i:5 * i + 5]), pt), ()))
+        (out,), st = _batch_call("p2_ecgfp5_mul_batch", [n, n_p], "mul_batch: one point per scalar", [(u64, 10)], device, host,
+                                 lambda fn, n, outs, status: fn(ks, ps, n, outs[0], status, device))
+        return _points_out(out, len(st)), st
 
     @staticmethod
     def mul_batch_device(d_k, d_p, count, d_out, d_status, device=0, stream=None):
         """Every buffer a raw device pointer (p2_ecgfp5_mul_batch_device); asynchronous on `stream`."""
-        if lib().p2_ecgfp5_mul_batch_device(d_k, d_p, count, d_out, d_status, device, stream):
-            raise P2Error("p2_ecgfp5_mul_batch_device failed: " + _err())
+        _device_call("p2_ecgfp5_mul_batch_device", d_k, d_p, count, d_out, d_status, device, stream)
 
     # ---- ElGamal in GPU batches (csrc/kernels_elgamal.h).  Every list is per item; a caller with one key repeats it.  Statuses:
     # 0 done, 1 no result, 2 malformed (a word not below p, a scalar not below n, a point outside the group); a row whose status
@@ -1789,40 +1796,29 @@ class ecgfp5:
         return _int5(arr[5 * i:5 * i + 5]) < ecgfp5.group_order()
 
     @staticmethod
-    def _cipher_batch(name, ins, out_widths, device, ok, host):
-        """ins: three (array, n); -> ([flat output arrays], statuses).  The host loop calls host(i, outs) where ok(i)."""
-        n = ins[0][1]
-        if any(m != n for _, m in ins):
-            raise P2Error(name + ": every list has one entry per item")
-        if n == 0:
-            return [[] for _ in out_widths], []
-        outs, status = [(u64 * (w * n))() for w in out_widths], (C.c_int * n)()
-        if device is None:
-            for i in range(n):
-                if not ok(i):
-                    status[i] = ecgfp5.MALFORMED
-                elif host(i, outs):
-                    raise P2Error(name + " (host) failed: " + _err())
-        elif getattr(lib(), "p2_" + name)(*[a for a, _ in ins], n, *outs, status, device):
-            raise P2Error("p2_%s failed: %s" % (name, _err()))
-        return outs, list(status)
+    def _elgamal_call(name, ins, out_widths, device, ok, twin):
+        """What the four ciphers hand to _batch_call.  ins: three (array, n); -> ([flat output arrays], statuses).  The host loop
+        calls the single-item entry point twin(i, outs) where ok(i)."""
+        def host(i, outs, status):
+            if not ok(i):
+                status[i] = ecgfp5.MALFORMED
+            elif twin(i, outs):
+                raise P2Error(name + " (host) failed: " + _err())
+        return _batch_call("p2_" + name, [m for _, m in ins], name + ": every list has one entry per item", [(u64, w) for w in out_widths], device, host,
+                           lambda fn, n, outs, status: fn(*[a for a, _ in ins], n, *outs, status, device))
 
     @staticmethod
     def decompress_batch(ws, device=0):
         """-> (points, statuses): decompress_into_subgroup per item; status 1 where w encodes no group element"""
         w, n = ecgfp5._word_rows(ws, "compressed points")
-        if n == 0:
-            return [], []
-        out, status = (u64 * (10 * n))(), (C.c_int * n)()
-        if device is None:
-            for i in range(n):
-                if any(v >= P for v in w[5 * i:5 * i + 5]):
-                    status[i] = ecgfp5.MALFORMED
-                else:
-                    status[i] = ecgfp5.NO_RESULT if lib().p2_ecgfp5_decompress(_at(w, 5 * i), _at(out, 10 * i)) else ecgfp5.DONE
-        elif lib().p2_ecgfp5_decompress_batch(w, n, out, status, device):
-            raise P2Error("p2_ecgfp5_decompress_batch failed: " + _err())
-        return _points_out(out, n), list(status)
+
+        def host(i, outs, status):
+            if any(v >= P for v in w[5 * i:5 * i + 5]):
+                status[i] = ecgfp5.MALFORMED
+            else:
+                status[i] = ecgfp5.NO_RESULT if lib().p2_ecgfp5_decompress(_at(w, 5 * i), _at(outs[0], 10 * i)) else ecgfp5.DONE
+        (out,), st = _batch_call("p2_ecgfp5_decompress_batch", [n], None, [(u64, 10)], device, host, lambda fn, n, outs, status: fn(w, n, outs[0], status, device))
+        return _points_out(out, len(st)), st
 
     @staticmethod
     def _encode_args(xs, pads):
@@ -1842,20 +1838,17 @@ class ecgfp5:
         rows of five 32-bit words (draw them from a CSPRNG: they hide nothing, but a fixed list makes encodings recognisable).
         -> (points, used, statuses): used[i] the number of the attempt taken; status 1 and used = attempts where none decodes."""
         limbs, pad, n, attempts = ecgfp5._encode_args(xs, pads)
-        if n == 0:
-            return [], [], []
-        out, used, status = (u64 * (10 * n))(), (C.c_uint32 * n)(), (C.c_int * n)()
-        if device is None:
+
+        def host(i, outs, status):
             if not 1 <= attempts <= 256:
                 raise P2Error("attempts is between 1 and 256")
             u = C.c_uint32()
-            for i in range(n):
-                rc = lib().p2_ecgfp5_encode_binary_padded(C.cast(C.byref(limbs, 20 * i), u32p), C.cast(C.byref(pad, 20 * attempts * i), u32p), attempts, _at(out, 10 * i),
-                                                         C.byref(u))
-                used[i], status[i] = u.value, ecgfp5.NO_RESULT if rc else ecgfp5.DONE
-        elif lib().p2_ecgfp5_encode_binary_batch(limbs, pad, attempts, n, out, used, status, device):
-            raise P2Error("p2_ecgfp5_encode_binary_batch failed: " + _err())
-        return _points_out(out, n), list(used), list(status)
+            rc = lib().p2_ecgfp5_encode_binary_padded(C.cast(C.byref(limbs, 20 * i), u32p), C.cast(C.byref(pad, 20 * attempts * i), u32p), attempts, _at(outs[0], 10 * i),
+                                                     C.byref(u))
+            outs[1][i], status[i] = u.value, ecgfp5.NO_RESULT if rc else ecgfp5.DONE
+        (out, used), st = _batch_call("p2_ecgfp5_encode_binary_batch", [n], None, [(u64, 10), (C.c_uint32, 1)], device, host,
+                                      lambda fn, n, outs, status: fn(limbs, pad, attempts, n, *outs, status, device))
+        return _points_out(out, len(st)), list(used), st
 
     @staticmethod
     def decode_binary_batch(points):
@@ -1866,7 +1859,7 @@ class ecgfp5:
     def elgamal_encrypt_batch(pks, nonces, msgs, device=0):
         """-> (c0s, c1s, statuses): c0 = nonce G, c1 = msg + nonce pk (elgamal.rs:11)"""
         pk, k, m = ecgfp5._point_rows(pks, "public keys"), _rows([_sc_words(x) for x in nonces], "nonces")[:2], ecgfp5._point_rows(msgs, "messages")
-        outs, st = ecgfp5._cipher_batch(
+        outs, st = ecgfp5._elgamal_call(
             "elgamal_encrypt_batch", [pk, k, m], (10, 10), device, lambda i: ecgfp5._scalar_ok(k[0], i) and ecgfp5._point_ok(pk[0], i) and ecgfp5._point_ok(m[0], i),
             lambda i, o: lib().p2_elgamal_encrypt(_at(pk[0], 10 * i), _at(k[0], 5 * i), _at(m[0], 10 * i), _at(o[0], 10 * i), _at(o[1], 10 * i)))
         return _points_out(outs[0], len(st)), _points_out(outs[1], len(st)), st
@@ -1875,7 +1868,7 @@ class ecgfp5:
     def elgamal_decrypt_batch(sks, c0s, c1s, device=0):
         """-> (msgs, statuses): msg = c1 - sk c0 (elgamal.rs:19); sks are Python ints"""
         k, a, b = _rows([_sc_words(x) for x in sks], "secret keys")[:2], ecgfp5._point_rows(c0s, "c0"), ecgfp5._point_rows(c1s, "c1")
-        outs, st = ecgfp5._cipher_batch(
+        outs, st = ecgfp5._elgamal_call(
             "elgamal_decrypt_batch", [k, a, b], (10,), device, lambda i: ecgfp5._scalar_ok(k[0], i) and ecgfp5._point_ok(a[0], i) and ecgfp5._point_ok(b[0], i),
             lambda i, o: lib().p2_elgamal_decrypt(_at(k[0], 5 * i), _at(a[0], 10 * i), _at(b[0], 10 * i), _at(o[0], 10 * i)))
         return _points_out(outs[0], len(st)), st
@@ -1884,7 +1877,7 @@ class ecgfp5:
     def hashed_elgamal_encrypt_batch(pks, nonces, msgs, device=0):
         """-> (c0s, cts, statuses): messages and ciphertexts are five field elements (hashed_elgamal.rs:19)"""
         pk, k, m = ecgfp5._point_rows(pks, "public keys"), _rows([_sc_words(x) for x in nonces], "nonces")[:2], ecgfp5._word_rows(msgs, "messages")
-        outs, st = ecgfp5._cipher_batch(
+        outs, st = ecgfp5._elgamal_call(
             "hashed_elgamal_encrypt_batch", [pk, k, m], (10, 5), device,
             lambda i: ecgfp5._scalar_ok(k[0], i) and all(w < P for w in m[0][5 * i:5 * i + 5]) and ecgfp5._point_ok(pk[0], i),
             lambda i, o: lib().p2_hashed_elgamal_encrypt(_at(pk[0], 10 * i), _at(k[0], 5 * i), _at(m[0], 5 * i), _at(o[0], 10 * i), _at(o[1], 5 * i)))
@@ -1894,7 +1887,7 @@ class ecgfp5:
     def hashed_elgamal_decrypt_batch(sks, c0s, cts, device=0):
         """-> (msgs, statuses) (hashed_elgamal.rs:28)"""
         k, a, c = _rows([_sc_words(x) for x in sks], "secret keys")[:2], ecgfp5._point_rows(c0s, "c0"), ecgfp5._word_rows(cts, "ciphertexts")
-        outs, st = ecgfp5._cipher_batch(
+        outs, st = ecgfp5._elgamal_call(
             "hashed_elgamal_decrypt_batch", [k, a, c], (5,), device,
             lambda i: ecgfp5._scalar_ok(k[0], i) and all(w < P for w in c[0][5 * i:5 * i + 5]) and ecgfp5._point_ok(a[0], i),
             lambda i, o: lib().p2_hashed_elgamal_decrypt(_at(k[0], 5 * i), _at(a[0], 10 * i), _at(c[0], 5 * i), _at(o[0], 5 * i)))
@@ -1902,39 +1895,34 @@ class ecgfp5:
 
     # the _device forms: every buffer a raw device pointer, asynchronous on `stream`; keys and nonces stay in device memory
     @staticmethod
-    def _device_call(name, *args):
-        if getattr(lib(), name)(*args):
-            raise P2Error("%s failed: %s" % (name, _err()))
-
-    @staticmethod
     def decompress_batch_device(d_w, count, d_out, d_status, device=0, stream=None):
-        ecgfp5._device_call("p2_ecgfp5_decompress_batch_device", d_w, count, d_out, d_status, device, stream)
+        _device_call("p2_ecgfp5_decompress_batch_device", d_w, count, d_out, d_status, device, stream)
 
     @staticmethod
     def encode_binary_batch_device(d_limbs, d_pad, attempts, count, d_out, d_used, d_status, device=0, stream=None):
-        ecgfp5._device_call("p2_ecgfp5_encode_binary_batch_device", d_limbs, d_pad, attempts, count, d_out, d_used, d_status, device, stream)
+        _device_call("p2_ecgfp5_encode_binary_batch_device", d_limbs, d_pad, attempts, count, d_out, d_used, d_status, device, stream)
 
     @staticmethod
     def elgamal_encrypt_batch_device(d_pk, d_nonce, d_msg, count, d_c0, d_c1, d_status, device=0, stream=None):
-        ecgfp5._device_call("p2_elgamal_encrypt_batch_device", d_pk, d_nonce, d_msg, count, d_c0, d_c1, d_status, device, stream)
+        _device_call("p2_elgamal_encrypt_batch_device", d_pk, d_nonce, d_msg, count, d_c0, d_c1, d_status, device, stream)
 
     @staticmethod
     def elgamal_decrypt_batch_device(d_sk, d_c0, d_c1, count, d_msg, d_status, device=0, stream=None):
-        ecgfp5._device_call("p2_elgamal_decrypt_batch_device", d_sk, d_c0, d_c1, count, d_msg, d_status, device, stream)
+        _device_call("p2_elgamal_decrypt_batch_device", d_sk, d_c0, d_c1, count, d_msg, d_status, device, stream)
 
     @staticmethod
     def hashed_elgamal_encrypt_batch_device(d_pk, d_nonce, d_msg, count, d_c0, d_ct, d_status, device=0, stream=None):
-        ecgfp5._device_call("p2_hashed_elgamal_encrypt_batch_device", d_pk, d_nonce, d_msg, count, d_c0, d_ct, d_status, device, stream)
+        _device_call("p2_hashed_elgamal_encrypt_batch_device", d_pk, d_nonce, d_msg, count, d_c0, d_ct, d_status, device, stream)
 
     @staticmethod
     def hashed_elgamal_decrypt_batch_device(d_sk, d_c0, d_ct, count, d_msg, d_status, device=0, stream=None):
-        ecgfp5._device_call("p2_hashed_elgamal_decrypt_batch_device", d_sk, d_c0, d_ct, count, d_msg, d_status, device, stream)
+        _device_call("p2_hashed_elgamal_decrypt_batch_device", d_sk, d_c0, d_ct, count, d_msg, d_status, device, stream)
 
     @staticmethod
     def scalar_bits_device(d_k, count, d_out, stride, device=0, stream=None):
         """d_out[i stride + j] = bit j of scalar i (j < 320 <= stride, in words): a scalar's 320 bit targets in a row of the value
         matrix that prove_batch_device reads, without the host spelling the bits"""
-        ecgfp5._device_call("p2_ecgfp5_scalar_bits_device", d_k, count, d_out, stride, device, stream)
+        _device_call("p2_ecgfp5_scalar_bits_device", d_k, count, d_out, stride, device, stream)
 
 
 def _at(arr, words):
@@ -2006,22 +1994,15 @@ class schnorr:
         sk, n, _ = _rows([_sc_words(k) for k in sks], "secret keys")
         ks, n_k, _ = _rows([_sc_words(k) for k in nonces], "nonces")
         mg, n_m, msg_len = _rows(msgs, "messages")
-        if n != n_k or n != n_m:
-            raise P2Error("sign_batch: one nonce and one message per secret key")
-        if n == 0:
-            return [], [], []
-        sig, pk, status = (u64 * (9 * n))(), (u64 * (10 * n))(), (C.c_int * n)()
-        if device is None:
+
+        def host(i, outs, status):
             st = C.c_int()
-            for i in range(n):
-                m = C.cast(C.byref(mg, 8 * i * msg_len), u64p) if msg_len else None
-                if lib().p2_schnorr_sign(C.cast(C.byref(sk, 40 * i), u64p), C.cast(C.byref(ks, 40 * i), u64p), m, msg_len, C.cast(C.byref(sig, 72 * i), u64p),
-                                         C.cast(C.byref(pk, 80 * i), u64p), C.byref(st)):
-                    raise P2Error("p2_schnorr_sign failed: " + _err())
-                status[i] = st.value
-        elif lib().p2_schnorr_sign_batch(sk, ks, mg, msg_len, n, sig, pk, status, device):
-            raise P2Error("p2_schnorr_sign_batch failed: " + _err())
-        return ([schnorr._sig_out(sig[9 * i:9 * i + 9]) for i in range(n)], [_pt_out(pk[10 * i:10 * i + 10]) for i in range(n)], list(status))
+            if lib().p2_schnorr_sign(_at(sk, 5 * i), _at(ks, 5 * i), _at(mg, i * msg_len) if msg_len else None, msg_len, _at(outs[0], 9 * i), _at(outs[1], 10 * i), C.byref(st)):
+                raise P2Error("p2_schnorr_sign failed: " + _err())
+            status[i] = st.value
+        (sig, pk), st = _batch_call("p2_schnorr_sign_batch", [n, n_k, n_m], "sign_batch: one nonce and one message per secret key", [(u64, 9), (u64, 10)], device, host,
+                                    lambda fn, n, outs, status: fn(sk, ks, mg, msg_len, n, *outs, status, device))
+        return [schnorr._sig_out(sig[9 * i:9 * i + 9]) for i in range(len(st))], _points_out(pk, len(st)), st
 
     @staticmethod
     def verify_batch(pks, msgs, sigs, device=0):
@@ -2030,33 +2011,24 @@ class schnorr:
         pk, n, _ = _rows([list(p[0]) + list(p[1]) for p in pks], "public keys")
         mg, n_m, msg_len = _rows(msgs, "messages")
         sg, n_s, _ = _rows([_sc_words(s[0]) + [int(w) for w in s[1]] for s in sigs], "signatures")
-        if n != n_m or n != n_s:
-            raise P2Error("verify_batch: one message and one signature per public key")
-        if n == 0:
-            return []
-        status = (C.c_int * n)()
-        if device is None:
+
+        def host(i, outs, status):
             st = C.c_int()
-            for i in range(n):
-                m = C.cast(C.byref(mg, 8 * i * msg_len), u64p) if msg_len else None
-                if lib().p2_schnorr_verify(C.cast(C.byref(pk, 80 * i), u64p), m, msg_len, C.cast(C.byref(sg, 72 * i), u64p), C.byref(st)):
-                    raise P2Error("p2_schnorr_verify failed: " + _err())
-                status[i] = st.value
-        elif lib().p2_schnorr_verify_batch(pk, mg, msg_len, sg, n, status, device):
-            raise P2Error("p2_schnorr_verify_batch failed: " + _err())
-        return list(status)
+            if lib().p2_schnorr_verify(_at(pk, 10 * i), _at(mg, i * msg_len) if msg_len else None, msg_len, _at(sg, 9 * i), C.byref(st)):
+                raise P2Error("p2_schnorr_verify failed: " + _err())
+            status[i] = st.value
+        return _batch_call("p2_schnorr_verify_batch", [n, n_m, n_s], "verify_batch: one message and one signature per public key", [], device, host,
+                           lambda fn, n, outs, status: fn(pk, mg, msg_len, sg, n, status, device))[1]
 
     @staticmethod
     def sign_batch_device(d_sk, d_nonce, d_msg, msg_len, count, d_sig, d_pk, d_status, device=0, stream=None):
         """Every buffer a raw device pointer (p2_schnorr_sign_batch_device; d_pk may be None); asynchronous on `stream`.  The
         secret keys and nonces stay in device memory the caller owns."""
-        if lib().p2_schnorr_sign_batch_device(d_sk, d_nonce, d_msg, msg_len, count, d_sig, d_pk, d_status, device, stream):
-            raise P2Error("p2_schnorr_sign_batch_device failed: " + _err())
+        _device_call("p2_schnorr_sign_batch_device", d_sk, d_nonce, d_msg, msg_len, count, d_sig, d_pk, d_status, device, stream)
 
     @staticmethod
     def verify_batch_device(d_pk, d_msg, msg_len, d_sig, count, d_status, device=0, stream=None):
-        if lib().p2_schnorr_verify_batch_device(d_pk, d_msg, msg_len, d_sig, count, d_status, device, stream):
-            raise P2Error("p2_schnorr_verify_batch_device failed: " + _err())
+        _device_call("p2_schnorr_verify_batch_device", d_pk, d_msg, msg_len, d_sig, count, d_status, device, stream)
 
 
 class ECGFP5SecretKey:

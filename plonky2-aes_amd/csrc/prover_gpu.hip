@@ -2043,6 +2043,78 @@ static int witness_explain_impl(p2_circuit* C, const p2_assignment* input, int* 
     return P2_OK;
 }
 
+// ---------------------------------------------------------------------------------- the device of a call, the one-launch runner
+static int pick_device(int device) {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return set_error("no HIP device available"), P2_ERR_NO_DEVICE;
+    if (device < 0 || device >= ndev) return set_error("device index out of range"), P2_ERR_INVALID;
+    HIPCHECK(hipSetDevice(device));
+    return 0;
+}
+// ---- one runner for the calls that are one launch over buffers the caller sizes: the per-item batch calls in their host and
+// _device forms, and the single-launch test primitives.  A call states its shape check, count, where it runs, its buffers in the
+// order the launch takes them, and the launch.  run_batch does the rest, in this order (callers see it): the shape error;
+// count == 0 is P2_OK; a buffer that is NULL although it has elements and is not optional is "null argument"; pick_device; then
+// host buffers are staged (ins uploaded, outs allocated), the launch goes on the stream -- the null stream for host buffers --
+// and the outs are copied back in list order, so the call returns with the results in host memory.  For device buffers nothing
+// but the launch is enqueued.  The launch gets NULL for a buffer of zero elements and for an optional buffer the caller left
+// out, in both forms; every other buffer is the staged copy or the caller's device pointer.
+enum BufDir { BUF_IN, BUF_OUT, BUF_INOUT };
+struct Buf {
+    void* p;
+    size_t n, elem;  // total elements, bytes per element
+    BufDir dir;
+    bool optional;  // may be NULL although n > 0: the launch gets NULL and nothing is copied
+};
+template <class T>
+static Buf buf_in(const T* p, size_t n) { return {(void*)p, n, sizeof(T), BUF_IN, false}; }
+template <class T>
+static Buf buf_out(T* p, size_t n, bool optional = false) { return {p, n, sizeof(T), BUF_OUT, optional}; }
+template <class T>
+static Buf buf_inout(T* p, size_t n) { return {p, n, sizeof(T), BUF_INOUT, false}; }
+struct DevPtr {  // a device pointer as the launch takes it: it converts to the kernel's parameter type
+    void* p = nullptr;
+    template <class T>
+    operator T*() const { return (T*)p; }
+};
+struct Where {
+    int device;
+    bool on_device;  // the buffers are device memory: nothing is staged and the launch goes on `stream`
+    hipStream_t stream;
+};
+static Where on_host(int device) { return {device, false, nullptr}; }
+static Where on_device(int device, void* stream) { return {device, true, (hipStream_t)stream}; }
+template <size_t N, class Launch>
+static int run_batch(const char* bad_shape, size_t count, Where w, const Buf (&bufs)[N], Launch&& launch) {
+    return guarded_rc([&]() -> int {
+        if (bad_shape) return set_error(bad_shape), P2_ERR_INVALID;
+        if (count == 0) return (int)P2_OK;
+        for (const Buf& b : bufs)
+            if (b.n && !b.p && !b.optional) return set_error("null argument"), P2_ERR_INVALID;
+        if (int rc = pick_device(w.device)) return rc;
+        Allocs tmp;
+        DevPtr d[N];
+        for (size_t i = 0; i < N; i++) {
+            const Buf& b = bufs[i];
+            if (!b.n || !b.p) continue;
+            if (w.on_device) {
+                d[i].p = b.p;
+                continue;
+            }
+            char* q;
+            if (dalloc(tmp, &q, b.n * b.elem)) return P2_ERR_HIP;
+            d[i].p = q;
+            if (b.dir != BUF_OUT) HIPCHECK(hipMemcpy(q, b.p, b.n * b.elem, hipMemcpyHostToDevice));
+        }
+        launch(d, w.stream);
+        HIPCHECK(hipGetLastError());
+        if (w.on_device) return (int)P2_OK;
+        for (size_t i = 0; i < N; i++)
+            if (d[i].p && bufs[i].dir != BUF_IN) HIPCHECK(hipMemcpy(bufs[i].p, d[i].p, bufs[i].n * bufs[i].elem, hipMemcpyDeviceToHost));
+        return (int)P2_OK;
+    });
+}
+
 extern "C" {
 
 int p2_gpu_device_count(void) {
@@ -2446,13 +2518,6 @@ int p2_circuit_debug_read(p2_circuit* C, const char* name_c, size_t index, uint6
 }
 
 // ---------------------------------------------------------------------------------- primitives (parity tests)
-static int pick_device(int device) {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return set_error("no HIP device available"), P2_ERR_NO_DEVICE;
-    if (device < 0 || device >= ndev) return set_error("device index out of range"), P2_ERR_INVALID;
-    HIPCHECK(hipSetDevice(device));
-    return 0;
-}
 // ---- device self-test
 namespace p2k {
 __global__ void k_selftest(unsigned long long* bad, u64 seed, size_t threads) {
@@ -2851,16 +2916,15 @@ int p2_gpu_zeta_pows(const uint64_t* z, size_t n, uint64_t* pows, int device) {
     return P2_OK;
 }
 
-int p2_gpu_poseidon(uint64_t* states, size_t n_perm, int device) {
-    if (int rc = pick_device(device)) return rc;
-    Allocs mem;
-    u64* d;
-    if (upload(mem, &d, (const u64*)states, n_perm * 12)) return P2_ERR_HIP;
-    hipLaunchKernelGGL(k_poseidon_states, g1(n_perm, 256), dim3(256), 0, 0, d, n_perm);
-    HIPCHECK(hipGetLastError());
-    HIPCHECK(hipMemcpy(states, d, n_perm * 96, hipMemcpyDeviceToHost));
-    return P2_OK;
+// k_poseidon_states, k_partial_rounds and k_merged_middle on their own (tests): `count` states of 12 words, in place
+static int states_in_place(void (*kernel)(u64*, size_t), const char* bad_shape, uint64_t* states, size_t count, int device) {
+    return run_batch(bad_shape, count, on_host(device), {buf_inout(states, 12 * count)},
+                     [&](const DevPtr* d, hipStream_t s) { hipLaunchKernelGGL(kernel, g1(count, 256), dim3(256), 0, s, d[0], count); });
 }
+static const char* states_count_shape(size_t count) { return count == 0 || count > (1u << 24) ? "count out of range" : nullptr; }
+int p2_gpu_poseidon(uint64_t* states, size_t n_perm, int device) { return states_in_place(k_poseidon_states, nullptr, states, n_perm, device); }
+int p2_gpu_partial_rounds(uint64_t* states, size_t count, int device) { return states_in_place(k_partial_rounds, states_count_shape(count), states, count, device); }
+int p2_gpu_merged_middle(uint64_t* states, size_t count, int device) { return states_in_place(k_merged_middle, states_count_shape(count), states, count, device); }
 // The three tree kernels on their own (tests): host arrays in, host arrays out, one launch each.
 //   data [batch][min(active_cols, cols)][num_leaves] -> digests [batch][num_leaves][4]
 int p2_gpu_hash_leaves(const uint64_t* data, size_t cols, size_t active_cols, size_t num_leaves, size_t batch, uint64_t* digests, int device) {
@@ -2877,41 +2941,13 @@ int p2_gpu_hash_leaves(const uint64_t* data, size_t cols, size_t active_cols, si
     HIPCHECK(hipMemcpy(digests, d_out, batch * num_leaves * 32, hipMemcpyDeviceToHost));
     return P2_OK;
 }
-int p2_gpu_partial_rounds(uint64_t* states, size_t count, int device) {
-    if (count == 0 || count > (1u << 24)) return set_error("count out of range"), P2_ERR_INVALID;
-    if (int rc = pick_device(device)) return rc;
-    Allocs mem;
-    u64* d;
-    if (upload(mem, &d, (const u64*)states, count * 12)) return P2_ERR_HIP;
-    hipLaunchKernelGGL(k_partial_rounds, g1(count, 256), dim3(256), 0, 0, d, count);
-    HIPCHECK(hipGetLastError());
-    HIPCHECK(hipMemcpy(states, d, count * 96, hipMemcpyDeviceToHost));
-    return P2_OK;
-}
 // p2_host_ecstep_constraints on the device: the <FBase> instantiation the quotient-side kernel runs
 int p2_gpu_ecstep_constraints(const uint64_t* wires, size_t count, uint64_t* out, int device) {
-    if (count == 0 || count > (1u << 20) || !wires || !out) return set_error("count out of range"), P2_ERR_INVALID;
-    for (size_t i = 0; i < 80 * count; i++)
-        if (wires[i] >= gl::P) return set_error("p2_gpu_ecstep_constraints: non-canonical wire"), P2_ERR_INVALID;
-    if (int rc = pick_device(device)) return rc;
-    Allocs mem;
-    u64 *d_in, *d_out;
-    if (upload(mem, &d_in, (const u64*)wires, count * 80) || dalloc(mem, &d_out, count * 40)) return P2_ERR_HIP;
-    hipLaunchKernelGGL(k_ecstep_selftest, g1(count, 256), dim3(256), 0, 0, d_in, count, d_out);
-    HIPCHECK(hipGetLastError());
-    HIPCHECK(hipMemcpy(out, d_out, count * 40 * 8, hipMemcpyDeviceToHost));
-    return P2_OK;
-}
-int p2_gpu_merged_middle(uint64_t* states, size_t count, int device) {
-    if (count == 0 || count > (1u << 24)) return set_error("count out of range"), P2_ERR_INVALID;
-    if (int rc = pick_device(device)) return rc;
-    Allocs mem;
-    u64* d;
-    if (upload(mem, &d, (const u64*)states, count * 12)) return P2_ERR_HIP;
-    hipLaunchKernelGGL(k_merged_middle, g1(count, 256), dim3(256), 0, 0, d, count);
-    HIPCHECK(hipGetLastError());
-    HIPCHECK(hipMemcpy(states, d, count * 96, hipMemcpyDeviceToHost));
-    return P2_OK;
+    const char* bad = count == 0 || count > (1u << 20) || !wires || !out ? "count out of range" : nullptr;
+    for (size_t i = 0; !bad && i < 80 * count; i++)
+        if (wires[i] >= gl::P) bad = "p2_gpu_ecstep_constraints: non-canonical wire";
+    return run_batch(bad, count, on_host(device), {buf_in(wires, 80 * count), buf_out(out, 40 * count)},
+                     [&](const DevPtr* d, hipStream_t s) { hipLaunchKernelGGL(k_ecstep_selftest, g1(count, 256), dim3(256), 0, s, d[0], count, d[1]); });
 }
 //   child [batch][2 * num_parents][4] -> parent [batch][num_parents][4]
 int p2_gpu_merkle_level(const uint64_t* child, size_t num_parents, size_t batch, uint64_t* parent, int device) {
@@ -2928,16 +2964,12 @@ int p2_gpu_merkle_level(const uint64_t* child, size_t num_parents, size_t batch,
 }
 //   vals [batch][2][len] (the two components of len extension values) -> digests [batch][len / arity][4]
 int p2_gpu_hash_fri_leaves(const uint64_t* vals, size_t len, int arity, size_t batch, uint64_t* digests, int device) {
-    if (arity < 1 || arity > 64 || len == 0 || len % (size_t)arity || batch == 0 || batch > 65535) return set_error("shape out of range"), P2_ERR_INVALID;
-    if (int rc = pick_device(device)) return rc;
-    const size_t leaves = len / (size_t)arity;
-    Allocs mem;
-    u64 *d_in, *d_out;
-    if (upload(mem, &d_in, (const u64*)vals, batch * 2 * len) || dalloc(mem, &d_out, batch * leaves * 4)) return P2_ERR_HIP;
-    hipLaunchKernelGGL(k_hash_fri_leaves, g1(leaves, 256, (u32)batch), dim3(256), 0, 0, d_in, len, 2 * len, arity, d_out, leaves * 4);
-    HIPCHECK(hipGetLastError());
-    HIPCHECK(hipMemcpy(digests, d_out, batch * leaves * 32, hipMemcpyDeviceToHost));
-    return P2_OK;
+    const bool bad = arity < 1 || arity > 64 || len == 0 || len % (size_t)arity || batch == 0 || batch > 65535;
+    const size_t leaves = bad ? 0 : len / (size_t)arity;
+    return run_batch(bad ? "shape out of range" : nullptr, batch, on_host(device), {buf_in(vals, batch * 2 * len), buf_out(digests, batch * leaves * 4)},
+                     [&](const DevPtr* d, hipStream_t s) {
+                         hipLaunchKernelGGL(k_hash_fri_leaves, g1(leaves, 256, (u32)batch), dim3(256), 0, s, d[0], len, 2 * len, arity, d[1], leaves * 4);
+                     });
 }
 // What the NTT / Merkle primitives need of a handle: a lane, the transform tables of one size and the allocations behind them.
 struct PrimCtx {
@@ -3202,16 +3234,14 @@ static int mt_update(MerkleTreeHandle& T, const u64* d_indices, const u64* d_lea
     HIPCHECK(hipEventRecord(T.built, stream));  // also behind a launch that failed half-way: what was enqueued still runs
     return rc;
 }
-static int mt_verify_shape(size_t leaf_len, size_t depth, int cap_height) {
-    if (leaf_len < 1 || leaf_len > 0xFFFFFFFFull || cap_height < 0 || cap_height > 16 || depth + (size_t)cap_height > 32)
-        return set_error("leaf_len >= 1, cap_height 0 to 16, siblings + cap_height at most 32"), P2_ERR_INVALID;
-    return P2_OK;
-}
-static int mt_verify(const u64* d_leaves, size_t leaf_len, const u64* d_indices, const u64* d_siblings, size_t depth, const u64* d_cap, int cap_height, size_t n,
-                     int* d_status, hipStream_t stream) {
-    hipLaunchKernelGGL(k_mt_verify, g1(n, 64), dim3(64), 0, stream, d_leaves, (u32)leaf_len, d_indices, d_siblings, (u32)depth, d_cap, (u32)cap_height, n, d_status);
-    HIPCHECK(hipGetLastError());
-    return P2_OK;
+static int mt_verify(const uint64_t* leaves, size_t leaf_len, const uint64_t* indices, const uint64_t* siblings, size_t depth, const uint64_t* cap, int cap_height, size_t n,
+                     int* status, Where w) {
+    const bool bad = leaf_len < 1 || leaf_len > 0xFFFFFFFFull || cap_height < 0 || cap_height > 16 || depth + (size_t)cap_height > 32;
+    return run_batch(bad ? "leaf_len >= 1, cap_height 0 to 16, siblings + cap_height at most 32" : nullptr, n, w,
+                     {buf_in(leaves, n * leaf_len), buf_in(indices, n), buf_in(siblings, n * 4 * depth), buf_in(cap, bad ? 0 : (size_t)4 << cap_height), buf_out(status, n)},
+                     [&](const DevPtr* d, hipStream_t s) {
+                         hipLaunchKernelGGL(k_mt_verify, g1(n, 64), dim3(64), 0, s, d[0], (u32)leaf_len, d[1], d[2], (u32)depth, d[3], (u32)cap_height, n, d[4]);
+                     });
 }
 
 int p2_merkle_tree_new(const uint64_t* leaves, size_t num_leaves, size_t leaf_len, int cap_height, int device, void** tree) {
@@ -3309,31 +3339,11 @@ int p2_merkle_tree_last_update_hashes(void* tree, uint64_t* hashes) {
 }
 int p2_merkle_verify_batch(const uint64_t* leaves, size_t leaf_len, const uint64_t* indices, const uint64_t* siblings, size_t depth, const uint64_t* cap, int cap_height,
                            size_t n, int* status, int device) {
-    return guarded_rc([&]() -> int {
-        if (int rc = mt_verify_shape(leaf_len, depth, cap_height)) return rc;
-        if (n == 0) return (int)P2_OK;
-        if (!leaves || !indices || !cap || !status || (depth && !siblings)) return set_error("null argument"), P2_ERR_INVALID;
-        if (int rc = pick_device(device)) return rc;
-        Allocs tmp;
-        u64 *d_leaves, *d_idx, *d_sib, *d_cap;
-        int* d_st;
-        if (upload(tmp, &d_leaves, (const u64*)leaves, n * leaf_len) || upload(tmp, &d_idx, (const u64*)indices, n) || upload(tmp, &d_sib, (const u64*)siblings, n * 4 * depth) ||
-            upload(tmp, &d_cap, (const u64*)cap, (size_t)4 << cap_height) || dalloc(tmp, &d_st, n))
-            return P2_ERR_HIP;
-        if (int rc = mt_verify(d_leaves, leaf_len, d_idx, d_sib, depth, d_cap, cap_height, n, d_st, nullptr)) return rc;
-        HIPCHECK(hipMemcpy(status, d_st, n * sizeof(int), hipMemcpyDeviceToHost));
-        return (int)P2_OK;
-    });
+    return mt_verify(leaves, leaf_len, indices, siblings, depth, cap, cap_height, n, status, on_host(device));
 }
 int p2_merkle_verify_batch_device(const uint64_t* d_leaves, size_t leaf_len, const uint64_t* d_indices, const uint64_t* d_siblings, size_t depth, const uint64_t* d_cap,
                                   int cap_height, size_t n, int* d_status, int device, void* stream) {
-    return guarded_rc([&]() -> int {
-        if (int rc = mt_verify_shape(leaf_len, depth, cap_height)) return rc;
-        if (n == 0) return (int)P2_OK;
-        if (!d_leaves || !d_indices || !d_cap || !d_status || (depth && !d_siblings)) return set_error("null argument"), P2_ERR_INVALID;
-        if (int rc = pick_device(device)) return rc;
-        return mt_verify((const u64*)d_leaves, leaf_len, (const u64*)d_indices, (const u64*)d_siblings, depth, (const u64*)d_cap, cap_height, n, d_status, (hipStream_t)stream);
-    });
+    return mt_verify(d_leaves, leaf_len, d_indices, d_siblings, depth, d_cap, cap_height, n, d_status, on_device(device, stream));
 }
 // Bench hook (tools/gpu_merkle_bench.py): one tree build on buffers the caller owns.  d_dig: 8 * num_leaves words, the level
 // layout.  with_transpose = 0: merkle_build on d_scratch, column-major [leaf_len][num_leaves] (the build of p2_gpu_merkle_cap);
@@ -3363,334 +3373,153 @@ static EcWords ec_generator_words() {
     p2_ecgfp5_generator(g.w);
     return g;
 }
-static int schnorr_shape(size_t msg_len) {
-    if (msg_len > SCHNORR_MAX_MSG_LEN) return set_error("msg_len is at most 1024 words"), P2_ERR_INVALID;
-    return P2_OK;
-}
-static int ec_mul_launch(const u64* d_k, const u64* d_p, size_t count, u64* d_out, int* d_status, hipStream_t stream) {
-    hipLaunchKernelGGL(k_ec_mul_batch, g1(count, 64), dim3(64), 0, stream, d_k, d_p, count, d_out, d_status);
-    HIPCHECK(hipGetLastError());
-    return P2_OK;
-}
-static int schnorr_sign_launch(const u64* d_sk, const u64* d_nonce, const u64* d_msg, size_t msg_len, size_t count, u64* d_sig, u64* d_pk, int* d_status, hipStream_t stream) {
-    hipLaunchKernelGGL(k_schnorr_sign, g1(count, 64), dim3(64), 0, stream, d_sk, d_nonce, d_msg, (u32)msg_len, count, ec_generator_words(), d_sig, d_pk, d_status);
-    HIPCHECK(hipGetLastError());
-    return P2_OK;
-}
-static int schnorr_verify_launch(const u64* d_pk, const u64* d_msg, size_t msg_len, const u64* d_sig, size_t count, int* d_status, hipStream_t stream) {
-    hipLaunchKernelGGL(k_schnorr_verify, g1(count, 64), dim3(64), 0, stream, d_pk, d_msg, (u32)msg_len, d_sig, count, ec_generator_words(), d_status);
-    HIPCHECK(hipGetLastError());
-    return P2_OK;
+static const char* schnorr_shape(size_t msg_len) { return msg_len > SCHNORR_MAX_MSG_LEN ? "msg_len is at most 1024 words" : nullptr; }
+// Each pair of entry points below is one function that states the buffers and the launch (run_batch), called by the host form
+// with on_host(device) and by the _device form with on_device(device, stream).
+static int ec_mul_batch(const uint64_t* k, const uint64_t* p, size_t count, uint64_t* out, int* status, Where w) {
+    return run_batch(nullptr, count, w, {buf_in(k, 5 * count), buf_in(p, 10 * count), buf_out(out, 10 * count), buf_out(status, count)},
+                     [&](const DevPtr* d, hipStream_t s) { hipLaunchKernelGGL(k_ec_mul_batch, g1(count, 64), dim3(64), 0, s, d[0], d[1], count, d[2], d[3]); });
 }
 int p2_ecgfp5_mul_batch(const uint64_t* k, const uint64_t* p, size_t count, uint64_t* out, int* status, int device) {
-    return guarded_rc([&]() -> int {
-        if (count == 0) return (int)P2_OK;
-        if (!k || !p || !out || !status) return set_error("null argument"), P2_ERR_INVALID;
-        if (int rc = pick_device(device)) return rc;
-        Allocs tmp;
-        u64 *d_k, *d_p, *d_out;
-        int* d_st;
-        if (upload(tmp, &d_k, (const u64*)k, 5 * count) || upload(tmp, &d_p, (const u64*)p, 10 * count) || dalloc(tmp, &d_out, 10 * count) || dalloc(tmp, &d_st, count)) return P2_ERR_HIP;
-        if (int rc = ec_mul_launch(d_k, d_p, count, d_out, d_st, nullptr)) return rc;
-        HIPCHECK(hipMemcpy(out, d_out, 10 * count * 8, hipMemcpyDeviceToHost));
-        HIPCHECK(hipMemcpy(status, d_st, count * sizeof(int), hipMemcpyDeviceToHost));
-        return (int)P2_OK;
-    });
+    return ec_mul_batch(k, p, count, out, status, on_host(device));
 }
 int p2_ecgfp5_mul_batch_device(const uint64_t* d_k, const uint64_t* d_p, size_t count, uint64_t* d_out, int* d_status, int device, void* stream) {
-    return guarded_rc([&]() -> int {
-        if (count == 0) return (int)P2_OK;
-        if (!d_k || !d_p || !d_out || !d_status) return set_error("null argument"), P2_ERR_INVALID;
-        if (int rc = pick_device(device)) return rc;
-        return ec_mul_launch((const u64*)d_k, (const u64*)d_p, count, (u64*)d_out, d_status, (hipStream_t)stream);
-    });
+    return ec_mul_batch(d_k, d_p, count, d_out, d_status, on_device(device, stream));
+}
+// pk may be NULL: the kernel then writes no public keys
+static int schnorr_sign_batch(const uint64_t* sk, const uint64_t* nonce, const uint64_t* msg, size_t msg_len, size_t count, uint64_t* sig, uint64_t* pk, int* status, Where w) {
+    return run_batch(schnorr_shape(msg_len), count, w,
+                     {buf_in(sk, 5 * count), buf_in(nonce, 5 * count), buf_in(msg, msg_len * count), buf_out(sig, 9 * count), buf_out(pk, 10 * count, true), buf_out(status, count)},
+                     [&](const DevPtr* d, hipStream_t s) {
+                         hipLaunchKernelGGL(k_schnorr_sign, g1(count, 64), dim3(64), 0, s, d[0], d[1], d[2], (u32)msg_len, count, ec_generator_words(), d[3], d[4], d[5]);
+                     });
 }
 int p2_schnorr_sign_batch(const uint64_t* sk, const uint64_t* nonce, const uint64_t* msg, size_t msg_len, size_t count, uint64_t* sig, uint64_t* pk, int* status, int device) {
-    return guarded_rc([&]() -> int {
-        if (int rc = schnorr_shape(msg_len)) return rc;
-        if (count == 0) return (int)P2_OK;
-        if (!sk || !nonce || !sig || !status || (msg_len && !msg)) return set_error("null argument"), P2_ERR_INVALID;
-        if (int rc = pick_device(device)) return rc;
-        Allocs tmp;
-        u64 *d_sk, *d_k, *d_msg, *d_sig, *d_pk = nullptr;
-        int* d_st;
-        if (upload(tmp, &d_sk, (const u64*)sk, 5 * count) || upload(tmp, &d_k, (const u64*)nonce, 5 * count) || upload(tmp, &d_msg, (const u64*)msg, msg_len * count) ||
-            dalloc(tmp, &d_sig, 9 * count) || (pk && dalloc(tmp, &d_pk, 10 * count)) || dalloc(tmp, &d_st, count))
-            return P2_ERR_HIP;
-        if (int rc = schnorr_sign_launch(d_sk, d_k, d_msg, msg_len, count, d_sig, d_pk, d_st, nullptr)) return rc;
-        HIPCHECK(hipMemcpy(sig, d_sig, 9 * count * 8, hipMemcpyDeviceToHost));
-        if (pk) HIPCHECK(hipMemcpy(pk, d_pk, 10 * count * 8, hipMemcpyDeviceToHost));
-        HIPCHECK(hipMemcpy(status, d_st, count * sizeof(int), hipMemcpyDeviceToHost));
-        return (int)P2_OK;
-    });
+    return schnorr_sign_batch(sk, nonce, msg, msg_len, count, sig, pk, status, on_host(device));
 }
 int p2_schnorr_sign_batch_device(const uint64_t* d_sk, const uint64_t* d_nonce, const uint64_t* d_msg, size_t msg_len, size_t count, uint64_t* d_sig, uint64_t* d_pk,
                                  int* d_status, int device, void* stream) {
-    return guarded_rc([&]() -> int {
-        if (int rc = schnorr_shape(msg_len)) return rc;
-        if (count == 0) return (int)P2_OK;
-        if (!d_sk || !d_nonce || !d_sig || !d_status || (msg_len && !d_msg)) return set_error("null argument"), P2_ERR_INVALID;
-        if (int rc = pick_device(device)) return rc;
-        return schnorr_sign_launch((const u64*)d_sk, (const u64*)d_nonce, (const u64*)d_msg, msg_len, count, (u64*)d_sig, (u64*)d_pk, d_status, (hipStream_t)stream);
-    });
+    return schnorr_sign_batch(d_sk, d_nonce, d_msg, msg_len, count, d_sig, d_pk, d_status, on_device(device, stream));
+}
+static int schnorr_verify_batch(const uint64_t* pk, const uint64_t* msg, size_t msg_len, const uint64_t* sig, size_t count, int* status, Where w) {
+    return run_batch(schnorr_shape(msg_len), count, w, {buf_in(pk, 10 * count), buf_in(msg, msg_len * count), buf_in(sig, 9 * count), buf_out(status, count)},
+                     [&](const DevPtr* d, hipStream_t s) {
+                         hipLaunchKernelGGL(k_schnorr_verify, g1(count, 64), dim3(64), 0, s, d[0], d[1], (u32)msg_len, d[2], count, ec_generator_words(), d[3]);
+                     });
 }
 int p2_schnorr_verify_batch(const uint64_t* pk, const uint64_t* msg, size_t msg_len, const uint64_t* sig, size_t count, int* status, int device) {
-    return guarded_rc([&]() -> int {
-        if (int rc = schnorr_shape(msg_len)) return rc;
-        if (count == 0) return (int)P2_OK;
-        if (!pk || !sig || !status || (msg_len && !msg)) return set_error("null argument"), P2_ERR_INVALID;
-        if (int rc = pick_device(device)) return rc;
-        Allocs tmp;
-        u64 *d_pk, *d_msg, *d_sig;
-        int* d_st;
-        if (upload(tmp, &d_pk, (const u64*)pk, 10 * count) || upload(tmp, &d_msg, (const u64*)msg, msg_len * count) || upload(tmp, &d_sig, (const u64*)sig, 9 * count) ||
-            dalloc(tmp, &d_st, count))
-            return P2_ERR_HIP;
-        if (int rc = schnorr_verify_launch(d_pk, d_msg, msg_len, d_sig, count, d_st, nullptr)) return rc;
-        HIPCHECK(hipMemcpy(status, d_st, count * sizeof(int), hipMemcpyDeviceToHost));
-        return (int)P2_OK;
-    });
+    return schnorr_verify_batch(pk, msg, msg_len, sig, count, status, on_host(device));
 }
 int p2_schnorr_verify_batch_device(const uint64_t* d_pk, const uint64_t* d_msg, size_t msg_len, const uint64_t* d_sig, size_t count, int* d_status, int device, void* stream) {
-    return guarded_rc([&]() -> int {
-        if (int rc = schnorr_shape(msg_len)) return rc;
-        if (count == 0) return (int)P2_OK;
-        if (!d_pk || !d_sig || !d_status || (msg_len && !d_msg)) return set_error("null argument"), P2_ERR_INVALID;
-        if (int rc = pick_device(device)) return rc;
-        return schnorr_verify_launch((const u64*)d_pk, (const u64*)d_msg, msg_len, (const u64*)d_sig, count, d_status, (hipStream_t)stream);
-    });
+    return schnorr_verify_batch(d_pk, d_msg, msg_len, d_sig, count, d_status, on_device(device, stream));
 }
 // test entry: out[i] = (a[i] b[i] + c[i]) mod n, one thread per triple
 int p2_gpu_ecgfp5_scalar_muladd(const uint64_t* a, const uint64_t* b, const uint64_t* c, size_t count, uint64_t* out, int device) {
-    return guarded_rc([&]() -> int {
-        if (count == 0) return (int)P2_OK;
-        if (!a || !b || !c || !out) return set_error("null argument"), P2_ERR_INVALID;
-        if (int rc = pick_device(device)) return rc;
-        Allocs tmp;
-        u64 *d_a, *d_b, *d_c, *d_out;
-        if (upload(tmp, &d_a, (const u64*)a, 5 * count) || upload(tmp, &d_b, (const u64*)b, 5 * count) || upload(tmp, &d_c, (const u64*)c, 5 * count) || dalloc(tmp, &d_out, 5 * count))
-            return P2_ERR_HIP;
-        hipLaunchKernelGGL(k_ec_scalar_muladd, g1(count, 64), dim3(64), 0, nullptr, d_a, d_b, d_c, count, d_out);
-        HIPCHECK(hipGetLastError());
-        HIPCHECK(hipMemcpy(out, d_out, 5 * count * 8, hipMemcpyDeviceToHost));
-        return (int)P2_OK;
-    });
+    return run_batch(nullptr, count, on_host(device), {buf_in(a, 5 * count), buf_in(b, 5 * count), buf_in(c, 5 * count), buf_out(out, 5 * count)},
+                     [&](const DevPtr* d, hipStream_t s) { hipLaunchKernelGGL(k_ec_scalar_muladd, g1(count, 64), dim3(64), 0, s, d[0], d[1], d[2], count, d[3]); });
 }
 
 // ---- ElGamal on ecGFp5 in batches (kernels_elgamal.h; the host twins are in ecgfp5.h)
 static const size_t ENCODE_MAX_ATTEMPTS = 256;
-static int ec_decompress_launch(const u64* d_w, size_t count, u64* d_out, int* d_status, hipStream_t stream) {
-    hipLaunchKernelGGL(k_ec_decompress_batch, g1(count, 64), dim3(64), 0, stream, d_w, count, d_out, d_status);
-    HIPCHECK(hipGetLastError());
-    return P2_OK;
-}
-static int ec_encode_shape(size_t attempts) {
-    if (attempts == 0 || attempts > ENCODE_MAX_ATTEMPTS) return set_error("attempts is between 1 and 256"), P2_ERR_INVALID;
-    return P2_OK;
-}
-static int ec_encode_launch(const u32* d_limbs, const u32* d_pad, size_t attempts, size_t count, u64* d_out, u32* d_used, int* d_status, hipStream_t stream) {
-    hipLaunchKernelGGL(k_ec_encode_binary, g1(count, 64), dim3(64), 0, stream, d_limbs, d_pad, (u32)attempts, count, d_out, d_used, d_status);
-    HIPCHECK(hipGetLastError());
-    return P2_OK;
-}
-// The four ciphers share one call shape: three input arrays and one or two output arrays of fixed row widths (words).
-enum EgOp { EG_ENCRYPT, EG_DECRYPT, EG_HASHED_ENCRYPT, EG_HASHED_DECRYPT };
-struct EgShape {
-    size_t in[3], out[2];
-};
-static const EgShape EG_SHAPES[4] = {{{10, 5, 10}, {10, 10}}, {{5, 10, 10}, {10, 0}}, {{10, 5, 5}, {10, 5}}, {{5, 10, 5}, {5, 0}}};
-static int eg_launch(EgOp op, const u64* d_a, const u64* d_b, const u64* d_c, size_t count, u64* d_o0, u64* d_o1, int* d_status, hipStream_t stream) {
-    const dim3 grid = g1(count, 64), block(64);
-    switch (op) {
-    case EG_ENCRYPT: hipLaunchKernelGGL(k_elgamal_encrypt, grid, block, 0, stream, d_a, d_b, d_c, count, ec_generator_words(), d_o0, d_o1, d_status); break;
-    case EG_DECRYPT: hipLaunchKernelGGL(k_elgamal_decrypt, grid, block, 0, stream, d_a, d_b, d_c, count, d_o0, d_status); break;
-    case EG_HASHED_ENCRYPT: hipLaunchKernelGGL(k_hashed_elgamal_encrypt, grid, block, 0, stream, d_a, d_b, d_c, count, ec_generator_words(), d_o0, d_o1, d_status); break;
-    case EG_HASHED_DECRYPT: hipLaunchKernelGGL(k_hashed_elgamal_decrypt, grid, block, 0, stream, d_a, d_b, d_c, count, d_o0, d_status); break;
-    }
-    HIPCHECK(hipGetLastError());
-    return P2_OK;
-}
-static int eg_batch(EgOp op, const uint64_t* a, const uint64_t* b, const uint64_t* c, size_t count, uint64_t* o0, uint64_t* o1, int* status, int device) {
-    return guarded_rc([&]() -> int {
-        const EgShape& s = EG_SHAPES[op];
-        if (count == 0) return (int)P2_OK;
-        if (!a || !b || !c || !o0 || (s.out[1] && !o1) || !status) return set_error("null argument"), P2_ERR_INVALID;
-        if (int rc = pick_device(device)) return rc;
-        Allocs tmp;
-        u64 *d_a, *d_b, *d_c, *d_o0, *d_o1 = nullptr;
-        int* d_st;
-        if (upload(tmp, &d_a, (const u64*)a, s.in[0] * count) || upload(tmp, &d_b, (const u64*)b, s.in[1] * count) || upload(tmp, &d_c, (const u64*)c, s.in[2] * count) ||
-            dalloc(tmp, &d_o0, s.out[0] * count) || (s.out[1] && dalloc(tmp, &d_o1, s.out[1] * count)) || dalloc(tmp, &d_st, count))
-            return P2_ERR_HIP;
-        if (int rc = eg_launch(op, d_a, d_b, d_c, count, d_o0, d_o1, d_st, nullptr)) return rc;
-        HIPCHECK(hipMemcpy(o0, d_o0, s.out[0] * count * 8, hipMemcpyDeviceToHost));
-        if (s.out[1]) HIPCHECK(hipMemcpy(o1, d_o1, s.out[1] * count * 8, hipMemcpyDeviceToHost));
-        HIPCHECK(hipMemcpy(status, d_st, count * sizeof(int), hipMemcpyDeviceToHost));
-        return (int)P2_OK;
-    });
-}
-static int eg_batch_device(EgOp op, const uint64_t* d_a, const uint64_t* d_b, const uint64_t* d_c, size_t count, uint64_t* d_o0, uint64_t* d_o1, int* d_status, int device,
-                           void* stream) {
-    return guarded_rc([&]() -> int {
-        if (count == 0) return (int)P2_OK;
-        if (!d_a || !d_b || !d_c || !d_o0 || (EG_SHAPES[op].out[1] && !d_o1) || !d_status) return set_error("null argument"), P2_ERR_INVALID;
-        if (int rc = pick_device(device)) return rc;
-        return eg_launch(op, (const u64*)d_a, (const u64*)d_b, (const u64*)d_c, count, (u64*)d_o0, (u64*)d_o1, d_status, (hipStream_t)stream);
-    });
+static int ec_decompress_batch(const uint64_t* w5, size_t count, uint64_t* out, int* status, Where w) {
+    return run_batch(nullptr, count, w, {buf_in(w5, 5 * count), buf_out(out, 10 * count), buf_out(status, count)},
+                     [&](const DevPtr* d, hipStream_t s) { hipLaunchKernelGGL(k_ec_decompress_batch, g1(count, 64), dim3(64), 0, s, d[0], count, d[1], d[2]); });
 }
 int p2_ecgfp5_decompress_batch(const uint64_t* w, size_t count, uint64_t* out, int* status, int device) {
-    return guarded_rc([&]() -> int {
-        if (count == 0) return (int)P2_OK;
-        if (!w || !out || !status) return set_error("null argument"), P2_ERR_INVALID;
-        if (int rc = pick_device(device)) return rc;
-        Allocs tmp;
-        u64 *d_w, *d_out;
-        int* d_st;
-        if (upload(tmp, &d_w, (const u64*)w, 5 * count) || dalloc(tmp, &d_out, 10 * count) || dalloc(tmp, &d_st, count)) return P2_ERR_HIP;
-        if (int rc = ec_decompress_launch(d_w, count, d_out, d_st, nullptr)) return rc;
-        HIPCHECK(hipMemcpy(out, d_out, 10 * count * 8, hipMemcpyDeviceToHost));
-        HIPCHECK(hipMemcpy(status, d_st, count * sizeof(int), hipMemcpyDeviceToHost));
-        return (int)P2_OK;
-    });
+    return ec_decompress_batch(w, count, out, status, on_host(device));
 }
 int p2_ecgfp5_decompress_batch_device(const uint64_t* d_w, size_t count, uint64_t* d_out, int* d_status, int device, void* stream) {
-    return guarded_rc([&]() -> int {
-        if (count == 0) return (int)P2_OK;
-        if (!d_w || !d_out || !d_status) return set_error("null argument"), P2_ERR_INVALID;
-        if (int rc = pick_device(device)) return rc;
-        return ec_decompress_launch((const u64*)d_w, count, (u64*)d_out, d_status, (hipStream_t)stream);
-    });
+    return ec_decompress_batch(d_w, count, d_out, d_status, on_device(device, stream));
+}
+static int ec_encode_batch(const uint32_t* limbs, const uint32_t* pad, size_t attempts, size_t count, uint64_t* out, uint32_t* used, int* status, Where w) {
+    const bool bad = attempts == 0 || attempts > ENCODE_MAX_ATTEMPTS;
+    return run_batch(bad ? "attempts is between 1 and 256" : nullptr, count, w,
+                     {buf_in(limbs, 5 * count), buf_in(pad, 5 * attempts * count), buf_out(out, 10 * count), buf_out(used, count), buf_out(status, count)},
+                     [&](const DevPtr* d, hipStream_t s) {
+                         hipLaunchKernelGGL(k_ec_encode_binary, g1(count, 64), dim3(64), 0, s, d[0], d[1], (u32)attempts, count, d[2], d[3], d[4]);
+                     });
 }
 int p2_ecgfp5_encode_binary_batch(const uint32_t* limbs, const uint32_t* pad, size_t attempts, size_t count, uint64_t* out, uint32_t* used, int* status, int device) {
-    return guarded_rc([&]() -> int {
-        if (int rc = ec_encode_shape(attempts)) return rc;
-        if (count == 0) return (int)P2_OK;
-        if (!limbs || !pad || !out || !used || !status) return set_error("null argument"), P2_ERR_INVALID;
-        if (int rc = pick_device(device)) return rc;
-        Allocs tmp;
-        u32 *d_limbs, *d_pad, *d_used;
-        u64* d_out;
-        int* d_st;
-        if (upload(tmp, &d_limbs, (const u32*)limbs, 5 * count) || upload(tmp, &d_pad, (const u32*)pad, 5 * attempts * count) || dalloc(tmp, &d_out, 10 * count) ||
-            dalloc(tmp, &d_used, count) || dalloc(tmp, &d_st, count))
-            return P2_ERR_HIP;
-        if (int rc = ec_encode_launch(d_limbs, d_pad, attempts, count, d_out, d_used, d_st, nullptr)) return rc;
-        HIPCHECK(hipMemcpy(out, d_out, 10 * count * 8, hipMemcpyDeviceToHost));
-        HIPCHECK(hipMemcpy(used, d_used, count * sizeof(u32), hipMemcpyDeviceToHost));
-        HIPCHECK(hipMemcpy(status, d_st, count * sizeof(int), hipMemcpyDeviceToHost));
-        return (int)P2_OK;
-    });
+    return ec_encode_batch(limbs, pad, attempts, count, out, used, status, on_host(device));
 }
 int p2_ecgfp5_encode_binary_batch_device(const uint32_t* d_limbs, const uint32_t* d_pad, size_t attempts, size_t count, uint64_t* d_out, uint32_t* d_used, int* d_status,
                                          int device, void* stream) {
-    return guarded_rc([&]() -> int {
-        if (int rc = ec_encode_shape(attempts)) return rc;
-        if (count == 0) return (int)P2_OK;
-        if (!d_limbs || !d_pad || !d_out || !d_used || !d_status) return set_error("null argument"), P2_ERR_INVALID;
-        if (int rc = pick_device(device)) return rc;
-        return ec_encode_launch((const u32*)d_limbs, (const u32*)d_pad, attempts, count, (u64*)d_out, (u32*)d_used, d_status, (hipStream_t)stream);
-    });
+    return ec_encode_batch(d_limbs, d_pad, attempts, count, d_out, d_used, d_status, on_device(device, stream));
+}
+// The two encryptions share one call shape, the two decryptions another; `words` is the row width of a message and of the
+// second ciphertext half: 10 (a point) for ElGamal, 5 for the hashed form.
+using EgEncryptKernel = void (*)(const u64*, const u64*, const u64*, size_t, EcWords, u64*, u64*, int*);
+using EgDecryptKernel = void (*)(const u64*, const u64*, const u64*, size_t, u64*, int*);
+static int eg_encrypt(EgEncryptKernel kernel, size_t words, const uint64_t* pk, const uint64_t* nonce, const uint64_t* msg, size_t count, uint64_t* c0, uint64_t* c1,
+                      int* status, Where w) {
+    return run_batch(nullptr, count, w,
+                     {buf_in(pk, 10 * count), buf_in(nonce, 5 * count), buf_in(msg, words * count), buf_out(c0, 10 * count), buf_out(c1, words * count), buf_out(status, count)},
+                     [&](const DevPtr* d, hipStream_t s) {
+                         hipLaunchKernelGGL(kernel, g1(count, 64), dim3(64), 0, s, d[0], d[1], d[2], count, ec_generator_words(), d[3], d[4], d[5]);
+                     });
+}
+static int eg_decrypt(EgDecryptKernel kernel, size_t words, const uint64_t* sk, const uint64_t* c0, const uint64_t* c1, size_t count, uint64_t* msg, int* status, Where w) {
+    return run_batch(nullptr, count, w, {buf_in(sk, 5 * count), buf_in(c0, 10 * count), buf_in(c1, words * count), buf_out(msg, words * count), buf_out(status, count)},
+                     [&](const DevPtr* d, hipStream_t s) { hipLaunchKernelGGL(kernel, g1(count, 64), dim3(64), 0, s, d[0], d[1], d[2], count, d[3], d[4]); });
 }
 int p2_elgamal_encrypt_batch(const uint64_t* pk, const uint64_t* nonce, const uint64_t* msg, size_t count, uint64_t* c0, uint64_t* c1, int* status, int device) {
-    return eg_batch(EG_ENCRYPT, pk, nonce, msg, count, c0, c1, status, device);
+    return eg_encrypt(k_elgamal_encrypt, 10, pk, nonce, msg, count, c0, c1, status, on_host(device));
 }
 int p2_elgamal_encrypt_batch_device(const uint64_t* d_pk, const uint64_t* d_nonce, const uint64_t* d_msg, size_t count, uint64_t* d_c0, uint64_t* d_c1, int* d_status,
                                     int device, void* stream) {
-    return eg_batch_device(EG_ENCRYPT, d_pk, d_nonce, d_msg, count, d_c0, d_c1, d_status, device, stream);
+    return eg_encrypt(k_elgamal_encrypt, 10, d_pk, d_nonce, d_msg, count, d_c0, d_c1, d_status, on_device(device, stream));
 }
 int p2_elgamal_decrypt_batch(const uint64_t* sk, const uint64_t* c0, const uint64_t* c1, size_t count, uint64_t* msg, int* status, int device) {
-    return eg_batch(EG_DECRYPT, sk, c0, c1, count, msg, nullptr, status, device);
+    return eg_decrypt(k_elgamal_decrypt, 10, sk, c0, c1, count, msg, status, on_host(device));
 }
 int p2_elgamal_decrypt_batch_device(const uint64_t* d_sk, const uint64_t* d_c0, const uint64_t* d_c1, size_t count, uint64_t* d_msg, int* d_status, int device, void* stream) {
-    return eg_batch_device(EG_DECRYPT, d_sk, d_c0, d_c1, count, d_msg, nullptr, d_status, device, stream);
+    return eg_decrypt(k_elgamal_decrypt, 10, d_sk, d_c0, d_c1, count, d_msg, d_status, on_device(device, stream));
 }
 int p2_hashed_elgamal_encrypt_batch(const uint64_t* pk, const uint64_t* nonce, const uint64_t* msg, size_t count, uint64_t* c0, uint64_t* ct, int* status, int device) {
-    return eg_batch(EG_HASHED_ENCRYPT, pk, nonce, msg, count, c0, ct, status, device);
+    return eg_encrypt(k_hashed_elgamal_encrypt, 5, pk, nonce, msg, count, c0, ct, status, on_host(device));
 }
 int p2_hashed_elgamal_encrypt_batch_device(const uint64_t* d_pk, const uint64_t* d_nonce, const uint64_t* d_msg, size_t count, uint64_t* d_c0, uint64_t* d_ct,
                                            int* d_status, int device, void* stream) {
-    return eg_batch_device(EG_HASHED_ENCRYPT, d_pk, d_nonce, d_msg, count, d_c0, d_ct, d_status, device, stream);
+    return eg_encrypt(k_hashed_elgamal_encrypt, 5, d_pk, d_nonce, d_msg, count, d_c0, d_ct, d_status, on_device(device, stream));
 }
 int p2_hashed_elgamal_decrypt_batch(const uint64_t* sk, const uint64_t* c0, const uint64_t* ct, size_t count, uint64_t* msg, int* status, int device) {
-    return eg_batch(EG_HASHED_DECRYPT, sk, c0, ct, count, msg, nullptr, status, device);
+    return eg_decrypt(k_hashed_elgamal_decrypt, 5, sk, c0, ct, count, msg, status, on_host(device));
 }
 int p2_hashed_elgamal_decrypt_batch_device(const uint64_t* d_sk, const uint64_t* d_c0, const uint64_t* d_ct, size_t count, uint64_t* d_msg, int* d_status, int device,
                                            void* stream) {
-    return eg_batch_device(EG_HASHED_DECRYPT, d_sk, d_c0, d_ct, count, d_msg, nullptr, d_status, device, stream);
+    return eg_decrypt(k_hashed_elgamal_decrypt, 5, d_sk, d_c0, d_ct, count, d_msg, d_status, on_device(device, stream));
 }
 int p2_ecgfp5_scalar_bits_device(const uint64_t* d_k, size_t count, uint64_t* d_out, size_t stride, int device, void* stream) {
-    return guarded_rc([&]() -> int {
-        if (stride < 320) return set_error("stride is at least 320 words"), P2_ERR_INVALID;
-        if (count == 0) return (int)P2_OK;
-        if (!d_k || !d_out) return set_error("null argument"), P2_ERR_INVALID;
-        if (int rc = pick_device(device)) return rc;
-        hipLaunchKernelGGL(k_ec_scalar_bits, g1(count, 64), dim3(64), 0, (hipStream_t)stream, (const u64*)d_k, count, (u64*)d_out, stride);
-        HIPCHECK(hipGetLastError());
-        return (int)P2_OK;
-    });
+    return run_batch(stride < 320 ? "stride is at least 320 words" : nullptr, count, on_device(device, stream), {buf_in(d_k, 5 * count), buf_out(d_out, stride * count)},
+                     [&](const DevPtr* d, hipStream_t s) { hipLaunchKernelGGL(k_ec_scalar_bits, g1(count, 64), dim3(64), 0, s, d[0], count, d[1], stride); });
 }
 
 // ---- the Poseidon cipher in batches (kernels_pcipher.h; the host twins are in poseidon_cipher.h).  Encryption and decryption
 // share one call shape: ks, nonce, one input row and one output row per item, of 5 l and 5 (pad3(l) + 1) words in this or the
 // other order.
 static const size_t PCIPHER_MAX_LEN = 3072;
-static int pcipher_shape(size_t l) {
-    if (l > PCIPHER_MAX_LEN) return set_error("l is at most 3072 elements"), P2_ERR_INVALID;
-    return P2_OK;
-}
-static size_t pcipher_msg_words(size_t l) { return 5 * l; }
-static size_t pcipher_ct_words(size_t l) { return 5 * ((l + 2) / 3 * 3 + 1); }
-static int pcipher_launch(bool decrypt, const u64* d_ks, const u64* d_nonce, const u64* d_in, size_t l, size_t count, u64* d_out, int* d_status, hipStream_t stream) {
-    if (decrypt)
-        hipLaunchKernelGGL(k_pcipher_decrypt, g1(count, 64), dim3(64), 0, stream, d_ks, d_nonce, d_in, (u32)l, count, d_out, d_status);
-    else
-        hipLaunchKernelGGL(k_pcipher_encrypt, g1(count, 64), dim3(64), 0, stream, d_ks, d_nonce, d_in, (u32)l, count, d_out, d_status);
-    HIPCHECK(hipGetLastError());
-    return P2_OK;
-}
-static int pcipher_batch(bool decrypt, const uint64_t* ks, const uint64_t* nonce, const uint64_t* in, size_t l, size_t count, uint64_t* out, int* status, int device) {
-    return guarded_rc([&]() -> int {
-        if (int rc = pcipher_shape(l)) return rc;
-        if (count == 0) return (int)P2_OK;
-        const size_t n_in = decrypt ? pcipher_ct_words(l) : pcipher_msg_words(l), n_out = decrypt ? pcipher_msg_words(l) : pcipher_ct_words(l);
-        if (!ks || !nonce || !status || (n_in && !in) || (n_out && !out)) return set_error("null argument"), P2_ERR_INVALID;
-        if (int rc = pick_device(device)) return rc;
-        Allocs tmp;
-        u64 *d_ks, *d_nonce, *d_in, *d_out;
-        int* d_st;
-        if (upload(tmp, &d_ks, (const u64*)ks, 10 * count) || upload(tmp, &d_nonce, (const u64*)nonce, 2 * count) || upload(tmp, &d_in, (const u64*)in, n_in * count) ||
-            dalloc(tmp, &d_out, n_out * count) || dalloc(tmp, &d_st, count))
-            return P2_ERR_HIP;
-        if (int rc = pcipher_launch(decrypt, d_ks, d_nonce, d_in, l, count, d_out, d_st, nullptr)) return rc;
-        if (n_out) HIPCHECK(hipMemcpy(out, d_out, n_out * count * 8, hipMemcpyDeviceToHost));
-        HIPCHECK(hipMemcpy(status, d_st, count * sizeof(int), hipMemcpyDeviceToHost));
-        return (int)P2_OK;
-    });
-}
-static int pcipher_batch_device(bool decrypt, const uint64_t* d_ks, const uint64_t* d_nonce, const uint64_t* d_in, size_t l, size_t count, uint64_t* d_out, int* d_status,
-                                int device, void* stream) {
-    return guarded_rc([&]() -> int {
-        if (int rc = pcipher_shape(l)) return rc;
-        if (count == 0) return (int)P2_OK;
-        const size_t n_in = decrypt ? pcipher_ct_words(l) : pcipher_msg_words(l), n_out = decrypt ? pcipher_msg_words(l) : pcipher_ct_words(l);
-        if (!d_ks || !d_nonce || !d_status || (n_in && !d_in) || (n_out && !d_out)) return set_error("null argument"), P2_ERR_INVALID;
-        if (int rc = pick_device(device)) return rc;
-        return pcipher_launch(decrypt, (const u64*)d_ks, (const u64*)d_nonce, (const u64*)d_in, l, count, (u64*)d_out, d_status, (hipStream_t)stream);
-    });
+static int pcipher_run(bool decrypt, const uint64_t* ks, const uint64_t* nonce, const uint64_t* in, size_t l, size_t count, uint64_t* out, int* status, Where w) {
+    const bool bad = l > PCIPHER_MAX_LEN;
+    const size_t msg_words = bad ? 0 : 5 * l, ct_words = bad ? 0 : 5 * ((l + 2) / 3 * 3 + 1);
+    const auto kernel = decrypt ? k_pcipher_decrypt : k_pcipher_encrypt;
+    return run_batch(bad ? "l is at most 3072 elements" : nullptr, count, w,
+                     {buf_in(ks, 10 * count), buf_in(nonce, 2 * count), buf_in(in, (decrypt ? ct_words : msg_words) * count),
+                      buf_out(out, (decrypt ? msg_words : ct_words) * count), buf_out(status, count)},
+                     [&](const DevPtr* d, hipStream_t s) { hipLaunchKernelGGL(kernel, g1(count, 64), dim3(64), 0, s, d[0], d[1], d[2], (u32)l, count, d[3], d[4]); });
 }
 int p2_poseidon_encrypt_batch(const uint64_t* ks, const uint64_t* nonce, const uint64_t* msg, size_t l, size_t count, uint64_t* ct, int* status, int device) {
-    return pcipher_batch(false, ks, nonce, msg, l, count, ct, status, device);
+    return pcipher_run(false, ks, nonce, msg, l, count, ct, status, on_host(device));
 }
 int p2_poseidon_encrypt_batch_device(const uint64_t* d_ks, const uint64_t* d_nonce, const uint64_t* d_msg, size_t l, size_t count, uint64_t* d_ct, int* d_status, int device,
                                      void* stream) {
-    return pcipher_batch_device(false, d_ks, d_nonce, d_msg, l, count, d_ct, d_status, device, stream);
+    return pcipher_run(false, d_ks, d_nonce, d_msg, l, count, d_ct, d_status, on_device(device, stream));
 }
 int p2_poseidon_decrypt_batch(const uint64_t* ks, const uint64_t* nonce, const uint64_t* ct, size_t l, size_t count, uint64_t* msg, int* status, int device) {
-    return pcipher_batch(true, ks, nonce, ct, l, count, msg, status, device);
+    return pcipher_run(true, ks, nonce, ct, l, count, msg, status, on_host(device));
 }
 int p2_poseidon_decrypt_batch_device(const uint64_t* d_ks, const uint64_t* d_nonce, const uint64_t* d_ct, size_t l, size_t count, uint64_t* d_msg, int* d_status, int device,
                                      void* stream) {
-    return pcipher_batch_device(true, d_ks, d_nonce, d_ct, l, count, d_msg, d_status, device, stream);
+    return pcipher_run(true, d_ks, d_nonce, d_ct, l, count, d_msg, d_status, on_device(device, stream));
 }
 
 // ---- batched verification
