@@ -818,6 +818,9 @@ int p2_gpu_zeta_pows(const uint64_t* z, size_t n, uint64_t* pows, int device);
  * ("wires", "wires_cap", "zs", "zs_cap", "quotient_coeffs", "quotient_cap", "challenges", "openings",
  * "public_inputs_hash", ...) */
 int p2_circuit_debug_read(p2_circuit*, const char* name, size_t index, uint64_t* out, size_t cap, size_t* n_written);
+/* debug: how many device allocations, pinned host allocations, streams and events the library holds right now, over all
+ * handles, trees and running calls of the process; a handle or tree that is freed takes all of its own with it */
+size_t p2_debug_live_resources(void);
 
 #ifdef __cplusplus
 }

@@ -294,6 +294,7 @@ def lib():
         "p2_gpu_merkle_cap": (C.c_int, [u64p, sz, sz, C.c_int, u64p, C.c_int]),
         "p2_gpu_zeta_pows": (C.c_int, [u64p, sz, u64p, C.c_int]),
         "p2_circuit_debug_read": (C.c_int, [vp, C.c_char_p, sz, u64p, sz, C.POINTER(sz)]),
+        "p2_debug_live_resources": (sz, []),
         "p2_builder_permute_swapped": (C.c_int, [vp, u64p, u64, u64p]), "p2_builder_hash_or_noop": (C.c_int, [vp, u64p, sz, u64p]),
         "p2_builder_add_virtual_hash": (C.c_int, [vp, u64p]), "p2_builder_add_virtual_cap": (C.c_int, [vp, C.c_int, u64p]),
         "p2_builder_connect_hashes": (C.c_int, [vp, u64p, u64p]),

@@ -16,6 +16,7 @@
 #include <thread>
 
 #include "capi_common.h"
+#include "hip_owners.h"
 #include "os_random.h"
 #include "kernels.h"
 #include "kernels2.h"
@@ -28,16 +29,19 @@
 #include "kernels_schnorr.h"
 #include "kernels_witness_io.h"
 #include "merkle_host.h"
+#include "pool.h"
 #include "verifier.h"
 
 using namespace p2;
 using namespace p2k;
 
-#define HIPCHECK(expr)                                                                          \
+// HIPCHECK_AS: the error names `text`, the HIP call an owner's method makes, where the expression itself would name the method
+#define HIPCHECK(expr) HIPCHECK_AS(#expr, expr)
+#define HIPCHECK_AS(text, expr)                                                                 \
     do {                                                                                        \
         hipError_t _e = (expr);                                                                 \
         if (_e != hipSuccess) {                                                                 \
-            set_error(std::string(#expr) + ": " + hipGetErrorString(_e));                       \
+            set_error(std::string(text) + ": " + hipGetErrorString(_e));                        \
             return P2_ERR_HIP;                                                                  \
         }                                                                                       \
     } while (0)
@@ -51,15 +55,31 @@ struct Tree {
 static size_t level_off(u32 bits, u32 l) { return 4 * (((size_t)2 << bits) - ((size_t)2 << (bits - l))); }
 static size_t cap_off(const Tree& t, u32 cap_height) { return level_off(t.bits, t.bits - cap_height); }
 
-// Device allocations with one owner -- a handle, a PrimCtx, one call of a primitive -- freed when it goes, on every path out.
-struct Allocs : std::vector<void*> {
-    ~Allocs() { for (void* p : *this) (void)hipFree(p); }
+// Device allocations with one owner -- a handle, a workspace, a PrimCtx, one call of a primitive -- freed when it goes, on every
+// path out.
+class Allocs {
+    std::vector<void*> v;
+
+public:
+    Allocs() = default;
+    Allocs(const Allocs&) = delete;
+    ~Allocs() { clear(); }
+    bool empty() const { return v.empty(); }
+    hipError_t alloc(void** p, size_t bytes) {
+        const hipError_t e = hipMalloc(p, bytes);
+        if (e == hipSuccess) v.push_back(*p), g_live_resources++;
+        return e;
+    }
+    void clear() {
+        for (void* p : v) (void)hipFree(p);
+        g_live_resources -= v.size();
+        v.clear();
+    }
 };
 template <class T>
 static int dalloc(Allocs& mem, T** p, size_t count) {
     void* q = nullptr;
-    HIPCHECK(hipMalloc(&q, std::max<size_t>(count, 1) * sizeof(T)));
-    mem.push_back(q);
+    HIPCHECK_AS("hipMalloc(&q, std::max<size_t>(count, 1) * sizeof(T))", mem.alloc(&q, std::max<size_t>(count, 1) * sizeof(T)));
     *p = (T*)q;
     return 0;
 }
@@ -72,24 +92,26 @@ static int upload(Allocs& mem, T** p, const T* host, size_t count) {
 
 // What a launch needs: its stream and, while per-kernel timing is on, the event pairs that collect_timing has yet to read.
 struct Lane {
-    hipStream_t stream = nullptr;
+    hipStream_t stream = nullptr;  // where the launches go: `own` (open), or a caller's stream (mt_build)
+    Stream own;
     bool timing = false;  // follows p2_circuit::timing_on (p2_circuit_set_timing, build_workspace)
-    std::vector<std::pair<std::string, std::pair<hipEvent_t, hipEvent_t>>> pending;
+    std::vector<std::pair<std::string, std::pair<Event, Event>>> pending;
+    hipError_t open(unsigned flags) { const hipError_t e = own.create(flags); return stream = own, e; }
 };
 // Launch on a lane, with optional per-kernel event timing under `name`.
 #define LAUNCH(lane, name, kernel, grid, block, shmem, ...)                                  \
     do {                                                                                     \
         Lane& _l = (lane);                                                                   \
-        hipEvent_t _e0 = nullptr, _e1 = nullptr;                                             \
+        Event _e0, _e1;                                                                      \
         if (_l.timing) {                                                                     \
-            (void)hipEventCreate(&_e0);                                                      \
-            (void)hipEventCreate(&_e1);                                                      \
+            (void)_e0.create(hipEventDefault);                                               \
+            (void)_e1.create(hipEventDefault);                                               \
             (void)hipEventRecord(_e0, _l.stream);                                            \
         }                                                                                    \
         hipLaunchKernelGGL(kernel, grid, block, shmem, _l.stream, __VA_ARGS__);              \
         if (_l.timing) {                                                                     \
             (void)hipEventRecord(_e1, _l.stream);                                            \
-            _l.pending.push_back({name, {_e0, _e1}});                                        \
+            _l.pending.emplace_back(name, std::make_pair(std::move(_e0), std::move(_e1)));   \
         }                                                                                    \
         HIPCHECK(hipGetLastError());                                                         \
     } while (0)
@@ -121,8 +143,9 @@ struct Oracle {
 };
 
 struct Workspace {
-    Lane lane;                  // the proving stream
-    hipEvent_t done = nullptr;  // recorded after the last kernel of a call; the caller's stream waits on it
+    Allocs mem;  // everything below that build_workspace allocates; declared first: freed after the lane has gone
+    Lane lane;   // the proving stream
+    Event done;  // recorded after the last kernel of a call; the caller's stream waits on it
     u32* d_input_slots = nullptr;      // slot of every input target, as last uploaded to this workspace
     std::vector<u32> h_input_slots;    // host copy: re-uploaded only when a call brings a different target list
     u64* d_input_values = nullptr;
@@ -131,9 +154,8 @@ struct Workspace {
     int* d_status = nullptr;
     u64* d_advice = nullptr;
     u64* d_pi_hash = nullptr;          // [chunk][4] public-input hash per proof (k_pi_hash; circuits with public inputs)
-    u32* d_out_slots = nullptr;        // slot of every out-target (p2_prove_batch_outputs*), as last uploaded; grown on demand
+    DevBuf<u32> d_out_slots;           // slot of every out-target (p2_prove_batch_outputs*), as last uploaded; grown on demand
     std::vector<u32> h_out_slots;
-    size_t cap_out_slots = 0;
     Oracle wires, zs, quot;
     u64 *d_permq = nullptr, *d_perm_seg = nullptr, *d_fri_seg = nullptr, *d_lktmp = nullptr;
     u64 *d_qvals = nullptr, *d_qres = nullptr;
@@ -149,11 +171,15 @@ struct Workspace {
     uint8_t* d_proofs = nullptr;
     PolyRef* d_polyrefs = nullptr;
     EvalRef* d_evalrefs = nullptr;
+    ~Workspace() { if (lane.stream) (void)hipStreamSynchronize(lane.stream); }
 };
 
+// Members go in reverse order: the pools and the proving workspaces (each waits for its own stream first), then the setup lane,
+// and `allocs` -- the tables all of them read -- last.
 struct p2_circuit {
     Circuit c;
     int device = 0;
+    Allocs allocs;
     Lane setup;  // load-time work (preprocessing); the proving lanes are the workspaces'
     Domain dom;
     size_t n = 0, N = 0;
@@ -186,12 +212,11 @@ struct p2_circuit {
     u32 n_obs = 0, n_ser = 0, ev_count = 0;
     // ---- per-stream workspaces: chunks are dealt round-robin to streams so that the latency-bound stages of one
     // chunk (witness levels, Fiat-Shamir, PoW tail) overlap with the Poseidon-heavy stages of another
-    std::vector<struct Workspace*> ws;
-    hipEvent_t ev_witness = nullptr;  // end of the latest witness kernel on any proving stream
+    std::vector<std::unique_ptr<Workspace>> ws;
+    Event ev_witness;  // end of the latest witness kernel on any proving stream
     bool witness_recorded = false;
     u32 ws_inputs = 0;
-    size_t chunk = 0, ws_alloc_begin = 0;  // allocs[ws_alloc_begin..] belong to the workspaces
-    bool ws_allocs_open = false;
+    size_t chunk = 0;
     // tuning options (p2_circuit_set_option; the environment is read ONCE, at load): proofs per chunk, proving streams,
     // phase timing of the host path on stderr
     size_t opt_chunk = 128, opt_streams = 2;
@@ -202,14 +227,11 @@ struct p2_circuit {
     u32 opt_witness_fuse = 1;
     bool opt_debug_timing = false;
     // host-path staging (p2_prove_batch): persistent device buffers + pinned host buffers, one set per concurrent caller
-    std::vector<struct Staging*> staging_free;
-    std::mutex staging_mu;
+    Pool<struct Staging, NoKey> staging;
     // batched verification (p2_verify_batch): layout tables built at load, workspaces leased per call like the staging sets
     std::string vfy_error;  // non-empty: a precondition of the verifier kernels does not hold for this circuit
     VerifyArgs vfy_args{};  // layout and circuit fields; the per-call pointers are filled in by proof_run
-    size_t vfy_chunk = 0;
-    std::vector<struct VerifyWs*> vfy_free;
-    std::mutex vfy_mu;
+    Pool<struct VerifyWs> vfy;     // keyed by the option "verify_chunk"
     // compressed proofs (kernels_compress.h): the source of every word of the full layout
     u32* d_cmp_wmap = nullptr;
     // Keccak circuits: the word index of every hash of the unpacked proof, the caps first (k_kcv_range)
@@ -219,16 +241,16 @@ struct p2_circuit {
     // leased per call like the verification ones, and the tables of the fault check, uploaded by the first p2_witness_explain
     u32* d_wired_slots = nullptr;
     u32 n_wired = 0;
-    size_t wit_chunk = 256;  // option "witness_chunk"
-    std::vector<struct WitnessWs*> wit_free;
-    std::mutex wit_mu;
-    struct ExplainTables* explain = nullptr;
+    Pool<struct WitnessWs> wit{256};  // keyed by the option "witness_chunk"
+    std::unique_ptr<struct ExplainTables> explain;
+    std::mutex explain_mu;
     long fail_alloc_after = -1;            // test hook, see dalloc_ws
     // timing
     bool timing_on = false;
     std::map<std::string, std::pair<float, u32>> times;
-    Allocs allocs;
     std::mutex mu;
+    p2_circuit();  // both defined below the leased workspaces, whose types they need complete
+    ~p2_circuit();
 };
 
 // Launch outside the timing map (the verification / compression driver, whose kernels run on a caller's or a workspace's stream).
@@ -698,7 +720,7 @@ static int circuit_setup(p2_circuit* C) {
 // Reads the event pairs of every lane into the timing map (waits for the launches they bracket).
 static void collect_timing(p2_circuit* C) {
     std::vector<Lane*> lanes{&C->setup};
-    for (Workspace* W : C->ws) lanes.push_back(&W->lane);
+    for (auto& W : C->ws) lanes.push_back(&W->lane);
     for (Lane* L : lanes) {
         for (auto& pe : L->pending) {
             float ms = 0;
@@ -707,31 +729,15 @@ static void collect_timing(p2_circuit* C) {
             auto& t = C->times[pe.first];
             t.first += ms;
             t.second++;
-            (void)hipEventDestroy(pe.second.first);
-            (void)hipEventDestroy(pe.second.second);
         }
-        L->pending.clear();
+        L->pending.clear();  // (destroys the events)
     }
 }
 // Drains and releases every per-stream workspace; the handle is left with none (chunk == 0), ready to allocate again.
 static void release_workspaces(p2_circuit* C) {
-    for (Workspace* W : C->ws) {
+    for (auto& W : C->ws)
         if (W->lane.stream) (void)hipStreamSynchronize(W->lane.stream);
-        for (auto& pe : W->lane.pending) {
-            (void)hipEventDestroy(pe.second.first);
-            (void)hipEventDestroy(pe.second.second);
-        }
-        if (W->lane.stream) (void)hipStreamDestroy(W->lane.stream);
-        if (W->done) (void)hipEventDestroy(W->done);
-        if (W->d_out_slots) (void)hipFree(W->d_out_slots);
-        delete W;
-    }
     C->ws.clear();
-    if (C->ws_allocs_open) {
-        for (size_t i = C->ws_alloc_begin; i < C->allocs.size(); i++) (void)hipFree(C->allocs[i]);
-        C->allocs.resize(C->ws_alloc_begin);
-        C->ws_allocs_open = false;
-    }
     C->chunk = 0;
     C->ws_inputs = 0;
     C->witness_recorded = false;
@@ -754,20 +760,17 @@ static int setup_polyrefs(p2_circuit* C, Workspace& W) {
     for (u32 b = 0; b < OS_SLOTS; b++)
         for (u32 i = 0; i < oracle[b]->cols; i++) e.push_back({oracle[b]->coef, oracle[b]->coef_stride, i, b == OS_Z_NEXT, os.slot_base[b] + i, 0});
     C->n_evalrefs = (u32)e.size();
-    if (upload(C->allocs, &W.d_evalrefs, e.data(), e.size())) return P2_ERR_HIP;
-    return upload(C->allocs, &W.d_polyrefs, v.data(), v.size());
+    if (upload(W.mem, &W.d_evalrefs, e.data(), e.size())) return P2_ERR_HIP;
+    return upload(W.mem, &W.d_polyrefs, v.data(), v.size());
 }
 // Test hook (P2AES_TEST_FAIL_ALLOC_AFTER=k in the environment when the handle is loaded): the k-th workspace allocation
 // fails as if the device were out of memory.  Exercises the roll-back below without needing a full HBM.
-static int dalloc_ws(p2_circuit* C, size_t& counter, void** p, size_t bytes) {
+static int dalloc_ws(p2_circuit* C, Allocs& mem, size_t& counter, void** p, size_t bytes) {
     if (C->fail_alloc_after >= 0 && (long)counter++ == C->fail_alloc_after) {
         C->fail_alloc_after = -1;  // one shot: the retry must succeed
         return set_error("hipMalloc: injected allocation failure (test hook)"), P2_ERR_HIP;
     }
-    void* q = nullptr;
-    HIPCHECK(hipMalloc(&q, std::max<size_t>(bytes, 8)));
-    C->allocs.push_back(q);
-    *p = q;
+    HIPCHECK_AS("hipMalloc(&q, std::max<size_t>(bytes, 8))", mem.alloc(p, std::max<size_t>(bytes, 8)));
     return 0;
 }
 // entries of the per-proof table of FRI alpha powers: the longer of the two batches.  From the layout, which the handle has from
@@ -778,10 +781,10 @@ static int build_workspace(p2_circuit* C, Workspace* W, size_t chunk, u32 ws_inp
     const size_t n = C->n, N = C->N;
     const u32 NC = c.cfg.num_challenges;
     W->lane.timing = C->timing_on;
-    if (hipStreamCreateWithFlags(&W->lane.stream, hipStreamNonBlocking) != hipSuccess) return set_error("hipStreamCreate failed"), P2_ERR_HIP;
-    if (hipEventCreateWithFlags(&W->done, hipEventDisableTiming) != hipSuccess) return set_error("hipEventCreate failed"), P2_ERR_HIP;
+    if (W->lane.open(hipStreamNonBlocking) != hipSuccess) return set_error("hipStreamCreate failed"), P2_ERR_HIP;
+    if (W->done.create(hipEventDisableTiming) != hipSuccess) return set_error("hipEventCreate failed"), P2_ERR_HIP;
 #define WS_ALLOC(field, count)                                                                       \
-    if (dalloc_ws(C, counter, (void**)&(field), (size_t)(count) * sizeof(*(field)))) return P2_ERR_HIP
+    if (dalloc_ws(C, W->mem, counter, (void**)&(field), (size_t)(count) * sizeof(*(field)))) return P2_ERR_HIP
     WS_ALLOC(W->d_input_slots, ws_inputs);
     WS_ALLOC(W->d_input_values, chunk * ws_inputs);
     WS_ALLOC(W->d_values, chunk * c.num_slots);
@@ -849,14 +852,11 @@ static int alloc_workspace(p2_circuit* C, size_t chunk, u32 n_inputs, size_t nst
         nstreams = std::max(nstreams, C->ws.size());
         release_workspaces(C);
     }
-    C->ws_alloc_begin = C->allocs.size();
-    C->ws_allocs_open = true;
     const u32 ws_inputs = std::max<u32>(n_inputs, 1);
     size_t counter = 0;
     for (size_t wi = 0; wi < nstreams; wi++) {
-        Workspace* W = new Workspace();
-        C->ws.push_back(W);  // owned by the handle from here on: release_workspaces() frees a half-built one too
-        if (build_workspace(C, W, chunk, ws_inputs, counter)) {
+        C->ws.push_back(std::make_unique<Workspace>());  // owned by the handle from here on: release_workspaces() frees a half-built one too
+        if (build_workspace(C, C->ws.back().get(), chunk, ws_inputs, counter)) {
             std::string why = g_last_error;
             release_workspaces(C);
             set_error("workspace allocation failed (" + why + "); the handle holds no workspace now, a smaller batch may fit");
@@ -1184,69 +1184,26 @@ static int prove_chunk(p2_circuit* C, Workspace& W, u32 B, u32 n_inputs, const u
     return 0;
 }
 
+// The leased workspaces (pool.h) have a stream of their own, and those whose calls may return before their kernels have run an
+// event `done` behind the last of them.  After a failed call the lease drains the workspace; a destructor first waits for the
+// last user, then the members free themselves.
+static void ws_drain(hipStream_t own, bool has_caller = false, void* caller = nullptr) {
+    if (has_caller) (void)hipStreamSynchronize((hipStream_t)caller);
+    if (own) (void)hipStreamSynchronize(own);
+}
 // Host-path staging: device buffers, pinned host mirrors and a stream, kept across p2_prove_batch calls (they only grow).
 // A caller leases one set for the duration of its call; concurrent callers on one handle each get their own.
 struct Staging {
-    hipStream_t stream = nullptr;
-    u64 *d_vals = nullptr, *h_vals = nullptr;
-    uint8_t *d_proofs = nullptr, *h_proofs = nullptr;
-    int *d_stat = nullptr, *h_stat = nullptr;
-    u64 *d_out = nullptr, *h_out = nullptr;  // witness outputs (p2_prove_batch_outputs); never allocated by p2_prove_batch
-    size_t cap_vals = 0, cap_proofs = 0, cap_stat = 0, cap_out = 0;
-    void release() {
-        if (d_vals) (void)hipFree(d_vals);
-        if (d_proofs) (void)hipFree(d_proofs);
-        if (d_stat) (void)hipFree(d_stat);
-        if (d_out) (void)hipFree(d_out);
-        if (h_out) (void)hipHostFree(h_out);
-        if (h_vals) (void)hipHostFree(h_vals);
-        if (h_proofs) (void)hipHostFree(h_proofs);
-        if (h_stat) (void)hipHostFree(h_stat);
-        if (stream) (void)hipStreamDestroy(stream);
-        *this = Staging();
-    }
-    template <class T>
-    static bool grow(T** d, T** h, size_t* cap, size_t bytes) {
-        if (*cap >= bytes) return true;
-        if (*d) (void)hipFree(*d);
-        if (*h) (void)hipHostFree(*h);
-        *d = nullptr, *h = nullptr, *cap = 0;
-        size_t want = bytes + bytes / 4;
-        if (hipMalloc((void**)d, want) != hipSuccess || hipHostMalloc((void**)h, want, hipHostMallocDefault) != hipSuccess) return false;
-        *cap = want;
-        return true;
-    }
-};
-struct StagingLease {
-    p2_circuit* C;
-    Staging* S = nullptr;
-    explicit StagingLease(p2_circuit* c) : C(c) {}
-    Staging* get(size_t vals_bytes, size_t proofs_bytes, size_t batch, size_t out_bytes) {
-        {
-            std::lock_guard<std::mutex> lock(C->staging_mu);
-            if (!C->staging_free.empty()) {
-                S = C->staging_free.back();
-                C->staging_free.pop_back();
-            }
-        }
-        if (!S) S = new Staging();
-        if ((!S->stream && hipStreamCreateWithFlags(&S->stream, hipStreamNonBlocking) != hipSuccess) ||
-            !Staging::grow(&S->d_vals, &S->h_vals, &S->cap_vals, vals_bytes) || !Staging::grow(&S->d_proofs, &S->h_proofs, &S->cap_proofs, proofs_bytes) ||
-            !Staging::grow(&S->d_stat, &S->h_stat, &S->cap_stat, batch * sizeof(int)) || !Staging::grow(&S->d_out, &S->h_out, &S->cap_out, out_bytes)) {
-            set_error("staging buffers for p2_prove_batch could not be allocated");
-            S->release();
-            delete S;
-            S = nullptr;
-        }
-        return S;
-    }
-    ~StagingLease() {
-        if (!S) return;
-        // every path out of p2_prove_batch, the error returns after an async copy included: nothing may still be reading or
-        // writing these buffers when the next caller leases them (a no-op on the success path, which has synchronised already)
-        if (S->stream) (void)hipStreamSynchronize(S->stream);
-        std::lock_guard<std::mutex> lock(C->staging_mu);
-        C->staging_free.push_back(S);
+    NoKey key;
+    Staged<u64> vals, out;  // out: witness outputs (p2_prove_batch_outputs); never allocated by p2_prove_batch
+    Staged<uint8_t> proofs;
+    Staged<int> stat;
+    Stream stream;  // (after the memory, as in every workspace: the stream goes first)
+    void drain(bool has_caller, void* caller) { ws_drain(stream, has_caller, caller); }
+    ~Staging() { ws_drain(stream); }
+    bool fit(size_t vals_bytes, size_t proofs_bytes, size_t batch, size_t out_bytes) {
+        return (stream || stream.create(hipStreamNonBlocking) == hipSuccess) && vals.grow(vals_bytes) && proofs.grow(proofs_bytes) &&
+               stat.grow(batch * sizeof(int)) && out.grow(out_bytes);
     }
 };
 
@@ -1269,27 +1226,21 @@ static int guarded_rc(F&& f) {
 // Per-call workspace: device buffers for one chunk of proofs, a stream for the host path and an event that orders the next
 // user of the workspace behind the last kernel that read it (the device path returns before its kernels have run).
 struct VerifyWs {
-    hipStream_t stream = nullptr;
-    hipEvent_t done = nullptr;
-    size_t chunk = 0;
-    u64 *d_words = nullptr, *d_chal = nullptr, *d_vq = nullptr, *d_vd = nullptr, *d_pi_hash = nullptr;
-    u32 *d_flags = nullptr, *d_qfail = nullptr;
-    uint8_t* d_proofs = nullptr;
-    int *d_status = nullptr, *h_status = nullptr;
+    size_t key = 0, chunk = 0;  // the "verify_chunk" option it was made under = the proofs it holds
+    DevBuf<u64> d_words, d_chal, d_vq, d_vd, d_pi_hash;
+    DevBuf<u32> d_flags, d_qfail;
+    DevBuf<uint8_t> d_proofs;
+    DevBuf<int> d_status;
+    PinBuf<int> h_status;
     // compressed proofs, allocated by their first use (cmp_ensure); never by plain verification
-    CmpPlan* d_plan = nullptr;
-    uint8_t* d_cout = nullptr;
-    u32 *d_len = nullptr, *h_len = nullptr;
-    void release() {
-        for (void* p : {(void*)d_words, (void*)d_chal, (void*)d_vq, (void*)d_vd, (void*)d_pi_hash, (void*)d_flags, (void*)d_qfail, (void*)d_proofs, (void*)d_status,
-                        (void*)d_plan, (void*)d_cout, (void*)d_len})
-            if (p) (void)hipFree(p);
-        if (h_status) (void)hipHostFree(h_status);
-        if (h_len) (void)hipHostFree(h_len);
-        if (stream) (void)hipStreamDestroy(stream);
-        if (done) (void)hipEventDestroy(done);
-        *this = VerifyWs();
-    }
+    DevBuf<CmpPlan> d_plan;
+    DevBuf<uint8_t> d_cout;
+    DevBuf<u32> d_len;
+    PinBuf<u32> h_len;
+    Stream stream;
+    Event done;
+    void drain(bool has_caller, void* caller) { ws_drain(stream, has_caller, caller); }
+    ~VerifyWs() { if (done) (void)hipEventSynchronize(done); }
 };
 struct VdArg {
     u64 w[4 * 16 + 4];
@@ -1412,8 +1363,8 @@ static int verify_setup(p2_circuit* C) {
     a.k_is = C->d_k_is;
     // chunk: the unpacked words and the staged proofs of a chunk within ~256 MiB, at most 512 proofs
     const size_t per_proof = 8 * (size_t)a.W + C->pbytes + 8 * (CH_WORDS + VQ_WORDS) + 16;
-    C->vfy_chunk = std::max<size_t>(1, std::min<size_t>(512, ((size_t)256 << 20) / per_proof));
-    if (const char* e = getenv("P2AES_VERIFY_CHUNK")) C->vfy_chunk = (size_t)std::min(4096, std::max(1, atoi(e)));
+    C->vfy.set_key(std::max<size_t>(1, std::min<size_t>(512, ((size_t)256 << 20) / per_proof)));
+    if (const char* e = getenv("P2AES_VERIFY_CHUNK")) C->vfy.set_key((size_t)std::min(4096, std::max(1, atoi(e))));
     return 0;
 }
 
@@ -1442,58 +1393,28 @@ static int cmp_setup(p2_circuit* C) {
     return upload(C->allocs, &C->d_cmp_wmap, wmap.data(), wmap.size());
 }
 
-static VerifyWs* verify_lease(p2_circuit* C) {
-    VerifyWs* W = nullptr;
-    std::vector<VerifyWs*> stale;  // made before the "verify_chunk" option changed: drained and freed after the lock is released
-    size_t chunk;
-    {
-        std::lock_guard<std::mutex> lock(C->vfy_mu);
-        chunk = C->vfy_chunk;
-        while (!C->vfy_free.empty() && !W) {
-            W = C->vfy_free.back();
-            C->vfy_free.pop_back();
-            if (W->chunk != chunk) {
-                stale.push_back(W);
-                W = nullptr;
-            }
-        }
-    }
-    for (VerifyWs* S : stale) {
-        (void)hipEventSynchronize(S->done);
-        S->release();
-        delete S;
-    }
-    if (W) return W;
-    W = new VerifyWs();
+static std::unique_ptr<VerifyWs> verify_make(const p2_circuit* C, size_t chunk) {
+    auto W = std::make_unique<VerifyWs>();
     const VerifyArgs& a = C->vfy_args;
-    W->chunk = chunk;
-    bool ok = hipStreamCreateWithFlags(&W->stream, hipStreamNonBlocking) == hipSuccess && hipEventCreateWithFlags(&W->done, hipEventDisableTiming) == hipSuccess &&
-              hipMalloc((void**)&W->d_words, chunk * a.W * 8) == hipSuccess && hipMalloc((void**)&W->d_chal, chunk * CH_WORDS * 8) == hipSuccess &&
-              hipMalloc((void**)&W->d_vq, chunk * VQ_WORDS * 8) == hipSuccess && hipMalloc((void**)&W->d_vd, sizeof(VdArg)) == hipSuccess &&
-              hipMalloc((void**)&W->d_pi_hash, chunk * 4 * 8) == hipSuccess &&
-              hipMalloc((void**)&W->d_flags, chunk * 4) == hipSuccess && hipMalloc((void**)&W->d_qfail, chunk * 4) == hipSuccess &&
-              hipMalloc((void**)&W->d_proofs, chunk * C->pbytes) == hipSuccess && hipMalloc((void**)&W->d_status, chunk * sizeof(int)) == hipSuccess &&
-              hipHostMalloc((void**)&W->h_status, chunk * sizeof(int), hipHostMallocDefault) == hipSuccess;
-    if (!ok) {
-        set_error("verification workspace could not be allocated");
-        W->release();
-        delete W;
-        return nullptr;
-    }
+    W->key = W->chunk = chunk;
+    const bool ok = W->stream.create(hipStreamNonBlocking) == hipSuccess && W->done.create(hipEventDisableTiming) == hipSuccess &&
+                    W->d_words.alloc(chunk * a.W) == hipSuccess && W->d_chal.alloc(chunk * CH_WORDS) == hipSuccess && W->d_vq.alloc(chunk * VQ_WORDS) == hipSuccess &&
+                    W->d_vd.alloc(sizeof(VdArg) / 8) == hipSuccess && W->d_pi_hash.alloc(chunk * 4) == hipSuccess && W->d_flags.alloc(chunk) == hipSuccess &&
+                    W->d_qfail.alloc(chunk) == hipSuccess && W->d_proofs.alloc(chunk * C->pbytes) == hipSuccess && W->d_status.alloc(chunk) == hipSuccess &&
+                    W->h_status.alloc(chunk) == hipSuccess;
+    if (!ok) return set_error("verification workspace could not be allocated"), nullptr;
     return W;
 }
-static void verify_return(p2_circuit* C, VerifyWs* W) {
-    std::lock_guard<std::mutex> lock(C->vfy_mu);
-    C->vfy_free.push_back(W);
-}
+struct VerifyLease : Lease<VerifyWs> {
+    explicit VerifyLease(p2_circuit* C) : Lease(C->vfy, [C](size_t chunk) { return verify_make(C, chunk); }) {}
+};
 
 // ---- the driver: verify, compress, decompress, verify compressed
 enum ProofOp { OP_VERIFY, OP_COMPRESS, OP_DECOMPRESS, OP_VERIFY_COMPRESSED };
 static int cmp_ensure(p2_circuit* C, VerifyWs* W) {
     if (W->d_plan) return P2_OK;
     const size_t n = W->chunk;
-    if (hipMalloc((void**)&W->d_plan, n * sizeof(CmpPlan)) != hipSuccess || hipMalloc((void**)&W->d_cout, n * C->pbytes) != hipSuccess ||
-        hipMalloc((void**)&W->d_len, n * 4) != hipSuccess || hipHostMalloc((void**)&W->h_len, n * 4, hipHostMallocDefault) != hipSuccess)
+    if (W->d_plan.alloc(n) != hipSuccess || W->d_cout.alloc(n * C->pbytes) != hipSuccess || W->d_len.alloc(n) != hipSuccess || W->h_len.alloc(n) != hipSuccess)
         return set_error("compression workspace could not be allocated"), P2_ERR_HIP;
     return P2_OK;
 }
@@ -1613,13 +1534,13 @@ static int proof_batch_impl(p2_circuit* C, ProofOp op, size_t batch, const uint8
     if (vd_words > sizeof(vd.w) / 8) return set_error("internal: verifier data larger than the kernel argument"), P2_ERR_INVALID;
     memcpy(vd.w, verifier_data ? verifier_data : C->verifier_data.data(), vd_words * 8);
     HIPCHECK(hipSetDevice(C->device));
-    VerifyWs* W = verify_lease(C);
+    VerifyLease lease(C);
+    VerifyWs* W = lease.ws.get();
     if (!W) return P2_ERR_HIP;
+    if (!host) lease.on_stream(st);
     int rc = op == OP_VERIFY ? P2_OK : cmp_ensure(C, W);  // plain verification never allocates the compression buffers
-    if (rc == P2_OK) rc = proof_run(C, W, op, batch, in, lengths, out, lengths_out, vd, status, host ? W->stream : st, host);
-    // the workspace may still be in use by what was enqueued before the failure: drain before handing it out again
-    if (rc != P2_OK) (void)hipStreamSynchronize(host ? W->stream : st);
-    verify_return(C, W);
+    if (rc == P2_OK) rc = proof_run(C, W, op, batch, in, lengths, out, lengths_out, vd, status, host ? (hipStream_t)W->stream : st, host);
+    lease.failed = rc != P2_OK;
     return rc;
 }
 
@@ -1672,11 +1593,10 @@ static int vanishing_flags_impl(p2_circuit* C, size_t batch, const uint8_t* buff
     for (size_t i = 0; i < batch * 4; i++)
         if (pi_hashes[i] >= gl::P) return set_error("p2_gpu_vanishing_flags: non-canonical public-inputs hash"), P2_ERR_INVALID;
     HIPCHECK(hipSetDevice(C->device));
-    VerifyWs* W = verify_lease(C);
-    if (!W) return P2_ERR_HIP;
-    const int rc = vanishing_flags_run(C, W, batch, buffers, challenges, pi_hashes, flags);
-    if (rc != P2_OK) (void)hipStreamSynchronize(W->stream);  // what was enqueued before the failure may still use the workspace
-    verify_return(C, W);
+    VerifyLease lease(C);
+    if (!lease) return P2_ERR_HIP;
+    const int rc = vanishing_flags_run(C, lease.ws.get(), batch, buffers, challenges, pi_hashes, flags);
+    lease.failed = rc != P2_OK;
     return rc;
 }
 
@@ -1686,35 +1606,25 @@ static int vanishing_flags_impl(p2_circuit* C, size_t batch, const uint8_t* buff
 // the oracles of DESIGN.md section 4.  The witness-only path launches the k_witness instantiations the prover launches and
 // does not join the prover's ev_witness chain.
 struct WitnessWs {
-    hipStream_t stream = nullptr;  // the host forms' stream
-    hipEvent_t done = nullptr;     // behind the last kernel that used the workspace
-    size_t chunk = 0, asked = 0;   // witnesses it holds; the "witness_chunk" option it was made under (chunk is that, capped by free HBM)
-    u64 *d_values = nullptr, *d_advice = nullptr;
-    u32* d_mult = nullptr;
+    size_t key = 0, chunk = 0;  // the "witness_chunk" option it was made under; the witnesses it holds (that, capped by free HBM)
+    DevBuf<u64> d_values, d_advice;
+    DevBuf<u32> d_mult;
     // the target lists as last uploaded (re-uploaded only when a call brings other ones), grown on demand
-    u32 *d_input_slots = nullptr, *d_out_slots = nullptr;
+    DevBuf<u32> d_input_slots, d_out_slots;
     std::vector<u32> h_input_slots, h_out_slots;
-    size_t cap_input_slots = 0, cap_out_slots = 0;
-    // host forms: staging of inputs, outputs and statuses (device + pinned host), grown on demand
-    u64 *d_in = nullptr, *h_in = nullptr, *d_out = nullptr, *h_out = nullptr;
-    int *d_status = nullptr, *h_status = nullptr;
-    size_t cap_in = 0, cap_out = 0, cap_status = 0;  // bytes
+    // host forms: staging of inputs, outputs and statuses, grown on demand
+    Staged<u64> in, out;
+    Staged<int> status;
     // p2_witness_explain
-    u64* d_ex_in = nullptr;
-    u32* d_prev = nullptr;
-    size_t cap_ex_in = 0, cap_prev = 0;
-    unsigned long long* d_keys = nullptr;  // the two reduction keys, then the run's status word
-    p2_witness_fault *d_fault = nullptr, *h_fault = nullptr;
-    void release() {
-        for (void* p : {(void*)d_values, (void*)d_advice, (void*)d_mult, (void*)d_input_slots, (void*)d_out_slots, (void*)d_in, (void*)d_out, (void*)d_status,
-                        (void*)d_ex_in, (void*)d_prev, (void*)d_keys, (void*)d_fault})
-            if (p) (void)hipFree(p);
-        for (void* p : {(void*)h_in, (void*)h_out, (void*)h_status, (void*)h_fault})
-            if (p) (void)hipHostFree(p);
-        if (stream) (void)hipStreamDestroy(stream);
-        if (done) (void)hipEventDestroy(done);
-        *this = WitnessWs();
-    }
+    DevBuf<u64> d_ex_in;
+    DevBuf<u32> d_prev;
+    DevBuf<unsigned long long> d_keys;  // the two reduction keys, then the run's status word
+    DevBuf<p2_witness_fault> d_fault;
+    PinBuf<p2_witness_fault> h_fault;  // and the status word behind it
+    Stream stream;                     // the host forms' stream
+    Event done;                        // behind the last kernel that used the workspace
+    void drain(bool has_caller, void* caller) { ws_drain(stream, has_caller, caller); }
+    ~WitnessWs() { if (done) (void)hipEventSynchronize(done); }
 };
 // the tables of the fault check on the device (witness_check.h), uploaded by the first p2_witness_explain of a handle: the
 // ops in blob order are as large as the scheduled copy, so a handle that never explains does not carry them
@@ -1725,74 +1635,26 @@ struct ExplainTables {
     u64* d_slot_target = nullptr;
     u32 n_free = 0;
 };
-static void witness_release_all(p2_circuit* C) {
-    for (WitnessWs* W : C->wit_free) {
-        W->release();
-        delete W;
-    }
-    C->wit_free.clear();
-    delete C->explain;
-    C->explain = nullptr;
-}
 // device bytes one witness takes in a WitnessWs
 static size_t witness_ws_bytes(const p2_circuit* C) {
     return 8 * (size_t)C->c.num_slots + 4 * std::max<size_t>(C->total_lut_entries, 1) + 8 * 55 * std::max<size_t>(C->c.poseidon_rows.size(), 1);
 }
-template <class T>
-static bool grow_dev(T** d, size_t* cap, size_t count) {
-    if (*cap >= count) return true;
-    if (*d) (void)hipFree(*d);
-    *d = nullptr, *cap = 0;
-    const size_t want = count + count / 4;
-    if (hipMalloc((void**)d, want * sizeof(T)) != hipSuccess) return false;
-    *cap = want;
-    return true;
-}
-static WitnessWs* witness_lease(p2_circuit* C) {
-    WitnessWs* W = nullptr;
-    std::vector<WitnessWs*> stale;  // made before the "witness_chunk" option changed
-    size_t chunk;
-    {
-        std::lock_guard<std::mutex> lock(C->wit_mu);
-        chunk = C->wit_chunk;
-        while (!C->wit_free.empty() && !W) {
-            W = C->wit_free.back();
-            C->wit_free.pop_back();
-            if (W->asked != chunk) {
-                stale.push_back(W);
-                W = nullptr;
-            }
-        }
-    }
-    for (WitnessWs* S : stale) {
-        (void)hipEventSynchronize(S->done);
-        S->release();
-        delete S;
-    }
-    if (W) return W;
+static std::unique_ptr<WitnessWs> witness_make(const p2_circuit* C, size_t chunk) {
+    auto W = std::make_unique<WitnessWs>();
+    W->key = chunk;
     // the same cap as the prover's: a workspace takes at most 80 % of the HBM that is free
-    const size_t per = witness_ws_bytes(C);
     size_t free_b = 0, total_b = 0;
-    W = new WitnessWs();
-    W->asked = chunk;
-    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) chunk = std::max<size_t>(1, std::min(chunk, (size_t)(0.8 * (double)free_b) / per));
+    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) chunk = std::max<size_t>(1, std::min(chunk, (size_t)(0.8 * (double)free_b) / witness_ws_bytes(C)));
     W->chunk = chunk;
-    const bool ok = hipStreamCreateWithFlags(&W->stream, hipStreamNonBlocking) == hipSuccess && hipEventCreateWithFlags(&W->done, hipEventDisableTiming) == hipSuccess &&
-                    hipMalloc((void**)&W->d_values, chunk * 8 * (size_t)C->c.num_slots) == hipSuccess &&
-                    hipMalloc((void**)&W->d_mult, chunk * 4 * std::max<size_t>(C->total_lut_entries, 1)) == hipSuccess &&
-                    hipMalloc((void**)&W->d_advice, chunk * 8 * 55 * std::max<size_t>(C->c.poseidon_rows.size(), 1)) == hipSuccess;
-    if (!ok) {
-        set_error("witness workspace could not be allocated");
-        W->release();
-        delete W;
-        return nullptr;
-    }
+    const bool ok = W->stream.create(hipStreamNonBlocking) == hipSuccess && W->done.create(hipEventDisableTiming) == hipSuccess &&
+                    W->d_values.alloc(chunk * (size_t)C->c.num_slots) == hipSuccess && W->d_mult.alloc(chunk * std::max<size_t>(C->total_lut_entries, 1)) == hipSuccess &&
+                    W->d_advice.alloc(chunk * 55 * std::max<size_t>(C->c.poseidon_rows.size(), 1)) == hipSuccess;
+    if (!ok) return set_error("witness workspace could not be allocated"), nullptr;
     return W;
 }
-static void witness_return(p2_circuit* C, WitnessWs* W) {
-    std::lock_guard<std::mutex> lock(C->wit_mu);
-    C->wit_free.push_back(W);
-}
+struct WitnessLease : Lease<WitnessWs> {
+    explicit WitnessLease(p2_circuit* C) : Lease(C->wit, [C](size_t chunk) { return witness_make(C, chunk); }) {}
+};
 // targets -> slots; `what` names the list in the error ("input" / "output")
 static int target_slots(const p2_circuit* C, const p2_target* targets, size_t n, const char* what, std::vector<u32>& slots) {
     slots.resize(n);
@@ -1805,11 +1667,11 @@ static int target_slots(const p2_circuit* C, const p2_target* targets, size_t n,
 }
 // A slot list of a workspace: uploaded only when it differs from the one the workspace holds, and then behind everything that
 // still reads the old one.
-static int witness_put_slots(WitnessWs* W, u32** d, size_t* cap, std::vector<u32>& held, const std::vector<u32>& slots) {
-    if (held == slots && *d) return P2_OK;
+static int witness_put_slots(WitnessWs* W, DevBuf<u32>& d, std::vector<u32>& held, const std::vector<u32>& slots) {
+    if (held == slots && d) return P2_OK;
     HIPCHECK(hipEventSynchronize(W->done));
-    if (!grow_dev(d, cap, std::max<size_t>(slots.size(), 1))) return set_error("witness workspace could not be allocated"), P2_ERR_HIP;
-    if (!slots.empty()) HIPCHECK(hipMemcpy(*d, slots.data(), slots.size() * 4, hipMemcpyHostToDevice));
+    if (!d.grow(std::max<size_t>(slots.size(), 1))) return set_error("witness workspace could not be allocated"), P2_ERR_HIP;
+    if (!slots.empty()) HIPCHECK(hipMemcpy(d, slots.data(), slots.size() * 4, hipMemcpyHostToDevice));
     held = slots;
     return P2_OK;
 }
@@ -1850,22 +1712,6 @@ static int witness_run(p2_circuit* C, WitnessWs* W, size_t batch, u32 n_inputs, 
     HIPCHECK(hipEventRecord(W->done, st));
     return P2_OK;
 }
-// RAII lease: the workspace goes back on every way out; after a failure whatever was enqueued is drained first
-struct WitnessLease {
-    p2_circuit* C;
-    WitnessWs* W;
-    hipStream_t drain = nullptr;  // the caller's stream of a device form (NULL = the default stream)
-    bool failed = true;
-    explicit WitnessLease(p2_circuit* c) : C(c), W(witness_lease(c)) {}
-    ~WitnessLease() {
-        if (!W) return;
-        if (failed) {
-            (void)hipStreamSynchronize(drain);
-            (void)hipStreamSynchronize(W->stream);
-        }
-        witness_return(C, W);
-    }
-};
 static int witness_null_handle(const char* name) {
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return set_error("no HIP device available: witness generation on a handle has no CPU fallback"), P2_ERR_NO_DEVICE;
@@ -1882,11 +1728,11 @@ static int witness_batch_device_impl(p2_circuit* C, size_t batch, const p2_targe
     if (batch == 0) return P2_OK;
     HIPCHECK(hipSetDevice(C->device));
     WitnessLease lease(C);
-    WitnessWs* W = lease.W;
+    WitnessWs* W = lease.ws.get();
     if (!W) return P2_ERR_HIP;
-    lease.drain = (hipStream_t)stream;
-    if (int rc = witness_put_slots(W, &W->d_input_slots, &W->cap_input_slots, W->h_input_slots, in_slots)) return rc;
-    if (int rc = witness_put_slots(W, &W->d_out_slots, &W->cap_out_slots, W->h_out_slots, out_slots)) return rc;
+    lease.on_stream(stream);
+    if (int rc = witness_put_slots(W, W->d_input_slots, W->h_input_slots, in_slots)) return rc;
+    if (int rc = witness_put_slots(W, W->d_out_slots, W->h_out_slots, out_slots)) return rc;
     if (int rc = witness_run(C, W, batch, (u32)n_targets, d_values, (u32)n_out, d_out, d_status, (hipStream_t)stream)) return rc;
     lease.failed = false;
     return P2_OK;
@@ -1959,39 +1805,36 @@ static int witness_batch_impl(p2_circuit* C, size_t batch, const p2_assignment* 
     if (int rc = target_slots(C, pk.targets, pk.nt, "input", in_slots)) return rc;
     HIPCHECK(hipSetDevice(C->device));
     WitnessLease lease(C);
-    WitnessWs* W = lease.W;
+    WitnessWs* W = lease.ws.get();
     if (!W) return P2_ERR_HIP;
     const size_t nvals = pk.nvals(batch), nouts = batch * std::max<size_t>(n_out, 1);
     HIPCHECK(hipEventSynchronize(W->done));  // the staging buffers may be replaced below
-    if (!Staging::grow(&W->d_in, &W->h_in, &W->cap_in, nvals * 8) || !Staging::grow(&W->d_out, &W->h_out, &W->cap_out, nouts * 8) ||
-        !Staging::grow(&W->d_status, &W->h_status, &W->cap_status, batch * sizeof(int)))
+    if (!W->in.grow(nvals * 8) || !W->out.grow(nouts * 8) || !W->status.grow(batch * sizeof(int)))
         return set_error("staging buffers for p2_witness_batch could not be allocated"), P2_ERR_HIP;
-    pk.fill(batch, inputs, W->h_in, false);
-    if (int rc = witness_put_slots(W, &W->d_input_slots, &W->cap_input_slots, W->h_input_slots, in_slots)) return rc;
-    if (int rc = witness_put_slots(W, &W->d_out_slots, &W->cap_out_slots, W->h_out_slots, out_slots)) return rc;
-    HIPCHECK(hipMemcpyAsync(W->d_in, W->h_in, nvals * 8, hipMemcpyHostToDevice, W->stream));
-    if (int rc = witness_run(C, W, batch, (u32)pk.nt, W->d_in, (u32)n_out, W->d_out, W->d_status, W->stream)) return rc;
-    if (n_out) HIPCHECK(hipMemcpyAsync(W->h_out, W->d_out, batch * n_out * 8, hipMemcpyDeviceToHost, W->stream));
-    HIPCHECK(hipMemcpyAsync(W->h_status, W->d_status, batch * sizeof(int), hipMemcpyDeviceToHost, W->stream));
+    pk.fill(batch, inputs, W->in.h, false);
+    if (int rc = witness_put_slots(W, W->d_input_slots, W->h_input_slots, in_slots)) return rc;
+    if (int rc = witness_put_slots(W, W->d_out_slots, W->h_out_slots, out_slots)) return rc;
+    HIPCHECK(hipMemcpyAsync(W->in.d, W->in.h, nvals * 8, hipMemcpyHostToDevice, W->stream));
+    if (int rc = witness_run(C, W, batch, (u32)pk.nt, W->in.d, (u32)n_out, W->out.d, W->status.d, W->stream)) return rc;
+    if (n_out) HIPCHECK(hipMemcpyAsync(W->out.h, W->out.d, batch * n_out * 8, hipMemcpyDeviceToHost, W->stream));
+    HIPCHECK(hipMemcpyAsync(W->status.h, W->status.d, batch * sizeof(int), hipMemcpyDeviceToHost, W->stream));
     HIPCHECK(hipStreamSynchronize(W->stream));
-    if (n_out) memcpy(out_values, W->h_out, batch * n_out * 8);
-    for (size_t i = 0; i < batch; i++) status[i] = pk.host_status[i] ? pk.host_status[i] : W->h_status[i];
+    if (n_out) memcpy(out_values, W->out.h, batch * n_out * 8);
+    for (size_t i = 0; i < batch; i++) status[i] = pk.host_status[i] ? pk.host_status[i] : W->status.h[i];
     lease.failed = false;
     return P2_OK;
 }
 
 static int explain_tables(p2_circuit* C) {
-    std::lock_guard<std::mutex> lock(C->wit_mu);
+    std::lock_guard<std::mutex> lock(C->explain_mu);
     if (C->explain) return P2_OK;
     const WitnessTables T = witness_tables(C->c, false);
-    ExplainTables* E = new ExplainTables();
+    auto E = std::make_unique<ExplainTables>();
     E->n_free = (u32)T.free_slots.size();
     if (upload(E->mem, &E->d_ops, C->c.ops.data(), C->c.ops.size()) || upload(E->mem, &E->d_free_slots, T.free_slots.data(), T.free_slots.size()) ||
-        upload(E->mem, &E->d_slot_row, T.slot_row.data(), T.slot_row.size()) || upload(E->mem, &E->d_slot_target, T.slot_target.data(), T.slot_target.size())) {
-        delete E;
+        upload(E->mem, &E->d_slot_row, T.slot_row.data(), T.slot_row.size()) || upload(E->mem, &E->d_slot_target, T.slot_target.data(), T.slot_target.size()))
         return P2_ERR_HIP;
-    }
-    C->explain = E;
+    C->explain = std::move(E);
     return P2_OK;
 }
 static int witness_explain_impl(p2_circuit* C, const p2_assignment* input, int* status, p2_witness_fault* out) {
@@ -2003,7 +1846,7 @@ static int witness_explain_impl(p2_circuit* C, const p2_assignment* input, int* 
     if (int rc = explain_tables(C)) return rc;
     const ExplainTables& E = *C->explain;
     WitnessLease lease(C);
-    WitnessWs* W = lease.W;
+    WitnessWs* W = lease.ws.get();
     if (!W) return P2_ERR_HIP;
     const u32 ni = (u32)input->count;
     const std::vector<u32> prev = input_prev_links(in_slots, C->c.num_slots);
@@ -2011,13 +1854,11 @@ static int witness_explain_impl(p2_circuit* C, const p2_assignment* input, int* 
     for (u32 i = 0; i < ni; i++)
         if (input->values[i] >= gl::P) force_status = 1;
     HIPCHECK(hipEventSynchronize(W->done));
-    if (!grow_dev(&W->d_ex_in, &W->cap_ex_in, std::max<size_t>(ni, 1))) return set_error("witness workspace could not be allocated"), P2_ERR_HIP;
-    if (!grow_dev(&W->d_prev, &W->cap_prev, std::max<size_t>(ni, 1))) return set_error("witness workspace could not be allocated"), P2_ERR_HIP;
-    if (!W->d_keys && (hipMalloc((void**)&W->d_keys, 24) != hipSuccess || hipMalloc((void**)&W->d_fault, sizeof(p2_witness_fault)) != hipSuccess ||
-                       hipHostMalloc((void**)&W->h_fault, sizeof(p2_witness_fault) + sizeof(int), hipHostMallocDefault) != hipSuccess))
+    if (!W->d_ex_in.grow(std::max<size_t>(ni, 1)) || !W->d_prev.grow(std::max<size_t>(ni, 1))) return set_error("witness workspace could not be allocated"), P2_ERR_HIP;
+    if (!W->d_keys && (W->d_keys.alloc(3) != hipSuccess || W->d_fault.alloc(1) != hipSuccess || W->h_fault.alloc_bytes(sizeof(p2_witness_fault) + sizeof(int)) != hipSuccess))
         return set_error("witness workspace could not be allocated"), P2_ERR_HIP;
     int* d_status = (int*)(W->d_keys + 2);
-    if (int rc = witness_put_slots(W, &W->d_input_slots, &W->cap_input_slots, W->h_input_slots, in_slots)) return rc;
+    if (int rc = witness_put_slots(W, W->d_input_slots, W->h_input_slots, in_slots)) return rc;
     hipStream_t st = W->stream;
     if (ni) {
         HIPCHECK(hipMemcpy(W->d_ex_in, input->values, (size_t)ni * 8, hipMemcpyHostToDevice));
@@ -2124,7 +1965,6 @@ int p2_gpu_device_count(void) {
 }
 
 p2_circuit* p2_circuit_load(const uint8_t* blob, size_t len, int device) {
-    p2_circuit* C = nullptr;
     try {
         int ndev = 0;
         if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
@@ -2135,7 +1975,8 @@ p2_circuit* p2_circuit_load(const uint8_t* blob, size_t len, int device) {
             set_error("device index out of range");
             return nullptr;
         }
-        C = new p2_circuit();
+        std::unique_ptr<p2_circuit, void (*)(p2_circuit*)> owner(new p2_circuit(), p2_circuit_free);  // until the load has succeeded
+        p2_circuit* C = owner.get();
         C->c = deserialize(blob, len);
         const Circuit& c = C->c;
         if (c.cfg.rate_bits != 3 || c.cfg.num_challenges != 2 || c.cfg.quotient_degree_factor != 8 || c.cfg.num_routed_wires != 80 || c.cfg.arity_bits != 4 ||
@@ -2157,13 +1998,13 @@ p2_circuit* p2_circuit_load(const uint8_t* blob, size_t len, int device) {
         if (const char* e = getenv("P2AES_STREAMS")) C->opt_streams = (size_t)std::min(8, std::max(1, atoi(e)));
         if (const char* e = getenv("P2AES_WITNESS_FUSE")) C->opt_witness_fuse = (u32)std::min(1024, std::max(1, atoi(e)));
         C->opt_debug_timing = getenv("P2AES_DEBUG_TIMING") != nullptr;
-        if (const char* e = getenv("P2AES_WITNESS_CHUNK")) C->wit_chunk = (size_t)std::min(4096, std::max(1, atoi(e)));
+        if (const char* e = getenv("P2AES_WITNESS_CHUNK")) C->wit.set_key((size_t)std::min(4096, std::max(1, atoi(e))));
         if (const char* e = getenv("P2AES_TEST_FAIL_ALLOC_AFTER")) C->fail_alloc_after = atol(e);
         C->layout = make_proof_layout(c);
         C->pbytes = C->layout.bytes;
         if (hipSetDevice(device) != hipSuccess) throw std::runtime_error("hipSetDevice failed");
-        if (hipStreamCreate(&C->setup.stream) != hipSuccess) throw std::runtime_error("hipStreamCreate failed");
-        if (hipEventCreateWithFlags(&C->ev_witness, hipEventDisableTiming) != hipSuccess) throw std::runtime_error("hipEventCreate failed");
+        if (C->setup.open(hipStreamDefault) != hipSuccess) throw std::runtime_error("hipStreamCreate failed");
+        if (C->ev_witness.create(hipEventDisableTiming) != hipSuccess) throw std::runtime_error("hipEventCreate failed");
         if (raise_ntt_lds_limits() != hipSuccess) throw std::runtime_error("cannot raise the dynamic LDS limit for the NTT kernels");
         // opening maps: the evaluation slots in observed and in serialised order
         const std::vector<u32> obs = C->layout.set.slots_in(true), ser = C->layout.set.slots_in(false);
@@ -2174,30 +2015,22 @@ p2_circuit* p2_circuit_load(const uint8_t* blob, size_t len, int device) {
         if (upload(C->allocs, &C->d_map_obs, obs.data(), obs.size()) || upload(C->allocs, &C->d_map_ser, ser.data(), ser.size())) throw std::runtime_error(g_last_error);
         if (circuit_setup(C)) throw std::runtime_error(g_last_error);
         if (verify_setup(C) || cmp_setup(C)) throw std::runtime_error(g_last_error);
-        return C;
+        return owner.release();
     } catch (std::exception& e) {
-        set_error(e.what());
-        if (C) p2_circuit_free(C);
-        return nullptr;
+        return set_error(e.what()), nullptr;
     }
 }
+p2_circuit::p2_circuit() = default;
+p2_circuit::~p2_circuit() {
+    if (setup.stream) (void)hipStreamSynchronize(setup.stream);
+    release_workspaces(this);
+}
+size_t p2_debug_live_resources(void) { return g_live_resources.load(); }
 
 void p2_circuit_free(p2_circuit* C) {
     if (!C) return;
     (void)hipSetDevice(C->device);
     (void)hipDeviceSynchronize();
-    release_workspaces(C);
-    for (Staging* S : C->staging_free) {
-        S->release();
-        delete S;
-    }
-    for (VerifyWs* W : C->vfy_free) {
-        W->release();
-        delete W;
-    }
-    witness_release_all(C);
-    if (C->setup.stream) (void)hipStreamDestroy(C->setup.stream);
-    if (C->ev_witness) (void)hipEventDestroy(C->ev_witness);
     delete C;
 }
 
@@ -2278,16 +2111,10 @@ static int prove_batch_device_impl(p2_circuit* C, size_t batch, const p2_target*
     // inputs) and the caller's stream then waits for the proofs.  NULL means the legacy default stream, which is
     // ordered the same way (an event recorded on stream 0) -- no device-wide synchronisation, so consecutive calls
     // pipeline into each other.
-    struct EventGuard {
-        hipEvent_t e = nullptr;
-        ~EventGuard() {
-            if (e) (void)hipEventDestroy(e);
-        }
-    } ev_guard;
-    HIPCHECK(hipEventCreateWithFlags(&ev_guard.e, hipEventDisableTiming));
-    hipEvent_t ev_in = ev_guard.e;
+    Event ev_in;
+    HIPCHECK_AS("hipEventCreateWithFlags(&ev_guard.e, hipEventDisableTiming)", ev_in.create(hipEventDisableTiming));
     HIPCHECK(hipEventRecord(ev_in, caller));
-    for (Workspace* W : C->ws) HIPCHECK(hipStreamWaitEvent(W->lane.stream, ev_in, 0));
+    for (auto& W : C->ws) HIPCHECK(hipStreamWaitEvent(W->lane.stream, ev_in, 0));
     // the blinding counter advances before anything is enqueued: a batch that fails half-way must not leave its proof
     // indices to be used again under the same key
     const u64 proof_base0 = C->zk_counter;
@@ -2303,7 +2130,7 @@ static int prove_batch_device_impl(p2_circuit* C, size_t batch, const p2_target*
         }
         if (n_out && (W.h_out_slots != out_slots || !W.d_out_slots)) {  // likewise the out-target list
             HIPCHECK(hipStreamSynchronize(W.lane.stream));
-            if (!grow_dev(&W.d_out_slots, &W.cap_out_slots, n_out)) return set_error("out-target list could not be allocated"), P2_ERR_HIP;
+            if (!W.d_out_slots.grow(n_out)) return set_error("out-target list could not be allocated"), P2_ERR_HIP;
             HIPCHECK(hipMemcpy(W.d_out_slots, out_slots.data(), n_out * 4, hipMemcpyHostToDevice));
             W.h_out_slots = out_slots;
         }
@@ -2311,7 +2138,7 @@ static int prove_batch_device_impl(p2_circuit* C, size_t batch, const p2_target*
                              d_status + done, proof_base0 + done);
         if (rc) return rc;
     }
-    for (Workspace* W : C->ws) {
+    for (auto& W : C->ws) {
         HIPCHECK(hipEventRecord(W->done, W->lane.stream));
         HIPCHECK(hipStreamWaitEvent(caller, W->done, 0));
     }
@@ -2340,7 +2167,7 @@ int p2_circuit_synchronize(p2_circuit* C) {
     std::lock_guard<std::mutex> lock(C->mu);
     HIPCHECK(hipSetDevice(C->device));
     HIPCHECK(hipStreamSynchronize(C->setup.stream));
-    for (Workspace* W : C->ws) HIPCHECK(hipStreamSynchronize(W->lane.stream));
+    for (auto& W : C->ws) HIPCHECK(hipStreamSynchronize(W->lane.stream));
     if (C->timing_on) collect_timing(C);
     return P2_OK;
 }
@@ -2358,33 +2185,36 @@ static int prove_batch_impl(p2_circuit* C, size_t batch, const p2_assignment* in
     PackedInputs pk;  // the layout of the batch on one target list, and the witnesses the host rejects
     pk.plan(batch, inputs);
     const size_t nt = pk.nt, nvals = pk.nvals(batch);
-    StagingLease lease(C);
-    Staging* S = lease.get(nvals * 8, batch * C->pbytes, batch, batch * n_out * 8);
-    if (!S) return P2_ERR_HIP;
+    Lease<Staging, NoKey> S(C->staging, [](NoKey) { return std::make_unique<Staging>(); });
+    if (!S->fit(nvals * 8, batch * C->pbytes, batch, batch * n_out * 8)) {
+        S.ws.reset();  // dropped, not returned to the pool
+        return set_error("staging buffers for p2_prove_batch could not be allocated"), P2_ERR_HIP;
+    }
     const auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     const bool dbg = C->opt_debug_timing;
     double t_a = now();
-    pk.fill(batch, inputs, S->h_vals, true);  // pinned: the values are laid out straight into the buffer the DMA engine reads
+    pk.fill(batch, inputs, S->vals.h, true);  // pinned: the values are laid out straight into the buffer the DMA engine reads
     double t_b = now();
     // one stream carries upload -> prove -> download; p2_prove_batch_device orders the proving streams with it
-    HIPCHECK(hipMemcpyAsync(S->d_vals, S->h_vals, nvals * 8, hipMemcpyHostToDevice, S->stream));
-    int rc = p2_prove_batch_outputs_device(C, batch, pk.targets, nt, S->d_vals, out_targets, n_out, S->d_out, S->d_proofs, S->d_stat, (void*)S->stream);
-    if (rc != P2_OK) return rc;  // (the lease drains S->stream on every way out)
-    HIPCHECK(hipMemcpyAsync(S->h_proofs, S->d_proofs, batch * C->pbytes, hipMemcpyDeviceToHost, S->stream));
-    HIPCHECK(hipMemcpyAsync(S->h_stat, S->d_stat, batch * sizeof(int), hipMemcpyDeviceToHost, S->stream));
-    if (n_out) HIPCHECK(hipMemcpyAsync(S->h_out, S->d_out, batch * n_out * 8, hipMemcpyDeviceToHost, S->stream));
+    HIPCHECK(hipMemcpyAsync(S->vals.d, S->vals.h, nvals * 8, hipMemcpyHostToDevice, S->stream));
+    int rc = p2_prove_batch_outputs_device(C, batch, pk.targets, nt, S->vals.d, out_targets, n_out, S->out.d, S->proofs.d, S->stat.d, (void*)S->stream);
+    if (rc != P2_OK) return rc;  // (the lease drains S->stream)
+    HIPCHECK(hipMemcpyAsync(S->proofs.h, S->proofs.d, batch * C->pbytes, hipMemcpyDeviceToHost, S->stream));
+    HIPCHECK(hipMemcpyAsync(S->stat.h, S->stat.d, batch * sizeof(int), hipMemcpyDeviceToHost, S->stream));
+    if (n_out) HIPCHECK(hipMemcpyAsync(S->out.h, S->out.d, batch * n_out * 8, hipMemcpyDeviceToHost, S->stream));
     double t_c = now();
     HIPCHECK(hipStreamSynchronize(S->stream));
     double t_d = now();
-    memcpy(proofs, S->h_proofs, batch * C->pbytes);
-    memcpy(status, S->h_stat, batch * sizeof(int));
-    if (n_out) memcpy(out_values, S->h_out, batch * n_out * 8);
+    memcpy(proofs, S->proofs.h, batch * C->pbytes);
+    memcpy(status, S->stat.h, batch * sizeof(int));
+    if (n_out) memcpy(out_values, S->out.h, batch * n_out * 8);
     for (size_t i = 0; i < batch; i++)
         if (pk.host_status[i]) {
             status[i] = pk.host_status[i];
             memset(proofs + i * C->pbytes, 0, C->pbytes);
             std::fill(out_values + i * n_out, out_values + (i + 1) * n_out, P2_VALUE_UNSET);  // what ran was not this witness
         }
+    S.failed = false;
     if (dbg) fprintf(stderr, "[p2aes] pack %.3f enqueue %.3f wait %.3f unpack %.3f s\n", t_b - t_a, t_c - t_b, t_d - t_c, now() - t_d);
     return P2_OK;
 }
@@ -2441,12 +2271,10 @@ int p2_circuit_set_option(p2_circuit* C, const char* name, long value) {
         C->opt_debug_timing = value != 0;
     } else if (k == "verify_chunk") {
         if (value < 1 || value > 4096) return set_error("option verify_chunk: 1..4096 proofs"), P2_ERR_INVALID;
-        std::lock_guard<std::mutex> vlock(C->vfy_mu);
-        C->vfy_chunk = (size_t)value;
+        C->vfy.set_key((size_t)value);
     } else if (k == "witness_chunk") {
         if (value < 1 || value > 4096) return set_error("option witness_chunk: 1..4096 witnesses"), P2_ERR_INVALID;
-        std::lock_guard<std::mutex> wlock(C->wit_mu);
-        C->wit_chunk = (size_t)value;
+        C->wit.set_key((size_t)value);
     } else {
         return set_error("unknown option (known: chunk, streams, debug_timing, verify_chunk, witness_chunk)"), P2_ERR_INVALID;
     }
@@ -2456,7 +2284,7 @@ int p2_circuit_set_option(p2_circuit* C, const char* name, long value) {
 int p2_circuit_set_timing(p2_circuit* C, int enable) {
     std::lock_guard<std::mutex> lock(C->mu);
     C->timing_on = C->setup.timing = enable != 0;
-    for (Workspace* W : C->ws) W->lane.timing = C->timing_on;
+    for (auto& W : C->ws) W->lane.timing = C->timing_on;
     C->times.clear();
     return P2_OK;
 }
@@ -2482,7 +2310,7 @@ int p2_circuit_debug_read(p2_circuit* C, const char* name_c, size_t index, uint6
     const Circuit& c = C->c;
     std::string name(name_c);
     // `index` addresses proof (index % chunk) of the workspace that handled chunk (index / chunk) of the last call
-    Workspace* W = C->ws.empty() ? nullptr : C->ws[(index / C->chunk) % C->ws.size()];
+    Workspace* W = C->ws.empty() ? nullptr : C->ws[(index / C->chunk) % C->ws.size()].get();
     if (W) index %= C->chunk;
     const size_t n = C->n, N = C->N;
     const u64* src = nullptr;
@@ -2973,23 +2801,20 @@ int p2_gpu_hash_fri_leaves(const uint64_t* vals, size_t len, int arity, size_t b
 }
 // What the NTT / Merkle primitives need of a handle: a lane, the transform tables of one size and the allocations behind them.
 struct PrimCtx {
+    Allocs mem;  // declared first: freed after the lane's stream has gone
     Lane lane;
     Domain dom;
-    Allocs mem;
     u64* d_shift_inv_pows = nullptr;  // with_quotient: [8][n] (g w^j)^-i / n
     // the tables come from the loader's own builder (build_transform_tables); `arities` as the circuit's FRI schedule
     int init(int device, int degree_bits, const std::vector<u32>& arities = {}, bool with_quotient = false) {
         if (int rc = pick_device(device)) return rc;
         dom.logn = (u32)degree_bits;
         dom.arities = arities;
-        HIPCHECK(hipStreamCreate(&lane.stream));
+        HIPCHECK_AS("hipStreamCreate(&lane.stream)", lane.open(hipStreamDefault));
         HIPCHECK(raise_ntt_lds_limits());
         return build_transform_tables(lane, dom, mem, with_quotient ? &d_shift_inv_pows : nullptr);
     }
-    ~PrimCtx() {  // (`mem` goes after this body: nothing is still running on what it frees)
-        if (lane.stream) (void)hipStreamSynchronize(lane.stream);
-        if (lane.stream) (void)hipStreamDestroy(lane.stream);
-    }
+    ~PrimCtx() { if (lane.stream) (void)hipStreamSynchronize(lane.stream); }
 };
 int p2_gpu_intt(const uint64_t* values, size_t cols, int degree_bits, uint64_t* coeffs, int device) {
     if (degree_bits < 1 || degree_bits > 22) return set_error("degree_bits must be in 1..22"), P2_ERR_INVALID;
@@ -3087,24 +2912,21 @@ struct MerkleTreeHandle {
     int device = 0;
     u32 leaf_len = 0, cap_height = 0;
     Tree t;
-    Allocs mem;
-    Allocs scratch;              // the column-major copy of the leaves: needed until the build has run
-    Lane lane;                   // the stream of the host forms
-    hipEvent_t built = nullptr;  // recorded behind the last kernel of the build and of every update, on whichever stream ran it
+    Allocs mem;      // (the memory first: freed after the stream and the event have gone)
+    Allocs scratch;  // the column-major copy of the leaves: needed until the build has run
     // updates (mt_update): a grow-only block for keys, node versions and the sort, never freed under a running kernel, and the
     // hash counter and the bad-item flag of the last update
-    u64* upd = nullptr;
-    size_t upd_words = 0;
+    DevBuf<u64> upd;
     u64* upd_ctl = nullptr;  // [0] the counter, [1] the flag (its low word)
+    Lane lane;               // the stream of the host forms
+    Event built;             // recorded behind the last kernel of the build and of every update, on whichever stream ran it
     void drop_scratch(bool wait) {
         if (scratch.empty() || (wait ? hipEventSynchronize(built) : hipEventQuery(built)) != hipSuccess) return;
-        for (void* p : scratch) (void)hipFree(p);
         scratch.clear();
     }
     ~MerkleTreeHandle() {
-        if (built) (void)hipEventSynchronize(built), (void)hipEventDestroy(built);
-        if (lane.stream) (void)hipStreamSynchronize(lane.stream), (void)hipStreamDestroy(lane.stream);
-        if (upd) (void)hipFree(upd);
+        if (built) (void)hipEventSynchronize(built);
+        if (lane.stream) (void)hipStreamSynchronize(lane.stream);
     }
     u32 depth() const { return t.bits - cap_height; }
 };
@@ -3145,8 +2967,8 @@ static int mt_new(const u64* leaves, bool on_device, size_t num_leaves, size_t l
     HIPCHECK(hipMemGetInfo(&free_b, &total_b));
     const size_t need = 8 * T->t.stride() + 8 * words + (on_device ? 0 : 8 * words);  // digests, the column-major copy, the upload
     if (need > free_b) return set_error("the tree needs " + std::to_string(need) + " bytes of device memory, " + std::to_string(free_b) + " are free"), P2_ERR_INVALID;
-    HIPCHECK(hipStreamCreateWithFlags(&T->lane.stream, hipStreamNonBlocking));
-    HIPCHECK(hipEventCreateWithFlags(&T->built, hipEventDisableTiming));
+    HIPCHECK_AS("hipStreamCreateWithFlags(&T->lane.stream, hipStreamNonBlocking)", T->lane.open(hipStreamNonBlocking));
+    HIPCHECK_AS("hipEventCreateWithFlags(&T->built, hipEventDisableTiming)", T->built.create(hipEventDisableTiming));
     if (dalloc(T->mem, &T->t.dig, T->t.stride())) return P2_ERR_HIP;
     if (on_device) {
         if (int rc = mt_build(*T, leaves, stream)) return rc;
@@ -3221,12 +3043,9 @@ static int mt_update(MerkleTreeHandle& T, const u64* d_indices, const u64* d_lea
     const size_t sort_off = (10 * k + 31) & ~(size_t)31;  // keys A | keys B | v A | v B, then the sort's block on a 256-byte boundary
     const size_t need = sort_off + (sort_bytes + 7) / 8;
     if (!T.upd_ctl && dalloc(T.mem, &T.upd_ctl, 2)) return P2_ERR_HIP;
-    if (need > T.upd_words) {  // grow: the last update may still be reading the old block
+    if (need * 8 > T.upd.bytes()) {  // grow: the last update may still be reading the old block
         HIPCHECK(hipEventSynchronize(T.built));
-        if (T.upd) HIPCHECK(hipFree(T.upd));
-        T.upd = nullptr, T.upd_words = 0;
-        HIPCHECK(hipMalloc((void**)&T.upd, need * 8));
-        T.upd_words = need;
+        HIPCHECK_AS("hipMalloc((void**)&T.upd, need * 8)", T.upd.alloc(need));  // exactly `need` words, the old block freed first
     }
     HIPCHECK(hipStreamWaitEvent(stream, T.built, 0));
     const int rc = mt_update_launch(T, d_indices, d_leaves, k, d_sib, sib_stride, d_root, root_stride, d_status, stream, T.upd, T.upd + k, T.upd + 2 * k, T.upd + 6 * k,
