@@ -16,7 +16,8 @@
  *     aes-gcm/src/circuit_aes.rs:283, circuit_gcm.rs:779-781 (20 sites)
  *   data.verify(proof)                                                       p2_verify (host),
  *     aes-gcm/src/circuit_gcm.rs:782 (19 sites)                              p2_verify_batch (GPU, batched)
- *   native_gcm::encrypt (witness values)  aes-gcm/src/native_gcm.rs:16       p2_native_aes_gcm_encrypt
+ *   native_gcm::encrypt (witness values)  aes-gcm/src/native_gcm.rs:16       p2_native_aes_gcm_encrypt(_aad), in GPU batches
+ *                                                                            p2_aes_gcm_encrypt_batch, p2_aes_gcm_decrypt_batch
  *   MerkleTree::new / prove, verify_merkle_proof_to_cap (upstream plonky2;   p2_merkle_tree_*, p2_merkle_verify_batch,
  *     not called by the reference: committed sets for pod2-style users)      p2_builder_verify_merkle_proof_to_cap
  *
@@ -178,6 +179,11 @@ int p2_builder_set_ghash_tables(p2_builder*, int lanes);
 /* AesGcmTarget<NK,4,NR,L,TAG>::build.  Outputs: key[4*nk], nonce[12], pt[L], ct[L], tag[16]. */
 int p2_aes_gcm_build(p2_builder*, int nk, int nr, size_t L, int with_tag, p2_target* key, p2_target* nonce, p2_target* pt,
                      p2_target* ct, p2_target* tag);
+/* The same with aad_len range-checked byte targets of additional authenticated data (not in the reference, whose a = []), out in
+ * aad[aad_len] (NULL allowed for 0): hashed in front of the ciphertext, aad || 0^v || ct || 0^u || [8 aad_len]_64 || [8 L]_64.
+ * They are created after the tag targets, so aad_len = 0 is p2_aes_gcm_build target for target.  aad_len > 0 needs with_tag. */
+int p2_aes_gcm_build_aad(p2_builder*, int nk, int nr, size_t L, int with_tag, size_t aad_len, p2_target* key, p2_target* nonce,
+                         p2_target* pt, p2_target* ct, p2_target* tag, p2_target* aad);
 
 /* ------------------------------------------------------------------ Poseidon hashing / poseidon-cipher (host) */
 /* builder.hash_n_to_m_no_pad::<PoseidonHash>(inputs, m)  (poseidon-cipher/src/circuit.rs:123): PoseidonGate rows */
@@ -397,6 +403,13 @@ void p2_native_aes_encrypt_block(const uint8_t* key, int nk, int nr, const uint8
 void p2_native_gf_2_128_mul(const uint8_t* x16, const uint8_t* y16, uint8_t* out16);
 void p2_native_ghash(const uint8_t* h16, const uint8_t* x, size_t len, uint8_t* out16);
 void p2_native_gctr(const uint8_t* key, int nk, int nr, const uint8_t* icb16, const uint8_t* x, size_t len, uint8_t* y);
+/* with additional authenticated data, which the reference leaves out (its a = []): the tag is over aad || 0^v || ct || 0^u ||
+ * [8 aad_len]_64 || [8 len]_64 (SP 800-38D section 7.1); aad_len = 0 is p2_native_aes_gcm_encrypt */
+void p2_native_aes_gcm_encrypt_aad(const uint8_t* key, int nk, int nr, const uint8_t* nonce12, const uint8_t* aad, size_t aad_len, const uint8_t* pt,
+                                   size_t len, uint8_t* ct, uint8_t* tag16);
+/* authenticated decryption: 0 and the plaintext when the tag over (aad, ct) matches in all 16 bytes; 1 and pt zeroed when not */
+int p2_native_aes_gcm_decrypt(const uint8_t* key, int nk, int nr, const uint8_t* nonce12, const uint8_t* aad, size_t aad_len, const uint8_t* ct, size_t len,
+                              const uint8_t* tag16, uint8_t* pt);
 void p2_native_aes_gcm_encrypt(const uint8_t* key, int nk, int nr, const uint8_t* nonce12, const uint8_t* pt, size_t len,
                                uint8_t* ct, uint8_t* tag16);
 
@@ -775,6 +788,45 @@ int p2_poseidon_encrypt_batch_device(const uint64_t* d_ks, const uint64_t* d_non
 int p2_poseidon_decrypt_batch(const uint64_t* ks, const uint64_t* nonce, const uint64_t* ct, size_t l, size_t count, uint64_t* msg, int* status, int device);
 int p2_poseidon_decrypt_batch_device(const uint64_t* d_ks, const uint64_t* d_nonce, const uint64_t* d_ct, size_t l, size_t count, uint64_t* d_msg, int* d_status,
                                      int device, void* stream);
+
+/* ------------------------------------------------------------------ AES-GCM in GPU batches */
+/* Encryption and authenticated decryption with additional authenticated data (SP 800-38D; 96-bit nonces, 16-byte tags), the call
+ * shape of the sections above (csrc/kernels_gcm.h).  Rows are bytes and contiguous per item: key
+ * [count][4 nk], nonce [count][12], aad [count][aad_len], pt and ct [count][len], tag [count][16]; nk, len and aad_len are one value
+ * per call, and a caller with one key repeats it.  The _device forms take `row_stride` >= len, the distance in bytes between pt
+ * rows and between ct rows (the host forms pass len): with both bases and the stride multiples of 16 whole blocks move as 128
+ * bits, otherwise byte by byte.  They also take d_work, 16-byte aligned device memory of p2_aes_gcm_batch_workspace bytes that
+ * the call uses as scratch (round keys, H and its multiplier table per item); the host forms allocate it.  Limits: nk 4, 6 or 8,
+ * len <= 2^24, aad_len <= 2^16, row_stride >= len; anything else is P2_ERR_INVALID before any launch.  status[i]:
+ *   0  done
+ *   1  decrypt only, the pt row zeroed: the tag does not match
+ * There is no malformed status: every byte string is a valid input.  Outputs are p2_native_aes_gcm_encrypt_aad's and
+ * p2_native_aes_gcm_decrypt's byte for byte.
+ *   bytes_to_words_device  d_out[i stride_words + j] = d_bytes[i byte_stride + j], j < row_bytes <= stride_words: a byte row as
+ *                          the ByteTarget segment of a row of the prover's value matrix, so keys, plaintexts and computed
+ *                          ciphertexts and tags go from device memory into p2_prove_batch_device without a host round trip */
+size_t p2_aes_gcm_batch_workspace(int nk, size_t len, size_t aad_len, size_t count); /* bytes of d_work; 0 for an nk that is refused */
+int p2_aes_gcm_encrypt_batch(const uint8_t* key, int nk, const uint8_t* nonce, const uint8_t* aad, size_t aad_len, const uint8_t* pt, size_t len, size_t count,
+                             uint8_t* ct, uint8_t* tag, int* status, int device);
+int p2_aes_gcm_decrypt_batch(const uint8_t* key, int nk, const uint8_t* nonce, const uint8_t* aad, size_t aad_len, const uint8_t* ct, const uint8_t* tag,
+                             size_t len, size_t count, uint8_t* pt, int* status, int device);
+int p2_aes_gcm_encrypt_batch_device(const uint8_t* d_key, int nk, const uint8_t* d_nonce, const uint8_t* d_aad, size_t aad_len, const uint8_t* d_pt, size_t len,
+                                    size_t row_stride, size_t count, uint8_t* d_ct, uint8_t* d_tag, int* d_status, void* d_work, int device, void* stream);
+int p2_aes_gcm_decrypt_batch_device(const uint8_t* d_key, int nk, const uint8_t* d_nonce, const uint8_t* d_aad, size_t aad_len, const uint8_t* d_ct,
+                                    const uint8_t* d_tag, size_t len, size_t row_stride, size_t count, uint8_t* d_pt, int* d_status, void* d_work,
+                                    int device, void* stream);
+int p2_bytes_to_words_device(const uint8_t* d_bytes, size_t row_bytes, size_t byte_stride, size_t count, uint64_t* d_out, size_t stride_words, int device,
+                             void* stream);
+/* test entries (tests/test_gpu_gcm.py): the GHASH kernel alone with lanes = 1 (one thread per item) or 64 (one wave per item),
+ * h [count][16], x [count][16 blocks] -> out [count][16] = p2_native_ghash(h[i], x[i]); the block cipher alone, in and out
+ * [count][16], out[i] = p2_native_aes_encrypt_block(key[i], in[i]) */
+int p2_gpu_gcm_ghash(const uint8_t* h, const uint8_t* x, size_t blocks, size_t count, int lanes, uint8_t* out, int device);
+int p2_gpu_aes_encrypt_blocks(const uint8_t* key, int nk, const uint8_t* in, size_t count, uint8_t* out, int device);
+/* bench entry (tools/gpu_gcm_bench.py): encryptions of `count` items on device buffers that the call fills with random bytes
+ * (rows 16 ceil(len / 16) bytes apart, 128-bit path), one warm-up and then `repeats` runs with an event between the kernels:
+ * ns[3 r + 0 .. 2] = k_gcm_setup, k_gcm_ctr, k_gcm_ghash of run r in nanoseconds.  lanes 1 or 64 forces that GHASH kernel, 0 is
+ * the public calls' choice. */
+int p2_gpu_gcm_kernel_times(int nk, size_t len, size_t aad_len, size_t count, int lanes, size_t repeats, uint64_t* ns, int device);
 
 /* ------------------------------------------------------------------ GPU primitives (parity tests / microbench) */
 int p2_gpu_device_count(void);

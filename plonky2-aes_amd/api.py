@@ -246,6 +246,9 @@ def lib():
         "p2_native_ghash": (None, [C.c_char_p, C.c_char_p, sz, C.c_char_p]),
         "p2_native_gctr": (None, [C.c_char_p, C.c_int, C.c_int, C.c_char_p, C.c_char_p, sz, C.c_char_p]),
         "p2_native_aes_gcm_encrypt": (None, [C.c_char_p, C.c_int, C.c_int, C.c_char_p, C.c_char_p, sz, C.c_char_p, C.c_char_p]),
+        "p2_native_aes_gcm_encrypt_aad": (None, [C.c_char_p, C.c_int, C.c_int, C.c_char_p, C.c_char_p, sz, C.c_char_p, sz, C.c_char_p, C.c_char_p]),
+        "p2_native_aes_gcm_decrypt": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_char_p, C.c_char_p, sz, C.c_char_p, sz, C.c_char_p, C.c_char_p]),
+        "p2_aes_gcm_build_aad": (C.c_int, [vp, C.c_int, C.c_int, sz, C.c_int, sz, u64p, u64p, u64p, u64p, u64p, u64p]),
         "p2_blob_info": (C.c_int, [C.c_char_p, sz, C.POINTER(_Info)]),
         "p2_witness_schedule_check": (C.c_int, [C.c_char_p, sz, C.c_uint32, u32p]),
         "p2_verify": (C.c_int, [C.c_char_p, sz, u64p, sz, C.c_char_p, sz]),
@@ -354,6 +357,15 @@ def lib():
         "p2_poseidon_encrypt_batch_device": (C.c_int, [vp, vp, vp, sz, sz, vp, vp, C.c_int, vp]),
         "p2_poseidon_decrypt_batch": (C.c_int, [u64p, u64p, u64p, sz, sz, u64p, C.POINTER(C.c_int), C.c_int]),
         "p2_poseidon_decrypt_batch_device": (C.c_int, [vp, vp, vp, sz, sz, vp, vp, C.c_int, vp]),
+        "p2_aes_gcm_batch_workspace": (sz, [C.c_int, sz, sz, sz]),
+        "p2_aes_gcm_encrypt_batch": (C.c_int, [C.c_char_p, C.c_int, C.c_char_p, C.c_char_p, sz, C.c_char_p, sz, sz, C.c_char_p, C.c_char_p, C.POINTER(C.c_int), C.c_int]),
+        "p2_aes_gcm_decrypt_batch": (C.c_int, [C.c_char_p, C.c_int, C.c_char_p, C.c_char_p, sz, C.c_char_p, C.c_char_p, sz, sz, C.c_char_p, C.POINTER(C.c_int), C.c_int]),
+        "p2_aes_gcm_encrypt_batch_device": (C.c_int, [vp, C.c_int, vp, vp, sz, vp, sz, sz, sz, vp, vp, vp, vp, C.c_int, vp]),
+        "p2_aes_gcm_decrypt_batch_device": (C.c_int, [vp, C.c_int, vp, vp, sz, vp, vp, sz, sz, sz, vp, vp, vp, C.c_int, vp]),
+        "p2_bytes_to_words_device": (C.c_int, [vp, sz, sz, sz, vp, sz, C.c_int, vp]),
+        "p2_gpu_gcm_ghash": (C.c_int, [C.c_char_p, C.c_char_p, sz, sz, C.c_int, C.c_char_p, C.c_int]),
+        "p2_gpu_aes_encrypt_blocks": (C.c_int, [C.c_char_p, C.c_int, C.c_char_p, sz, C.c_char_p, C.c_int]),
+        "p2_gpu_gcm_kernel_times": (C.c_int, [C.c_int, sz, sz, sz, C.c_int, sz, u64p, C.c_int]),
     }
     missing = []
     for name, (res, args) in sig.items():
@@ -1170,21 +1182,24 @@ class CircuitData:
 
 
 class AesGcmTarget:
-    """AesGcmTarget<NK, 4, NR, L, TAG> (aes-gcm/src/circuit_gcm.rs:24-209)."""
+    """AesGcmTarget<NK, 4, NR, L, TAG> (aes-gcm/src/circuit_gcm.rs:24-209).  aad_len > 0 (not in the reference, whose a = []):
+    that many byte targets `aad` of additional authenticated data, hashed in front of the ciphertext; it needs the tag."""
 
     @staticmethod
-    def build(builder, nk=4, nr=10, L=16, tag=False):
+    def build(builder, nk=4, nr=10, L=16, tag=False, aad_len=0):
         t = AesGcmTarget()
-        t.nk, t.nr, t.L, t.TAG = nk, nr, L, tag
+        t.nk, t.nr, t.L, t.TAG, t.aad_len = nk, nr, L, tag, aad_len
         key, nonce, pt, ct, tg = (u64 * (4 * nk))(), (u64 * 12)(), (u64 * max(L, 1))(), (u64 * max(L, 1))(), (u64 * 16)()
-        if lib().p2_aes_gcm_build(builder._h, nk, nr, L, int(tag), key, nonce, pt, ct, tg):
+        aad = (u64 * max(aad_len, 1))()
+        if lib().p2_aes_gcm_build_aad(builder._h, nk, nr, L, int(tag), aad_len, key, nonce, pt, ct, tg, aad):
             raise P2Error(_err())
-        t.key, t.nonce, t.pt, t.ct, t.tag = list(key), list(nonce), list(pt)[:L], list(ct)[:L], list(tg)
+        t.key, t.nonce, t.pt, t.ct, t.tag, t.aad = list(key), list(nonce), list(pt)[:L], list(ct)[:L], list(tg), list(aad)[:aad_len]
         return t
 
-    def set_targets(self, pw, key, nonce, pt, ct, tag):
+    def set_targets(self, pw, key, nonce, pt, ct, tag, aad=b""):
         # effective contract of circuit_gcm.rs:183-193: len(pt) == len(ct) == L (copy_from_slice panics otherwise)
-        assert len(pt) == self.L and len(ct) == self.L and len(key) == 4 * self.nk and len(nonce) == 12
+        assert len(pt) == self.L and len(ct) == self.L and len(key) == 4 * self.nk and len(nonce) == 12 and len(aad) == self.aad_len
+        for t, v in zip(self.aad, aad): pw.set_byte_target(t, v)
         for t, v in zip(self.key, key): pw.set_byte_target(t, v)
         for t, v in zip(self.nonce, nonce): pw.set_byte_target(t, v)
         for t, v in zip(self.pt, pt): pw.set_byte_target(t, v)
@@ -2085,8 +2100,116 @@ class native:
         return out.raw[: len(x)]
 
     @staticmethod
-    def gcm_encrypt(key, nonce, pt):
+    def gcm_encrypt(key, nonce, pt, aad=b""):
+        """aad: additional authenticated data (SP 800-38D), which the reference leaves out; b"" is native_gcm::encrypt"""
         nk = len(key) // 4
         ct, tag = C.create_string_buffer(max(len(pt), 1)), C.create_string_buffer(16)
-        lib().p2_native_aes_gcm_encrypt(bytes(key), nk, nk + 6, bytes(nonce), bytes(pt), len(pt), ct, tag)
+        lib().p2_native_aes_gcm_encrypt_aad(bytes(key), nk, nk + 6, bytes(nonce), bytes(aad), len(aad), bytes(pt), len(pt), ct, tag)
         return ct.raw[: len(pt)], tag.raw
+
+    @staticmethod
+    def gcm_decrypt(key, nonce, ct, tag, aad=b""):
+        """-> the plaintext; P2Error when the tag over (aad, ct) does not match"""
+        nk = native._nk(key)
+        if len(nonce) != 12 or len(tag) != 16:
+            raise P2Error("gcm_decrypt: a nonce is 12 bytes, a tag 16")
+        pt = C.create_string_buffer(max(len(ct), 1))
+        if lib().p2_native_aes_gcm_decrypt(bytes(key), nk, nk + 6, bytes(nonce), bytes(aad), len(aad), bytes(ct), len(ct), bytes(tag), pt):
+            raise P2Error(_err())
+        return pt.raw[: len(ct)]
+
+    # ---- AES-GCM in GPU batches (csrc/kernels_gcm.h; DESIGN.md section 9k).  Every list is per item and holds bytes: keys of
+    # 16, 24 or 32 bytes, nonces of 12, tags of 16; within a call all keys have one length, all messages one length (at most
+    # 2^24) and all aads one length (at most 2^16; aads=None is no aad).  Statuses: 0 done, 1 (decrypt) the tag does not match
+    # and the plaintext row holds zeros.  device=None: a host loop over gcm_encrypt / gcm_decrypt's entry points.
+    DONE, REJECTED = 0, 1
+    MAX_LEN, MAX_AAD = 1 << 24, 1 << 16
+
+    @staticmethod
+    def _nk(key):
+        if len(key) not in (16, 24, 32):
+            raise P2Error("a key is 16, 24 or 32 bytes (nk is 4, 6 or 8)")
+        return len(key) // 4
+
+    @staticmethod
+    def _byte_rows(rows, what):
+        """[n] byte strings of one length -> (their concatenation, n, that length)"""
+        rows = [bytes(r) for r in rows]
+        k = len(rows[0]) if rows else 0
+        if any(len(r) != k for r in rows):
+            raise P2Error("%s must all have one length" % what)
+        return b"".join(rows), len(rows), k
+
+    @staticmethod
+    def _gcm_args(name, keys, nonces, rows, aads, tags=None):
+        """-> (key, nonce, rows, aad, tag or None, nk, len, aad_len, list lengths)"""
+        key, n, kl = native._byte_rows(keys, "keys")
+        nn, n_n, nl = native._byte_rows(nonces, "nonces")
+        data, n_r, l = native._byte_rows(rows, "messages and ciphertexts")
+        aad, n_a, al = native._byte_rows(aads if aads is not None else [b""] * n, "aads")
+        tag, n_t, tl = native._byte_rows(tags, "tags") if tags is not None else (None, n, 16)
+        counts = [n, n_n, n_r, n_a, n_t]
+        nk = native._nk(key[:kl]) if n else 4
+        if n and all(m == n for m in counts):
+            if nl != 12 or tl != 16:
+                raise P2Error("%s: nonces are 12 bytes, tags 16" % name)
+            if l > native.MAX_LEN or al > native.MAX_AAD:
+                raise P2Error("%s: a message is at most 2^24 bytes, an aad at most 2^16" % name)
+        return key, nn, data, aad, tag, nk, l, al, counts
+
+    @staticmethod
+    def gcm_batch_workspace(nk, length, aad_len, count):
+        """bytes of the d_work that the _device forms take"""
+        if nk not in (4, 6, 8):
+            raise P2Error("nk is 4, 6 or 8")
+        return lib().p2_aes_gcm_batch_workspace(nk, length, aad_len, count)
+
+    @staticmethod
+    def gcm_encrypt_batch(keys, nonces, pts, aads=None, device=0):
+        """-> (cts, tags, statuses): (cts[i], tags[i]) = gcm_encrypt(keys[i], nonces[i], pts[i], aads[i])"""
+        key, nn, pt, aad, _, nk, l, al, counts = native._gcm_args("gcm_encrypt_batch", keys, nonces, pts, aads)
+        kl = 4 * nk
+
+        def host(i, outs, status):
+            ct, tag = native.gcm_encrypt(key[kl * i:kl * (i + 1)], nn[12 * i:12 * (i + 1)], pt[l * i:l * (i + 1)], aad[al * i:al * (i + 1)])
+            outs[0][l * i:l * (i + 1)] = ct
+            outs[1][16 * i:16 * (i + 1)] = tag
+        (ct, tag), st = _batch_call("p2_aes_gcm_encrypt_batch", counts, "gcm_encrypt_batch: every list has one entry per item", [(C.c_char, l), (C.c_char, 16)], device, host,
+                                    lambda fn, n, outs, status: fn(key, nk, nn, aad, al, pt, l, n, outs[0], outs[1], status, device))
+        n = len(st)
+        ct, tag = (ct.raw, tag.raw) if n else (b"", b"")
+        return [ct[l * i:l * (i + 1)] for i in range(n)], [tag[16 * i:16 * (i + 1)] for i in range(n)], st
+
+    @staticmethod
+    def gcm_decrypt_batch(keys, nonces, cts, tags, aads=None, device=0):
+        """-> (pts, statuses): pts[i] = gcm_decrypt(keys[i], nonces[i], cts[i], tags[i], aads[i]); status 1 and zeros where it raises"""
+        key, nn, ct, aad, tag, nk, l, al, counts = native._gcm_args("gcm_decrypt_batch", keys, nonces, cts, aads, tags)
+        kl = 4 * nk
+
+        def host(i, outs, status):
+            try:
+                outs[0][l * i:l * (i + 1)] = native.gcm_decrypt(key[kl * i:kl * (i + 1)], nn[12 * i:12 * (i + 1)], ct[l * i:l * (i + 1)], tag[16 * i:16 * (i + 1)],
+                                                                aad[al * i:al * (i + 1)])
+            except P2Error:
+                status[i] = native.REJECTED
+        (pt,), st = _batch_call("p2_aes_gcm_decrypt_batch", counts, "gcm_decrypt_batch: every list has one entry per item", [(C.c_char, l)], device, host,
+                                lambda fn, n, outs, status: fn(key, nk, nn, aad, al, ct, tag, l, n, outs[0], status, device))
+        n = len(st)
+        pt = pt.raw if n else b""
+        return [pt[l * i:l * (i + 1)] for i in range(n)], st
+
+    @staticmethod
+    def gcm_encrypt_batch_device(d_key, nk, d_nonce, d_aad, aad_len, d_pt, length, row_stride, count, d_ct, d_tag, d_status, d_work, device=0, stream=None):
+        """Every buffer a raw device pointer (p2_aes_gcm_encrypt_batch_device); asynchronous on `stream`.  pt and ct rows are
+        row_stride >= length bytes apart; d_work: gcm_batch_workspace(...) bytes, 16-byte aligned."""
+        _device_call("p2_aes_gcm_encrypt_batch_device", d_key, nk, d_nonce, d_aad, aad_len, d_pt, length, row_stride, count, d_ct, d_tag, d_status, d_work, device, stream)
+
+    @staticmethod
+    def gcm_decrypt_batch_device(d_key, nk, d_nonce, d_aad, aad_len, d_ct, d_tag, length, row_stride, count, d_pt, d_status, d_work, device=0, stream=None):
+        _device_call("p2_aes_gcm_decrypt_batch_device", d_key, nk, d_nonce, d_aad, aad_len, d_ct, d_tag, length, row_stride, count, d_pt, d_status, d_work, device, stream)
+
+    @staticmethod
+    def bytes_to_words_device(d_bytes, row_bytes, byte_stride, count, d_out, stride_words, device=0, stream=None):
+        """d_out[i stride_words + j] = d_bytes[i byte_stride + j] (j < row_bytes <= stride_words): a byte row as the ByteTarget
+        segment of a row of the value matrix that prove_batch_device reads, without a host round trip"""
+        _device_call("p2_bytes_to_words_device", d_bytes, row_bytes, byte_stride, count, d_out, stride_words, device, stream)

@@ -24,18 +24,8 @@ typedef std::array<ByteTarget, 4> WordTarget;
 
 // ---------------------------------------------------------------- constants (aes-gcm/src/constants.rs)
 static const uint8_t SBOX[256] = {
-    0x63, 0x7c, 0x77, 0x7b, 0xf2, 0x6b, 0x6f, 0xc5, 0x30, 0x01, 0x67, 0x2b, 0xfe, 0xd7, 0xab, 0x76, 0xca, 0x82, 0xc9, 0x7d, 0xfa, 0x59,
-    0x47, 0xf0, 0xad, 0xd4, 0xa2, 0xaf, 0x9c, 0xa4, 0x72, 0xc0, 0xb7, 0xfd, 0x93, 0x26, 0x36, 0x3f, 0xf7, 0xcc, 0x34, 0xa5, 0xe5, 0xf1,
-    0x71, 0xd8, 0x31, 0x15, 0x04, 0xc7, 0x23, 0xc3, 0x18, 0x96, 0x05, 0x9a, 0x07, 0x12, 0x80, 0xe2, 0xeb, 0x27, 0xb2, 0x75, 0x09, 0x83,
-    0x2c, 0x1a, 0x1b, 0x6e, 0x5a, 0xa0, 0x52, 0x3b, 0xd6, 0xb3, 0x29, 0xe3, 0x2f, 0x84, 0x53, 0xd1, 0x00, 0xed, 0x20, 0xfc, 0xb1, 0x5b,
-    0x6a, 0xcb, 0xbe, 0x39, 0x4a, 0x4c, 0x58, 0xcf, 0xd0, 0xef, 0xaa, 0xfb, 0x43, 0x4d, 0x33, 0x85, 0x45, 0xf9, 0x02, 0x7f, 0x50, 0x3c,
-    0x9f, 0xa8, 0x51, 0xa3, 0x40, 0x8f, 0x92, 0x9d, 0x38, 0xf5, 0xbc, 0xb6, 0xda, 0x21, 0x10, 0xff, 0xf3, 0xd2, 0xcd, 0x0c, 0x13, 0xec,
-    0x5f, 0x97, 0x44, 0x17, 0xc4, 0xa7, 0x7e, 0x3d, 0x64, 0x5d, 0x19, 0x73, 0x60, 0x81, 0x4f, 0xdc, 0x22, 0x2a, 0x90, 0x88, 0x46, 0xee,
-    0xb8, 0x14, 0xde, 0x5e, 0x0b, 0xdb, 0xe0, 0x32, 0x3a, 0x0a, 0x49, 0x06, 0x24, 0x5c, 0xc2, 0xd3, 0xac, 0x62, 0x91, 0x95, 0xe4, 0x79,
-    0xe7, 0xc8, 0x37, 0x6d, 0x8d, 0xd5, 0x4e, 0xa9, 0x6c, 0x56, 0xf4, 0xea, 0x65, 0x7a, 0xae, 0x08, 0xba, 0x78, 0x25, 0x2e, 0x1c, 0xa6,
-    0xb4, 0xc6, 0xe8, 0xdd, 0x74, 0x1f, 0x4b, 0xbd, 0x8b, 0x8a, 0x70, 0x3e, 0xb5, 0x66, 0x48, 0x03, 0xf6, 0x0e, 0x61, 0x35, 0x57, 0xb9,
-    0x86, 0xc1, 0x1d, 0x9e, 0xe1, 0xf8, 0x98, 0x11, 0x69, 0xd9, 0x8e, 0x94, 0x9b, 0x1e, 0x87, 0xe9, 0xce, 0x55, 0x28, 0xdf, 0x8c, 0xa1,
-    0x89, 0x0d, 0xbf, 0xe6, 0x42, 0x68, 0x41, 0x99, 0x2d, 0x0f, 0xb0, 0x54, 0xbb, 0x16};
+#include "aes_sbox.inc"
+};
 static const uint8_t RCON[11] = {0x00, 0x01, 0x02, 0x04, 0x08, 0x10, 0x20, 0x40, 0x80, 0x1B, 0x36};
 static const size_t TAG_LEN = 128;
 
@@ -169,28 +159,66 @@ inline std::array<uint8_t, 16> ghash(const uint8_t* h, const uint8_t* x, size_t 
     }
     return y;
 }
-// native_gcm.rs:16-68.  Returns (ciphertext, 16-byte tag); no AAD, 96-bit nonce.
-inline void gcm_encrypt(int NK, int NR, const uint8_t* key, const uint8_t* nonce, const uint8_t* pt, size_t len, uint8_t* ct, uint8_t* tag) {
-    auto w = key_expansion(NK, NR, key);
+// The tag of (aad, c) under the expanded key w (SP 800-38D section 7.1, steps 4 to 6): GHASH_H over
+// aad || 0^v || c || 0^u || [8 aad_len]_64 || [8 len]_64, then GCTR from J0 = nonce || 0^31 || 1.
+inline std::array<uint8_t, 16> gcm_tag(int NR, const std::vector<std::array<uint8_t, 4>>& w, const uint8_t* nonce, const uint8_t* aad, size_t aad_len,
+                                       const uint8_t* c, size_t len) {
     uint8_t zero[16] = {0};
     auto h = flatten_state(encrypt_block(NR, zero, w));
     uint8_t j0[16] = {0};
     memcpy(j0, nonce, 12);
     j0[15] = 1;
-    uint8_t j0i[16];
-    memcpy(j0i, j0, 16);
-    inc32(j0i);
-    auto c = gctr(NR, w, j0i, pt, len);
-    size_t u = (16 - len % 16) % 16;
-    std::vector<uint8_t> gin(c);
-    gin.resize(len + u, 0);
-    uint64_t clen = (uint64_t)len * 8;
-    for (int i = 0; i < 8; i++) gin.push_back(0);
+    std::vector<uint8_t> gin;
+    gin.reserve(aad_len + len + 48);
+    if (aad_len) gin.insert(gin.end(), aad, aad + aad_len);
+    gin.resize((aad_len + 15) / 16 * 16, 0);
+    if (len) gin.insert(gin.end(), c, c + len);
+    gin.resize((gin.size() + 15) / 16 * 16, 0);
+    uint64_t alen = (uint64_t)aad_len * 8, clen = (uint64_t)len * 8;
+    for (int i = 7; i >= 0; i--) gin.push_back((uint8_t)(alen >> (8 * i)));
     for (int i = 7; i >= 0; i--) gin.push_back((uint8_t)(clen >> (8 * i)));
     auto s = ghash(h.data(), gin.data(), gin.size());
     auto t = gctr(NR, w, j0, s.data(), 16);
+    std::array<uint8_t, 16> tag;
+    memcpy(tag.data(), t.data(), 16);
+    return tag;
+}
+// the counter mode of the message: GCTR from inc32(J0)
+inline std::vector<uint8_t> gcm_ctr(int NR, const std::vector<std::array<uint8_t, 4>>& w, const uint8_t* nonce, const uint8_t* x, size_t len) {
+    uint8_t j0i[16] = {0};
+    memcpy(j0i, nonce, 12);
+    j0i[15] = 1;
+    inc32(j0i);
+    return gctr(NR, w, j0i, x, len);
+}
+// native_gcm.rs:16-68 with the additional authenticated data it leaves out (its a = []).  96-bit nonce, 16-byte tag.
+inline void gcm_encrypt_aad(int NK, int NR, const uint8_t* key, const uint8_t* nonce, const uint8_t* aad, size_t aad_len, const uint8_t* pt, size_t len,
+                            uint8_t* ct, uint8_t* tag) {
+    auto w = key_expansion(NK, NR, key);
+    auto c = gcm_ctr(NR, w, nonce, pt, len);
+    auto t = gcm_tag(NR, w, nonce, aad, aad_len, c.data(), len);
     if (len) memcpy(ct, c.data(), len);
     memcpy(tag, t.data(), 16);
+}
+// native_gcm.rs:16-68.  Returns (ciphertext, 16-byte tag); no AAD, 96-bit nonce.
+inline void gcm_encrypt(int NK, int NR, const uint8_t* key, const uint8_t* nonce, const uint8_t* pt, size_t len, uint8_t* ct, uint8_t* tag) {
+    gcm_encrypt_aad(NK, NR, key, nonce, nullptr, 0, pt, len, ct, tag);
+}
+// Authenticated decryption (SP 800-38D section 7.2; not in the reference): the tag over (aad, ct) is recomputed and all 16 bytes
+// compared, without an early exit; the counter mode runs only when they match.  false: pt is zeroed.
+inline bool gcm_decrypt(int NK, int NR, const uint8_t* key, const uint8_t* nonce, const uint8_t* aad, size_t aad_len, const uint8_t* ct, size_t len,
+                        const uint8_t* tag, uint8_t* pt) {
+    auto w = key_expansion(NK, NR, key);
+    auto t = gcm_tag(NR, w, nonce, aad, aad_len, ct, len);
+    uint8_t diff = 0;
+    for (int i = 0; i < 16; i++) diff |= (uint8_t)(t[i] ^ tag[i]);
+    if (diff) {
+        if (len) memset(pt, 0, len);
+        return false;
+    }
+    auto p = gcm_ctr(NR, w, nonce, ct, len);
+    if (len) memcpy(pt, p.data(), len);
+    return true;
 }
 
 // ---------------------------------------------------------------- LUT builders
@@ -589,9 +617,12 @@ struct AesGcmTarget {
     int NK, NR;
     size_t L;
     bool TAG;
-    std::vector<ByteTarget> key, nonce, pt, ct, tag;
+    std::vector<ByteTarget> key, nonce, pt, ct, tag, aad;
 
-    static AesGcmTarget build(CircuitBuilder& b, int NK, int NR, size_t L, bool TAG) {
+    // aad_len > 0 (not in the reference, whose a = []): that many range-checked byte targets of additional authenticated data,
+    // created after the tag targets so that aad_len = 0 numbers every target as before, and hashed in front of the ciphertext.
+    static AesGcmTarget build(CircuitBuilder& b, int NK, int NR, size_t L, bool TAG, size_t aad_len = 0) {
+        if (aad_len && !TAG) throw std::runtime_error("aad needs the tag");
         AesGcmTarget t;
         t.NK = NK;
         t.NR = NR;
@@ -602,6 +633,7 @@ struct AesGcmTarget {
         for (int i = 0; i < 12; i++) t.nonce.push_back(add_virtual_byte_target(b, sbox));
         for (size_t i = 0; i < L; i++) t.pt.push_back(add_virtual_byte_target(b, sbox));
         for (size_t i = 0; i < TAG_LEN / 8; i++) t.tag.push_back(add_virtual_byte_target(b, sbox));
+        for (size_t i = 0; i < aad_len; i++) t.aad.push_back(add_virtual_byte_target(b, sbox));
         StateTarget mix = state_mix_matrix(b);
         auto expanded_key = key_expansion_t(b, NK, NR, xorl, sbox, t.key);
         StateTarget es = empty_state(b);
@@ -614,11 +646,14 @@ struct AesGcmTarget {
         BlockTarget inc32_j0 = inc32_target(b, j0);
         t.ct = gctr_target(b, NR, xorl, mull, sbox, mix, expanded_key, inc32_j0, t.pt);
         if (!TAG) return t;
-        size_t u = (16 - L % 16) % 16;
-        uint64_t clen = (uint64_t)L * 8;
-        std::vector<ByteTarget> gin(t.ct);
+        size_t u = (16 - L % 16) % 16, v = (16 - aad_len % 16) % 16;
+        uint64_t clen = (uint64_t)L * 8, alen = (uint64_t)aad_len * 8;
+        std::vector<ByteTarget> gin(t.aad);
+        if (aad_len)
+            for (size_t i = 0; i < v; i++) gin.push_back(zb);
+        gin.insert(gin.end(), t.ct.begin(), t.ct.end());
         for (size_t i = 0; i < u; i++) gin.push_back(zb);
-        for (int i = 0; i < 8; i++) gin.push_back(byte_constant(b, 0));
+        for (int i = 7; i >= 0; i--) gin.push_back(byte_constant(b, (uint8_t)(alen >> (8 * i))));
         for (int i = 7; i >= 0; i--) gin.push_back(byte_constant(b, (uint8_t)(clen >> (8 * i))));
         BlockTarget s;
         if (b.ghash_tables()) {

@@ -314,9 +314,16 @@ int p2_gcm_ghash_tables(p2_builder* b, size_t xl, size_t lol, size_t hil, const 
     });
 }
 int p2_aes_gcm_build(p2_builder* b, int nk, int nr, size_t L, int with_tag, p2_target* key, p2_target* nonce, p2_target* pt, p2_target* ct, p2_target* tag) {
+    return p2_aes_gcm_build_aad(b, nk, nr, L, with_tag, 0, key, nonce, pt, ct, tag, nullptr);
+}
+int p2_aes_gcm_build_aad(p2_builder* b, int nk, int nr, size_t L, int with_tag, size_t aad_len, p2_target* key, p2_target* nonce, p2_target* pt, p2_target* ct,
+                         p2_target* tag, p2_target* aad) {
     if (!((nk == 4 && nr == 10) || (nk == 6 && nr == 12) || (nk == 8 && nr == 14))) return set_error("unsupported (NK, NR)"), P2_ERR_INVALID;
+    if (aad_len && !with_tag) return set_error("aad needs the tag"), P2_ERR_INVALID;
+    if (aad_len && !aad) return set_error("p2_aes_gcm_build_aad: null argument"), P2_ERR_INVALID;
     try {
-        auto t = aes::AesGcmTarget::build(b->b, nk, nr, L, with_tag != 0);
+        auto t = aes::AesGcmTarget::build(b->b, nk, nr, L, with_tag != 0, aad_len);
+        std::copy(t.aad.begin(), t.aad.end(), aad);
         std::copy(t.key.begin(), t.key.end(), key);
         std::copy(t.nonce.begin(), t.nonce.end(), nonce);
         std::copy(t.pt.begin(), t.pt.end(), pt);
@@ -885,6 +892,17 @@ void p2_native_gctr(const uint8_t* key, int nk, int nr, const uint8_t* icb, cons
     });
 }
 void p2_native_aes_gcm_encrypt(const uint8_t* key, int nk, int nr, const uint8_t* nonce, const uint8_t* pt, size_t len, uint8_t* ct, uint8_t* tag) { (void)guarded([&] {    aes::gcm_encrypt(nk, nr, key, nonce, pt, len, ct, tag);}); }
+void p2_native_aes_gcm_encrypt_aad(const uint8_t* key, int nk, int nr, const uint8_t* nonce, const uint8_t* aad, size_t aad_len, const uint8_t* pt, size_t len,
+                                   uint8_t* ct, uint8_t* tag) {
+    (void)guarded([&] { aes::gcm_encrypt_aad(nk, nr, key, nonce, aad, aad_len, pt, len, ct, tag); });
+}
+int p2_native_aes_gcm_decrypt(const uint8_t* key, int nk, int nr, const uint8_t* nonce, const uint8_t* aad, size_t aad_len, const uint8_t* ct, size_t len,
+                              const uint8_t* tag, uint8_t* pt) {
+    bool ok = false;
+    if (guarded([&] { ok = aes::gcm_decrypt(nk, nr, key, nonce, aad, aad_len, ct, len, tag, pt); })) return P2_ERR_INVALID;
+    if (!ok) set_error("aes-gcm decrypt: authentication failed");
+    return ok ? 0 : 1;
+}
 
 // ---- info / verify
 int p2_blob_info(const uint8_t* blob, size_t len, p2_circuit_info* out) {

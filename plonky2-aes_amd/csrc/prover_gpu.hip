@@ -25,6 +25,7 @@
 #include "kernels_merkle.h"
 #include "kernels_merkle_update.h"
 #include "kernels_elgamal.h"
+#include "kernels_gcm.h"
 #include "kernels_pcipher.h"
 #include "kernels_schnorr.h"
 #include "kernels_witness_io.h"
@@ -1899,8 +1900,10 @@ static int pick_device(int device) {
 // host buffers are staged (ins uploaded, outs allocated), the launch goes on the stream -- the null stream for host buffers --
 // and the outs are copied back in list order, so the call returns with the results in host memory.  For device buffers nothing
 // but the launch is enqueued.  The launch gets NULL for a buffer of zero elements and for an optional buffer the caller left
-// out, in both forms; every other buffer is the staged copy or the caller's device pointer.
-enum BufDir { BUF_IN, BUF_OUT, BUF_INOUT };
+// out, in both forms; every other buffer is the staged copy or the caller's device pointer.  A scratch buffer is working memory
+// of the launch, never copied: host forms pass no pointer and get an allocation for the call, device forms pass the caller's.
+// The launch may enqueue more than one kernel on the stream.
+enum BufDir { BUF_IN, BUF_OUT, BUF_INOUT, BUF_SCRATCH };
 struct Buf {
     void* p;
     size_t n, elem;  // total elements, bytes per element
@@ -1913,6 +1916,8 @@ template <class T>
 static Buf buf_out(T* p, size_t n, bool optional = false) { return {p, n, sizeof(T), BUF_OUT, optional}; }
 template <class T>
 static Buf buf_inout(T* p, size_t n) { return {p, n, sizeof(T), BUF_INOUT, false}; }
+template <class T>
+static Buf buf_scratch(T* p, size_t n) { return {p, n, sizeof(T), BUF_SCRATCH, false}; }
 struct DevPtr {  // a device pointer as the launch takes it: it converts to the kernel's parameter type
     void* p = nullptr;
     template <class T>
@@ -1931,13 +1936,13 @@ static int run_batch(const char* bad_shape, size_t count, Where w, const Buf (&b
         if (bad_shape) return set_error(bad_shape), P2_ERR_INVALID;
         if (count == 0) return (int)P2_OK;
         for (const Buf& b : bufs)
-            if (b.n && !b.p && !b.optional) return set_error("null argument"), P2_ERR_INVALID;
+            if (b.n && !b.p && !b.optional && (b.dir != BUF_SCRATCH || w.on_device)) return set_error("null argument"), P2_ERR_INVALID;
         if (int rc = pick_device(w.device)) return rc;
         Allocs tmp;
         DevPtr d[N];
         for (size_t i = 0; i < N; i++) {
             const Buf& b = bufs[i];
-            if (!b.n || !b.p) continue;
+            if (!b.n || (!b.p && b.dir != BUF_SCRATCH)) continue;
             if (w.on_device) {
                 d[i].p = b.p;
                 continue;
@@ -1945,13 +1950,13 @@ static int run_batch(const char* bad_shape, size_t count, Where w, const Buf (&b
             char* q;
             if (dalloc(tmp, &q, b.n * b.elem)) return P2_ERR_HIP;
             d[i].p = q;
-            if (b.dir != BUF_OUT) HIPCHECK(hipMemcpy(q, b.p, b.n * b.elem, hipMemcpyHostToDevice));
+            if (b.dir == BUF_IN || b.dir == BUF_INOUT) HIPCHECK(hipMemcpy(q, b.p, b.n * b.elem, hipMemcpyHostToDevice));
         }
         launch(d, w.stream);
         HIPCHECK(hipGetLastError());
         if (w.on_device) return (int)P2_OK;
         for (size_t i = 0; i < N; i++)
-            if (d[i].p && bufs[i].dir != BUF_IN) HIPCHECK(hipMemcpy(bufs[i].p, d[i].p, bufs[i].n * bufs[i].elem, hipMemcpyDeviceToHost));
+            if (d[i].p && (bufs[i].dir == BUF_OUT || bufs[i].dir == BUF_INOUT)) HIPCHECK(hipMemcpy(bufs[i].p, d[i].p, bufs[i].n * bufs[i].elem, hipMemcpyDeviceToHost));
         return (int)P2_OK;
     });
 }
@@ -3339,6 +3344,171 @@ int p2_poseidon_decrypt_batch(const uint64_t* ks, const uint64_t* nonce, const u
 int p2_poseidon_decrypt_batch_device(const uint64_t* d_ks, const uint64_t* d_nonce, const uint64_t* d_ct, size_t l, size_t count, uint64_t* d_msg, int* d_status, int device,
                                      void* stream) {
     return pcipher_run(true, d_ks, d_nonce, d_ct, l, count, d_msg, d_status, on_device(device, stream));
+}
+
+// ---- AES-GCM in batches (kernels_gcm.h; the host twins are aes::gcm_encrypt_aad and aes::gcm_decrypt).  Encryption and
+// decryption share one call shape: key, nonce and aad rows, one input row and one output row per item `stride` bytes apart, and
+// the tag, which encryption writes and decryption reads.  Three launches over the scratch workspace: setup, then counter mode and
+// GHASH in the order the direction needs.
+static const size_t GCM_MAX_LEN = (size_t)1 << 24, GCM_MAX_AAD = (size_t)1 << 16;
+// From this many GHASH blocks per item the one-wave-per-item kernel runs, below it the one-thread-per-item kernel: the smallest
+// measured block count from which the wide form is faster (profiles/gcm_bench.jsonl).
+static const size_t GCM_WIDE_MIN_BLOCKS = 128;
+static bool gcm_nk_ok(int nk) { return nk == 4 || nk == 6 || nk == 8; }
+static bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+static void gcm_ghash_launch(int lanes, hipStream_t s, const u32* ws, int nk, const GhashIn& in, size_t count, const uint8_t* given, uint8_t* out, int* status) {
+    if (lanes == 64)
+        hipLaunchKernelGGL(k_gcm_ghash<64>, dim3((u32)count), dim3(64), 0, s, ws, nk, in, count, given, out, status);
+    else
+        hipLaunchKernelGGL(k_gcm_ghash<1>, g1(count, 64), dim3(64), 0, s, ws, nk, in, count, given, out, status);
+}
+// One call on device pointers, and its three steps.  tag is written by an encryption and read by a decryption; lanes 0 is the
+// choice by GCM_WIDE_MIN_BLOCKS.
+struct GcmCall {
+    bool decrypt;
+    int nk;
+    size_t aad_len, len, stride, count;
+    const uint8_t *key, *nonce, *aad, *in;
+    uint8_t *tag, *out;
+    int* status;
+    u32* ws;
+    int lanes;
+    size_t blocks() const { return (len + 15) / 16; }
+    bool aligned() const { return aligned16(in) && aligned16(out) && stride % 16 == 0; }
+};
+static void gcm_setup_step(const GcmCall& c, hipStream_t s) {
+    hipLaunchKernelGGL(k_gcm_setup, g1(c.count, 64), dim3(64), 0, s, c.key, c.nk, c.nonce, (const uint8_t*)nullptr, c.count, c.ws);
+}
+static void gcm_ctr_step(const GcmCall& c, hipStream_t s) {
+    if (!c.blocks()) return;
+    const int* gate = c.decrypt ? c.status : nullptr;
+    if (c.aligned())
+        hipLaunchKernelGGL(k_gcm_ctr<true>, g1(c.count * c.blocks(), 256), dim3(256), 0, s, c.ws, c.nk, c.in, c.len, c.stride, c.count, gate, c.out);
+    else
+        hipLaunchKernelGGL(k_gcm_ctr<false>, g1(c.count * c.blocks(), 256), dim3(256), 0, s, c.ws, c.nk, c.in, c.len, c.stride, c.count, gate, c.out);
+}
+static void gcm_ghash_step(const GcmCall& c, hipStream_t s) {
+    const uint8_t* ct = c.decrypt ? c.in : c.out;
+    const GhashIn g{c.aad, ct, c.aad_len, c.len, c.stride, false, aligned16(ct) && c.stride % 16 == 0};
+    const int lanes = c.lanes ? c.lanes : (c.aad_len + 15) / 16 + c.blocks() + 1 >= GCM_WIDE_MIN_BLOCKS ? 64 : 1;
+    gcm_ghash_launch(lanes, s, c.ws, c.nk, g, c.count, c.decrypt ? c.tag : nullptr, c.decrypt ? nullptr : c.tag, c.status);
+}
+static int gcm_run(bool decrypt, const uint8_t* key, int nk, const uint8_t* nonce, const uint8_t* aad, size_t aad_len, const uint8_t* in, uint8_t* tag, size_t len,
+                   size_t stride, size_t count, uint8_t* out, int* status, void* work, Where w) {
+    const char* bad = nullptr;
+    if (!gcm_nk_ok(nk)) bad = "nk is 4, 6 or 8";
+    else if (len > GCM_MAX_LEN) bad = "len is at most 2^24 bytes";
+    else if (aad_len > GCM_MAX_AAD) bad = "aad_len is at most 2^16 bytes";
+    else if (stride < len) bad = "row_stride is at least len";
+    else if (count >> 31 || (count * ((len + 15) / 16) / 256) >> 31) bad = "count is too large for one launch";
+    else if (w.on_device && !aligned16(work)) bad = "d_work is 16-byte aligned";
+    if (bad) nk = 4, len = aad_len = stride = 0;
+    return run_batch(bad, count, w,
+                     {buf_in(key, (size_t)4 * nk * count), buf_in(nonce, 12 * count), buf_in(aad, aad_len * count), buf_in(in, stride * count),
+                      decrypt ? buf_in(tag, 16 * count) : buf_out(tag, 16 * count), buf_out(out, stride * count), buf_out(status, count),
+                      buf_scratch((u32*)work, (size_t)gcm_ws_words(nk + 6) * count)},
+                     [&](const DevPtr* d, hipStream_t s) {
+                         const GcmCall c{decrypt, nk, aad_len, len, stride, count, d[0], d[1], d[2], d[3], d[4], d[5], d[6], d[7], 0};
+                         gcm_setup_step(c, s);
+                         if (decrypt) gcm_ghash_step(c, s), gcm_ctr_step(c, s);  // the status first: it gates the counter mode
+                         else gcm_ctr_step(c, s), gcm_ghash_step(c, s);
+                     });
+}
+size_t p2_aes_gcm_batch_workspace(int nk, size_t len, size_t aad_len, size_t count) {
+    (void)len, (void)aad_len;  // the workspace holds per-item key material only
+    return gcm_nk_ok(nk) ? (size_t)gcm_ws_words(nk + 6) * 4 * count : 0;
+}
+int p2_aes_gcm_encrypt_batch(const uint8_t* key, int nk, const uint8_t* nonce, const uint8_t* aad, size_t aad_len, const uint8_t* pt, size_t len, size_t count,
+                             uint8_t* ct, uint8_t* tag, int* status, int device) {
+    return gcm_run(false, key, nk, nonce, aad, aad_len, pt, tag, len, len, count, ct, status, nullptr, on_host(device));
+}
+int p2_aes_gcm_decrypt_batch(const uint8_t* key, int nk, const uint8_t* nonce, const uint8_t* aad, size_t aad_len, const uint8_t* ct, const uint8_t* tag, size_t len,
+                             size_t count, uint8_t* pt, int* status, int device) {
+    return gcm_run(true, key, nk, nonce, aad, aad_len, ct, (uint8_t*)tag, len, len, count, pt, status, nullptr, on_host(device));
+}
+int p2_aes_gcm_encrypt_batch_device(const uint8_t* d_key, int nk, const uint8_t* d_nonce, const uint8_t* d_aad, size_t aad_len, const uint8_t* d_pt, size_t len,
+                                    size_t row_stride, size_t count, uint8_t* d_ct, uint8_t* d_tag, int* d_status, void* d_work, int device, void* stream) {
+    return gcm_run(false, d_key, nk, d_nonce, d_aad, aad_len, d_pt, d_tag, len, row_stride, count, d_ct, d_status, d_work, on_device(device, stream));
+}
+int p2_aes_gcm_decrypt_batch_device(const uint8_t* d_key, int nk, const uint8_t* d_nonce, const uint8_t* d_aad, size_t aad_len, const uint8_t* d_ct,
+                                    const uint8_t* d_tag, size_t len, size_t row_stride, size_t count, uint8_t* d_pt, int* d_status, void* d_work, int device,
+                                    void* stream) {
+    return gcm_run(true, d_key, nk, d_nonce, d_aad, aad_len, d_ct, (uint8_t*)d_tag, len, row_stride, count, d_pt, d_status, d_work, on_device(device, stream));
+}
+int p2_bytes_to_words_device(const uint8_t* d_bytes, size_t row_bytes, size_t byte_stride, size_t count, uint64_t* d_out, size_t stride_words, int device,
+                             void* stream) {
+    const char* bad = row_bytes > stride_words ? "stride_words is at least row_bytes" : nullptr;
+    return run_batch(bad, row_bytes ? count : 0, on_device(device, stream), {buf_in(d_bytes, row_bytes * count), buf_out(d_out, stride_words * count)},
+                     [&](const DevPtr* d, hipStream_t s) {
+                         hipLaunchKernelGGL(k_bytes_to_words, g1(count * row_bytes, 256), dim3(256), 0, s, d[0], row_bytes, byte_stride, count, d[1], stride_words);
+                     });
+}
+// test entries: the GHASH kernel alone with the lane count chosen, against p2_native_ghash; the block cipher alone, against
+// p2_native_aes_encrypt_block
+int p2_gpu_gcm_ghash(const uint8_t* h, const uint8_t* x, size_t blocks, size_t count, int lanes, uint8_t* out, int device) {
+    const char* bad = lanes != 1 && lanes != 64 ? "lanes is 1 or 64" : blocks > GCM_MAX_LEN / 16 ? "at most 2^20 blocks" : nullptr;
+    return run_batch(bad, count, on_host(device),
+                     {buf_in(h, 16 * count), buf_in(x, 16 * blocks * count), buf_out(out, 16 * count), buf_scratch((u32*)nullptr, (size_t)gcm_ws_words(10) * count)},
+                     [&](const DevPtr* d, hipStream_t s) {
+                         hipLaunchKernelGGL(k_gcm_setup, g1(count, 64), dim3(64), 0, s, (const uint8_t*)nullptr, 4, (const uint8_t*)nullptr, d[0], count, d[3]);
+                         GhashIn g{nullptr, d[1], 0, 16 * blocks, 16 * blocks, true, true};
+                         gcm_ghash_launch(lanes, s, d[3], 4, g, count, nullptr, d[2], nullptr);
+                     });
+}
+int p2_gpu_aes_encrypt_blocks(const uint8_t* key, int nk, const uint8_t* in, size_t count, uint8_t* out, int device) {
+    const bool bad = !gcm_nk_ok(nk);
+    if (bad) nk = 4;
+    return run_batch(bad ? "nk is 4, 6 or 8" : nullptr, count, on_host(device),
+                     {buf_in(key, (size_t)4 * nk * count), buf_in(in, 16 * count), buf_out(out, 16 * count), buf_scratch((u32*)nullptr, (size_t)gcm_ws_words(nk + 6) * count)},
+                     [&](const DevPtr* d, hipStream_t s) {
+                         hipLaunchKernelGGL(k_gcm_setup, g1(count, 64), dim3(64), 0, s, d[0], nk, (const uint8_t*)nullptr, (const uint8_t*)nullptr, count, d[3]);
+                         hipLaunchKernelGGL(k_aes_encrypt_blocks, g1(count, 64), dim3(64), 0, s, d[3], nk, d[1], count, d[2]);
+                     });
+}
+// bench entry (tools/gpu_gcm_bench.py): encryptions of `count` items on device buffers filled here with random bytes, one
+// warm-up and then `repeats` runs with an event between the kernels: ns[3 r + 0 .. 2] = k_gcm_setup, k_gcm_ctr, k_gcm_ghash of
+// run r, in nanoseconds.  lanes 1 or 64 forces the GHASH kernel, 0 leaves the public calls' choice.
+int p2_gpu_gcm_kernel_times(int nk, size_t len, size_t aad_len, size_t count, int lanes, size_t repeats, uint64_t* ns, int device) {
+    return guarded_rc([&]() -> int {
+        if (!gcm_nk_ok(nk) || len > GCM_MAX_LEN || aad_len > GCM_MAX_AAD || !count || count >> 31 || (lanes != 0 && lanes != 1 && lanes != 64) || !repeats || !ns)
+            return set_error("p2_gpu_gcm_kernel_times: argument out of range"), P2_ERR_INVALID;
+        if (int rc = pick_device(device)) return rc;
+        Allocs tmp;
+        const size_t stride = (len + 15) / 16 * 16, sizes[4] = {(size_t)4 * nk * count, 12 * count, aad_len * count, stride * count};
+        uint8_t* in[4];
+        std::mt19937_64 gen(1);
+        for (int k = 0; k < 4; k++) {
+            std::vector<uint64_t> host(sizes[k] / 8 + 1);
+            for (auto& v : host) v = gen();
+            if (upload(tmp, &in[k], (const uint8_t*)host.data(), sizes[k])) return P2_ERR_HIP;
+        }
+        uint8_t *out, *tag;
+        int* status;
+        u32* ws;
+        if (dalloc(tmp, &out, stride * count) || dalloc(tmp, &tag, 16 * count) || dalloc(tmp, &status, count) || dalloc(tmp, &ws, (size_t)gcm_ws_words(nk + 6) * count))
+            return P2_ERR_HIP;
+        const GcmCall c{false, nk, aad_len, len, stride, count, in[0], in[1], in[2], in[3], tag, out, status, ws, lanes};
+        Event ev[4];
+        for (Event& e : ev) HIPCHECK(e.create(hipEventDefault));
+        for (size_t r = 0; r <= repeats; r++) {
+            HIPCHECK(hipEventRecord(ev[0], nullptr));
+            gcm_setup_step(c, nullptr);
+            HIPCHECK(hipEventRecord(ev[1], nullptr));
+            gcm_ctr_step(c, nullptr);
+            HIPCHECK(hipEventRecord(ev[2], nullptr));
+            gcm_ghash_step(c, nullptr);
+            HIPCHECK(hipEventRecord(ev[3], nullptr));
+            HIPCHECK(hipEventSynchronize(ev[3]));
+            HIPCHECK(hipGetLastError());
+            if (r)
+                for (int k = 0; k < 3; k++) {
+                    float ms = 0;
+                    HIPCHECK(hipEventElapsedTime(&ms, ev[k], ev[k + 1]));
+                    ns[3 * (r - 1) + k] = (uint64_t)((double)ms * 1e6);
+                }
+        }
+        return (int)P2_OK;
+    });
 }
 
 // ---- batched verification
