@@ -575,6 +575,63 @@ pub mod plonk {
             pub fn merkle_update<H>(&mut self, old_leaf: Vec<Target>, new_leaf: Vec<Target>, leaf_index_bits: &[BoolTarget], old_root: HashOutTarget, proof: &MerkleProofTarget) -> HashOutTarget {
                 self.merkle_update_to_cap::<H>(old_leaf, new_leaf, leaf_index_bits, &MerkleCapTarget(vec![old_root]), proof).0[0]
             }
+            /// Not upstream's: sparse keyed trees (`MerkleMap`, include/p2aes.h).  `key_bits` are the little-endian bits of the key.
+            /// The map with `cap` holds `value` at the key (`present` = 1) or nothing (`present` = 0, the value then unconstrained).
+            pub fn merkle_map_lookup_to_cap<H>(&mut self, key_bits: &[BoolTarget], value: Vec<Target>, present: BoolTarget, cap: &MerkleCapTarget, proof: &MerkleProofTarget) {
+                assert!(cap.0.len().is_power_of_two(), "the cap must hold a power of two of hashes");
+                let (bits, val, capw, sib) = Self::map_args(key_bits, &value, cap, proof);
+                let h = cap.0.len().trailing_zeros() as std::os::raw::c_int;
+                let rc = unsafe { ffi::p2_builder_merkle_map_lookup_to_cap(self.h, bits.as_ptr(), bits.len(), val.as_ptr(), val.len(), present.target.0, capw.as_ptr(), h, sib.as_ptr(), proof.siblings.len()) };
+                assert!(rc == ffi::P2_OK, "{}", last_error());
+            }
+            /// (`old_present`, `old_value`) at the key under `old_cap`; returns the cap with (`new_present`, `new_value`) there.
+            pub fn merkle_map_update_to_cap<H>(&mut self, key_bits: &[BoolTarget], old_present: BoolTarget, old_value: Vec<Target>, new_present: BoolTarget, new_value: Vec<Target>, old_cap: &MerkleCapTarget, proof: &MerkleProofTarget) -> MerkleCapTarget {
+                assert!(old_cap.0.len().is_power_of_two(), "the cap must hold a power of two of hashes");
+                assert!(old_value.len() == new_value.len(), "the old and the new value must have one length");
+                let (bits, old, capw, sib) = Self::map_args(key_bits, &old_value, old_cap, proof);
+                let new: Vec<u64> = new_value.iter().map(|t| t.0).collect();
+                let h = old_cap.0.len().trailing_zeros() as std::os::raw::c_int;
+                let mut out = vec![0u64; capw.len()];
+                let rc = unsafe { ffi::p2_builder_merkle_map_update_to_cap(self.h, bits.as_ptr(), bits.len(), old_present.target.0, old.as_ptr(), new_present.target.0, new.as_ptr(), old.len(), capw.as_ptr(), h, sib.as_ptr(), proof.siblings.len(), out.as_mut_ptr()) };
+                assert!(rc == ffi::P2_OK, "{}", last_error());
+                MerkleCapTarget(out.chunks(4).map(|c| HashOutTarget { elements: core::array::from_fn(|i| Target(c[i])) }).collect())
+            }
+            /// The key is absent under `old_cap`; returns the cap of the map with `value` at it.
+            pub fn merkle_map_insert_to_cap<H>(&mut self, key_bits: &[BoolTarget], value: Vec<Target>, old_cap: &MerkleCapTarget, proof: &MerkleProofTarget) -> MerkleCapTarget {
+                assert!(old_cap.0.len().is_power_of_two(), "the cap must hold a power of two of hashes");
+                let (bits, val, capw, sib) = Self::map_args(key_bits, &value, old_cap, proof);
+                let h = old_cap.0.len().trailing_zeros() as std::os::raw::c_int;
+                let mut out = vec![0u64; capw.len()];
+                let rc = unsafe { ffi::p2_builder_merkle_map_insert_to_cap(self.h, bits.as_ptr(), bits.len(), val.as_ptr(), val.len(), capw.as_ptr(), h, sib.as_ptr(), proof.siblings.len(), out.as_mut_ptr()) };
+                assert!(rc == ffi::P2_OK, "{}", last_error());
+                MerkleCapTarget(out.chunks(4).map(|c| HashOutTarget { elements: core::array::from_fn(|i| Target(c[i])) }).collect())
+            }
+            /// The key holds `value` under `old_cap`; returns the cap of the map without it.
+            pub fn merkle_map_remove_to_cap<H>(&mut self, key_bits: &[BoolTarget], value: Vec<Target>, old_cap: &MerkleCapTarget, proof: &MerkleProofTarget) -> MerkleCapTarget {
+                assert!(old_cap.0.len().is_power_of_two(), "the cap must hold a power of two of hashes");
+                let (bits, val, capw, sib) = Self::map_args(key_bits, &value, old_cap, proof);
+                let h = old_cap.0.len().trailing_zeros() as std::os::raw::c_int;
+                let mut out = vec![0u64; capw.len()];
+                let rc = unsafe { ffi::p2_builder_merkle_map_remove_to_cap(self.h, bits.as_ptr(), bits.len(), val.as_ptr(), val.len(), capw.as_ptr(), h, sib.as_ptr(), proof.siblings.len(), out.as_mut_ptr()) };
+                assert!(rc == ffi::P2_OK, "{}", last_error());
+                MerkleCapTarget(out.chunks(4).map(|c| HashOutTarget { elements: core::array::from_fn(|i| Target(c[i])) }).collect())
+            }
+            pub fn merkle_map_lookup<H>(&mut self, key_bits: &[BoolTarget], value: Vec<Target>, present: BoolTarget, root: HashOutTarget, proof: &MerkleProofTarget) {
+                self.merkle_map_lookup_to_cap::<H>(key_bits, value, present, &MerkleCapTarget(vec![root]), proof)
+            }
+            pub fn merkle_map_update<H>(&mut self, key_bits: &[BoolTarget], old_present: BoolTarget, old_value: Vec<Target>, new_present: BoolTarget, new_value: Vec<Target>, old_root: HashOutTarget, proof: &MerkleProofTarget) -> HashOutTarget {
+                self.merkle_map_update_to_cap::<H>(key_bits, old_present, old_value, new_present, new_value, &MerkleCapTarget(vec![old_root]), proof).0[0]
+            }
+            pub fn merkle_map_insert<H>(&mut self, key_bits: &[BoolTarget], value: Vec<Target>, old_root: HashOutTarget, proof: &MerkleProofTarget) -> HashOutTarget {
+                self.merkle_map_insert_to_cap::<H>(key_bits, value, &MerkleCapTarget(vec![old_root]), proof).0[0]
+            }
+            pub fn merkle_map_remove<H>(&mut self, key_bits: &[BoolTarget], value: Vec<Target>, old_root: HashOutTarget, proof: &MerkleProofTarget) -> HashOutTarget {
+                self.merkle_map_remove_to_cap::<H>(key_bits, value, &MerkleCapTarget(vec![old_root]), proof).0[0]
+            }
+            fn map_args(key_bits: &[BoolTarget], value: &[Target], cap: &MerkleCapTarget, proof: &MerkleProofTarget) -> (Vec<u64>, Vec<u64>, Vec<u64>, Vec<u64>) {
+                (key_bits.iter().map(|b| b.target.0).collect(), value.iter().map(|t| t.0).collect(),
+                 cap.0.iter().flat_map(|h| h.elements.iter().map(|t| t.0)).collect(), proof.siblings.iter().flat_map(|h| h.elements.iter().map(|t| t.0)).collect())
+            }
             /// Not upstream's: `multiply_point` (and `public_key`, `elgamal_encrypt`, `hashed_elgamal_encrypt` through it) as 320
             /// EcStepGate rows instead of arithmetic gates.  Off by default.
             pub fn set_ec_gate(&mut self, on: bool) {

@@ -20,6 +20,8 @@
  *                                                                            p2_aes_gcm_encrypt_batch, p2_aes_gcm_decrypt_batch
  *   MerkleTree::new / prove, verify_merkle_proof_to_cap (upstream plonky2;   p2_merkle_tree_*, p2_merkle_verify_batch,
  *     not called by the reference: committed sets for pod2-style users)      p2_builder_verify_merkle_proof_to_cap
+ *   MerkleMap: sparse keyed trees with non-membership proofs (this project's  p2_merkle_map_*, p2_native_merkle_map_*,
+ *     own scheme, UNPINNED against pod2: revocation lists, nullifier sets)   p2_builder_merkle_map_*
  *
  * Conventions: plain pointers and sizes only; every function that can fail returns 0 on success and a
  * non-zero code otherwise, with a thread-local message available from p2_last_error().  The caller owns
@@ -241,6 +243,59 @@ int p2_native_merkle_verify(const uint64_t* leaf, size_t leaf_len, size_t index,
  * nothing.  k = 0 is a no-op. */
 int p2_native_merkle_update(uint64_t* leaves, size_t num_leaves, size_t leaf_len, int cap_height, const uint64_t* indices, const uint64_t* new_leaves,
                             size_t k, uint64_t* siblings, uint64_t* root_after);
+/* Sparse keyed Merkle trees: MerkleMap(key_bits = D, value_len = V, cap_height = h), 1 <= D <= 64, 0 <= h <= min(D, 16),
+ * 0 <= V <= 134.  This project's own scheme: pod2's tree is not in the reference tree, so it is UNPINNED against pod2.
+ *   entries   (key, value[V]): key a u64 below 2^D and below p, value words canonical, keys distinct.
+ *   shape     the complete binary tree of depth D; the entry with key k sits at leaf k.
+ *   leaves    occupied: hash_or_noop(value | [1]) -- the padded words themselves for V <= 3, (1,0,0,0) for a set (V = 0), hashed
+ *             for V >= 4.  Empty: E_0 = (0,0,0,0); no occupied leaf equals it but by a Poseidon collision with zero.
+ *   nodes     two_to_one(left, right); an empty subtree of height l is E_l = two_to_one(E_{l-1}, E_{l-1}).
+ *   cap       the 2^h nodes of level D - h in index order, dense; an empty map's is 2^h copies of E_{D-h}.
+ *   proof     (present, value, siblings[D - h][4]) for key k: siblings[l] is node (k >> l) ^ 1 of level l.  Membership: the walk
+ *             from the leaf digest with the bits of k as swap bits reaches cap entry k >> (D - h).  Non-membership: the same walk
+ *             from (0,0,0,0).  The position binds the key, so the key is not hashed into the leaf.
+ * A map is immutable: a changed set is a new map.
+ * Gadgets (no new gate, witness op or kernel).  key_bits: the D little-endian bits of the key, as split_le gives them; n_bits =
+ * n_siblings + cap_height or P2_ERR_INVALID with nothing added, as for verify_merkle_proof_to_cap.
+ *   lookup   assert_bool(present); start = select(present, hash_or_noop(value | one), 0^4) word by word; then the walk and cap mux
+ *            of verify_merkle_proof_to_cap.  One statement serves either answer, so `present` can be a public output.  With
+ *            present = 0 the value targets are UNCONSTRAINED.
+ *   update   the old walk from (old_present, old_value), the new walk from (new_present, new_value) over the same siblings and
+ *            bits, new_cap (4 * 2^cap_height targets, out) from merkle_update_to_cap's demux tree.
+ *   insert, remove   update with the flags fixed at (0, 1) and (1, 0): no select and no assert_bool for them, the empty side
+ *            starts from zero() targets.
+ * Cost: a leaf digest is no row for V <= 3, ceil((V + 1) / 8) PoseidonGate rows above.  lookup: one digest, one row per level,
+ * at most 9 ops and the h + 8 (2^h - 1) ops of the cap mux.  update: two digests, two rows per level, at most 18 ops, the mux and the demux's
+ * 2 (2^h - 1) - 1 + 8 * 2^h ops (h >= 1).  insert / remove: one digest, two rows per level, mux and demux only.
+ * The forms without _to_cap are cap_height 0: root to root. */
+int p2_builder_merkle_map_lookup_to_cap(p2_builder*, const p2_target* key_bits, size_t n_bits, const p2_target* value, size_t value_len, p2_target present,
+                                        const p2_target* cap, int cap_height, const p2_target* siblings, size_t n_siblings);
+int p2_builder_merkle_map_lookup(p2_builder*, const p2_target* key_bits, size_t n_bits, const p2_target* value, size_t value_len, p2_target present,
+                                 const p2_target root[4], const p2_target* siblings, size_t n_siblings);
+int p2_builder_merkle_map_update_to_cap(p2_builder*, const p2_target* key_bits, size_t n_bits, p2_target old_present, const p2_target* old_value,
+                                        p2_target new_present, const p2_target* new_value, size_t value_len, const p2_target* old_cap, int cap_height,
+                                        const p2_target* siblings, size_t n_siblings, p2_target* new_cap);
+int p2_builder_merkle_map_update(p2_builder*, const p2_target* key_bits, size_t n_bits, p2_target old_present, const p2_target* old_value, p2_target new_present,
+                                 const p2_target* new_value, size_t value_len, const p2_target old_root[4], const p2_target* siblings, size_t n_siblings,
+                                 p2_target new_root[4]);
+int p2_builder_merkle_map_insert_to_cap(p2_builder*, const p2_target* key_bits, size_t n_bits, const p2_target* value, size_t value_len, const p2_target* old_cap,
+                                        int cap_height, const p2_target* siblings, size_t n_siblings, p2_target* new_cap);
+int p2_builder_merkle_map_insert(p2_builder*, const p2_target* key_bits, size_t n_bits, const p2_target* value, size_t value_len, const p2_target old_root[4],
+                                 const p2_target* siblings, size_t n_siblings, p2_target new_root[4]);
+int p2_builder_merkle_map_remove_to_cap(p2_builder*, const p2_target* key_bits, size_t n_bits, const p2_target* value, size_t value_len, const p2_target* old_cap,
+                                        int cap_height, const p2_target* siblings, size_t n_siblings, p2_target* new_cap);
+int p2_builder_merkle_map_remove(p2_builder*, const p2_target* key_bits, size_t n_bits, const p2_target* value, size_t value_len, const p2_target old_root[4],
+                                 const p2_target* siblings, size_t n_siblings, p2_target new_root[4]);
+/* The map on the host: the definition in code, and the twin of the p2_merkle_map_* calls below.  keys [n], values [n][value_len];
+ * it works on the sorted entries and never materialises 2^D nodes; every call builds what it needs again.  A duplicate key, a key
+ * not below 2^key_bits and p, a value word not below p, or D, h, V out of range: P2_ERR_INVALID naming the entry, nothing built.
+ * _get: *present, value[value_len] (zeros when absent) and siblings[D - h][4] for `key`.  _verify: *status <- 0 the walk reaches
+ * its cap entry, 1 it does not, 2 the item is malformed (key out of range, a word not below p, present other than 0 or 1). */
+int p2_native_merkle_map_cap(const uint64_t* keys, const uint64_t* values, size_t n, size_t value_len, int key_bits, int cap_height, uint64_t* cap);
+int p2_native_merkle_map_get(const uint64_t* keys, const uint64_t* values, size_t n, size_t value_len, int key_bits, int cap_height, uint64_t key, int* present,
+                             uint64_t* value, uint64_t* siblings);
+int p2_native_merkle_map_verify(uint64_t key, int key_bits, uint64_t present, const uint64_t* value, size_t value_len, const uint64_t* siblings,
+                                const uint64_t* cap, int cap_height, int* status);
 /* PoseidonEncryptTarget::<L>::build (poseidon-cipher/src/circuit.rs:49).  ks: 10 targets (x then u), m: 5*L,
  * nonce: 2, ct: 5*(L+1) */
 int p2_poseidon_cipher_build(p2_builder*, size_t L, p2_target* ks, p2_target* m, p2_target* nonce, p2_target* ct);
@@ -711,6 +766,34 @@ int p2_merkle_verify_batch_device(const uint64_t* d_leaves, size_t leaf_len, con
  * Asynchronous on `stream`. */
 int p2_gpu_merkle_build_device(const uint64_t* d_leaves, size_t num_leaves, size_t leaf_len, int cap_height, int with_transpose,
                                uint64_t* d_scratch, uint64_t* d_dig, int device, void* stream);
+/* MerkleMap on the GPU (the definition is with p2_native_merkle_map_* above): built once, immutable.  keys [n], values
+ * [n][value_len], fewer than 2^32 entries in any order.  The build validates the entries, sorts them, hashes every non-empty node
+ * exactly once (p2_merkle_map_hashes: the nodes above the leaves) and keeps, per level, the ascending ids of the non-empty nodes
+ * and their digests.  A bad entry is found on the device in both forms: P2_ERR_INVALID naming the first one (the lowest entry
+ * index; its key before its words before a duplicate), no handle.  Too little device memory is refused with a message.
+ * _new_device: the entries in device memory, read by kernels on `stream`; the call synchronises that stream once (for the level
+ * sizes and the bad-entry flag) and returns with the rest of the build enqueued; the buffers may be reused when it returns.
+ * Every later call on the handle waits on one event recorded behind the build, on whatever stream it runs.
+ * _get_batch: present[n] (0 / 1), values [n][value_len] (zeros when absent), siblings [n][D - h][4]; a key out of range is
+ * P2_ERR_INVALID naming it.  _get_batch_device: row j at d_out + j * out_stride_words words, with presence (one word), the value
+ * and the siblings at the given word offsets within the row, so proofs land in the [batch][n_targets] matrix of
+ * p2_prove_batch_device; d_status[j] <- 0, or 2 for a key out of range, whose row is left untouched.  Asynchronous on `stream`.
+ * _verify_batch: n proofs against one cap, keys [n], present [n] words, values [n][value_len], siblings [n][D - h][4]; status[i] as
+ * p2_native_merkle_map_verify gives it, proof for proof.  (p2_merkle_verify_batch's 32 index bits are unchanged.) */
+int p2_merkle_map_new(const uint64_t* keys, const uint64_t* values, size_t n, size_t value_len, int key_bits, int cap_height, int device, void** map);
+int p2_merkle_map_new_device(const uint64_t* d_keys, const uint64_t* d_values, size_t n, size_t value_len, int key_bits, int cap_height, int device, void* stream,
+                             void** map);
+void p2_merkle_map_free(void* map);
+int p2_merkle_map_cap(void* map, uint64_t* cap, size_t cap_words);
+int p2_merkle_map_len(void* map, size_t* n);
+int p2_merkle_map_hashes(void* map, uint64_t* hashes);
+int p2_merkle_map_get_batch(void* map, const uint64_t* keys, size_t n, uint64_t* present, uint64_t* values, uint64_t* siblings);
+int p2_merkle_map_get_batch_device(void* map, const uint64_t* d_keys, size_t n, uint64_t* d_out, size_t out_stride_words, size_t present_off, size_t value_off,
+                                   size_t siblings_off, int* d_status, void* stream);
+int p2_merkle_map_verify_batch(const uint64_t* keys, int key_bits, const uint64_t* present, const uint64_t* values, size_t value_len, const uint64_t* siblings,
+                               const uint64_t* cap, int cap_height, size_t n, int* status, int device);
+int p2_merkle_map_verify_batch_device(const uint64_t* d_keys, int key_bits, const uint64_t* d_present, const uint64_t* d_values, size_t value_len,
+                                      const uint64_t* d_siblings, const uint64_t* d_cap, int cap_height, size_t n, int* d_status, int device, void* stream);
 
 /* ------------------------------------------------------------------ native ecGFp5 and Schnorr signatures in GPU batches */
 /* One thread per item (csrc/kernels_schnorr.h); rows are contiguous: scalars [count][5], points [count][10], messages

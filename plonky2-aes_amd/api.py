@@ -320,6 +320,25 @@ def lib():
         "p2_merkle_tree_last_update_hashes": (C.c_int, [vp, u64p]),
         "p2_builder_merkle_update_to_cap": (C.c_int, [vp, u64p, u64p, sz, u64p, sz, u64p, C.c_int, u64p, sz, u64p]),
         "p2_builder_merkle_update": (C.c_int, [vp, u64p, u64p, sz, u64p, sz, u64p, u64p, sz, u64p]),
+        "p2_builder_merkle_map_lookup_to_cap": (C.c_int, [vp, u64p, sz, u64p, sz, u64, u64p, C.c_int, u64p, sz]),
+        "p2_builder_merkle_map_lookup": (C.c_int, [vp, u64p, sz, u64p, sz, u64, u64p, u64p, sz]),
+        "p2_builder_merkle_map_update_to_cap": (C.c_int, [vp, u64p, sz, u64, u64p, u64, u64p, sz, u64p, C.c_int, u64p, sz, u64p]),
+        "p2_builder_merkle_map_update": (C.c_int, [vp, u64p, sz, u64, u64p, u64, u64p, sz, u64p, u64p, sz, u64p]),
+        "p2_builder_merkle_map_insert_to_cap": (C.c_int, [vp, u64p, sz, u64p, sz, u64p, C.c_int, u64p, sz, u64p]),
+        "p2_builder_merkle_map_insert": (C.c_int, [vp, u64p, sz, u64p, sz, u64p, u64p, sz, u64p]),
+        "p2_builder_merkle_map_remove_to_cap": (C.c_int, [vp, u64p, sz, u64p, sz, u64p, C.c_int, u64p, sz, u64p]),
+        "p2_builder_merkle_map_remove": (C.c_int, [vp, u64p, sz, u64p, sz, u64p, u64p, sz, u64p]),
+        "p2_native_merkle_map_cap": (C.c_int, [u64p, u64p, sz, sz, C.c_int, C.c_int, u64p]),
+        "p2_native_merkle_map_get": (C.c_int, [u64p, u64p, sz, sz, C.c_int, C.c_int, u64, C.POINTER(C.c_int), u64p, u64p]),
+        "p2_native_merkle_map_verify": (C.c_int, [u64, C.c_int, u64, u64p, sz, u64p, u64p, C.c_int, C.POINTER(C.c_int)]),
+        "p2_merkle_map_new": (C.c_int, [u64p, u64p, sz, sz, C.c_int, C.c_int, C.c_int, C.POINTER(vp)]),
+        "p2_merkle_map_new_device": (C.c_int, [vp, vp, sz, sz, C.c_int, C.c_int, C.c_int, vp, C.POINTER(vp)]),
+        "p2_merkle_map_free": (None, [vp]), "p2_merkle_map_cap": (C.c_int, [vp, u64p, sz]),
+        "p2_merkle_map_len": (C.c_int, [vp, C.POINTER(sz)]), "p2_merkle_map_hashes": (C.c_int, [vp, u64p]),
+        "p2_merkle_map_get_batch": (C.c_int, [vp, u64p, sz, u64p, u64p, u64p]),
+        "p2_merkle_map_get_batch_device": (C.c_int, [vp, vp, sz, vp, sz, sz, sz, sz, vp, vp]),
+        "p2_merkle_map_verify_batch": (C.c_int, [u64p, C.c_int, u64p, u64p, sz, u64p, u64p, C.c_int, sz, C.POINTER(C.c_int), C.c_int]),
+        "p2_merkle_map_verify_batch_device": (C.c_int, [vp, C.c_int, vp, vp, sz, vp, vp, C.c_int, sz, vp, C.c_int, vp]),
         "p2_ecgfp5_scalar_muladd": (None, [u64p, u64p, u64p, u64p]),
         "p2_gpu_ecgfp5_scalar_muladd": (C.c_int, [u64p, u64p, u64p, sz, u64p, C.c_int]),
         "p2_schnorr_challenge": (C.c_int, [u64p, u64p, u64p, sz, u64p]),
@@ -643,6 +662,62 @@ class CircuitBuilder:
     def merkle_update(self, old_leaf, new_leaf, index_bits, old_root, siblings):
         return self.merkle_update_to_cap(old_leaf, new_leaf, index_bits, [old_root], siblings)[0]
 
+    # ---- sparse keyed trees (MerkleMap; include/p2aes.h has the definition and the gadgets' costs).  key_bits: the D
+    # little-endian bits of the key (split_le), the low len(siblings) walk the path, the rest choose the cap entry.
+    @staticmethod
+    def _map_args(who, key_bits, cap, siblings):
+        n_cap = len(cap)
+        if n_cap == 0 or n_cap & (n_cap - 1) or n_cap > 1 << 16 or any(len(h) != 4 for h in list(cap) + list(siblings)):
+            raise P2Error("%s: the cap is 2^h hashes (h <= 16) and every hash four targets" % who)
+        flat = lambda hs: _arr([t for h in hs for t in h]) if hs else None  # noqa: E731
+        return (_arr(key_bits) if key_bits else None, len(key_bits)), flat(cap), n_cap.bit_length() - 1, (flat(siblings), len(siblings))
+
+    def merkle_map_lookup_to_cap(self, key_bits, value, present, cap, siblings):
+        """The map with this cap holds `value` at the key (present = 1) or nothing (present = 0; the value targets are then
+        unconstrained).  `present` is made boolean here."""
+        (kb, nb), capw, h, (sb, ns) = self._map_args("merkle_map_lookup_to_cap", key_bits, cap, siblings)
+        if lib().p2_builder_merkle_map_lookup_to_cap(self._h, kb, nb, _arr(value) if value else None, len(value), present, capw, h, sb, ns):
+            raise P2Error(_err())
+
+    def merkle_map_lookup(self, key_bits, value, present, root, siblings):
+        self.merkle_map_lookup_to_cap(key_bits, value, present, [root], siblings)
+
+    def merkle_map_update_to_cap(self, key_bits, old_present, old_value, new_present, new_value, old_cap, siblings):
+        """(old_present, old_value) at the key under old_cap; returns the cap with (new_present, new_value) there.  siblings: the
+        proof of the key as the map stood before the change (MerkleMap.get)."""
+        (kb, nb), capw, h, (sb, ns) = self._map_args("merkle_map_update_to_cap", key_bits, old_cap, siblings)
+        if len(old_value) != len(new_value):
+            raise P2Error("merkle_map_update_to_cap: the old value has %d targets, the new one %d" % (len(old_value), len(new_value)))
+        out = (u64 * (4 * len(old_cap)))()
+        if lib().p2_builder_merkle_map_update_to_cap(self._h, kb, nb, old_present, _arr(old_value) if old_value else None, new_present,
+                                                     _arr(new_value) if new_value else None, len(old_value), capw, h, sb, ns, out):
+            raise P2Error(_err())
+        return [list(out[4 * i:4 * i + 4]) for i in range(len(old_cap))]
+
+    def merkle_map_update(self, key_bits, old_present, old_value, new_present, new_value, old_root, siblings):
+        return self.merkle_map_update_to_cap(key_bits, old_present, old_value, new_present, new_value, [old_root], siblings)[0]
+
+    def _map_fixed(self, name, key_bits, value, old_cap, siblings):
+        (kb, nb), capw, h, (sb, ns) = self._map_args(name, key_bits, old_cap, siblings)
+        out = (u64 * (4 * len(old_cap)))()
+        if getattr(lib(), "p2_builder_" + name)(self._h, kb, nb, _arr(value) if value else None, len(value), capw, h, sb, ns, out):
+            raise P2Error(_err())
+        return [list(out[4 * i:4 * i + 4]) for i in range(len(old_cap))]
+
+    def merkle_map_insert_to_cap(self, key_bits, value, old_cap, siblings):
+        """The key is absent under old_cap; returns the cap of the map with `value` at it."""
+        return self._map_fixed("merkle_map_insert_to_cap", key_bits, value, old_cap, siblings)
+
+    def merkle_map_insert(self, key_bits, value, old_root, siblings):
+        return self.merkle_map_insert_to_cap(key_bits, value, [old_root], siblings)[0]
+
+    def merkle_map_remove_to_cap(self, key_bits, value, old_cap, siblings):
+        """The key holds `value` under old_cap; returns the cap of the map without it."""
+        return self._map_fixed("merkle_map_remove_to_cap", key_bits, value, old_cap, siblings)
+
+    def merkle_map_remove(self, key_bits, value, old_root, siblings):
+        return self.merkle_map_remove_to_cap(key_bits, value, [old_root], siblings)[0]
+
     # ---- pod2 CircuitBuilderElliptic / CircuitBuilderBits and the ecgfp5 crate's builder traits.  A PointTarget is its ten
     # targets (x then u), a BigUInt320Target its 320 little-endian bit targets.
     def add_virtual_point_target(self):
@@ -840,6 +915,22 @@ class PartialWitness:
         if len(sibs) != len(siblings) or not 0 <= index < 1 << len(bits):
             raise P2Error("the path has %d siblings and the index %d bits" % (len(sibs), len(bits)))
         self.set_target_arr(bits, [(index >> i) & 1 for i in range(len(bits))])
+        for t, h in zip(sibs, siblings):
+            self.set_hash_target(t, h)
+
+    def set_merkle_map_proof_target(self, targets, key, proof):
+        """targets = (key_bits or None, present target or None, value targets, sibling hashes) as a merkle_map_* gadget took them;
+        proof = (present, value, siblings) as MerkleMap.get(key) returns it.  None: the circuit derives the bits (split_le) or
+        fixes the flag (insert, remove)."""
+        bits, present_t, value_t, sibs = targets
+        present, value, siblings = proof
+        if len(sibs) != len(siblings) or len(value_t) != len(value) or (bits is not None and not 0 <= key < 1 << len(bits)):
+            raise P2Error("the proof has %d siblings and %d value words, its targets %d and %d" % (len(siblings), len(value), len(sibs), len(value_t)))
+        if bits is not None:
+            self.set_target_arr(bits, [(key >> i) & 1 for i in range(len(bits))])
+        if present_t is not None:
+            self.set_target(present_t, int(present))
+        self.set_target_arr(value_t, value)
         for t, h in zip(sibs, siblings):
             self.set_hash_target(t, h)
 
@@ -1463,6 +1554,160 @@ class merkle:
     def verify_batch_device(d_leaves, leaf_len, d_indices, d_siblings, depth, d_cap, cap_height, n, d_status, device=0, stream=None):
         """Every buffer a raw device pointer (p2_merkle_verify_batch_device); asynchronous on `stream`."""
         _device_call("p2_merkle_verify_batch_device", d_leaves, leaf_len, d_indices, d_siblings, depth, d_cap, cap_height, n, d_status, device, stream)
+
+
+class MerkleMap:
+    """A sparse keyed Merkle tree, MerkleMap(key_bits = D, value_len = V, cap_height = h): the complete tree of depth D with the
+    entry of key k at leaf k, of which only the non-empty nodes exist (include/p2aes.h has the definition).  keys: distinct
+    integers below 2^D and p; values: one list of V canonical words per key (V = 0: a set).  device = an index: built and kept
+    on that GPU (p2_merkle_map_*); value_len: V of a map without entries; device = None: the host twin (p2_native_merkle_map_*), which keeps the entries and rebuilds
+    what it needs on every call.  Immutable: a changed set is a new MerkleMap."""
+
+    def __init__(self, keys, values, key_bits, cap_height=0, device=0, value_len=None):
+        self._h = None
+        keys = [int(k) for k in keys]
+        if any(not 0 <= k < 1 << 64 for k in keys):
+            raise P2Error("keys are 64-bit words")
+        vals, n, self.value_len = _rows(values, "values")
+        if n != len(keys):
+            raise P2Error("MerkleMap: one value per key")
+        if value_len is not None:                          # an empty map cannot tell from its values
+            if n and value_len != self.value_len:
+                raise P2Error("MerkleMap: the values have %d words, value_len says %d" % (self.value_len, value_len))
+            self.value_len = value_len
+        self.device, self.key_bits, self.cap_height, self._n = device, key_bits, cap_height, n
+        self.depth = key_bits - cap_height
+        self._keys, self._vals = (_arr(keys) if keys else None), vals
+        if device is None:
+            self.cap     # validates the shape and the entries
+        else:
+            h = C.c_void_p()
+            if lib().p2_merkle_map_new(self._keys, vals, n, self.value_len, key_bits, cap_height, device, C.byref(h)):
+                raise P2Error("p2_merkle_map_new failed: " + _err())
+            self._h = h
+            self._keys = self._vals = None
+
+    @classmethod
+    def from_device(cls, d_keys, d_values, n, value_len, key_bits, cap_height=0, device=0, stream=None):
+        """p2_merkle_map_new_device: raw device pointers to u64[n] and u64[n][value_len], read by kernels on `stream`; the call
+        synchronises that stream once and the buffers are free again when it returns."""
+        m = cls.__new__(cls)
+        m._h = None
+        m.device, m.key_bits, m.cap_height, m.value_len, m._n, m.depth = device, key_bits, cap_height, value_len, n, key_bits - cap_height
+        h = C.c_void_p()
+        if lib().p2_merkle_map_new_device(d_keys, d_values, n, value_len, key_bits, cap_height, device, stream, C.byref(h)):
+            raise P2Error("p2_merkle_map_new_device failed: " + _err())
+        m._h = h
+        return m
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            lib().p2_merkle_map_free(self._h)
+            self._h = None
+
+    def __len__(self):
+        if self._h is None:
+            return self._n
+        n = sz()
+        if lib().p2_merkle_map_len(self._h, C.byref(n)):
+            raise P2Error("p2_merkle_map_len failed: " + _err())
+        return n.value
+
+    @property
+    def cap(self):
+        """2^cap_height hashes, each a list of four field elements"""
+        n = 4 << min(max(self.cap_height, 0), 16)
+        out = (u64 * n)()
+        if self._h is None:
+            if lib().p2_native_merkle_map_cap(self._keys, self._vals, self._n, self.value_len, self.key_bits, self.cap_height, out):
+                raise P2Error("p2_native_merkle_map_cap failed: " + _err())
+        elif lib().p2_merkle_map_cap(self._h, out, n):
+            raise P2Error("p2_merkle_map_cap failed: " + _err())
+        return [list(out[4 * i:4 * i + 4]) for i in range(n // 4)]
+
+    @property
+    def hashes(self):
+        """two_to_one calls of the build on the device: the non-empty nodes above the leaves (a host map does not count)"""
+        if self._h is None:
+            raise P2Error("a host map does not count its hashes")
+        out = u64()
+        if lib().p2_merkle_map_hashes(self._h, C.byref(out)):
+            raise P2Error("p2_merkle_map_hashes failed: " + _err())
+        return out.value
+
+    def get_batch(self, keys):
+        """-> one (present, value, siblings) per key: present 0 or 1, value V words (zeros when absent), siblings one hash per
+        level, the lowest first"""
+        keys = [int(k) for k in keys]
+        if any(not 0 <= k < 1 << 64 for k in keys):
+            raise P2Error("keys are 64-bit words")
+        V, d = self.value_len, self.depth
+
+        def host(i, outs, status):
+            present = C.c_int()
+            value, sib = C.cast(C.byref(outs[1], 8 * i * V), u64p), C.cast(C.byref(outs[2], 32 * i * d), u64p)
+            if lib().p2_native_merkle_map_get(self._keys, self._vals, self._n, V, self.key_bits, self.cap_height, keys[i], C.byref(present), value, sib):
+                raise P2Error("p2_native_merkle_map_get failed: " + _err())
+            outs[0][i] = present.value
+
+        ka = _arr(keys) if keys else None
+        (present, value, sib), _ = _batch_call("p2_merkle_map_get_batch", [len(keys)], None, [(u64, 1), (u64, V), (u64, 4 * d)], self.device if self._h else None, host,
+                                               lambda fn, n, outs, status: fn(self._h, ka, n, outs[0], outs[1], outs[2]))
+        return [(int(present[i]), list(value[i * V:(i + 1) * V]), [list(sib[(i * d + l) * 4:(i * d + l) * 4 + 4]) for l in range(d)]) for i in range(len(keys))]
+
+    def get(self, key):
+        return self.get_batch([key])[0]
+
+    def get_batch_device(self, d_keys, n, d_out, out_stride_words, present_off, value_off, siblings_off, d_status, stream=None):
+        """Device-resident lookups (p2_merkle_map_get_batch_device): `d_keys` u64[n], `d_status` int32[n] and `d_out` are raw device
+        pointers; row j is at d_out + 8 * j * out_stride_words bytes and takes presence, the value and the siblings at the given
+        word offsets.  Asynchronous on `stream`."""
+        if self._h is None:
+            raise P2Error("a host map has no device forms")
+        _device_call("p2_merkle_map_get_batch_device", self._h, d_keys, n, d_out, out_stride_words, present_off, value_off, siblings_off, d_status, stream)
+
+
+class merkle_map:
+    """MerkleMap proofs checked outside a circuit: statuses 0 the walk reaches its cap entry, 1 it does not, 2 malformed (a key
+    out of range, a word not below p, present other than 0 or 1)."""
+
+    @staticmethod
+    def verify_batch(keys, key_bits, proofs, cap, device=0):
+        """keys [n], proofs [n] of (present, value, siblings) as MerkleMap.get returns them, cap 2^h hashes -> n statuses.  device =
+        an index: on that GPU (p2_merkle_map_verify_batch); None: a host loop over p2_native_merkle_map_verify."""
+        keys = [int(k) for k in keys]
+        proofs = list(proofs)
+        flags = [int(p[0]) for p in proofs]
+        vals, n_v, V = _rows([p[1] for p in proofs], "values")
+        sb, n_s, sib_words = _rows([[w for h in p[2] for w in _hash4(h)] for p in proofs], "paths")
+        capw, n_cap, _ = _rows([_hash4(h) for h in cap], "cap hashes")
+        if n_cap == 0 or n_cap & (n_cap - 1) or any(not 0 <= v < 1 << 64 for v in keys + flags):
+            raise P2Error("verify_batch: keys and flags of 64 bits, a cap of 2^h hashes")
+        cap_height = n_cap.bit_length() - 1
+        if proofs and sib_words != 4 * (key_bits - cap_height):
+            raise P2Error("verify_batch: a proof has key_bits - cap_height siblings")
+        st = C.c_int()
+
+        def host(i, outs, status):
+            value = C.cast(C.byref(vals, 8 * i * V), u64p) if V else None
+            path = C.cast(C.byref(sb, 8 * i * sib_words), u64p) if sib_words else None
+            if lib().p2_native_merkle_map_verify(keys[i], key_bits, flags[i], value, V, path, capw, cap_height, C.byref(st)):
+                raise P2Error("p2_native_merkle_map_verify failed: " + _err())
+            status[i] = st.value
+
+        ka, fa = (_arr(keys), _arr(flags)) if keys else (None, None)
+        _, status = _batch_call("p2_merkle_map_verify_batch", [len(keys), len(proofs)], "verify_batch: one proof per key", [], device, host,
+                                lambda fn, n, outs, status: fn(ka, key_bits, fa, vals, V, sb, capw, cap_height, n, status, device))
+        return status
+
+    @staticmethod
+    def verify(key, key_bits, proof, cap, device=0):
+        return merkle_map.verify_batch([key], key_bits, [proof], cap, device)[0]
+
+    @staticmethod
+    def verify_batch_device(d_keys, key_bits, d_present, d_values, value_len, d_siblings, d_cap, cap_height, n, d_status, device=0, stream=None):
+        """Every buffer a raw device pointer (p2_merkle_map_verify_batch_device); asynchronous on `stream`."""
+        _device_call("p2_merkle_map_verify_batch_device", d_keys, key_bits, d_present, d_values, value_len, d_siblings, d_cap, cap_height, n, d_status, device, stream)
 
 
 class keccak_native:

@@ -285,29 +285,34 @@ class CircuitBuilder {
         for (u32 i = 0; i < 4; i++) h[i] = o[i];
         return h;
     }
-    // leaf_data is the leaf at index sum index_bits[i] 2^i of a tree with the given cap: the low siblings.size() bits walk the
-    // path, the bits above them (log2 of the cap's size of them) choose the cap entry.  The path bits are made boolean by the
-    // PoseidonGate's swap constraint; the cap-index bits reach only `select`, which constrains nothing, so they are made
-    // boolean here with assert_bool.
-    void verify_merkle_proof_to_cap(const std::vector<Target>& leaf_data, const std::vector<BoolTarget>& index_bits, const std::vector<HashOutTarget>& cap,
-                                    const std::vector<HashOutTarget>& siblings) {
-        u32 cap_height = 0;
-        while (((size_t)1 << cap_height) < cap.size()) cap_height++;
-        if (cap.empty() || ((size_t)1 << cap_height) != cap.size()) throw std::runtime_error("verify_merkle_proof_to_cap: the cap must hold a power of two of hashes");
-        if (leaf_data.empty()) throw std::runtime_error("verify_merkle_proof_to_cap: empty leaf");
-        if (index_bits.size() != siblings.size() + cap_height)
-            throw std::runtime_error("verify_merkle_proof_to_cap: " + std::to_string(index_bits.size()) + " index bits for " + std::to_string(siblings.size()) +
-                                     " siblings and cap height " + std::to_string(cap_height));
-        HashOutTarget state = hash_or_noop(leaf_data);
+    // The walk from a digest: one PoseidonGate row per sibling, bit l the row's swap.  Returns the digest reached.
+    HashOutTarget merkle_walk(HashOutTarget state, const std::vector<BoolTarget>& index_bits, const std::vector<HashOutTarget>& siblings) {
         for (size_t l = 0; l < siblings.size(); l++) {
             std::array<Target, 12> in;
             for (u32 i = 0; i < 4; i++) in[i] = state[i], in[4 + i] = siblings[l][i], in[8 + i] = zero();
             std::array<Target, 12> out = permute_swapped(in, index_bits[l]);
             for (u32 i = 0; i < 4; i++) state[i] = out[i];
         }
+        return state;
+    }
+    // log2 of the cap's size; throws unless the cap holds a power of two of hashes and the bits are one per sibling and cap level
+    u32 merkle_check_lengths(const char* who, const std::vector<BoolTarget>& index_bits, const std::vector<HashOutTarget>& cap, const std::vector<HashOutTarget>& siblings) {
+        u32 cap_height = 0;
+        while (((size_t)1 << cap_height) < cap.size()) cap_height++;
+        if (cap.empty() || ((size_t)1 << cap_height) != cap.size()) throw std::runtime_error(std::string(who) + ": the cap must hold a power of two of hashes");
+        if (index_bits.size() != siblings.size() + cap_height)
+            throw std::runtime_error(std::string(who) + ": " + std::to_string(index_bits.size()) + " index bits for " + std::to_string(siblings.size()) +
+                                     " siblings and cap height " + std::to_string(cap_height));
+        return cap_height;
+    }
+    // The walk from `start` and the mux tree over the cap-index bits (made boolean here), then four copy constraints: what
+    // verify_merkle_proof_to_cap does behind its leaf digest, and the map lookups behind theirs.
+    void verify_merkle_walk_to_cap(const HashOutTarget& start, const std::vector<BoolTarget>& index_bits, const std::vector<HashOutTarget>& cap,
+                                   const std::vector<HashOutTarget>& siblings) {
+        HashOutTarget state = merkle_walk(start, index_bits, siblings);
         std::vector<HashOutTarget> entries = cap;
-        for (u32 j = 0; j < cap_height; j++) {
-            BoolTarget bit = index_bits[siblings.size() + j];
+        for (size_t j = siblings.size(); j < index_bits.size(); j++) {
+            BoolTarget bit = index_bits[j];
             assert_bool(bit.target);
             std::vector<HashOutTarget> half(entries.size() / 2);
             for (size_t i = 0; i < half.size(); i++)
@@ -315,6 +320,36 @@ class CircuitBuilder {
             entries.swap(half);
         }
         connect_hashes(state, entries[0]);
+    }
+    // new_cap[i] = select(i == cap index, new_root, old_cap[i]) by the demux tree over the cap-index bits (merkle_update_to_cap's
+    // comment has the counts); a cap of one is the new root itself.
+    std::vector<HashOutTarget> merkle_demux_cap(const HashOutTarget& new_root, const std::vector<BoolTarget>& index_bits, size_t n_siblings,
+                                                const std::vector<HashOutTarget>& old_cap) {
+        if (old_cap.size() == 1) return {new_root};
+        std::vector<Target> ind{one()};
+        for (size_t j = index_bits.size(); j-- > n_siblings;) {
+            std::vector<Target> next(2 * ind.size());
+            for (size_t i = 0; i < ind.size(); i++) {
+                next[2 * i + 1] = mul_sub(ind[i], index_bits[j].target, zero());  // the selects' constants: the ops share their gates
+                next[2 * i] = sub(ind[i], next[2 * i + 1]);
+            }
+            ind.swap(next);
+        }
+        std::vector<HashOutTarget> new_cap(old_cap.size());
+        for (size_t i = 0; i < old_cap.size(); i++)
+            for (u32 w = 0; w < 4; w++) new_cap[i][w] = select(BoolTarget{ind[i]}, new_root[w], old_cap[i][w]);
+        return new_cap;
+    }
+    // leaf_data is the leaf at index sum index_bits[i] 2^i of a tree with the given cap: the low siblings.size() bits walk the
+    // path, the bits above them (log2 of the cap's size of them) choose the cap entry.  The path bits are made boolean by the
+    // PoseidonGate's swap constraint; the cap-index bits reach only `select`, which constrains nothing, so they are made
+    // boolean here with assert_bool.
+    void verify_merkle_proof_to_cap(const std::vector<Target>& leaf_data, const std::vector<BoolTarget>& index_bits, const std::vector<HashOutTarget>& cap,
+                                    const std::vector<HashOutTarget>& siblings) {
+        if (cap.empty() || (cap.size() & (cap.size() - 1))) throw std::runtime_error("verify_merkle_proof_to_cap: the cap must hold a power of two of hashes");
+        if (leaf_data.empty()) throw std::runtime_error("verify_merkle_proof_to_cap: empty leaf");
+        merkle_check_lengths("verify_merkle_proof_to_cap", index_bits, cap, siblings);
+        verify_merkle_walk_to_cap(hash_or_noop(leaf_data), index_bits, cap, siblings);
     }
     void verify_merkle_proof(const std::vector<Target>& leaf_data, const std::vector<BoolTarget>& index_bits, const HashOutTarget& root,
                              const std::vector<HashOutTarget>& siblings) {
@@ -331,31 +366,76 @@ class CircuitBuilder {
         if (new_leaf.empty()) throw std::runtime_error("merkle_update_to_cap: empty leaf");
         if (new_leaf.size() != old_leaf.size()) throw std::runtime_error("merkle_update_to_cap: the old leaf has " + std::to_string(old_leaf.size()) + " targets, the new one " + std::to_string(new_leaf.size()));
         verify_merkle_proof_to_cap(old_leaf, index_bits, old_cap, siblings);  // throws on every other length mismatch, before anything is added
-        HashOutTarget state = hash_or_noop(new_leaf);
-        for (size_t l = 0; l < siblings.size(); l++) {
-            std::array<Target, 12> in;
-            for (u32 i = 0; i < 4; i++) in[i] = state[i], in[4 + i] = siblings[l][i], in[8 + i] = zero();
-            std::array<Target, 12> out = permute_swapped(in, index_bits[l]);
-            for (u32 i = 0; i < 4; i++) state[i] = out[i];
-        }
-        if (old_cap.size() == 1) return {state};
-        std::vector<Target> ind{one()};
-        for (size_t j = index_bits.size(); j-- > siblings.size();) {
-            std::vector<Target> next(2 * ind.size());
-            for (size_t i = 0; i < ind.size(); i++) {
-                next[2 * i + 1] = mul_sub(ind[i], index_bits[j].target, zero());  // the selects' constants: the ops share their gates
-                next[2 * i] = sub(ind[i], next[2 * i + 1]);
-            }
-            ind.swap(next);
-        }
-        std::vector<HashOutTarget> new_cap(old_cap.size());
-        for (size_t i = 0; i < old_cap.size(); i++)
-            for (u32 w = 0; w < 4; w++) new_cap[i][w] = select(BoolTarget{ind[i]}, state[w], old_cap[i][w]);
-        return new_cap;
+        return merkle_demux_cap(merkle_walk(hash_or_noop(new_leaf), index_bits, siblings), index_bits, siblings.size(), old_cap);
     }
     HashOutTarget merkle_update(const std::vector<Target>& old_leaf, const std::vector<Target>& new_leaf, const std::vector<BoolTarget>& index_bits,
                                 const HashOutTarget& old_root, const std::vector<HashOutTarget>& siblings) {
         return merkle_update_to_cap(old_leaf, new_leaf, index_bits, {old_root}, siblings)[0];
+    }
+
+    // ---- sparse keyed trees (merkle_host.h: MerkleMap; not upstream gadgets) ------------------------------------------
+    // key_bits are the D little-endian bits of the key: the low siblings.size() walk the path, the rest choose the cap entry, as
+    // in verify_merkle_proof_to_cap.  An occupied leaf is hash_or_noop(value | one), an empty one four zero() targets.
+    //   lookup   assert_bool(present) -- the selects alone constrain nothing about it --, start = select(present, occupied, 0^4)
+    //            word by word, then verify_merkle_walk_to_cap.  One statement serves both answers, so `present` may be a public
+    //            output.  With present = 0 the value targets are UNCONSTRAINED: a caller that reads them must gate on present.
+    //   update   the old walk as lookup's from (old_present, old_value); the new walk from (new_present, new_value) over the same
+    //            siblings and bits; the new cap from merkle_demux_cap.
+    //   insert / remove   update with the flags fixed at (0, 1) / (1, 0): no select and no assert_bool for them, the empty side
+    //            starts from zero() targets.
+    // Cost: a leaf digest is no row for value_len <= 3 and ceil((value_len + 1) / 8) PoseidonGate rows above.  lookup: one digest,
+    // one row per level, at most 9 ops (assert_bool, four selects; ops on the constant zero fold) and verify_merkle_proof_to_cap's h assert_bool + 8 (2^h - 1) mux ops.
+    // update: two digests, two rows per level, at most 18 ops, the mux ops and merkle_update_to_cap's demux ops (2 (2^h - 1) - 1 + 8 * 2^h
+    // for h >= 1).  insert / remove: one digest, two rows per level, the mux and demux ops only.
+    void merkle_map_check(const char* who, const std::vector<BoolTarget>& key_bits, size_t value_len, const std::vector<HashOutTarget>& cap,
+                          const std::vector<HashOutTarget>& siblings) {
+        if (key_bits.empty() || key_bits.size() > 64) throw std::runtime_error(std::string(who) + ": 1 to 64 key bits");
+        if (value_len > 134) throw std::runtime_error(std::string(who) + ": a value has at most 134 targets");
+        if (merkle_check_lengths(who, key_bits, cap, siblings) > 16) throw std::runtime_error(std::string(who) + ": cap_height must be 0 to 16");
+    }
+    HashOutTarget merkle_map_leaf(std::vector<Target> value) {
+        value.push_back(one());
+        return hash_or_noop(value);
+    }
+    HashOutTarget merkle_map_start(BoolTarget present, const std::vector<Target>& value) {
+        assert_bool(present.target);
+        HashOutTarget occupied = merkle_map_leaf(value), start;
+        for (u32 w = 0; w < 4; w++) start[w] = select(present, occupied[w], zero());
+        return start;
+    }
+    HashOutTarget merkle_map_empty() { return HashOutTarget{zero(), zero(), zero(), zero()}; }
+    void merkle_map_lookup_to_cap(const std::vector<BoolTarget>& key_bits, const std::vector<Target>& value, BoolTarget present, const std::vector<HashOutTarget>& cap,
+                                  const std::vector<HashOutTarget>& siblings) {
+        merkle_map_check("merkle_map_lookup_to_cap", key_bits, value.size(), cap, siblings);
+        verify_merkle_walk_to_cap(merkle_map_start(present, value), key_bits, cap, siblings);
+    }
+    // old_start under old_cap; the returned cap has new_start at the key
+    std::vector<HashOutTarget> merkle_map_transition(const HashOutTarget& old_start, const HashOutTarget& new_start, const std::vector<BoolTarget>& key_bits,
+                                                     const std::vector<HashOutTarget>& old_cap, const std::vector<HashOutTarget>& siblings) {
+        verify_merkle_walk_to_cap(old_start, key_bits, old_cap, siblings);
+        return merkle_demux_cap(merkle_walk(new_start, key_bits, siblings), key_bits, siblings.size(), old_cap);
+    }
+    std::vector<HashOutTarget> merkle_map_update_to_cap(const std::vector<BoolTarget>& key_bits, BoolTarget old_present, const std::vector<Target>& old_value,
+                                                        BoolTarget new_present, const std::vector<Target>& new_value, const std::vector<HashOutTarget>& old_cap,
+                                                        const std::vector<HashOutTarget>& siblings) {
+        if (old_value.size() != new_value.size())
+            throw std::runtime_error("merkle_map_update_to_cap: the old value has " + std::to_string(old_value.size()) + " targets, the new one " + std::to_string(new_value.size()));
+        merkle_map_check("merkle_map_update_to_cap", key_bits, old_value.size(), old_cap, siblings);
+        const HashOutTarget old_start = merkle_map_start(old_present, old_value);
+        const HashOutTarget new_start = merkle_map_start(new_present, new_value);
+        return merkle_map_transition(old_start, new_start, key_bits, old_cap, siblings);
+    }
+    std::vector<HashOutTarget> merkle_map_insert_to_cap(const std::vector<BoolTarget>& key_bits, const std::vector<Target>& value, const std::vector<HashOutTarget>& old_cap,
+                                                        const std::vector<HashOutTarget>& siblings) {
+        merkle_map_check("merkle_map_insert_to_cap", key_bits, value.size(), old_cap, siblings);
+        const HashOutTarget leaf = merkle_map_leaf(value);
+        return merkle_map_transition(merkle_map_empty(), leaf, key_bits, old_cap, siblings);
+    }
+    std::vector<HashOutTarget> merkle_map_remove_to_cap(const std::vector<BoolTarget>& key_bits, const std::vector<Target>& value, const std::vector<HashOutTarget>& old_cap,
+                                                        const std::vector<HashOutTarget>& siblings) {
+        merkle_map_check("merkle_map_remove_to_cap", key_bits, value.size(), old_cap, siblings);
+        const HashOutTarget leaf = merkle_map_leaf(value);
+        return merkle_map_transition(leaf, merkle_map_empty(), key_bits, old_cap, siblings);
     }
 
     // ---- ecGFp5 scalar-multiplication step (ecstep_gate.h; not an upstream gate) ---------------------

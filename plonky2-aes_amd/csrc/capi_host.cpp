@@ -446,6 +446,99 @@ int p2_native_merkle_verify(const uint64_t* leaf, size_t leaf_len, size_t index,
         *status = mt::host_verify(leaf, leaf_len, index, siblings, depth, cap, (u32)cap_height);
     });
 }
+// ---- sparse keyed trees: the gadgets (builder.h) and the host twin (merkle_host.h)
+static std::vector<BoolTarget> bools_at(const p2_target* t, size_t n) {
+    std::vector<BoolTarget> v(n);
+    for (size_t i = 0; i < n; i++) v[i] = BoolTarget{t[i]};
+    return v;
+}
+static std::vector<Target> targets_at(const p2_target* t, size_t n) { return n ? std::vector<Target>(t, t + n) : std::vector<Target>(); }
+static void map_cap_height(const char* who, int cap_height) {
+    if (cap_height < 0 || cap_height > 16) throw std::runtime_error(std::string(who) + ": cap_height must be 0 to 16");
+}
+static void cap_out(const std::vector<CircuitBuilder::HashOutTarget>& cap, p2_target* out) {
+    for (size_t i = 0; i < cap.size(); i++) std::copy(cap[i].begin(), cap[i].end(), out + 4 * i);
+}
+int p2_builder_merkle_map_lookup_to_cap(p2_builder* b, const p2_target* key_bits, size_t n_bits, const p2_target* value, size_t value_len, p2_target present,
+                                        const p2_target* cap, int cap_height, const p2_target* siblings, size_t n_siblings) {
+    return guarded([&] {
+        map_cap_height("merkle_map_lookup_to_cap", cap_height);
+        b->b.merkle_map_lookup_to_cap(bools_at(key_bits, n_bits), targets_at(value, value_len), BoolTarget{present}, hashes_at(cap, (size_t)1 << cap_height),
+                                      hashes_at(siblings, n_siblings));
+    });
+}
+int p2_builder_merkle_map_lookup(p2_builder* b, const p2_target* key_bits, size_t n_bits, const p2_target* value, size_t value_len, p2_target present,
+                                 const p2_target root[4], const p2_target* siblings, size_t n_siblings) {
+    return p2_builder_merkle_map_lookup_to_cap(b, key_bits, n_bits, value, value_len, present, root, 0, siblings, n_siblings);
+}
+int p2_builder_merkle_map_update_to_cap(p2_builder* b, const p2_target* key_bits, size_t n_bits, p2_target old_present, const p2_target* old_value, p2_target new_present,
+                                        const p2_target* new_value, size_t value_len, const p2_target* old_cap, int cap_height, const p2_target* siblings,
+                                        size_t n_siblings, p2_target* new_cap) {
+    return guarded([&] {
+        map_cap_height("merkle_map_update_to_cap", cap_height);
+        cap_out(b->b.merkle_map_update_to_cap(bools_at(key_bits, n_bits), BoolTarget{old_present}, targets_at(old_value, value_len), BoolTarget{new_present},
+                                              targets_at(new_value, value_len), hashes_at(old_cap, (size_t)1 << cap_height), hashes_at(siblings, n_siblings)),
+                new_cap);
+    });
+}
+int p2_builder_merkle_map_update(p2_builder* b, const p2_target* key_bits, size_t n_bits, p2_target old_present, const p2_target* old_value, p2_target new_present,
+                                 const p2_target* new_value, size_t value_len, const p2_target old_root[4], const p2_target* siblings, size_t n_siblings,
+                                 p2_target new_root[4]) {
+    return p2_builder_merkle_map_update_to_cap(b, key_bits, n_bits, old_present, old_value, new_present, new_value, value_len, old_root, 0, siblings, n_siblings, new_root);
+}
+int p2_builder_merkle_map_insert_to_cap(p2_builder* b, const p2_target* key_bits, size_t n_bits, const p2_target* value, size_t value_len, const p2_target* old_cap,
+                                        int cap_height, const p2_target* siblings, size_t n_siblings, p2_target* new_cap) {
+    return guarded([&] {
+        map_cap_height("merkle_map_insert_to_cap", cap_height);
+        cap_out(b->b.merkle_map_insert_to_cap(bools_at(key_bits, n_bits), targets_at(value, value_len), hashes_at(old_cap, (size_t)1 << cap_height),
+                                              hashes_at(siblings, n_siblings)),
+                new_cap);
+    });
+}
+int p2_builder_merkle_map_insert(p2_builder* b, const p2_target* key_bits, size_t n_bits, const p2_target* value, size_t value_len, const p2_target old_root[4],
+                                 const p2_target* siblings, size_t n_siblings, p2_target new_root[4]) {
+    return p2_builder_merkle_map_insert_to_cap(b, key_bits, n_bits, value, value_len, old_root, 0, siblings, n_siblings, new_root);
+}
+int p2_builder_merkle_map_remove_to_cap(p2_builder* b, const p2_target* key_bits, size_t n_bits, const p2_target* value, size_t value_len, const p2_target* old_cap,
+                                        int cap_height, const p2_target* siblings, size_t n_siblings, p2_target* new_cap) {
+    return guarded([&] {
+        map_cap_height("merkle_map_remove_to_cap", cap_height);
+        cap_out(b->b.merkle_map_remove_to_cap(bools_at(key_bits, n_bits), targets_at(value, value_len), hashes_at(old_cap, (size_t)1 << cap_height),
+                                              hashes_at(siblings, n_siblings)),
+                new_cap);
+    });
+}
+int p2_builder_merkle_map_remove(p2_builder* b, const p2_target* key_bits, size_t n_bits, const p2_target* value, size_t value_len, const p2_target old_root[4],
+                                 const p2_target* siblings, size_t n_siblings, p2_target new_root[4]) {
+    return p2_builder_merkle_map_remove_to_cap(b, key_bits, n_bits, value, value_len, old_root, 0, siblings, n_siblings, new_root);
+}
+int p2_native_merkle_map_cap(const uint64_t* keys, const uint64_t* values, size_t n, size_t value_len, int key_bits, int cap_height, uint64_t* cap) {
+    return guarded([&] {
+        mt::HostMap m(keys, values, n, value_len, key_bits, cap_height);
+        if (!cap) throw std::runtime_error("null argument");
+        m.cap(cap);
+    });
+}
+int p2_native_merkle_map_get(const uint64_t* keys, const uint64_t* values, size_t n, size_t value_len, int key_bits, int cap_height, uint64_t key, int* present,
+                             uint64_t* value, uint64_t* siblings) {
+    return guarded([&] {
+        mt::HostMap m(keys, values, n, value_len, key_bits, cap_height);
+        if (!present || (value_len && !value) || (m.depth() && !siblings)) throw std::runtime_error("null argument");
+        if (!mt::map_key_ok(key, m.D)) throw std::runtime_error("the key is not below 2^key_bits and p");
+        const ptrdiff_t at = m.find(key);
+        *present = at >= 0;
+        for (size_t w = 0; w < value_len; w++) value[w] = at >= 0 ? values[m.pos[(size_t)at] * value_len + w] : 0;
+        m.siblings(key, siblings);
+    });
+}
+int p2_native_merkle_map_verify(uint64_t key, int key_bits, uint64_t present, const uint64_t* value, size_t value_len, const uint64_t* siblings, const uint64_t* cap,
+                                int cap_height, int* status) {
+    return guarded([&] {
+        mt::map_check_shape(key_bits, cap_height, value_len);
+        if (!cap || !status || (value_len && !value) || (key_bits > cap_height && !siblings)) throw std::runtime_error("null argument");
+        *status = mt::host_map_verify(key, (u32)key_bits, present, value, value_len, siblings, cap, (u32)cap_height);
+    });
+}
 int p2_poseidon_cipher_build(p2_builder* b, size_t L, p2_target* ks, p2_target* m, p2_target* nonce, p2_target* ct) {
     try {
         auto t = pcipher::PoseidonEncryptTarget::build(b->b, L);

@@ -453,16 +453,21 @@ struct PoseidonTree {
 };
 
 // verify_merkle_to_cap: the leaf's digest climbed with `depth` siblings and compared with cap entry index >> depth
-template <class H>
-__device__ __forceinline__ bool vfy_merkle(const u64* leaf, u32 width, u32 index, const u64* cap, u32 cap_n, const u64* sib, u32 depth) {
-    u64 cur[4];
-    H::hash_or_noop(leaf, width, cur);
+// (vfy_merkle_walk: the same from a digest, with the index type of the caller's tree -- the sparse maps walk 64 bits)
+template <class H, class Index>
+__device__ __forceinline__ bool vfy_merkle_walk(u64* cur, Index index, const u64* cap, u32 cap_n, const u64* sib, u32 depth) {
     for (u32 l = 0; l < depth; l++) {
         H::compress(cur, sib + 4 * (size_t)l, index & 1);
         index >>= 1;
     }
     const u64* c = cap + 4 * (size_t)(index & (cap_n - 1));
     return index < cap_n && cur[0] == c[0] && cur[1] == c[1] && cur[2] == c[2] && cur[3] == c[3];
+}
+template <class H>
+__device__ __forceinline__ bool vfy_merkle(const u64* leaf, u32 width, u32 index, const u64* cap, u32 cap_n, const u64* sib, u32 depth) {
+    u64 cur[4];
+    H::hash_or_noop(leaf, width, cur);
+    return vfy_merkle_walk<H, u32>(cur, index, cap, cap_n, sib, depth);
 }
 // compute_evaluation: interpolate the arity-16 coset {(x_t, evals[bitrev t])} containing subgroup_x and evaluate at beta, as the
 // host's Lagrange sum.  The nodes are x_t = c g^t (c = coset start, g of order 16), so every denominator has a closed form:

@@ -24,6 +24,7 @@
 #include "kernels_keccak.h"
 #include "kernels_merkle.h"
 #include "kernels_merkle_update.h"
+#include "kernels_merkle_map.h"
 #include "kernels_elgamal.h"
 #include "kernels_gcm.h"
 #include "kernels_pcipher.h"
@@ -3188,6 +3189,265 @@ int p2_gpu_merkle_build_device(const uint64_t* d_leaves, size_t num_leaves, size
         if (with_transpose && mt_transpose(L, (const u64*)d_leaves, num_leaves, (u32)leaf_len, (u64*)d_scratch)) return P2_ERR_HIP;
         return merkle_build(L, D, (const u64*)d_scratch, (u32)leaf_len, (u32)leaf_len, num_leaves, 0, t, 1);
     });
+}
+
+// ---- sparse keyed Merkle trees (kernels_merkle_map.h; the definition and the host twin are mt::HostMap, merkle_host.h)
+// An immutable map on the device: per level the ascending ids of the non-empty nodes and their digests, the E_l table, the
+// dense cap, and the keys and values in key order.  The rules are MerkleTreeHandle's: owned resources, one event behind the
+// build that every later call waits on, a memory check in front of the allocations.
+struct MerkleMapHandle {
+    int device = 0;
+    u32 D = 0, h = 0, V = 0;
+    size_t n = 0;
+    std::vector<size_t> level_n;  // [depth + 1]: the non-empty nodes of every level
+    Allocs mem;                   // (the memory first: freed after the stream and the event have gone)
+    Allocs scratch;               // positions, the b sort, the (entry, child) ping-pong: needed until the build has run
+    u64 *keys = nullptr, *vals = nullptr, *ids = nullptr, *dig = nullptr, *empties = nullptr, *cap = nullptr;
+    u64* ctl = nullptr;  // [0] the lowest bad (entry, kind), [1] the hash counter, then the 65-bin histogram (u32)
+    MapLevel* levels = nullptr;
+    Lane lane;    // the stream of the host forms
+    Event built;  // recorded behind the last kernel of the build, on whichever stream ran it
+    void drop_scratch(bool wait) {
+        if (scratch.empty() || (wait ? hipEventSynchronize(built) : hipEventQuery(built)) != hipSuccess) return;
+        scratch.clear();
+    }
+    ~MerkleMapHandle() {
+        if (built) (void)hipEventSynchronize(built);
+        if (lane.stream) (void)hipStreamSynchronize(lane.stream);
+    }
+    u32 depth() const { return D - h; }
+};
+static const size_t MM_CTL_WORDS = 2 + 33;
+static int mm_refuse(const std::string& what, size_t need, size_t free_b) {
+    return set_error(what + " needs " + std::to_string(need) + " bytes of device memory, " + std::to_string(free_b) + " are free"), P2_ERR_INVALID;
+}
+// Everything on `st`.  One synchronisation: the histogram (every level's size) and the bad-entry flag come back together.
+static int mm_build(MerkleMapHandle& T, const u64* d_keys, const u64* d_values, hipStream_t st) {
+    const size_t n = T.n;
+    const u32 depth = T.depth();
+    const dim3 block(256);
+    Hash4 E[65];
+    mt::map_empty_digests(E);
+    std::vector<u64> ctl0(MM_CTL_WORDS, 0);
+    ctl0[0] = ~0ull;
+    if (dalloc(T.mem, &T.empties, 65 * 4) || dalloc(T.mem, &T.ctl, MM_CTL_WORDS) || dalloc(T.mem, &T.cap, (size_t)4 << T.h) || dalloc(T.mem, &T.levels, depth + 1))
+        return P2_ERR_HIP;
+    HIPCHECK(hipMemcpy(T.empties, E, sizeof(E), hipMemcpyHostToDevice));
+    HIPCHECK(hipMemcpy(T.ctl, ctl0.data(), MM_CTL_WORDS * 8, hipMemcpyHostToDevice));
+    unsigned long long* bad = (unsigned long long*)T.ctl;
+    u64* counter = T.ctl + 1;
+    u32* hist = (u32*)(T.ctl + 2);
+    T.level_n.assign(depth + 1, 0);
+    std::vector<MapLevel> levels(depth + 1, MapLevel{nullptr, nullptr, 0});
+    if (n) {
+        size_t free_b = 0, total_b = 0, sort_a = 0, sort_b = 0;
+        HIPCHECK(rocprim::radix_sort_pairs(nullptr, sort_a, (const u64*)nullptr, (u64*)nullptr, (const u32*)nullptr, (u32*)nullptr, n, 0u, T.D, st));
+        HIPCHECK(rocprim::radix_sort_pairs(nullptr, sort_b, (const u32*)nullptr, (u32*)nullptr, (const u32*)nullptr, (u32*)nullptr, n, 0u, 7u, st));
+        const size_t sort_bytes = std::max(sort_a, sort_b);
+        HIPCHECK(hipMemGetInfo(&free_b, &total_b));
+        const size_t need1 = 8 * n * (1 + T.V) + 10 * 4 * n + sort_bytes;  // keys and values in key order; ten u32 arrays; the sorts' block
+        if (need1 > free_b) return mm_refuse("sorting the map", need1, free_b);
+        u32 *pos_a, *pos_b, *bkey, *bkey_s, *idx, *order, *ent[2], *child[2];
+        char* sort_tmp;
+        if (dalloc(T.mem, &T.keys, n) || dalloc(T.mem, &T.vals, n * T.V) || dalloc(T.scratch, &pos_a, n) || dalloc(T.scratch, &pos_b, n) || dalloc(T.scratch, &bkey, n) ||
+            dalloc(T.scratch, &bkey_s, n) || dalloc(T.scratch, &idx, n) || dalloc(T.scratch, &order, n) || dalloc(T.scratch, &ent[0], n) || dalloc(T.scratch, &ent[1], n) ||
+            dalloc(T.scratch, &child[0], n) || dalloc(T.scratch, &child[1], n) || dalloc(T.scratch, &sort_tmp, sort_bytes))
+            return P2_ERR_HIP;
+        const dim3 grid = g1(n, 256);
+        hipLaunchKernelGGL(k_mm_check, grid, block, 0, st, d_keys, d_values, n, T.D, T.V, pos_a, bad);
+        HIPCHECK(hipGetLastError());
+        HIPCHECK(rocprim::radix_sort_pairs((void*)sort_tmp, sort_a, d_keys, T.keys, (const u32*)pos_a, pos_b, n, 0u, T.D, st));
+        hipLaunchKernelGGL(k_mm_diff, grid, block, 0, st, T.keys, pos_b, n, bkey, idx, hist, bad);
+        HIPCHECK(hipGetLastError());
+        HIPCHECK(rocprim::radix_sort_pairs((void*)sort_tmp, sort_b, (const u32*)bkey, bkey_s, (const u32*)idx, order, n, 0u, 7u, st));
+        if (T.V) hipLaunchKernelGGL(k_mm_gather, g1(n * T.V, 256), block, 0, st, d_values, pos_b, n, T.V, T.vals);
+        HIPCHECK(hipGetLastError());
+        std::vector<u64> ctl(MM_CTL_WORDS);
+        HIPCHECK(hipMemcpyAsync(ctl.data(), T.ctl, MM_CTL_WORDS * 8, hipMemcpyDeviceToHost, st));
+        HIPCHECK(hipStreamSynchronize(st));
+        if (ctl[0] != ~0ull) return set_error(mt::map_bad_message((size_t)(ctl[0] >> 2), (int)(ctl[0] & 3))), P2_ERR_INVALID;
+        const u32* h_hist = (const u32*)(ctl.data() + 2);
+        size_t above = 0, total = 0;
+        for (u32 l = 65; l-- > 0;) {  // n_l = #{i : b_i >= l}
+            above += h_hist[l];
+            if (l <= depth) T.level_n[l] = above, total += above;
+        }
+        if (T.level_n[0] != n) return set_error("the level histogram does not add up to the entries"), P2_ERR_HIP;
+        HIPCHECK(hipMemGetInfo(&free_b, &total_b));
+        const size_t need2 = 8 * (total - n) + 32 * total;  // the ids above the leaves, every digest
+        if (need2 > free_b) return mm_refuse("the map's " + std::to_string(total) + " nodes", need2, free_b);
+        if (dalloc(T.mem, &T.ids, total - n) || dalloc(T.mem, &T.dig, 4 * total)) return P2_ERR_HIP;
+        size_t off = 0;
+        for (u32 l = 0; l <= depth; l++) {
+            levels[l] = MapLevel{l ? T.ids + (off - n) : T.keys, T.dig + 4 * off, T.level_n[l]};
+            off += T.level_n[l];
+        }
+        auto group = [&](u32 l) { return l + 1 <= depth ? order + T.level_n[l + 1] : order; };  // the entries with b == l (used for l < depth only)
+        auto group_n = [&](u32 l) { return l + 1 <= depth ? T.level_n[l] - T.level_n[l + 1] : (size_t)0; };
+        hipLaunchKernelGGL(k_mm_leaves, grid, block, 0, st, T.vals, n, T.V, (u64*)levels[0].dig, depth >= 1 ? 1u : 0u, bkey, group(0), group_n(0), ent[0], child[0]);
+        HIPCHECK(hipGetLastError());
+        for (u32 l = 0; l < depth; l++) {
+            const u32 in = l & 1, place = l + 2 <= depth ? 1u : 0u;
+            hipLaunchKernelGGL(k_mm_level, g1(T.level_n[l + 1], 256), block, 0, st, l, levels[l].ids, levels[l].dig, levels[l].n, ent[in], child[in], T.level_n[l + 1],
+                               T.empties + 4 * l, (u64*)levels[l + 1].ids, (u64*)levels[l + 1].dig, place, bkey, group(l + 1), group_n(l + 1), ent[in ^ 1], child[in ^ 1],
+                               counter);
+        }
+        HIPCHECK(hipGetLastError());
+    }
+    HIPCHECK(hipMemcpy(T.levels, levels.data(), levels.size() * sizeof(MapLevel), hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_mm_cap, g1((size_t)1 << T.h, 256), block, 0, st, levels[depth].ids, levels[depth].dig, levels[depth].n, T.empties + 4 * depth, 1u << T.h, T.cap);
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipEventRecord(T.built, st));
+    return P2_OK;
+}
+static int mm_new(const u64* keys, const u64* values, bool on_device, size_t n, size_t value_len, int key_bits, int cap_height, int device, hipStream_t stream, void** map) {
+    if (!map) return set_error("null map pointer"), P2_ERR_INVALID;
+    *map = nullptr;
+    mt::map_check_shape(key_bits, cap_height, value_len);  // throws: P2_ERR_INVALID
+    if (n && (!keys || (value_len && !values))) return set_error("null argument"), P2_ERR_INVALID;
+    if (n >> 32) return set_error("a map takes fewer than 2^32 entries"), P2_ERR_INVALID;
+    if (int rc = pick_device(device)) return rc;
+    std::unique_ptr<MerkleMapHandle> T(new MerkleMapHandle());
+    T->device = device;
+    T->D = (u32)key_bits, T->h = (u32)cap_height, T->V = (u32)value_len, T->n = n;
+    HIPCHECK_AS("hipStreamCreateWithFlags(&T->lane.stream, hipStreamNonBlocking)", T->lane.open(hipStreamNonBlocking));
+    HIPCHECK_AS("hipEventCreateWithFlags(&T->built, hipEventDisableTiming)", T->built.create(hipEventDisableTiming));
+    if (on_device) {
+        if (int rc = mm_build(*T, keys, values, stream)) return (void)hipStreamSynchronize(stream), rc;  // what was enqueued has run before the handle goes
+    } else {
+        size_t free_b = 0, total_b = 0;
+        HIPCHECK(hipMemGetInfo(&free_b, &total_b));
+        if (8 * n * (1 + value_len) > free_b) return mm_refuse("uploading the entries", 8 * n * (1 + value_len), free_b);
+        Allocs tmp;  // the uploaded entries go when the build has run
+        u64 *d_keys, *d_values;
+        if (upload(tmp, &d_keys, keys, n) || upload(tmp, &d_values, values, n * value_len)) return P2_ERR_HIP;
+        const int rc = mm_build(*T, d_keys, d_values, T->lane.stream);
+        HIPCHECK(hipStreamSynchronize(T->lane.stream));  // before tmp goes, whatever rc says
+        if (rc) return rc;
+        T->drop_scratch(true);
+    }
+    *map = T.release();
+    return P2_OK;
+}
+static int mm_handle(void* map, MerkleMapHandle** T) {
+    if (!map) return set_error("null map handle"), P2_ERR_INVALID;
+    *T = (MerkleMapHandle*)map;
+    HIPCHECK(hipSetDevice((*T)->device));
+    (*T)->drop_scratch(false);
+    return P2_OK;
+}
+static int mm_get(MerkleMapHandle& T, const u64* d_keys, size_t nq, u64* d_out, size_t stride, size_t present_off, size_t value_off, size_t sib_off, int* d_status,
+                  hipStream_t stream) {
+    if (nq == 0) return P2_OK;
+    if (!d_keys || !d_out || !d_status) return set_error("null argument"), P2_ERR_INVALID;
+    const size_t sib_words = 4 * (size_t)T.depth();
+    if (present_off >= stride || value_off > stride || T.V > stride - value_off || sib_off > stride || sib_words > stride - sib_off)
+        return set_error("a row of out_stride_words words does not hold presence, " + std::to_string(T.V) + " value words and " + std::to_string(sib_words) +
+                         " sibling words at these offsets"),
+               P2_ERR_INVALID;
+    HIPCHECK(hipStreamWaitEvent(stream, T.built, 0));
+    hipLaunchKernelGGL(k_mm_get, g1(nq * (T.depth() + 1), 256), dim3(256), 0, stream, T.levels, T.vals, T.empties, T.D, T.depth(), T.V, d_keys, nq, d_out, stride, present_off,
+                       value_off, sib_off, d_status);
+    HIPCHECK(hipGetLastError());
+    return P2_OK;
+}
+static int mm_verify(const uint64_t* keys, int key_bits, const uint64_t* present, const uint64_t* values, size_t value_len, const uint64_t* siblings, const uint64_t* cap,
+                     int cap_height, size_t n, int* status, Where w) {
+    const bool bad = key_bits < 1 || key_bits > 64 || cap_height < 0 || cap_height > 16 || cap_height > key_bits || value_len > mt::MAP_MAX_VALUE_LEN;
+    const size_t depth = bad ? 0 : (size_t)(key_bits - cap_height);
+    return run_batch(bad ? "key_bits 1 to 64, cap_height 0 to min(key_bits, 16), value_len at most 134" : nullptr, n, w,
+                     {buf_in(keys, n), buf_in(present, n), buf_in(values, n * value_len), buf_in(siblings, n * 4 * depth), buf_in(cap, bad ? 0 : (size_t)4 << cap_height),
+                      buf_out(status, n)},
+                     [&](const DevPtr* d, hipStream_t s) {
+                         hipLaunchKernelGGL(k_mm_verify, g1(n, 64), dim3(64), 0, s, d[0], (u32)key_bits, d[1], d[2], (u32)value_len, d[3], d[4], (u32)cap_height, n, d[5]);
+                     });
+}
+
+int p2_merkle_map_new(const uint64_t* keys, const uint64_t* values, size_t n, size_t value_len, int key_bits, int cap_height, int device, void** map) {
+    return guarded_rc([&] { return mm_new((const u64*)keys, (const u64*)values, false, n, value_len, key_bits, cap_height, device, nullptr, map); });
+}
+int p2_merkle_map_new_device(const uint64_t* d_keys, const uint64_t* d_values, size_t n, size_t value_len, int key_bits, int cap_height, int device, void* stream,
+                             void** map) {
+    return guarded_rc([&] { return mm_new((const u64*)d_keys, (const u64*)d_values, true, n, value_len, key_bits, cap_height, device, (hipStream_t)stream, map); });
+}
+void p2_merkle_map_free(void* map) {
+    if (!map) return;
+    (void)hipSetDevice(((MerkleMapHandle*)map)->device);
+    delete (MerkleMapHandle*)map;
+}
+int p2_merkle_map_cap(void* map, uint64_t* cap, size_t cap_words) {
+    return guarded_rc([&]() -> int {
+        MerkleMapHandle* T;
+        if (int rc = mm_handle(map, &T)) return rc;
+        const size_t words = (size_t)4 << T->h;
+        if (!cap || cap_words < words) return set_error("the cap holds " + std::to_string(words) + " words"), P2_ERR_INVALID;
+        HIPCHECK(hipEventSynchronize(T->built));
+        T->drop_scratch(true);
+        HIPCHECK(hipMemcpy(cap, T->cap, words * 8, hipMemcpyDeviceToHost));
+        return (int)P2_OK;
+    });
+}
+int p2_merkle_map_len(void* map, size_t* n) {
+    return guarded_rc([&]() -> int {
+        MerkleMapHandle* T;
+        if (int rc = mm_handle(map, &T)) return rc;
+        if (!n) return set_error("null argument"), P2_ERR_INVALID;
+        *n = T->n;
+        return (int)P2_OK;
+    });
+}
+int p2_merkle_map_hashes(void* map, uint64_t* hashes) {
+    return guarded_rc([&]() -> int {
+        MerkleMapHandle* T;
+        if (int rc = mm_handle(map, &T)) return rc;
+        if (!hashes) return set_error("null argument"), P2_ERR_INVALID;
+        HIPCHECK(hipEventSynchronize(T->built));
+        HIPCHECK(hipMemcpy(hashes, T->ctl + 1, 8, hipMemcpyDeviceToHost));
+        return (int)P2_OK;
+    });
+}
+int p2_merkle_map_get_batch(void* map, const uint64_t* keys, size_t n, uint64_t* present, uint64_t* values, uint64_t* siblings) {
+    return guarded_rc([&]() -> int {
+        MerkleMapHandle* T;
+        if (int rc = mm_handle(map, &T)) return rc;
+        if (n == 0) return (int)P2_OK;
+        const size_t sib_words = 4 * (size_t)T->depth(), stride = 1 + T->V + sib_words;
+        if (!keys || !present || (T->V && !values) || (sib_words && !siblings)) return set_error("null argument"), P2_ERR_INVALID;
+        for (size_t i = 0; i < n; i++)
+            if (!mt::map_key_ok(keys[i], T->D)) return set_error("key " + std::to_string(keys[i]) + " (entry " + std::to_string(i) + ") is not below 2^key_bits and p"), P2_ERR_INVALID;
+        Allocs tmp;
+        u64 *d_keys, *d_out;
+        int* d_st;
+        if (upload(tmp, &d_keys, (const u64*)keys, n) || dalloc(tmp, &d_out, n * stride) || dalloc(tmp, &d_st, n)) return P2_ERR_HIP;
+        const int rc = mm_get(*T, d_keys, n, d_out, stride, 0, 1, 1 + T->V, d_st, T->lane.stream);
+        HIPCHECK(hipStreamSynchronize(T->lane.stream));  // before tmp goes, whatever rc says
+        if (rc) return rc;
+        std::vector<u64> rows(n * stride);
+        HIPCHECK(hipMemcpy(rows.data(), d_out, n * stride * 8, hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < n; i++) {
+            const u64* row = rows.data() + i * stride;
+            present[i] = row[0];
+            if (T->V) memcpy(values + i * T->V, row + 1, 8 * (size_t)T->V);
+            if (sib_words) memcpy(siblings + i * sib_words, row + 1 + T->V, 8 * sib_words);
+        }
+        return (int)P2_OK;
+    });
+}
+int p2_merkle_map_get_batch_device(void* map, const uint64_t* d_keys, size_t n, uint64_t* d_out, size_t out_stride_words, size_t present_off, size_t value_off,
+                                   size_t siblings_off, int* d_status, void* stream) {
+    return guarded_rc([&]() -> int {
+        MerkleMapHandle* T;
+        if (int rc = mm_handle(map, &T)) return rc;
+        return mm_get(*T, (const u64*)d_keys, n, (u64*)d_out, out_stride_words, present_off, value_off, siblings_off, d_status, (hipStream_t)stream);
+    });
+}
+int p2_merkle_map_verify_batch(const uint64_t* keys, int key_bits, const uint64_t* present, const uint64_t* values, size_t value_len, const uint64_t* siblings,
+                               const uint64_t* cap, int cap_height, size_t n, int* status, int device) {
+    return mm_verify(keys, key_bits, present, values, value_len, siblings, cap, cap_height, n, status, on_host(device));
+}
+int p2_merkle_map_verify_batch_device(const uint64_t* d_keys, int key_bits, const uint64_t* d_present, const uint64_t* d_values, size_t value_len,
+                                      const uint64_t* d_siblings, const uint64_t* d_cap, int cap_height, size_t n, int* d_status, int device, void* stream) {
+    return mm_verify(d_keys, key_bits, d_present, d_values, value_len, d_siblings, d_cap, cap_height, n, d_status, on_device(device, stream));
 }
 
 // ---- native ecGFp5 in batches: scalar multiplication and Schnorr signatures (kernels_schnorr.h; the host twins are in schnorr.h)
